@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- Msplats/s of the RaDe-GS rasterizer hot path (fwd+bwd) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     (N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
           --master-port P bench.py --gpus N --steps K --warmup W; `python bench.py --gpus N` alone starts the
           N ranks itself as child processes)
@@ -27,9 +27,18 @@ wall clock, max over ranks -> `value`; the same K steps are also bracketed by de
 Per-kernel times for `roofline` come from a separate short instrumented pass AFTER the timed region (HIP events on
 the launch stream around the dominant kernels), so the timed region carries no instrumentation.
 
-Prints ONE JSON line on rank 0 with `roofline` (dominant kernel + whole step, against the 8 TB/s specification and
-against a float4 copy measured on this box) and `cpu_baseline` (the C port under oracle/, bounded samples, rank 0 at
-N=1 only).
+Prints ONE JSON line on rank 0.  A plain run does only what the headline needs: set up, W warm-up steps, the K timed
+steps, the line (`value`, `ms_per_step`, `device_ms_median`, `config`).  --full adds everything measured beside it, after
+the timed region: `variants` (`value_fixed_view`, `value_ext`), `roofline` (dominant kernel + whole step, against the
+8 TB/s specification and against a float4 copy measured on the same GPU; `traffic` from live counters) and `cpu_baseline` +
+`grad_max_rel_err` (the C port under oracle/, bounded samples, rank 0 at N=1 only); --no-variants / --no-live-pmc /
+--no-cpu-baseline leave parts of it out.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step handed its caller -- the five images and
+the gradients of the parameter tensors (--dn-loss: the model's outputs, the loss terms and the gradients) -- as
+DIR/<name>.npy in float32.  Image-shaped arrays are sampled at one fixed, seeded set of pixels and per-Gaussian arrays at
+one fixed, seeded set of rows (whole when smaller than the sample), at most 64 MB in all; the inputs depend on the
+arguments alone, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -101,7 +110,18 @@ def parse():
                     help="also write the line with everything behind it (per-view counts, per-tensor errors, graph / arena / path "
                          "counters, live counters) as indented JSON: the printed line itself stays under 4 KB so that the driver's "
                          "record carries it whole")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the variants, the roofline pass (copy roof, per-kernel events, live "
+                         "counters), the CPU baseline and the gradient check against the C port; default: the headline alone")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (images and gradients; fixed seeded samples of the large "
+                         "ones, <= 64 MB) as DIR/<name>.npy, float32 (rank 0; bench_outputs/ is git-ignored)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.graphed:
+        ap.error("--dump-outputs records the eager step's outputs: not with --graphed")
+    return args
 
 
 def algorithmic_bytes(kernel: str, N: int, I: int, P: int, n_feat: int = 0, n_channels: int = 3) -> float:
@@ -313,7 +333,7 @@ def live_pmc(args):
     if not os.path.exists(exe) or "rocprof" in os.environ.get("LD_PRELOAD", "") or any(k.startswith("ROCPROF") for k in os.environ):
         return None
     root = tempfile.mkdtemp(prefix="misplat_pmc_", dir="/tmp")
-    child = [sys.executable, os.path.abspath(__file__), "--steps", "4", "--warmup", "4", "--no-cpu-baseline", "--no-variants",
+    child = [sys.executable, os.path.abspath(__file__), "--steps", "4", "--warmup", "4", "--full", "--no-cpu-baseline", "--no-variants",
              "--no-live-pmc", "--gaussians", str(args.gaussians), "--width", str(args.width), "--height", str(args.height),
              "--render-mode", args.render_mode, "--rasterize-mode", args.rasterize_mode]
     child += ["--fixed-view"] if args.fixed_view else []
@@ -456,6 +476,47 @@ def traversed_entries(meta, W, H):
     return int((bands - beg + 1).clamp(min=0).sum().item())
 
 
+DUMP_PIXELS = 1 << 17           # --dump-outputs: pixels sampled from every image-shaped output
+DUMP_ROWS = 1 << 17             # ... and Gaussians (rows) from every per-Gaussian one
+DUMP_BYTES = 64_000_000        # everything written, at most (64 MB)
+DUMP_SEED = 20261               # the samples are the same in every run with the same sizes
+
+
+def _sample(n_total: int, n_keep: int, salt: int) -> torch.Tensor:
+    """Sorted indices of a fixed, seeded sample of n_keep out of n_total (all of them when n_keep >= n_total)."""
+    if n_keep >= n_total:
+        return torch.arange(n_total)
+    g = torch.Generator().manual_seed(DUMP_SEED + salt)
+    return torch.randperm(n_total, generator=g)[:n_keep].sort().values
+
+
+def dump_outputs(path: str, images: dict, rows: dict, other: dict, H: int, W: int, N: int) -> dict:
+    """--dump-outputs: write the tensors a step handed its caller as ``path/<name>.npy`` (float32).  ``images``: [..., H, W(, C)]
+    arrays, sampled at one set of pixels; ``rows``: [N, ...] arrays, sampled at one set of rows; ``other``: small arrays,
+    written whole.  Returns {name: shape written}."""
+    import numpy as np
+    img = {k: t.detach().reshape(H * W, -1) for k, t in images.items() if t is not None}
+    row = {k: t.detach().reshape(N, -1) for k, t in rows.items() if t is not None}
+    oth = {k: t.detach().reshape(-1) for k, t in other.items() if t is not None}
+    n_pix, n_row = min(DUMP_PIXELS, H * W), min(DUMP_ROWS, N)
+    fixed = 4 * sum(t.numel() for t in oth.values()) + 256 * (len(img) + len(row) + len(oth))
+    while True:
+        size = fixed + 4 * (n_pix * sum(t.shape[1] for t in img.values()) + n_row * sum(t.shape[1] for t in row.values()))
+        if size <= DUMP_BYTES or (n_pix <= 1 and n_row <= 1):
+            break
+        n_pix, n_row = max(n_pix // 2, 1), max(n_row // 2, 1)
+    if size > DUMP_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs needs {size} bytes for the small arrays alone (> {DUMP_BYTES})")
+    os.makedirs(path, exist_ok=True)
+    written = {}
+    for group, sel in ((img, _sample(H * W, n_pix, 0)), (row, _sample(N, n_row, 1)), (oth, None)):
+        for k, t in group.items():
+            a = (t if sel is None else t.index_select(0, sel.to(t.device))).float().cpu().numpy().astype(np.float32)
+            np.save(os.path.join(path, k + ".npy"), a)
+            written[k] = list(a.shape)
+    return written
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -486,7 +547,8 @@ def main():
     Ks = sc["Ks"].to(dev)
     cd = {"RGB": 3, "RGB+ED": 4, "RGB+D": 4}[args.render_mode]
     g = torch.Generator().manual_seed(7)
-    info = {"allreduce_ms": [], "it": 0, "isects": []}
+    # (dump_it: the step counter of the LAST timed step of the headline, whose results --dump-outputs writes; -1: none)
+    info = {"allreduce_ms": [], "it": 0, "isects": [], "dump_it": args.warmup + args.steps - 1 if args.dump_outputs else -1}
     bucket = None
     mode = {"ext": bool(args.ext_activations), "fixed": bool(args.fixed_view)}
 
@@ -523,6 +585,11 @@ def main():
             functools.reduce(torch.add, loss.values()).backward()      # (nerfstudio's trainer sums the dictionary this way)
             if bucket is not None:
                 info["allreduce_ms"].append(bucket.allreduce())
+            if info["it"] == info["dump_it"]:      # --dump-outputs: the last timed step's results (detached: no graph kept)
+                res = {k: v.detach() for k, v in out.items() if torch.is_tensor(v)}
+                info["dump"] = ({k: v for k, v in res.items() if v.dim() >= 2},
+                                {"grad_" + k: p.grad for k, p in zip(parallel.GRAD_KEYS, leaves)},
+                                dict({"loss_" + k: v.detach() for k, v in loss.items()}, **{k: v for k, v in res.items() if v.dim() < 2}))
             info["n_isects"], info["n_visible"] = model.info["n_isects"], model.info["radii"]
             info["meta"] = unit_tensors(model.info)
             info["isects"].append(int(model.info["n_isects"]))
@@ -547,6 +614,9 @@ def main():
             torch.autograd.backward(list(out[:5]), ups)
             if bucket is not None:
                 info["allreduce_ms"].append(bucket.allreduce())
+            if info["it"] == info["dump_it"]:      # --dump-outputs: the last timed step's results (detached: no graph kept)
+                info["dump"] = ({k: o.detach() for k, o in zip(("render", "alpha", "exp_depth", "med_depth", "normal"), out[:5])},
+                                {"grad_" + k: p.grad for k, p in params.items()}, {})
             # (only plain tensors are kept between steps: a reference to `out` / its meta would keep this step's autograd
             # graph alive, which a whole-step capture -- --graphed -- cannot tolerate)
             m = out[5]
@@ -599,7 +669,7 @@ def main():
                                      for g in sorted({x[0] for x in pauses})}}
         return dt, dev_ms[len(dev_ms) // 2]
 
-    roof, roof_variants = copy_roof(dev) if rank == 0 else (0.0, [])
+    roof, roof_variants = copy_roof(dev) if rank == 0 and args.full else (0.0, [])
     eager_step, graphed = step, None
     if args.graphed:
         if args.dn_loss or shared or args.buckets:
@@ -637,7 +707,9 @@ def main():
                 return graphed_views.replay((turn["i"] - 1) % 8)
     stats0 = dict(ops.PATH_STATS)
     g_start = ops.graph_cache_stats()
+    n_seen = len(info["isects"])
     dt, dev_med = timed(step, args.steps, args.warmup)
+    timed_isects = info["isects"][n_seen:][-args.steps:]      # (the eager steps' host counts; none for graph replays)
     host_trace_head = info.pop("host_trace", None)
     took = {k: ops.PATH_STATS[k] - stats0.get(k, 0) for k in ops.PATH_STATS}
     if ops.KEY_TRACE and rank == 0:                # MISPLAT_KEY_TRACE=1: which argument fields moved between two visits of a view
@@ -667,6 +739,12 @@ def main():
         step()                                     # (eager again: info[...] must not point into the graph's pool)
     allreduce_ms = sorted(ev[0].elapsed_time(ev[1]) for ev in info["allreduce_ms"] if ev is not None)
 
+    # ---- --dump-outputs: what the last timed step handed its caller, written before anything else runs on these tensors
+    dumped = info.pop("dump", None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *dumped, H, W, N)
+    dumped = None
+
     # ---- the other corners of {torch, extension activations} x {cycling, fixed view}: same protocol, after the headline
     variants = {}
 
@@ -676,7 +754,7 @@ def main():
     ms_head = dt / args.steps * 1e3
     variants[label(headline_mode)] = {"ms_per_step": round(ms_head, 4), "device_ms_median": round(dev_med, 4),
                                       "value": round(world * N / (dt / args.steps) / 1e6, 3)}
-    if not args.no_variants and not args.dn_loss and graphed is None:
+    if args.full and not args.no_variants and not args.dn_loss and graphed is None:
         for ext in (False, True):
             for fixed in (False, True):
                 m = {"ext": ext, "fixed": fixed}
@@ -687,7 +765,7 @@ def main():
                 variants[label(m)] = {"ms_per_step": round(dtv / args.steps * 1e3, 4), "device_ms_median": round(medv, 4),
                                       "value": round(world * N / (dtv / args.steps) / 1e6, 3)}
         mode.update(headline_mode)
-    if args.features > 0 and not args.no_variants and graphed is None:
+    if args.full and args.features > 0 and not args.no_variants and graphed is None:
         # the reference's own composition (spherical_harmonics -> clamp_min -> cat -> rasterization(sh_degree=None)), same views
         mode.update(headline_mode, composed=True)
         dtv, medv = timed(step, args.steps, args.warmup)
@@ -699,24 +777,29 @@ def main():
     # ---- instrumented pass (outside the timed region): HIP events on the launch stream around the compositing kernels
     # (the same path as the timed region: the one-entry C calls record the events themselves, directly before and
     # after the kernel, and launch plainly instead of replaying a graph while they carry events)
-    ops.KERNEL_EVENTS = {}
-    info["isects"].clear()
-    n_inst = 10
     units = []
-    stats_i = dict(ops.PATH_STATS)
-    for i in range(n_inst):
-        step()
-        if rank == 0 and i >= 2:
-            units.append(visited_units(info["meta"], W, H, N, int(info["n_isects"])))
-    torch.cuda.synchronize()
-    events, ops.KERNEL_EVENTS = ops.KERNEL_EVENTS, None
-    took_i = {k: ops.PATH_STATS[k] - stats_i.get(k, 0) for k in ops.PATH_STATS}
+    if args.full:
+        ops.KERNEL_EVENTS = {}
+        info["isects"].clear()
+        n_inst = 10
+        stats_i = dict(ops.PATH_STATS)
+        for i in range(n_inst):
+            step()
+            if rank == 0 and i >= 2:
+                units.append(visited_units(info["meta"], W, H, N, int(info["n_isects"])))
+        torch.cuda.synchronize()
+        events, ops.KERNEL_EVENTS = ops.KERNEL_EVENTS, None
+        took_i = {k: ops.PATH_STATS[k] - stats_i.get(k, 0) for k in ops.PATH_STATS}
 
     if rank == 0:
-        isects = info["isects"][2:] or [int(info["n_isects"])]
-        I = int(sum(isects) / len(isects))         # mean over the instrumented launches (the views differ)
+        if args.full:
+            isects = info["isects"][2:] or [int(info["n_isects"])]
+        else:
+            isects = timed_isects or [int(info["n_isects"])]
+        I = int(sum(isects) / len(isects))         # mean over the instrumented launches, or the timed steps (the views differ)
         n_vis = int((info["n_visible"] > 0).any(-1).sum().item())
         P_px = W * H
+    if rank == 0 and args.full:
         ktimes = {}
         for k, v in events.items():                # ms; the first two instrumented steps are warm-up; MEAN duration per launch
             ts = [a.elapsed_time(b) for a, b in v[2:]] or [0.0]
@@ -745,6 +828,7 @@ def main():
             except Exception:
                 pmc = {}
         vif = pmc.get("valu_issue_frac")
+    if rank == 0:
         view_txt = "1 fixed view" if headline_mode["fixed"] else "8 cycling views"
         if args.dn_loss:
             wl = (f"{N} shared Gaussians, {view_txt} {W}x{H}, model step: get_outputs -> "
@@ -773,46 +857,53 @@ def main():
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_head, 4),
             "device_ms_median": round(dev_med, 4),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            # the literal configs[2] figure (ONE view) beside the headline's eight cycling views, and the activations-in-kernel extension
-            "value_fixed_view": var(fixed_l).get("value"), "ms_fixed_view": var(fixed_l).get("ms_per_step"),
-            "value_ext": var("ext_activations+cycling_views").get("value"),
-            "variants": {k: [v["ms_per_step"], v["value"]] for k, v in variants.items()},
-            "config": {"workload": wl, "views": 1 if headline_mode["fixed"] else 8, "n_isects": I, "n_visible": n_vis,
-                       "parallelism": par, "git_rev": git_rev(),
-                       "graph_hit_rate": graph_timed["hit_rate"] if args.dn_loss else graph_all["hit_rate_of_replayable"],
-                       "graph_timed": [graph_timed["hits"], graph_timed["captures"], graph_timed["calls"]],
-                       "path": {k: took.get(k, 0) for k in ("forward", "forward_lazy_colour", "forward_view_order", "capacity_redo",
-                                                           "backward_one_call", "backward_background_fill", "forward_front_only",
-                                                           "forward_probe", "forward_plan_hit", "backward_plan_hit")},
-                       "host": "whole-step hipGraphs" if graphed is not None else "eager"},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
-                         "traffic": pmc.get(dom), "traffic_source": "file",
-                         "algorithmic_bytes": abytes, "bytes_basis": "visited" if abytes is visited and sparse_paths else "nominal",
-                         "achieved_nominal": round(nominal / (ktimes[dom] * 1e-3) / 1e9, 2),
-                         "frac_nominal": round(nominal / (ktimes[dom] * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
-                         "units": u,
-                         "kernel_ms": {k: round(v, 4) for k, v in ktimes.items()},
-                         "valu_busy": vif.get(dom) if isinstance(vif, dict) else None,
-                         "copy_roof_GBs": round(roof, 1),
-                         "step_GBs": round(step_gbs, 1), "step_frac": round(step_gbs / HBM_PEAK_GBS, 5),
-                         "step_frac_nominal": round(step_nominal / (dev_med * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)},
         }
+        if args.full:
+            line.update({
+                # the literal configs[2] figure (ONE view) beside the headline's eight cycling views, and the activations-in-kernel
+                # extension
+                "value_fixed_view": var(fixed_l).get("value"), "ms_fixed_view": var(fixed_l).get("ms_per_step"),
+                "value_ext": var("ext_activations+cycling_views").get("value"),
+                "variants": {k: [v["ms_per_step"], v["value"]] for k, v in variants.items()}})
+        line["config"] = {"workload": wl, "views": 1 if headline_mode["fixed"] else 8, "n_isects": I, "n_visible": n_vis,
+                          "parallelism": par, "git_rev": git_rev(),
+                          "graph_hit_rate": graph_timed["hit_rate"] if args.dn_loss else graph_all["hit_rate_of_replayable"],
+                          "graph_timed": [graph_timed["hits"], graph_timed["captures"], graph_timed["calls"]],
+                          "path": {k: took.get(k, 0) for k in ("forward", "forward_lazy_colour", "forward_view_order", "capacity_redo",
+                                                              "backward_one_call", "backward_background_fill", "forward_front_only",
+                                                              "forward_probe", "forward_plan_hit", "backward_plan_hit")},
+                          "host": "whole-step hipGraphs" if graphed is not None else "eager"}
+        if args.full:
+            line["roofline"] = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
+                                "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
+                                "traffic": pmc.get(dom), "traffic_source": "file",
+                                "algorithmic_bytes": abytes, "bytes_basis": "visited" if abytes is visited and sparse_paths else "nominal",
+                                "achieved_nominal": round(nominal / (ktimes[dom] * 1e-3) / 1e9, 2),
+                                "frac_nominal": round(nominal / (ktimes[dom] * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
+                                "units": u,
+                                "kernel_ms": {k: round(v, 4) for k, v in ktimes.items()},
+                                "valu_busy": vif.get(dom) if isinstance(vif, dict) else None,
+                                "copy_roof_GBs": round(roof, 1),
+                                "step_GBs": round(step_gbs, 1), "step_frac": round(step_gbs / HBM_PEAK_GBS, 5),
+                                "step_frac_nominal": round(step_nominal / (dev_med * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)}
         details = {"variants": variants, "graph_cache": ops.graph_cache_stats(), "graph_cache_timed": graph_timed,
                    "graph_cache_headline": graph_all, "arena": dict(__import__("collab_splats_amd.arena", fromlist=["STATS"]).STATS),
-                   "path": dict(took), "n_isects_per_view": isects[:8], "copy_roof_variants_GBs": roof_variants,
-                   "units_per_step": units, "parallel_stats": dict(parallel.STATS), "host_trace": host_trace_head}
+                   "path": dict(took), "n_isects_per_view": isects[:8]}
+        if args.full:
+            details.update(copy_roof_variants_GBs=roof_variants, units_per_step=units)
+        details.update(parallel_stats=dict(parallel.STATS), host_trace=host_trace_head)
         # (compact: the slowest step's enqueue time on the host -- a pause of the interpreter or the OS in one of K short steps)
         line["config"]["host_enqueue_ms"] = [host_trace_head["enqueue_ms_median"], host_trace_head["enqueue_ms_max"]] if host_trace_head else None
         if allreduce_ms:
             line["allreduce_ms"] = round(allreduce_ms[len(allreduce_ms) // 2], 4)
-        if world == 1 and not args.no_cpu_baseline and not args.no_live_pmc and not args.dn_loss and args.features == 0 and graphed is None:
+        if (args.full and world == 1 and not args.no_cpu_baseline and not args.no_live_pmc and not args.dn_loss and args.features == 0
+                and graphed is None):
             live = live_pmc(args)
             if live and dom in live:
                 rf = line["roofline"]
                 rf["traffic"], rf["valu_busy"], rf["traffic_source"] = live[dom]["traffic"], live[dom]["valu_busy"], "live"
                 details["pmc_live"] = live
-        if world == 1 and not args.no_cpu_baseline and not args.dn_loss and args.features == 0:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.dn_loss and args.features == 0:
             import numpy as np
             from oracle.craster import CRaster
             base, keep = cpu_baseline(args, seed)

@@ -6,8 +6,9 @@ set -e
 TAG=$1; KER=$2; shift; shift
 OUT=$GRAFT_REPO_ROOT/gpurun_out/pmck_$TAG
 mkdir -p $OUT
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-ARGS="$GRAFT_REPO_ROOT/bench.py --steps 4 --warmup 4 --no-cpu-baseline --no-variants $*"
+ARGS="$ROOT/bench.py --full --steps 4 --warmup 4 --no-cpu-baseline --no-variants $*"
 rocprofv3 --pmc FETCH_SIZE GRBM_GUI_ACTIVE --output-format csv -d $OUT/fetch -- python3 $ARGS > $OUT/fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/write -- python3 $ARGS > $OUT/write.log 2>&1
 n=0; for grp in ${PMCK_EXTRA:-}; do n=$((n+1))       # PMCK_EXTRA="A,B C,D": one more counters-only pass per group

@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out/r05a; mkdir -p $O
 timeout -k 10 900 python -m pytest tests/test_parity_gpu.py -x -q -m gpu -k "rccl_world_of_one or sparse_reduce_without or gradient_sink" > $O/rccl_test.txt 2>&1 || { tail -50 $O/rccl_test.txt; exit 1; }
 tail -3 $O/rccl_test.txt
-B="--no-cpu-baseline --no-variants --no-live-pmc"
+B="--full --no-cpu-baseline --no-variants --no-live-pmc"
 timeout -k 10 300 python bench.py $B > $O/bwd_base.json 2> $O/bwd_base.err
 MISPLAT_LIB=$PWD/collab_splats_amd/_exp/libmisplat_noatomic.so timeout -k 10 300 python bench.py $B > $O/bwd_noatomic.json 2> $O/bwd_noatomic.err
 MISPLAT_LIB=$PWD/collab_splats_amd/_exp/libmisplat_rowstores.so timeout -k 10 300 python bench.py $B > $O/bwd_rowstores.json 2> $O/bwd_rowstores.err

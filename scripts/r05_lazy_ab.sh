@@ -2,7 +2,7 @@
 set -e -o pipefail
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/lazyab; mkdir -p $O
-B="--no-cpu-baseline --no-variants --no-live-pmc"
+B="--full --no-cpu-baseline --no-variants --no-live-pmc"
 for m in auto 0; do
   MISPLAT_LAZY_SH=$m timeout -k 10 300 python bench.py $B > $O/lazy_$m.json 2>$O/lazy_$m.err
 done

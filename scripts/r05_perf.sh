@@ -3,7 +3,7 @@
 set -e -o pipefail
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/${1:-perf}; shift; mkdir -p $O
-B="--no-cpu-baseline --no-variants --no-live-pmc"
+B="--full --no-cpu-baseline --no-variants --no-live-pmc"
 for tag in "$@"; do
   L=$PWD/collab_splats_amd/_exp/libmisplat_$tag.so; [ "$tag" = main ] && L=$PWD/collab_splats_amd/libmisplat.so
   MISPLAT_LIB=$L timeout -k 10 300 python bench.py $B > $O/$tag.json 2> $O/$tag.err

@@ -3,8 +3,9 @@
 set -e
 OUT=$GRAFT_REPO_ROOT/gpurun_out/tl1m
 mkdir -p $OUT
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $OUT/t1m -- python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --steps 30 "$@" > $OUT/b1m.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $OUT/t1m -- python3 $ROOT/bench.py --full --no-cpu-baseline --steps 30 "$@" > $OUT/b1m.log 2>&1
 cd $GRAFT_REPO_ROOT
 f=$(find $OUT/t1m -name "*kernel_trace.csv" | head -1)
 python3 scripts/timeline.py $f > $OUT/t1m.txt
