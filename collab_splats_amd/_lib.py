@@ -116,6 +116,8 @@ SYMBOLS = {
     "misplat_touched_bits": (C.c_int, 4), "misplat_union_count": (C.c_int, 5), "misplat_union_scan": (C.c_int, 5), "misplat_union_ids": (C.c_int, 7),
     "misplat_rows_pack": (C.c_int, 8), "misplat_rows_unpack": (C.c_int, 8),
     "misplat_debug_memset_replay": (C.c_int, 5),
+    "misplat_tsdf_mark": (C.c_int, 10), "misplat_tsdf_alloc": (C.c_int, 6), "misplat_tsdf_integrate": (C.c_int, 14),
+    "misplat_tsdf_order": (C.c_int, 5), "misplat_tsdf_mc_count": (C.c_int, 11), "misplat_tsdf_mc_emit": (C.c_int, 13),
     "misplat_version": (C.c_char_p, 0),
 }
 

@@ -35,6 +35,8 @@ SOURCES = {
     "epilogue.hip": [],
     "ssim.hip": [],
     "optim.hip": [],
+    # tsdf.hip: fixed IEEE operation order, as project.hip: the voxel grids equal the fp32 restatement (tests/) bit for bit
+    "tsdf.hip": ["-ffp-contract=off"],
 }
 
 
@@ -55,7 +57,8 @@ def _stale(target: str, deps) -> bool:
 def build(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(OBJ, exist_ok=True)
     hipcc = _hipcc()
-    headers = [os.path.join(INCLUDE, "misplat.h"), os.path.join(CSRC, "sh_eval.h"), os.path.join(CSRC, "internal.h")]
+    headers = [os.path.join(INCLUDE, "misplat.h"), os.path.join(CSRC, "sh_eval.h"), os.path.join(CSRC, "internal.h"),
+               os.path.join(CSRC, "mc_tables.h")]
     jobs = []
     objs = []
     for src, extra in SOURCES.items():

@@ -461,20 +461,28 @@ class RadegsModel(nn.Module):
         return self.get_outputs(camera.to(self.device) if hasattr(camera, "to") else camera)
 
     @torch.no_grad()
-    def render_views(self, cameras: Sequence, batch_size: int = 4) -> Dict[str, Tensor]:
+    def render_views(self, cameras: Sequence, batch_size: int = 4, crop_box=None) -> Dict[str, Tensor]:
         """Eval-time batch rendering for the TSDF hand-off (the reference renders
         every training view one by one through ``get_outputs_for_camera`` and copies each map to the host,
         mesh.py:1572-1630).  ``batch_size`` views go through ONE rasterization call (the camera batch dimension of
         the kernels), the a3 epilogue runs per view (its ``max`` reductions are per image), and the stacked maps
         ``rgb[V,H,W,3] depth[V,H,W,1] median_depth[V,H,W,1] accumulation[V,H,W,1] normals[V,H,W,3]`` stay on
-        the device.  Values are identical to ``get_outputs`` in eval mode, view by view."""
+        the device.  Values are identical to ``get_outputs`` in eval mode, view by view.  ``crop_box`` (or None): only the
+        Gaussians inside it are rendered, as ``get_outputs`` does with the model's crop box in evaluation; it must keep at
+        least one Gaussian (``get_outputs`` returns ``get_empty_outputs`` instead, which has no depth maps)."""
         if self.config.rasterize_mode not in ["antialiased", "classic"]:
             raise ValueError("Unknown rasterize_mode: %s", self.config.rasterize_mode)
+        pick = lambda t: t                                                                   # noqa: E731
+        if crop_box is not None:
+            crop_ids = crop_box.within(self.means).squeeze()
+            if crop_ids.sum() == 0:
+                raise ValueError("render_views: the crop box holds no Gaussian")
+            pick = lambda t: t[crop_ids]                                                     # noqa: E731
         if self.config.sh_degree > 0:
-            colors = (self.features_dc, self.features_rest)
+            colors = (pick(self.features_dc), pick(self.features_rest))
             sh_degree_to_use = min(self.step // self.config.sh_degree_interval, self.config.sh_degree)
         else:
-            colors, sh_degree_to_use = torch.sigmoid(self.features_dc), None
+            colors, sh_degree_to_use = torch.sigmoid(pick(self.features_dc)), None
         bg_list = self._background_list()
         out: Dict[str, List[Tensor]] = {k: [] for k in ("rgb", "depth", "median_depth", "accumulation", "normals")}
         cameras = list(cameras)
@@ -487,7 +495,8 @@ class RadegsModel(nn.Module):
             cp["viewmats"] = torch.cat([p["viewmats"] for p in params], dim=0)
             cp["Ks"] = torch.cat([p["Ks"] for p in params], dim=0)
             render, alpha, exp_d, med_d, exp_n, _ = self._render(
-                means=self.means, quats=self.quats, scales=self.scales, opacities=self.opacities, colors=colors,
+                means=pick(self.means), quats=pick(self.quats), scales=pick(self.scales), opacities=pick(self.opacities),
+                colors=colors,
                 render_mode="RGB+ED", sh_degree_to_use=sh_degree_to_use, camera_params=cp)
             for c in range(len(params)):
                 sl = slice(c, c + 1)
@@ -495,6 +504,39 @@ class RadegsModel(nn.Module):
                 out["rgb"].append(ep[0]); out["depth"].append(ep[1]); out["median_depth"].append(ep[2])
                 out["normals"].append(ep[3]); out["accumulation"].append(alpha[sl])
         return {k: torch.cat(v, dim=0) for k, v in out.items()}
+
+    @torch.no_grad()
+    def extract_mesh(self, cameras: Sequence, voxel_size: float = 0.01, sdf_trunc: float = 0.03, depth_trunc: float = 1.0,
+                     depth_name: str = "median_depth", masks=None, obb_box=None, batch_size: int = 4):
+        """The TSDF part of the reference's ``Open3DTSDFFusion.main`` (mesh.py:1557-1632) on the device: crop (``set_crop``),
+        render ``batch_size`` views at a time (``render_views``), integrate each batch into a ``TSDFVolume`` and extract
+        the mesh.  Per view: depth ``outputs[depth_name]``, colour ``outputs["rgb"]``, extrinsic ``inv(c2w @ diag(1,-1,-1,1))``
+        and the camera's own intrinsics (``tsdf.camera_frame``); ``masks`` ([V,H,W(,1)] bool, or None) zero the depth where
+        False.  With ``obb_box`` the volume's bounds are the box's AABB padded by ``sdf_trunc`` (``tsdf.obb_bounds``), and a
+        box with no Gaussian inside gives an empty mesh.  Rendered maps are freed batch by batch and never reach the host.
+        Returns ``(vertices [M,3], triangles [T,3] int32, colors [M,3])`` on the device."""
+        from .tsdf import TSDFVolume, camera_frame, obb_bounds
+        self.set_crop(obb_box)
+        cameras = list(cameras)
+        vol = TSDFVolume(voxel_size, sdf_trunc, depth_trunc, bounds=obb_bounds(obb_box, sdf_trunc), device=self.device)
+        if obb_box is not None and obb_box.within(self.means).squeeze().sum() == 0:
+            return vol.extract_mesh()
+        if masks is not None:
+            masks = torch.as_tensor(masks).to(self.device)
+            if masks.shape[0] != len(cameras):
+                raise ValueError("extract_mesh: one mask per camera")
+        bs = max(1, int(batch_size))
+        for b in range(0, len(cameras), bs):
+            chunk = cameras[b:b + bs]
+            maps = self.render_views(chunk, batch_size=bs, crop_box=obb_box)
+            if depth_name not in maps:
+                raise KeyError(f"extract_mesh: depth_name {depth_name!r} is not among the rendered maps {sorted(maps)}")
+            frames = [camera_frame(c) for c in chunk]
+            vm = torch.stack([f[0] for f in frames]).to(self.device)
+            Ks = torch.stack([f[1] for f in frames]).to(self.device)
+            vol.integrate(maps[depth_name], vm, Ks, rgbs=maps["rgb"], masks=None if masks is None else masks[b:b + bs])
+            del maps
+        return vol.extract_mesh()
 
     def _scale_reg(self, dev) -> Tensor:
         """Splatfacto's scale regularisation: 0.1 * mean(max(max(s) / min(s), max_gauss_ratio) - max_gauss_ratio) of the

@@ -1,0 +1,292 @@
+"""TSDF fusion of depth maps and marching-cubes mesh extraction on the MI355X (csrc/tsdf.hip).
+
+``TSDFVolume`` restates Open3D's legacy ``ScalableTSDFVolume`` (what the reference's ``Open3DTSDFFusion`` integrates into,
+collab_splats/utils/mesh.py:1473-1630) in fp32: units of 16^3 voxels allocated per view from the depth samples, each view
+updating only the units it touches, and ``extract_triangle_mesh`` as a deterministic marching cubes.  Everything stays on
+the device; there is no CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional, Tuple
+
+import numpy as np
+import torch
+from torch import Tensor
+
+from ._lib import MisplatError, check, load, ptr, require_gpu, stream_ptr
+
+UNIT = 16
+UNIT_VOXELS = UNIT ** 3
+MAX_VIEWS = 64                       # views per kernel batch (bits of a unit's view word)
+MAX_UNITS = 1 << 26                  # dense unit map cap (include/misplat.h MISPLAT_TSDF_MAX_UNITS)
+
+
+class Grid(C.Structure):
+    """Mirror of ``misplat_tsdf_grid`` (include/misplat.h)."""
+    _fields_ = [("voxel_size", C.c_float), ("sdf_trunc", C.c_float), ("depth_trunc", C.c_float),
+                ("lo", C.c_int32 * 3), ("dims", C.c_int32 * 3), ("reserved", C.c_int32)]
+
+
+def _unit_range(lo_world, hi_world, ulen: float) -> Tuple[np.ndarray, np.ndarray]:
+    """Inclusive unit-coordinate range of the units overlapping the world box [lo, hi]."""
+    lo = np.floor(np.asarray(lo_world, np.float64) / ulen).astype(np.int64)
+    hi = np.floor(np.asarray(hi_world, np.float64) / ulen).astype(np.int64)
+    return lo, hi
+
+
+class TSDFVolume:
+    """Scalable TSDF volume on the GPU.
+
+    ``voxel_size`` / ``sdf_trunc`` / ``depth_trunc`` as Open3D's ``ScalableTSDFVolume(voxel_length, sdf_trunc)`` and
+    ``create_from_color_and_depth(depth_trunc, depth_scale=1)``.  ``bounds`` (optional, ``[[xmin, ymin, zmin], [xmax, ymax,
+    zmax]]``): units that do not overlap the box are never allocated.  The dense unit map otherwise covers the views' frusta
+    cut at ``depth_trunc`` (padded by ``sdf_trunc``) and grows with them; more than ``max_units`` units raise ``MisplatError``.
+    """
+
+    def __init__(self, voxel_size: float, sdf_trunc: float, depth_trunc: float = 3.0, bounds=None,
+                 device=None, max_units: int = MAX_UNITS):
+        if not (voxel_size > 0 and sdf_trunc > 0 and depth_trunc > 0):
+            raise ValueError("TSDFVolume: voxel_size, sdf_trunc and depth_trunc must be positive")
+        self.device = torch.device(device) if device is not None else torch.device("cuda")
+        if self.device.type != "cuda":
+            raise MisplatError("TSDFVolume runs on the MI355X only: there is no CPU fallback")
+        self.voxel_size, self.sdf_trunc, self.depth_trunc = float(voxel_size), float(sdf_trunc), float(depth_trunc)
+        self.ulen = float(np.float32(self.voxel_size) * np.float32(UNIT))
+        self.max_units = min(int(max_units), MAX_UNITS)
+        self.clip = None
+        if bounds is not None:
+            b = np.asarray(bounds, np.float64).reshape(2, 3)
+            if not np.all(b[1] >= b[0]):
+                raise ValueError("TSDFVolume: bounds must be [[min xyz], [max xyz]]")
+            self.clip = _unit_range(b[0], b[1], self.ulen)
+        self.lo = self.dims = None                 # unit map (none before the first integrate)
+        self.n_units = 0                           # allocated units (= pool slots in use)
+        self.n_views = 0
+        self._pool = None
+        self._counters = None                      # device {allocated slots, touched units of the batch}
+
+    # ------------------------------------------------------------------------------------------------------------ plumbing
+    def _grid(self) -> Grid:
+        g = Grid(self.voxel_size, self.sdf_trunc, self.depth_trunc)
+        g.lo[:] = [int(x) for x in self.lo]
+        g.dims[:] = [int(x) for x in self.dims]
+        return g
+
+    def _cover(self, lo: np.ndarray, hi: np.ndarray) -> bool:
+        """Make the unit map cover units lo..hi (inclusive, clipped to the bounds); False if nothing is left."""
+        if self.clip is not None:
+            lo, hi = np.maximum(lo, self.clip[0]), np.minimum(hi, self.clip[1])
+        if np.any(hi < lo):
+            return self.lo is not None
+        if self.lo is not None:
+            old_hi = self.lo + self.dims - 1
+            if np.all(lo >= self.lo) and np.all(hi <= old_hi):
+                return True
+            lo, hi = np.minimum(lo, self.lo), np.maximum(hi, old_hi)
+        dims = hi - lo + 1
+        n = int(np.prod(dims))
+        if n > self.max_units:
+            raise MisplatError(f"TSDFVolume: the views' frusta span {n} units of {UNIT}^3 voxels, above the cap of "
+                               f"{self.max_units}: pass bounds=, a smaller depth_trunc or a larger voxel_size")
+        slot_map = torch.full((n,), -1, dtype=torch.int32, device=self.device)
+        if self.n_units:                           # re-linearise the allocated units into the grown map
+            m = torch.nonzero(self._slot_map >= 0).squeeze(1)
+            nx, ny = int(self.dims[0]), int(self.dims[1])
+            cx, cy, cz = m % nx, (m // nx) % ny, m // (nx * ny)
+            o = self.lo - lo
+            lin = (cx + int(o[0])) + int(dims[0]) * ((cy + int(o[1])) + int(dims[1]) * (cz + int(o[2])))
+            slot_map[lin] = self._slot_map[m]
+        self.lo, self.dims = lo.astype(np.int64), dims.astype(np.int64)
+        self._slot_map = slot_map
+        self._words = torch.zeros(n, dtype=torch.int64, device=self.device)
+        self._touched = torch.empty(2 * n, dtype=torch.int32, device=self.device)
+        return True
+
+    def _frusta_units(self, viewmats: Tensor, Ks: Tensor, H: int, W: int) -> Tuple[np.ndarray, np.ndarray]:
+        """Units overlapping the AABB of the views' frusta cut at depth_trunc, padded by sdf_trunc (one host read)."""
+        vm, K = viewmats.double(), Ks.double()
+        R, t = vm[:, :3, :3], vm[:, :3, 3]
+        D = self.depth_trunc
+        uv = torch.tensor([[0.0, 0.0], [W, 0.0], [0.0, H], [W, H]], dtype=torch.float64, device=vm.device)
+        x = (uv[None, :, 0] - K[:, None, 0, 2]) * D / K[:, None, 0, 0]
+        y = (uv[None, :, 1] - K[:, None, 1, 2]) * D / K[:, None, 1, 1]
+        pc = torch.stack([x, y, torch.full_like(x, D)], -1)                        # [V,4,3] camera space
+        pc = torch.cat([pc, torch.zeros_like(pc[:, :1])], 1)                        # + the camera centre
+        pw = torch.einsum("vji,vkj->vki", R, pc - t[:, None, :])                    # R^T (p - t)
+        box = torch.stack([pw.amin((0, 1)), pw.amax((0, 1))]).cpu().numpy()
+        if not np.all(np.isfinite(box)):
+            raise ValueError("TSDFVolume.integrate: non-finite camera parameters")
+        lo, hi = _unit_range(box[0] - self.sdf_trunc, box[1] + self.sdf_trunc, self.ulen)
+        return lo - 1, hi + 1
+
+    def _grow_pool(self, n: int) -> None:
+        cap = 0 if self._pool is None else self._pool.shape[0]
+        if n <= cap:
+            return
+        new = torch.zeros((max(n, cap + cap // 2, 64), 5, UNIT_VOXELS), dtype=torch.float32, device=self.device)
+        if self.n_units:
+            new[:self.n_units] = self._pool[:self.n_units]
+        self._pool = new
+
+    # ------------------------------------------------------------------------------------------------------------ public
+    def integrate(self, depths: Tensor, viewmats: Tensor, Ks: Tensor, rgbs: Optional[Tensor] = None,
+                  masks: Optional[Tensor] = None) -> None:
+        """Integrate V views in order (after every view integrated before).  depths [V,H,W,1] (or [V,H,W]) fp32, metres along
+        the optical axis; viewmats [V,4,4] world->camera (OpenCV axes, the rasterizer's); Ks [V,3,3]; rgbs [V,H,W,3] in
+        [0,1] (colour uint8(rgb * 255)) or None (black); masks [V,H,W(,1)] bool or None (False: no data)."""
+        if depths.dim() == 4 and depths.shape[-1] == 1:
+            depths = depths.squeeze(-1)
+        if depths.dim() != 3 or depths.shape[0] < 1 or depths.shape[1] < 1 or depths.shape[2] < 1:
+            raise ValueError(f"TSDFVolume.integrate: depths must be [V,H,W,1], got {tuple(depths.shape)}")
+        V, H, W = depths.shape
+        if tuple(viewmats.shape) != (V, 4, 4) or tuple(Ks.shape) != (V, 3, 3):
+            raise ValueError(f"TSDFVolume.integrate: viewmats [V,4,4] and Ks [V,3,3] expected for V={V}, got "
+                             f"{tuple(viewmats.shape)} and {tuple(Ks.shape)}")
+        if rgbs is not None and tuple(rgbs.shape) != (V, H, W, 3):
+            raise ValueError(f"TSDFVolume.integrate: rgbs must be [{V},{H},{W},3], got {tuple(rgbs.shape)}")
+        if masks is not None:
+            if masks.dim() == 4 and masks.shape[-1] == 1:
+                masks = masks.squeeze(-1)
+            if tuple(masks.shape) != (V, H, W):
+                raise ValueError(f"TSDFVolume.integrate: masks must be [{V},{H},{W}(,1)], got {tuple(masks.shape)}")
+        require_gpu(depths, viewmats, Ks, rgbs, masks)
+        if depths.device != self.device and self.device.index is not None:
+            raise MisplatError(f"TSDFVolume on {self.device} got tensors on {depths.device}")
+        if self.device.index is None:
+            self.device = depths.device
+        depths = depths.to(torch.float32).contiguous()
+        viewmats = viewmats.to(torch.float32).contiguous()
+        Ks = Ks.to(torch.float32).contiguous()
+        rgbs = rgbs.to(torch.float32).contiguous() if rgbs is not None else None
+        masks = masks.to(torch.uint8).contiguous() if masks is not None else None
+        if not self._cover(*self._frusta_units(viewmats, Ks, H, W)):
+            self.n_views += V                      # every view lies outside the bounds: nothing to update
+            return
+        lib = load()
+        grid = self._grid()
+        if self._counters is None:
+            self._counters = torch.zeros(2, dtype=torch.int32, device=self.device)
+        for b in range(0, V, MAX_VIEWS):
+            n = min(MAX_VIEWS, V - b)
+            d, vm, k = depths[b:b + n], viewmats[b:b + n], Ks[b:b + n]
+            c = rgbs[b:b + n] if rgbs is not None else None
+            mk = masks[b:b + n] if masks is not None else None
+            self._words.zero_()
+            self._counters[1:].zero_()
+            s = stream_ptr()
+            check(lib.misplat_tsdf_mark(C.byref(grid), ptr(d), ptr(mk), n, H, W, ptr(vm), ptr(k), ptr(self._words), s),
+                  "misplat_tsdf_mark")
+            check(lib.misplat_tsdf_alloc(C.byref(grid), ptr(self._words), ptr(self._slot_map), ptr(self._counters),
+                                         ptr(self._touched), s), "misplat_tsdf_alloc")
+            n_units, n_touched = (int(x) for x in self._counters.tolist())     # the batch's one host read
+            if n_touched == 0:
+                continue
+            self._grow_pool(n_units)
+            self.n_units = n_units
+            check(lib.misplat_tsdf_integrate(C.byref(grid), ptr(self._touched), n_touched, ptr(self._words), ptr(d), ptr(mk),
+                                             ptr(c), n, H, W, ptr(vm), ptr(k), ptr(self._pool), stream_ptr()),
+                  "misplat_tsdf_integrate")
+        self.n_views += V
+
+    def extract_mesh(self) -> Tuple[Tensor, Tensor, Tensor]:
+        """Marching cubes over the allocated voxels: (vertices [M,3] fp32, triangles [T,3] int32, colors [M,3] fp32 in [0,1]),
+        on the device, in the deterministic order of DESIGN.md section 14 (two host reads: nothing else)."""
+        dev = self.device
+        empty = (torch.zeros((0, 3), dtype=torch.float32, device=dev), torch.zeros((0, 3), dtype=torch.int32, device=dev),
+                 torch.zeros((0, 3), dtype=torch.float32, device=dev))
+        if self.n_units == 0:
+            return empty
+        lib = load()
+        grid = self._grid()
+        n = self.n_units
+        nb = (int(np.prod(self.dims)) + 4095) // 4096
+        scratch = torch.empty(2 * nb + 1, dtype=torch.int32, device=dev)
+        order = torch.empty(n, dtype=torch.int32, device=dev)
+        check(lib.misplat_tsdf_order(C.byref(grid), ptr(self._slot_map), ptr(scratch), ptr(order), stream_ptr()),
+              "misplat_tsdf_order")
+        code = torch.empty(n * UNIT_VOXELS, dtype=torch.int16, device=dev)
+        cnt = torch.empty(n * UNIT_VOXELS, dtype=torch.uint8, device=dev)
+        unit_counts = torch.empty(2 * n, dtype=torch.int32, device=dev)
+        unit_offs = torch.empty(2 * n, dtype=torch.int32, device=dev)
+        totals = torch.empty(2, dtype=torch.int32, device=dev)
+        check(lib.misplat_tsdf_mc_count(C.byref(grid), ptr(self._slot_map), ptr(order), n, ptr(self._pool), ptr(code),
+                                        ptr(cnt), ptr(unit_counts), ptr(unit_offs), ptr(totals), stream_ptr()),
+              "misplat_tsdf_mc_count")
+        M, T = (int(x) for x in totals.tolist())
+        if M == 0:
+            return empty
+        vert_base = torch.empty(n * UNIT_VOXELS, dtype=torch.int32, device=dev)
+        vertices = torch.empty((M, 3), dtype=torch.float32, device=dev)
+        colors = torch.empty((M, 3), dtype=torch.float32, device=dev)
+        triangles = torch.empty((T, 3), dtype=torch.int32, device=dev)
+        check(lib.misplat_tsdf_mc_emit(C.byref(grid), ptr(self._slot_map), ptr(order), n, ptr(self._pool), ptr(code), ptr(cnt),
+                                       ptr(unit_offs), ptr(vert_base), ptr(vertices), ptr(colors), ptr(triangles),
+                                       stream_ptr()), "misplat_tsdf_mc_emit")
+        return vertices, triangles, colors
+
+    def units(self):
+        """The allocated units in map order, on the host (for tests and inspection): (coords [n,3] int64, tsdf [n,4096],
+        weight [n,4096], rgb [n,4096,3]); voxel i = lx + 16 ly + 256 lz."""
+        if self.n_units == 0:
+            z = np.zeros((0, UNIT_VOXELS), np.float32)
+            return np.zeros((0, 3), np.int64), z, z, np.zeros((0, UNIT_VOXELS, 3), np.float32)
+        m = torch.nonzero(self._slot_map >= 0).squeeze(1)
+        slots = self._slot_map[m].long()
+        data = self._pool[slots].cpu().numpy()
+        m = m.cpu().numpy()
+        nx, ny = int(self.dims[0]), int(self.dims[1])
+        coords = np.stack([m % nx, (m // nx) % ny, m // (nx * ny)], 1) + self.lo[None, :]
+        return coords, data[:, 0], data[:, 1], np.ascontiguousarray(data[:, 2:5].transpose(0, 2, 1))
+
+
+def write_ply(path: str, vertices, triangles, colors=None) -> None:
+    """Binary little-endian PLY: float x y z, uchar red green blue (round(255 colour)), int32 faces.  No Open3D needed."""
+    v = np.asarray(vertices.detach().cpu() if isinstance(vertices, Tensor) else vertices, np.float32).reshape(-1, 3)
+    f = np.asarray(triangles.detach().cpu() if isinstance(triangles, Tensor) else triangles, np.int32).reshape(-1, 3)
+    if colors is None:
+        c = np.zeros_like(v)
+    else:
+        c = np.asarray(colors.detach().cpu() if isinstance(colors, Tensor) else colors, np.float32).reshape(-1, 3)
+    if c.shape != v.shape:
+        raise ValueError("write_ply: colors must match vertices")
+    vrec = np.empty(len(v), dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("r", "u1"), ("g", "u1"), ("b", "u1")])
+    vrec["x"], vrec["y"], vrec["z"] = v[:, 0], v[:, 1], v[:, 2]
+    cu = np.round(np.clip(c, 0.0, 1.0) * 255.0).astype(np.uint8)
+    vrec["r"], vrec["g"], vrec["b"] = cu[:, 0], cu[:, 1], cu[:, 2]
+    frec = np.empty(len(f), dtype=[("n", "u1"), ("i", "<i4", (3,))])
+    frec["n"] = 3
+    frec["i"] = f
+    header = ("ply\nformat binary_little_endian 1.0\n"
+              f"element vertex {len(v)}\nproperty float x\nproperty float y\nproperty float z\n"
+              "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+              f"element face {len(f)}\nproperty list uchar int vertex_indices\nend_header\n")
+    with open(path, "wb") as fh:
+        fh.write(header.encode("ascii"))
+        fh.write(vrec.tobytes())
+        fh.write(frec.tobytes())
+
+
+def obb_bounds(obb, pad: float = 0.0):
+    """World AABB ``[[min], [max]]`` of an oriented box with nerfstudio ``OrientedBox`` fields ``R`` [3,3], ``T`` [3] and
+    ``S`` [3] (full side lengths), padded by ``pad``; None if the object has no such fields."""
+    if obb is None or not all(hasattr(obb, k) for k in ("R", "T", "S")):
+        return None
+    R = np.asarray(torch.as_tensor(obb.R).detach().double().cpu()).reshape(3, 3)
+    T = np.asarray(torch.as_tensor(obb.T).detach().double().cpu()).reshape(3)
+    S = np.asarray(torch.as_tensor(obb.S).detach().double().cpu()).reshape(3)
+    half = np.abs(R) @ (S / 2.0)
+    return np.stack([T - half - pad, T + half + pad])
+
+
+def camera_frame(camera) -> Tuple[Tensor, Tensor]:
+    """fp32 (viewmat [4,4], K [3,3]) the reference hands to Open3D for one view (mesh.py:1591-1604):
+    ``inv(c2w @ diag(1,-1,-1,1))`` in float64, and the camera's own intrinsics (fx, fy, cx, cy)."""
+    c2w = torch.eye(4, dtype=torch.float64)
+    c2w[:3, :4] = camera.camera_to_worlds.reshape(-1, 3, 4)[0].detach().double().cpu()
+    c2w = c2w @ torch.diag(torch.tensor([1.0, -1.0, -1.0, 1.0], dtype=torch.float64))
+    K = camera.get_intrinsics_matrices().reshape(-1, 3, 3)[0].detach().double().cpu()
+    return torch.linalg.inv(c2w).float(), K.float()
+
+
+__all__ = ["TSDFVolume", "write_ply", "obb_bounds", "camera_frame", "Grid", "MAX_VIEWS", "MAX_UNITS"]

@@ -630,6 +630,50 @@ int misplat_debug_memset_replay(void* counters16, void* add8, int32_t n_replays,
  * per lane + non-temporal stores, 3 the same with one contiguous piece per workgroup. */
 int misplat_stream_copy(const void* src, void* dst, int64_t n_float4, int32_t variant, misplat_stream_t stream);
 
+/* ---- TSDF fusion and marching cubes (csrc/tsdf.hip) ----------------------------------------------
+ * Open3D's legacy ScalableTSDFVolume restated in fp32 (the oracle is tests/tsdf_restatement.py; Open3D itself is unpinned).
+ * Units of 16^3 voxels; voxel g has its centre at (g + 0.5) voxel_size.  A DENSE unit map over the grid (lo, dims: units,
+ * x fastest; at most MISPLAT_TSDF_MAX_UNITS) holds per unit: slot_map (int32 pool slot, -1 unallocated) and words (uint64:
+ * bit j = view j of the batch touches the unit; zeroed by the caller before each batch).  pool: per slot 5 planes of 4096
+ * fp32 (tsdf, w, r, g, b; colours 0..255), voxel i = lx + 16 ly + 256 lz.  depths [V,H,W] fp32 (<= 0 or > depth_trunc: no
+ * data), masks [V,H,W] uint8 or NULL, rgbs [V,H,W,3] fp32 in [0,1] or NULL, viewmats [V,4,4] world->camera (OpenCV),
+ * Ks [V,3,3]; V <= MISPLAT_TSDF_MAX_VIEWS. */
+#define MISPLAT_TSDF_MAX_VIEWS 64
+#define MISPLAT_TSDF_MAX_UNITS (1ll << 26)
+typedef struct misplat_tsdf_grid {
+    float voxel_size, sdf_trunc, depth_trunc;
+    int32_t lo[3];     /* unit coordinate of map entry 0 */
+    int32_t dims[3];   /* units per axis */
+    int32_t reserved;
+} misplat_tsdf_grid;
+/* mark: words |= view bits of every unit a sampled pixel's box touches (sampling stride 4). */
+int misplat_tsdf_mark(const misplat_tsdf_grid* grid, const float* depths, const uint8_t* masks, int32_t n_views,
+                      int32_t height, int32_t width, const float* viewmats, const float* Ks, uint64_t* words,
+                      misplat_stream_t stream);
+/* alloc: a marked unit without a slot takes slot counters[0]++ (the caller grows the pool to counters[0] slots before
+ * integrating); every marked unit is appended to touched ({map index, slot} pairs, capacity = map size) at counters[1]++
+ * (counters[1] zeroed by the caller). */
+int misplat_tsdf_alloc(const misplat_tsdf_grid* grid, const uint64_t* words, int32_t* slot_map, int32_t* counters,
+                       int32_t* touched, misplat_stream_t stream);
+/* integrate: the batch's views, in view order, into the voxels of the n_touched listed units. */
+int misplat_tsdf_integrate(const misplat_tsdf_grid* grid, const int32_t* touched, int32_t n_touched, const uint64_t* words,
+                           const float* depths, const uint8_t* masks, const float* rgbs, int32_t n_views, int32_t height,
+                           int32_t width, const float* viewmats, const float* Ks, float* pool, misplat_stream_t stream);
+/* order: the map indices of the allocated units in ascending map order.  scratch: 2 ceil(map / 4096) + 1 int32. */
+int misplat_tsdf_order(const misplat_tsdf_grid* grid, const int32_t* slot_map, int32_t* scratch, int32_t* order,
+                       misplat_stream_t stream);
+/* mc_count: per voxel of the n_units ordered units, code (uint16: 256 | cube index if the cell is valid) and cnt (uint8: owned
+ * vertex mask | triangles << 3), both indexed slot * 4096 + i; unit_counts / unit_offs [2][n_units] = vertices / triangles
+ * per unit and their exclusive scans; totals[2] = vertex and triangle counts. */
+int misplat_tsdf_mc_count(const misplat_tsdf_grid* grid, const int32_t* slot_map, const int32_t* order, int32_t n_units,
+                          const float* pool, uint16_t* code, uint8_t* cnt, int32_t* unit_counts, int32_t* unit_offs,
+                          int32_t* totals, misplat_stream_t stream);
+/* mc_emit: vertices [M,3], colors [M,3] (0..1), triangles [T,3] int32 in the deterministic order (units in map order, voxels
+ * x-fastest, a voxel's vertices +x, +y, +z, triangles in table order).  vert_base: int32 per voxel (scratch). */
+int misplat_tsdf_mc_emit(const misplat_tsdf_grid* grid, const int32_t* slot_map, const int32_t* order, int32_t n_units,
+                         const float* pool, const uint16_t* code, const uint8_t* cnt, const int32_t* unit_offs,
+                         int32_t* vert_base, float* vertices, float* colors, int32_t* triangles, misplat_stream_t stream);
+
 /* Library identification ("misplat <version> gfx950"). */
 const char* misplat_version(void);
 
