@@ -118,6 +118,8 @@ SYMBOLS = {
     "misplat_debug_memset_replay": (C.c_int, 5),
     "misplat_tsdf_mark": (C.c_int, 10), "misplat_tsdf_alloc": (C.c_int, 6), "misplat_tsdf_integrate": (C.c_int, 14),
     "misplat_tsdf_order": (C.c_int, 5), "misplat_tsdf_mc_count": (C.c_int, 11), "misplat_tsdf_mc_emit": (C.c_int, 13),
+    "misplat_meshmap_workspace": (C.c_int64, 4), "misplat_meshmap_knn": (C.c_int, 12),
+    "misplat_meshmap_aggregate": (C.c_int, 13),
     "misplat_version": (C.c_char_p, 0),
 }
 

@@ -37,6 +37,8 @@ SOURCES = {
     "optim.hip": [],
     # tsdf.hip: fixed IEEE operation order, as project.hip: the voxel grids equal the fp32 restatement (tests/) bit for bit
     "tsdf.hip": ["-ffp-contract=off"],
+    # meshmap.hip: the same: the neighbour lists equal the fp32 restatement (tests/) bit for bit
+    "meshmap.hip": ["-ffp-contract=off"],
 }
 
 

@@ -1,0 +1,620 @@
+// meshmap.hip -- k-nearest-vertex mapping of per-point values onto mesh vertices.
+//
+// Semantics: the Gaussian-weighted kNN map of the reference's features2vertex / normals2vertex, restated in fp32
+// (tests/meshmap_restatement.py is the oracle).  Compiled with -ffp-contract=off: every expression is evaluated in the
+// written order, so the neighbour lists equal the restatement's bit for bit and two runs are bitwise equal.
+//
+// Spatial index: a hash of the OCCUPIED cells of edge h = sdf_trunc (open addressing, capacity a power of two >= 2 M), and
+// the vertices regrouped by cell (count, scan, fill): memory O(M) whatever the extent of the scene.
+// Query: one thread per point; the cells within sdf_trunc first (no vertex there: invalid, done), then rings of cells until
+// the k-th distance is below the distance to the unvisited space; beyond kMaxRings rings, a scan of every vertex.
+// Aggregation: sigma (fp64, fixed order) -> row weights -> a stable LSD radix sort of the contributions by vertex (each list
+// then in (i, j) order) -> per-chunk fp32 sums in list order -> per-vertex sum of the chunks in chunk order.  No float atomics.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "misplat.h"
+#include "internal.h"
+
+namespace {
+
+constexpr int kMaxRings = 6;          // rings beyond the sdf_trunc box before the query falls back to a scan of every vertex
+constexpr int kChunk = 512;           // contributions per partial sum (longer lists are split, cdna guide Appendix B)
+constexpr int kTile = 4096;           // radix sort: items per workgroup (256 threads x 16 rounds)
+constexpr int kScanBlock = 1024;
+constexpr float kCoordCells = 262144.f;   // |v| / h < 2^18 for every vertex (the host checks it)
+constexpr unsigned long long kEmpty = ~0ull;
+
+__device__ __forceinline__ unsigned long long cell_key(int cx, int cy, int cz) {
+    return (unsigned long long)(uint32_t)(cx + (1 << 20)) | ((unsigned long long)(uint32_t)(cy + (1 << 20)) << 21) |
+           ((unsigned long long)(uint32_t)(cz + (1 << 20)) << 42);
+}
+
+__device__ __forceinline__ uint32_t hash_slot(unsigned long long key, uint32_t mask) {
+    key ^= key >> 31;
+    key *= 0x7fb5d329728ea185ull;
+    key ^= key >> 27;
+    return (uint32_t)key & mask;
+}
+
+__device__ __forceinline__ int cell_of(float x, float inv_h) { return (int)floorf(x * inv_h); }
+
+// slot of an occupied cell, -1 if the cell holds no vertex
+__device__ __forceinline__ int find_cell(const unsigned long long* __restrict__ keys, uint32_t mask, unsigned long long key) {
+    uint32_t s = hash_slot(key, mask);
+    while (true) {
+        const unsigned long long k = keys[s];
+        if (k == key) return (int)s;
+        if (k == kEmpty) return -1;
+        s = (s + 1) & mask;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------ scan
+// Exclusive scan of n int32 in three launches: per-block sums, one workgroup over the block sums, per-block scans.
+// out[n] = total.  bsum: 2 ceil(n / 1024) + 1 int32.
+__device__ __forceinline__ int32_t block_scan_excl(int32_t x, int32_t* wsum, int32_t& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int32_t incl = x;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int32_t o = __shfl_up(incl, off);
+        if (lane >= off) incl += o;
+    }
+    __syncthreads();
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    int32_t before = 0;
+    total = 0;
+#pragma unroll
+    for (int w = 0; w < kScanBlock / 64; w++) { before += (w < wave) ? wsum[w] : 0; total += wsum[w]; }
+    return before + incl - x;
+}
+
+__global__ __launch_bounds__(kScanBlock) void scan_reduce_kernel(const int32_t* __restrict__ in, int64_t n,
+                                                                 int32_t* __restrict__ bsum) {
+    __shared__ int32_t wsum[kScanBlock / 64];
+    const int64_t i = (int64_t)blockIdx.x * kScanBlock + threadIdx.x;
+    int32_t total;
+    (void)block_scan_excl(i < n ? in[i] : 0, wsum, total);
+    if (threadIdx.x == 0) bsum[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(kScanBlock) void scan_top_kernel(const int32_t* __restrict__ bsum, int64_t nb,
+                                                              int32_t* __restrict__ boff) {
+    __shared__ int32_t wsum[kScanBlock / 64];
+    int32_t carry = 0;
+    for (int64_t b0 = 0; b0 < nb; b0 += kScanBlock) {
+        const int64_t b = b0 + threadIdx.x;
+        int32_t total;
+        const int32_t ex = block_scan_excl(b < nb ? bsum[b] : 0, wsum, total);
+        if (b < nb) boff[b] = carry + ex;
+        carry += total;
+    }
+    if (threadIdx.x == 0) boff[nb] = carry;
+}
+
+__global__ __launch_bounds__(kScanBlock) void scan_down_kernel(const int32_t* __restrict__ in, int64_t n,
+                                                               const int32_t* __restrict__ boff, int64_t nb,
+                                                               int32_t* __restrict__ out) {
+    __shared__ int32_t wsum[kScanBlock / 64];
+    const int64_t i = (int64_t)blockIdx.x * kScanBlock + threadIdx.x;
+    int32_t total;
+    const int32_t ex = block_scan_excl(i < n ? in[i] : 0, wsum, total);
+    if (i < n) out[i] = boff[blockIdx.x] + ex;
+    if (i == 0) out[n] = boff[nb];
+}
+
+void scan(const int32_t* in, int64_t n, int32_t* out, int32_t* scratch, hipStream_t s) {
+    const int64_t nb = (n + kScanBlock - 1) / kScanBlock;
+    if (nb > 0) hipLaunchKernelGGL(scan_reduce_kernel, dim3((unsigned)nb), dim3(kScanBlock), 0, s, in, n, scratch);
+    hipLaunchKernelGGL(scan_top_kernel, dim3(1), dim3(kScanBlock), 0, s, (const int32_t*)scratch, nb, scratch + nb);
+    hipLaunchKernelGGL(scan_down_kernel, dim3((unsigned)(nb > 0 ? nb : 1)), dim3(kScanBlock), 0, s, in, n,
+                       (const int32_t*)(scratch + nb), nb, out);
+}
+
+// --------------------------------------------------------------------------------------------------------- index
+// Insert every vertex's cell into the hash and count the vertices per slot.  Which slot a cell takes depends on the
+// insertion order; the lookups and every result do not.
+__global__ __launch_bounds__(256) void index_insert_kernel(const float* __restrict__ V, int64_t M, float inv_h,
+                                                           unsigned long long* __restrict__ keys, uint32_t mask,
+                                                           int32_t* __restrict__ vslot, int32_t* __restrict__ counts) {
+    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (v >= M) return;
+    const unsigned long long key = cell_key(cell_of(V[3 * v], inv_h), cell_of(V[3 * v + 1], inv_h), cell_of(V[3 * v + 2], inv_h));
+    uint32_t s = hash_slot(key, mask);
+    while (true) {
+        const unsigned long long prev = atomicCAS(&keys[s], kEmpty, key);
+        if (prev == kEmpty || prev == key) break;
+        s = (s + 1) & mask;
+    }
+    vslot[v] = (int32_t)s;
+    atomicAdd(&counts[s], 1);
+}
+
+// vertices regrouped by cell: cellpts[starts[s] ..) = (x, y, z, index bits); counts are consumed as cursors.  The order
+// inside a cell is arbitrary: the neighbour order (distance, index) does not depend on it.
+__global__ __launch_bounds__(256) void index_fill_kernel(const float* __restrict__ V, int64_t M, const int32_t* __restrict__ vslot,
+                                                         const int32_t* __restrict__ starts, int32_t* __restrict__ cursor,
+                                                         float4* __restrict__ cellpts) {
+    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (v >= M) return;
+    const int s = vslot[v];
+    const int pos = starts[s] + atomicSub(&cursor[s], 1) - 1;
+    cellpts[pos] = make_float4(V[3 * v], V[3 * v + 1], V[3 * v + 2], __int_as_float((int)v));
+}
+
+// ----------------------------------------------------------------------------------------------------------- query
+// k best of (d2 bits, vertex index) as one 64-bit key, ascending in best[KC - k .. KC - 1]; the KC - k slots in front hold 0
+// and never move (a real key is never below them).  Unset slots hold kEmpty.
+template <int KC>
+struct Best {
+    unsigned long long b[KC];
+    __device__ __forceinline__ void reset(int k) {
+#pragma unroll
+        for (int j = 0; j < KC; j++) b[j] = (j >= KC - k) ? kEmpty : 0ull;
+    }
+    __device__ __forceinline__ unsigned long long nearest(int k) const {      // b[KC - k] without a dynamic register index
+        unsigned long long r = 0ull;
+#pragma unroll
+        for (int j = 0; j < KC; j++) r = (j == KC - k) ? b[j] : r;
+        return r;
+    }
+    __device__ __forceinline__ void offer(unsigned long long key) {
+        if (key >= b[KC - 1]) return;
+#pragma unroll
+        for (int j = KC - 1; j > 0; j--) b[j] = (b[j - 1] > key) ? b[j - 1] : (b[j] > key ? key : b[j]);
+        b[0] = b[0] > key ? key : b[0];
+    }
+};
+
+__device__ __forceinline__ unsigned long long cand_key(float px, float py, float pz, float4 q) {
+    const float dx = px - q.x, dy = py - q.y, dz = pz - q.z;
+    const float d2 = (dx * dx + dy * dy) + dz * dz;
+    return ((unsigned long long)__float_as_uint(d2) << 32) | (uint32_t)__float_as_int(q.w);
+}
+
+struct Index {
+    const unsigned long long* keys;
+    const int32_t* starts;
+    const float4* pts;
+    uint32_t mask;
+};
+
+template <int KC>
+__device__ __forceinline__ void visit(const Index& ix, int cx, int cy, int cz, float px, float py, float pz, Best<KC>& best) {
+    const int s = find_cell(ix.keys, ix.mask, cell_key(cx, cy, cz));
+    if (s < 0) return;
+    const int e1 = ix.starts[s + 1];
+    for (int e = ix.starts[s]; e < e1; e++) best.offer(cand_key(px, py, pz, ix.pts[e]));
+}
+
+// cells of the box lo..hi that are not in the box lo + 1 .. hi - 1 (all of them if `all`)
+template <int KC>
+__device__ __forceinline__ void visit_box(const Index& ix, const int (&lo)[3], const int (&hi)[3], bool all, float px, float py,
+                                          float pz, Best<KC>& best) {
+    for (int cz = lo[2]; cz <= hi[2]; cz++)
+        for (int cy = lo[1]; cy <= hi[1]; cy++) {
+            const bool inner = !all && cz > lo[2] && cz < hi[2] && cy > lo[1] && cy < hi[1];
+            const int step = (inner && hi[0] > lo[0]) ? hi[0] - lo[0] : 1;
+            for (int cx = lo[0]; cx <= hi[0]; cx += step) visit<KC>(ix, cx, cy, cz, px, py, pz, best);
+        }
+}
+
+template <int KC>
+__global__ __launch_bounds__(256) void knn_kernel(Index ix, int64_t M, const float* __restrict__ P, int64_t N, int k, float trunc,
+                                                  float h, float inv_h, int32_t* __restrict__ idx, float* __restrict__ dist,
+                                                  uint8_t* __restrict__ valid) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    const float px = P[3 * i], py = P[3 * i + 1], pz = P[3 * i + 2];
+    const float amax = fmaxf(fmaxf(fabsf(px), fabsf(py)), fabsf(pz));
+    // Every vertex has |v| < 2^18 h: a point further out than 2^18 h + 2 h (or not finite) has none within h >= trunc.
+    bool ok = amax * inv_h < kCoordCells + 2.f;
+    Best<KC> best;
+    best.reset(k);
+    int lo[3], hi[3];
+    // rounding of the cell assignment, of the distances and of the box faces: the box and the stop test are widened by this
+    const float margin = 1e-5f * (amax + h * (float)(kMaxRings + 4));
+    if (ok) {
+        const float p[3] = {px, py, pz};
+        const float tt = trunc + margin;
+#pragma unroll
+        for (int a = 0; a < 3; a++) { lo[a] = cell_of(p[a] - tt, inv_h); hi[a] = cell_of(p[a] + tt, inv_h); }
+        visit_box<KC>(ix, lo, hi, true, px, py, pz, best);
+        const unsigned long long b0 = best.nearest(k);
+        ok = b0 != kEmpty && sqrtf(__uint_as_float((uint32_t)(b0 >> 32))) <= trunc;
+    }
+    if (!ok) {
+        valid[i] = 0;
+        for (int j = 0; j < k; j++) {
+            idx[i * k + j] = -1;
+            dist[i * k + j] = __int_as_float(0x7f800000);
+        }
+        return;
+    }
+    const float p[3] = {px, py, pz};
+    for (int r = 0;; r++) {
+        float gap = 3.4e38f;
+#pragma unroll
+        for (int a = 0; a < 3; a++) gap = fminf(gap, fminf(p[a] - (float)lo[a] * h, (float)(hi[a] + 1) * h - p[a]));
+        const unsigned long long kth = best.b[KC - 1];
+        if (kth != kEmpty && sqrtf(__uint_as_float((uint32_t)(kth >> 32))) < gap - margin) break;
+        if (r == kMaxRings) {                               // far-flung neighbours: every vertex, once
+            best.reset(k);
+            for (int64_t e = 0; e < M; e++) best.offer(cand_key(px, py, pz, ix.pts[e]));
+            break;
+        }
+#pragma unroll
+        for (int a = 0; a < 3; a++) { lo[a] -= 1; hi[a] += 1; }
+        visit_box<KC>(ix, lo, hi, false, px, py, pz, best);
+    }
+    valid[i] = 1;
+#pragma unroll
+    for (int j = 0; j < KC; j++) {
+        if (j < KC - k) continue;
+        idx[i * k + (j - (KC - k))] = (int32_t)(uint32_t)best.b[j];
+        dist[i * k + (j - (KC - k))] = sqrtf(__uint_as_float((uint32_t)(best.b[j] >> 32)));
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------- sigma
+// stats[0] = sum of the distances of the valid rows (fp64), stats[1] = number of valid rows.  Rows are summed in j order,
+// 256 rows per workgroup in a fixed tree, the workgroup sums in index order by one workgroup: the result does not depend on
+// scheduling.
+__device__ __forceinline__ double wave_sum(double x) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off);
+    return x;
+}
+
+__global__ __launch_bounds__(256) void sigma_partial_kernel(const float* __restrict__ dist, const uint8_t* __restrict__ valid,
+                                                            int64_t N, int k, double* __restrict__ part) {
+    __shared__ double ws[2][4];
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    double s = 0.0, c = 0.0;
+    if (i < N && valid[i]) {
+        for (int j = 0; j < k; j++) s += (double)dist[i * k + j];
+        c = 1.0;
+    }
+    s = wave_sum(s);
+    c = wave_sum(c);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) { ws[0][wave] = s; ws[1][wave] = c; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        part[2 * blockIdx.x] = ((ws[0][0] + ws[0][1]) + ws[0][2]) + ws[0][3];
+        part[2 * blockIdx.x + 1] = ((ws[1][0] + ws[1][1]) + ws[1][2]) + ws[1][3];
+    }
+}
+
+__global__ __launch_bounds__(256) void sigma_final_kernel(const double* __restrict__ part, int64_t nb, double* __restrict__ stats) {
+    __shared__ double ws[2][4];
+    double s = 0.0, c = 0.0;
+    for (int64_t b = threadIdx.x; b < nb; b += 256) { s += part[2 * b]; c += part[2 * b + 1]; }
+    s = wave_sum(s);
+    c = wave_sum(c);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) { ws[0][wave] = s; ws[1][wave] = c; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        stats[0] = ((ws[0][0] + ws[0][1]) + ws[0][2]) + ws[0][3];
+        stats[1] = ((ws[1][0] + ws[1][1]) + ws[1][2]) + ws[1][3];
+    }
+}
+
+// --------------------------------------------------------------------------------------------------------- weights
+// One thread per row.  w[i, j] = e_j / sum_j e_j with e_j = exp(-(d2_j - d2_0) / (2 sigma^2)) (e_0 = 1: never 0 / 0);
+// sigma = 0: 1 / k.  Sort keys: the vertex of each valid contribution, M (after every vertex) for an invalid row; values:
+// the contribution id i k + j.
+__device__ __forceinline__ float row_exp(float dj, float d02, float c, bool flat) {
+    const float delta = dj * dj - d02;
+    return (flat || !(delta > 0.f)) ? 1.f : expf(-(delta * c));
+}
+
+__global__ __launch_bounds__(256) void weights_kernel(const int32_t* __restrict__ idx, const float* __restrict__ dist,
+                                                      const uint8_t* __restrict__ valid, int64_t N, int k, int32_t M,
+                                                      const double* __restrict__ stats, float* __restrict__ w,
+                                                      int32_t* __restrict__ keys, int32_t* __restrict__ vals) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    const int64_t base = i * k;
+    for (int j = 0; j < k; j++) vals[base + j] = (int32_t)(base + j);
+    if (!valid[i]) {
+        for (int j = 0; j < k; j++) keys[base + j] = M;
+        return;
+    }
+    const double n_valid = stats[1];
+    const double sigma = stats[0] / (n_valid * (double)k);
+    const bool flat = !(sigma > 0.0);
+    const float c = flat ? 0.f : (float)(1.0 / (2.0 * sigma * sigma));
+    const float d0 = dist[base];
+    const float d02 = d0 * d0;
+    float sum = 0.f;
+    for (int j = 0; j < k; j++) sum += row_exp(dist[base + j], d02, c, flat);
+    for (int j = 0; j < k; j++) {
+        w[base + j] = row_exp(dist[base + j], d02, c, flat) / sum;
+        keys[base + j] = idx[base + j];
+    }
+}
+
+// ----------------------------------------------------------------------------------------------------- radix sort
+// Stable LSD radix sort of (key, value) by key, 8 bits per pass: per-workgroup digit histograms (digit-major, so one scan
+// gives every workgroup's stable offsets), then a scatter that ranks each round of 256 items in item order (ballots inside a
+// wave, per-wave counts across the workgroup).  The values enter in contribution order, so every vertex's list leaves in
+// (i, j) order.
+__global__ __launch_bounds__(256) void radix_hist_kernel(const int32_t* __restrict__ keys, int64_t E, int shift, int64_t nblk,
+                                                         int32_t* __restrict__ hist) {
+    __shared__ int32_t h[256];
+    h[threadIdx.x] = 0;
+    __syncthreads();
+    const int64_t e0 = (int64_t)blockIdx.x * kTile;
+    for (int r = 0; r < kTile / 256; r++) {
+        const int64_t e = e0 + r * 256 + threadIdx.x;
+        if (e < E) atomicAdd(&h[(keys[e] >> shift) & 255], 1);
+    }
+    __syncthreads();
+    hist[(int64_t)threadIdx.x * nblk + blockIdx.x] = h[threadIdx.x];
+}
+
+__global__ __launch_bounds__(256) void radix_scatter_kernel(const int32_t* __restrict__ keys, const int32_t* __restrict__ vals,
+                                                            int64_t E, int shift, int64_t nblk, const int32_t* __restrict__ hoff,
+                                                            int32_t* __restrict__ keys_out, int32_t* __restrict__ vals_out) {
+    __shared__ int32_t run[256];
+    __shared__ int32_t wcnt[4][256];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    run[threadIdx.x] = hoff[(int64_t)threadIdx.x * nblk + blockIdx.x];
+    const int64_t e0 = (int64_t)blockIdx.x * kTile;
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    for (int r = 0; r < kTile / 256; r++) {
+#pragma unroll
+        for (int w = 0; w < 4; w++) wcnt[w][threadIdx.x] = 0;
+        __syncthreads();
+        const int64_t e = e0 + r * 256 + threadIdx.x;
+        const bool act = e < E;
+        int32_t key = 0, val = 0;
+        int digit = 0;
+        if (act) { key = keys[e]; val = vals[e]; digit = (key >> shift) & 255; }
+        unsigned long long same = __ballot(act);
+#pragma unroll
+        for (int b = 0; b < 8; b++) {
+            const unsigned long long set = __ballot(act && ((digit >> b) & 1));
+            same &= ((digit >> b) & 1) ? set : ~set;
+        }
+        const int rank = __popcll(same & lt);
+        if (act && (same >> lane) == 1ull) wcnt[wave][digit] = __popcll(same);      // the group's highest lane
+        __syncthreads();
+        if (act) {
+            int before = run[digit] + rank;
+            for (int w = 0; w < wave; w++) before += wcnt[w][digit];
+            keys_out[before] = key;
+            vals_out[before] = val;
+        }
+        __syncthreads();
+        run[threadIdx.x] += ((wcnt[0][threadIdx.x] + wcnt[1][threadIdx.x]) + wcnt[2][threadIdx.x]) + wcnt[3][threadIdx.x];
+        __syncthreads();
+    }
+}
+
+// offs[v] = first sorted position whose key is >= v (a binary search), v = 0 .. M (offs[M]: number of valid contributions)
+__global__ __launch_bounds__(256) void list_offsets_kernel(const int32_t* __restrict__ skeys, int64_t E, int32_t M,
+                                                           int32_t* __restrict__ offs) {
+    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (v > M) return;
+    int64_t a = 0, b = E;
+    while (a < b) {
+        const int64_t m = (a + b) >> 1;
+        if (skeys[m] < v) a = m + 1;
+        else b = m;
+    }
+    offs[v] = (int32_t)a;
+}
+
+__global__ __launch_bounds__(256) void chunk_count_kernel(const int32_t* __restrict__ offs, int32_t M, int32_t* __restrict__ nch) {
+    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (v >= M) return;
+    nch[v] = (offs[v + 1] - offs[v] + kChunk - 1) / kChunk;
+}
+
+__global__ __launch_bounds__(256) void chunk_owner_kernel(const int32_t* __restrict__ choff, int32_t M, int32_t* __restrict__ owner) {
+    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (v >= M) return;
+    for (int32_t q = choff[v]; q < choff[v + 1]; q++) owner[q] = (int32_t)v;
+}
+
+// ------------------------------------------------------------------------------------------------------------- sums
+// One thread per (chunk, channel); channel D is the weight sum.  fp32, in list order.
+__global__ __launch_bounds__(256) void chunk_sum_kernel(const int32_t* __restrict__ owner, const int32_t* __restrict__ choff,
+                                                        const int32_t* __restrict__ offs, int32_t M,
+                                                        const int32_t* __restrict__ svals, const float* __restrict__ w,
+                                                        const float* __restrict__ F, int D, int k, int64_t q_cap,
+                                                        float* __restrict__ part) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t q = t / (D + 1);
+    const int c = (int)(t - q * (D + 1));
+    if (q >= q_cap || q >= choff[M]) return;
+    const int32_t v = owner[q];
+    const int32_t e0 = offs[v] + (int32_t)(q - choff[v]) * kChunk;
+    const int32_t e1 = min(e0 + kChunk, offs[v + 1]);
+    float acc = 0.f;
+    if (c < D) {
+        for (int32_t e = e0; e < e1; e++) {
+            const int32_t id = svals[e];
+            acc += w[id] * F[(int64_t)(id / k) * D + c];
+        }
+    } else {
+        for (int32_t e = e0; e < e1; e++) acc += w[svals[e]];
+    }
+    part[q * (D + 1) + c] = acc;
+}
+
+// One thread per vertex: the chunk sums in chunk order, divided by the weight sum (0 without a contribution); channels
+// 0 .. n_unit - 1 then divided by (their norm + 1e-8).
+__global__ __launch_bounds__(256) void vertex_sum_kernel(const int32_t* __restrict__ choff, int32_t M, const float* __restrict__ part,
+                                                         int D, int n_unit, float* __restrict__ out) {
+    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (v >= M) return;
+    const int32_t q0 = choff[v], q1 = choff[v + 1];
+    float den = 0.f;
+    for (int32_t q = q0; q < q1; q++) den += part[(int64_t)q * (D + 1) + D];
+    float* o = out + v * D;
+    for (int c = 0; c < D; c++) {
+        float num = 0.f;
+        for (int32_t q = q0; q < q1; q++) num += part[(int64_t)q * (D + 1) + c];
+        o[c] = den > 0.f ? num / den : 0.f;
+    }
+    if (n_unit == 3) {
+        const float x = o[0], y = o[1], z = o[2];
+        const float nrm = sqrtf((x * x + y * y) + z * z) + 1e-8f;
+        o[0] = x / nrm; o[1] = y / nrm; o[2] = z / nrm;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------- workspace
+inline int64_t al(int64_t b) { return (b + 255) & ~(int64_t)255; }
+
+struct Layout {
+    int64_t cap, nblk, E, q_cap, scan_n;
+    int64_t o_keys, o_counts, o_starts, o_vslot, o_pts, o_scan, o_sig, o_w, o_ka, o_va, o_kb, o_vb, o_hist, o_hoff, o_offs,
+        o_nch, o_choff, o_owner, o_part, total;
+};
+
+inline Layout layout(int64_t M, int64_t N, int k, int D) {
+    Layout L;
+    L.cap = 64;
+    while (L.cap < 2 * M) L.cap <<= 1;
+    L.E = N * k;
+    L.nblk = (L.E + kTile - 1) / kTile;
+    L.q_cap = M + L.E / kChunk + 1;
+    L.scan_n = L.cap;
+    if (256 * L.nblk > L.scan_n) L.scan_n = 256 * L.nblk;
+    if (M + 1 > L.scan_n) L.scan_n = M + 1;
+    int64_t o = 0;
+    L.o_keys = o;   o += al(8 * L.cap);
+    L.o_counts = o; o += al(4 * L.cap);
+    L.o_starts = o; o += al(4 * (L.cap + 1));
+    L.o_vslot = o;  o += al(4 * M);
+    L.o_pts = o;    o += al(16 * M);
+    L.o_scan = o;   o += al(4 * (2 * ((L.scan_n + kScanBlock - 1) / kScanBlock) + 2));
+    L.o_sig = o;    o += al(8 * (2 * ((N + 255) / 256) + 2));
+    L.o_w = o;      o += al(4 * L.E);
+    L.o_ka = o;     o += al(4 * L.E);
+    L.o_va = o;     o += al(4 * L.E);
+    L.o_kb = o;     o += al(4 * L.E);
+    L.o_vb = o;     o += al(4 * L.E);
+    L.o_hist = o;   o += al(4 * 256 * L.nblk);
+    L.o_hoff = o;   o += al(4 * (256 * L.nblk + 1));
+    L.o_offs = o;   o += al(4 * (M + 1));
+    L.o_nch = o;    o += al(4 * M);
+    L.o_choff = o;  o += al(4 * (M + 1));
+    L.o_owner = o;  o += al(4 * L.q_cap);
+    L.o_part = o;   o += al(4 * L.q_cap * (D + 1));
+    L.total = o;
+    return L;
+}
+
+inline bool sizes_ok(int64_t M, int64_t N, int k, int D) {
+    return M >= k && M < (1ll << 30) && N >= 0 && k >= 1 && k <= 16 && N * k < (1ll << 31) - kTile && D >= 0 && D <= 4096;
+}
+
+inline int launched() { return hipGetLastError() == hipSuccess ? MISPLAT_OK : MISPLAT_ELAUNCH; }
+
+inline unsigned blocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
+
+template <int KC>
+void launch_knn(const Index& ix, int64_t M, const float* P, int64_t N, int k, float trunc, float h, float inv_h, int32_t* idx,
+                float* dist, uint8_t* valid, hipStream_t s) {
+    hipLaunchKernelGGL(knn_kernel<KC>, dim3(blocks(N, 256)), dim3(256), 0, s, ix, M, P, N, k, trunc, h, inv_h, idx, dist, valid);
+}
+
+}  // namespace
+
+extern "C" int64_t misplat_meshmap_workspace(int64_t n_vertices, int64_t n_points, int32_t k, int32_t n_channels) {
+    if (!sizes_ok(n_vertices, n_points, k, n_channels)) return -1;
+    return layout(n_vertices, n_points, k, n_channels).total;
+}
+
+extern "C" int misplat_meshmap_knn(const float* vertices, int64_t n_vertices, const float* points, int64_t n_points, int32_t k,
+                                   float sdf_trunc, void* workspace, int64_t workspace_bytes, int32_t* idx, float* dist,
+                                   uint8_t* valid, misplat_stream_t stream) {
+    const int64_t M = n_vertices, N = n_points;
+    if (!sizes_ok(M, N, k, 0) || !(sdf_trunc > 0.f) || !(sdf_trunc < 3.0e37f) || !vertices || !workspace ||
+        (N > 0 && (!points || !idx || !dist || !valid)))
+        return MISPLAT_EINVAL;
+    const Layout L = layout(M, N, k, 0);
+    if (workspace_bytes < L.o_w) return MISPLAT_EWORKSPACE;
+    if (N == 0) return MISPLAT_OK;
+    char* ws = (char*)workspace;
+    hipStream_t s = (hipStream_t)stream;
+    unsigned long long* keys = (unsigned long long*)(ws + L.o_keys);
+    int32_t* counts = (int32_t*)(ws + L.o_counts);
+    int32_t* starts = (int32_t*)(ws + L.o_starts);
+    int32_t* vslot = (int32_t*)(ws + L.o_vslot);
+    float4* pts = (float4*)(ws + L.o_pts);
+    int32_t* scr = (int32_t*)(ws + L.o_scan);
+    const float h = sdf_trunc, inv_h = 1.f / sdf_trunc;
+    misplat_internal::fill_bytes(keys, 8 * L.cap, 0xffffffffu, s);          // (kernels, not memsets: internal.h)
+    misplat_internal::fill_bytes(counts, 4 * L.cap, 0u, s);
+    hipLaunchKernelGGL(index_insert_kernel, dim3(blocks(M, 256)), dim3(256), 0, s, vertices, M, inv_h, keys,
+                       (uint32_t)(L.cap - 1), vslot, counts);
+    scan(counts, L.cap, starts, scr, s);
+    hipLaunchKernelGGL(index_fill_kernel, dim3(blocks(M, 256)), dim3(256), 0, s, vertices, M, (const int32_t*)vslot,
+                       (const int32_t*)starts, counts, pts);
+    const Index ix{keys, starts, pts, (uint32_t)(L.cap - 1)};
+    if (k <= 4) launch_knn<4>(ix, M, points, N, k, sdf_trunc, h, inv_h, idx, dist, valid, s);
+    else if (k <= 8) launch_knn<8>(ix, M, points, N, k, sdf_trunc, h, inv_h, idx, dist, valid, s);
+    else launch_knn<16>(ix, M, points, N, k, sdf_trunc, h, inv_h, idx, dist, valid, s);
+    return launched();
+}
+
+extern "C" int misplat_meshmap_aggregate(int64_t n_vertices, int64_t n_points, int32_t k, const int32_t* idx, const float* dist,
+                                         const uint8_t* valid, const float* values, int32_t n_channels, int32_t n_unit,
+                                         void* workspace, int64_t workspace_bytes, float* out, misplat_stream_t stream) {
+    const int64_t M = n_vertices, N = n_points;
+    const int D = n_channels;
+    if (!sizes_ok(M, N, k, D) || D < 1 || !(n_unit == 0 || (n_unit == 3 && D >= 3)) || !workspace || !out ||
+        (N > 0 && (!idx || !dist || !valid || !values)))
+        return MISPLAT_EINVAL;
+    const Layout L = layout(M, N, k, D);
+    if (workspace_bytes < L.total) return MISPLAT_EWORKSPACE;
+    char* ws = (char*)workspace;
+    hipStream_t s = (hipStream_t)stream;
+    if (N == 0) {
+        misplat_internal::fill_bytes(out, 4 * M * D, 0u, s);
+        return launched();
+    }
+    int32_t* scr = (int32_t*)(ws + L.o_scan);
+    double* sig = (double*)(ws + L.o_sig);
+    float* w = (float*)(ws + L.o_w);
+    int32_t *ka = (int32_t*)(ws + L.o_ka), *va = (int32_t*)(ws + L.o_va), *kb = (int32_t*)(ws + L.o_kb), *vb = (int32_t*)(ws + L.o_vb);
+    int32_t* hist = (int32_t*)(ws + L.o_hist);
+    int32_t* hoff = (int32_t*)(ws + L.o_hoff);
+    int32_t* offs = (int32_t*)(ws + L.o_offs);
+    int32_t* nch = (int32_t*)(ws + L.o_nch);
+    int32_t* choff = (int32_t*)(ws + L.o_choff);
+    int32_t* owner = (int32_t*)(ws + L.o_owner);
+    float* part = (float*)(ws + L.o_part);
+    const int64_t nb_sig = (N + 255) / 256;
+    hipLaunchKernelGGL(sigma_partial_kernel, dim3((unsigned)nb_sig), dim3(256), 0, s, dist, valid, N, (int)k, sig + 2);
+    hipLaunchKernelGGL(sigma_final_kernel, dim3(1), dim3(256), 0, s, (const double*)(sig + 2), nb_sig, sig);
+    hipLaunchKernelGGL(weights_kernel, dim3(blocks(N, 256)), dim3(256), 0, s, idx, dist, valid, N, (int)k, (int32_t)M,
+                       (const double*)sig, w, ka, va);
+    const int64_t E = L.E;
+    for (int shift = 0; shift == 0 || (M >> shift) > 0; shift += 8) {
+        hipLaunchKernelGGL(radix_hist_kernel, dim3((unsigned)L.nblk), dim3(256), 0, s, (const int32_t*)ka, E, shift, L.nblk, hist);
+        scan(hist, 256 * L.nblk, hoff, scr, s);
+        hipLaunchKernelGGL(radix_scatter_kernel, dim3((unsigned)L.nblk), dim3(256), 0, s, (const int32_t*)ka, (const int32_t*)va, E,
+                           shift, L.nblk, (const int32_t*)hoff, kb, vb);
+        int32_t* t = ka; ka = kb; kb = t;
+        t = va; va = vb; vb = t;
+    }
+    hipLaunchKernelGGL(list_offsets_kernel, dim3(blocks(M + 1, 256)), dim3(256), 0, s, (const int32_t*)ka, E, (int32_t)M, offs);
+    hipLaunchKernelGGL(chunk_count_kernel, dim3(blocks(M, 256)), dim3(256), 0, s, (const int32_t*)offs, (int32_t)M, nch);
+    scan(nch, M, choff, scr, s);
+    hipLaunchKernelGGL(chunk_owner_kernel, dim3(blocks(M, 256)), dim3(256), 0, s, (const int32_t*)choff, (int32_t)M, owner);
+    hipLaunchKernelGGL(chunk_sum_kernel, dim3(blocks(L.q_cap * (D + 1), 256)), dim3(256), 0, s, (const int32_t*)owner,
+                       (const int32_t*)choff, (const int32_t*)offs, (int32_t)M, (const int32_t*)va, (const float*)w, values, D,
+                       (int)k, L.q_cap, part);
+    hipLaunchKernelGGL(vertex_sum_kernel, dim3(blocks(M, 256)), dim3(256), 0, s, (const int32_t*)choff, (int32_t)M,
+                       (const float*)part, D, (int)n_unit, out);
+    return launched();
+}

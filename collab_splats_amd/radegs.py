@@ -538,6 +538,27 @@ class RadegsModel(nn.Module):
             del maps
         return vol.extract_mesh()
 
+    @torch.no_grad()
+    def mesh_attributes(self, vertices: Tensor, k: int = 5, sdf_trunc: float = 0.03) -> Dict[str, Tensor]:
+        """What the reference's ``Open3DTSDFFusion.main`` maps onto the extracted mesh (mesh.py:1661-1702), on the device:
+        ``{"normals": [M,3]}`` (``normals2vertex`` of ``self.normals``) and, for a model with ``distill_features``, also
+        ``"distill_features": [M, latent]`` (``features2vertex``).  The points are all the means, uncropped.  One kNN serves
+        both maps: ``[normals | features]`` is mapped in one call, its first 3 channels then normalised; every channel
+        equals the separate call bit for bit."""
+        from .meshmap import map_to_vertices
+        # self.normals picks the rotation column with a one-hot bmm (a 13 ms batched GEMM at 1 M Gaussians); a gather of the
+        # same column gives the same bits (the products by 0 and 1 and the sums with 0 are exact)
+        rots = build_rotation(self.quats)
+        col = torch.argmin(torch.exp(self.scales), dim=-1)
+        normals = F.normalize(rots.gather(2, col[:, None, None].expand(-1, 3, 1)).squeeze(-1), dim=1)
+        feats = getattr(self, "distill_features", None)
+        vals = normals if feats is None else torch.cat([normals, feats.detach().float()], 1)
+        out = map_to_vertices(vertices, self.means.detach(), vals, k=k, sdf_trunc=sdf_trunc, n_unit=3)
+        res = {"normals": out[:, :3].contiguous()}
+        if feats is not None:
+            res["distill_features"] = out[:, 3:].contiguous()
+        return res
+
     def _scale_reg(self, dev) -> Tensor:
         """Splatfacto's scale regularisation: 0.1 * mean(max(max(s) / min(s), max_gauss_ratio) - max_gauss_ratio) of the
         activated scales, every 10th step; 0 otherwise [UNVERIFIED-UPSTREAM]."""

@@ -240,18 +240,30 @@ class TSDFVolume:
         return coords, data[:, 0], data[:, 1], np.ascontiguousarray(data[:, 2:5].transpose(0, 2, 1))
 
 
-def write_ply(path: str, vertices, triangles, colors=None) -> None:
-    """Binary little-endian PLY: float x y z, uchar red green blue (round(255 colour)), int32 faces.  No Open3D needed."""
-    v = np.asarray(vertices.detach().cpu() if isinstance(vertices, Tensor) else vertices, np.float32).reshape(-1, 3)
+def write_ply(path: str, vertices, triangles, colors=None, normals=None) -> None:
+    """Binary little-endian PLY: float x y z, float nx ny nz (only if ``normals`` are given), uchar red green blue
+    (round(255 colour)), int32 faces.  No Open3D needed."""
+    def host(x):
+        return np.asarray(x.detach().cpu() if isinstance(x, Tensor) else x, np.float32)
+
+    v = host(vertices).reshape(-1, 3)
     f = np.asarray(triangles.detach().cpu() if isinstance(triangles, Tensor) else triangles, np.int32).reshape(-1, 3)
     if colors is None:
         c = np.zeros_like(v)
     else:
-        c = np.asarray(colors.detach().cpu() if isinstance(colors, Tensor) else colors, np.float32).reshape(-1, 3)
+        c = host(colors).reshape(-1, 3)
     if c.shape != v.shape:
         raise ValueError("write_ply: colors must match vertices")
-    vrec = np.empty(len(v), dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("r", "u1"), ("g", "u1"), ("b", "u1")])
+    n = None if normals is None else host(normals).reshape(-1, 3)
+    if n is not None and n.shape != v.shape:
+        raise ValueError("write_ply: normals must match vertices")
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if n is not None:
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+    vrec = np.empty(len(v), dtype=fields + [("r", "u1"), ("g", "u1"), ("b", "u1")])
     vrec["x"], vrec["y"], vrec["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if n is not None:
+        vrec["nx"], vrec["ny"], vrec["nz"] = n[:, 0], n[:, 1], n[:, 2]
     cu = np.round(np.clip(c, 0.0, 1.0) * 255.0).astype(np.uint8)
     vrec["r"], vrec["g"], vrec["b"] = cu[:, 0], cu[:, 1], cu[:, 2]
     frec = np.empty(len(f), dtype=[("n", "u1"), ("i", "<i4", (3,))])
@@ -259,7 +271,8 @@ def write_ply(path: str, vertices, triangles, colors=None) -> None:
     frec["i"] = f
     header = ("ply\nformat binary_little_endian 1.0\n"
               f"element vertex {len(v)}\nproperty float x\nproperty float y\nproperty float z\n"
-              "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+              + ("property float nx\nproperty float ny\nproperty float nz\n" if n is not None else "")
+              + "property uchar red\nproperty uchar green\nproperty uchar blue\n"
               f"element face {len(f)}\nproperty list uchar int vertex_indices\nend_header\n")
     with open(path, "wb") as fh:
         fh.write(header.encode("ascii"))

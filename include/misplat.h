@@ -674,6 +674,25 @@ int misplat_tsdf_mc_emit(const misplat_tsdf_grid* grid, const int32_t* slot_map,
                          const float* pool, const uint16_t* code, const uint8_t* cnt, const int32_t* unit_offs,
                          int32_t* vert_base, float* vertices, float* colors, int32_t* triangles, misplat_stream_t stream);
 
+/* ---- kNN mapping of per-point values onto mesh vertices (csrc/meshmap.hip) ---------------------
+ * The reference's features2vertex / normals2vertex restated in fp32 (the oracle is tests/meshmap_restatement.py).
+ * vertices [M,3], points [N,3], values [N,D] fp32; 1 <= k <= 16, k <= M; every vertex finite with |x| / sdf_trunc
+ * < 2^18 per axis (the caller checks it).  Neighbours are ordered by (d2, vertex index), d2 = ((dx dx + dy dy) + dz dz) in
+ * fp32, d = sqrtf(d2); a point is valid iff d[0] <= sdf_trunc.  One workspace (bytes from misplat_meshmap_workspace for the
+ * largest D the caller will aggregate) serves both calls; nothing in it must survive between them. */
+/* workspace bytes for (M, N, k, D); -1 for sizes the library refuses. */
+int64_t misplat_meshmap_workspace(int64_t n_vertices, int64_t n_points, int32_t k, int32_t n_channels);
+/* knn: idx [N,k] int32 and dist [N,k] fp32 in ascending order, valid [N] uint8; an invalid row holds idx -1, dist +inf. */
+int misplat_meshmap_knn(const float* vertices, int64_t n_vertices, const float* points, int64_t n_points, int32_t k,
+                        float sdf_trunc, void* workspace, int64_t workspace_bytes, int32_t* idx, float* dist,
+                        uint8_t* valid, misplat_stream_t stream);
+/* aggregate: out [M,D] = sum w F / sum w over the valid (i, j) with idx = v, weights of DESIGN.md section 15, fp32 sums in
+ * ascending (i, j) order (deterministic, no float atomics); 0 without a contribution.  n_unit 3: channels 0..2 are then
+ * divided by (their norm + 1e-8); 0: none. */
+int misplat_meshmap_aggregate(int64_t n_vertices, int64_t n_points, int32_t k, const int32_t* idx, const float* dist,
+                              const uint8_t* valid, const float* values, int32_t n_channels, int32_t n_unit,
+                              void* workspace, int64_t workspace_bytes, float* out, misplat_stream_t stream);
+
 /* Library identification ("misplat <version> gfx950"). */
 const char* misplat_version(void);
 
