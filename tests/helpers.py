@@ -2,7 +2,11 @@
 import os
 
 import numpy as np
+import pytest
 import torch
+
+# the C port at full size (1 M Gaussians at 1080p and up) takes the GPU box's host cores; elsewhere these cases skip
+FULL_SIZE = pytest.mark.skipif((os.cpu_count() or 1) < 32, reason="the C port at full size needs the GPU box's host cores")
 
 
 def rel_err(a, b) -> float:

@@ -16,9 +16,15 @@ from oracle.craster import CRaster
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
 
-@pytest.mark.parametrize("mode,rm,deg", [("antialiased", "RGB+ED", 3), ("classic", "RGB", 1)])
+@pytest.mark.parametrize("mode,rm,deg", [("antialiased", "RGB+ED", 3), ("classic", "RGB", 1),
+                                         # the progressive schedule's first degrees (16-coefficient storage), and the degree-0
+                                         # features model's call: 16 pass-through channels (+ ED), sh_degree=None
+                                         ("antialiased", "RGB+ED", 0), ("antialiased", "RGB", 2),
+                                         ("antialiased", "RGB+ED", None)])
 def test_c_port_matches_autograd_oracle_fp64(mode, rm, deg):
     sc = small_scene()
+    if deg is None:
+        sc["sh"] = torch.rand(sc["sh"].shape[0], 16, generator=torch.Generator().manual_seed(4), dtype=torch.float64)
     ins = [sc[k].clone().requires_grad_(True) for k in ("means", "quats", "scales", "opacities", "sh")]
     r, a, ed, md, n, meta = O.rasterization(*ins, sc["viewmat"][None], sc["K"][None], sc["W"], sc["H"],
                                             sh_degree=deg, render_mode=rm, rasterize_mode=mode)
@@ -49,6 +55,12 @@ def test_c_port_matches_autograd_oracle_fp64(mode, rm, deg):
     gr = cr.backward(st, *[u[0].numpy() for u in ups])
     for name, t in zip(("v_means", "v_quats", "v_scales", "v_opacities", "v_colors"), ins):
         assert rel_err(gr[name], t.grad) < 1e-11, name
+    if deg is None:
+        assert r.shape[-1] == (17 if rm == "RGB+ED" else 16) and gr["v_colors"].shape == (ins[0].shape[0], 16)
+    else:
+        nb = (deg + 1) ** 2                              # coefficients above the active degree get exactly nothing
+        assert not gr["v_colors"][:, nb:].any() and not ins[4].grad[:, nb:].any()
+        assert np.abs(gr["v_colors"][:, nb - 1]).max() > 0
 
 
 def test_c_port_fp32_within_tolerance_of_fp64_oracle():

@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import FlipProof, assert_close_flips, rel_err, small_scene, upstream
+from helpers import FULL_SIZE, FlipProof, assert_close_flips, rel_err, small_scene, upstream
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -2154,7 +2154,7 @@ def test_fused_get_outputs_node_matches_separate_nodes(dev):
 
 
 # ---------------------------------------------------------------- the TIMED path itself against the oracle
-_FULL_SIZE = pytest.mark.skipif((os.cpu_count() or 1) < 32, reason="the C port at full size needs the GPU box's host cores")
+_FULL_SIZE = FULL_SIZE
 
 
 @pytest.mark.parametrize("lazy", ["1", "auto"])
