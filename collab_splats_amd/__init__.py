@@ -13,6 +13,7 @@ from .ops import set_deterministic  # noqa: F401
 from .optim import FusedAdam, step_all as fused_adam_step_all  # noqa: F401
 from .tsdf import TSDFVolume, write_ply  # noqa: F401
 from .meshmap import features2vertex, normals2vertex  # noqa: F401
+from .meshquery import cluster_labels, mesh_clustering, query_similarity, similarity_colors  # noqa: F401
 
 __version__ = "0.1.0"
 

@@ -120,6 +120,7 @@ SYMBOLS = {
     "misplat_tsdf_order": (C.c_int, 5), "misplat_tsdf_mc_count": (C.c_int, 11), "misplat_tsdf_mc_emit": (C.c_int, 13),
     "misplat_meshmap_workspace": (C.c_int64, 4), "misplat_meshmap_knn": (C.c_int, 12),
     "misplat_meshmap_aggregate": (C.c_int, 13),
+    "misplat_cluster_workspace": (C.c_int64, 1), "misplat_cluster_radius": (C.c_int, 11),
     "misplat_version": (C.c_char_p, 0),
 }
 

@@ -39,6 +39,8 @@ SOURCES = {
     "tsdf.hip": ["-ffp-contract=off"],
     # meshmap.hip: the same: the neighbour lists equal the fp32 restatement (tests/) bit for bit
     "meshmap.hip": ["-ffp-contract=off"],
+    # cluster.hip: the same: the radius graph's edge test d2 < r2 equals the fp32 restatement (tests/) bit for bit
+    "cluster.hip": ["-ffp-contract=off"],
 }
 
 
@@ -60,7 +62,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(OBJ, exist_ok=True)
     hipcc = _hipcc()
     headers = [os.path.join(INCLUDE, "misplat.h"), os.path.join(CSRC, "sh_eval.h"), os.path.join(CSRC, "internal.h"),
-               os.path.join(CSRC, "mc_tables.h")]
+               os.path.join(CSRC, "mc_tables.h"), os.path.join(CSRC, "cellhash.h")]
     jobs = []
     objs = []
     for src, extra in SOURCES.items():

@@ -1,0 +1,256 @@
+// cluster.hip -- connected components of the radius graph over the selected mesh vertices.
+//
+// Semantics: the reference's mesh_clustering restated (tests/meshquery_restatement.py is the oracle).  Vertices i != j with
+// mask set are joined iff d2 < r2, d2 = ((dx dx + dy dy) + dz dz) and r2 = r r in fp32 (compiled with -ffp-contract=off:
+// every expression is evaluated in the written order); clusters are the connected components with more than
+// min_cluster_size members, numbered in ascending order of their smallest vertex index.
+//
+// Spatial index (csrc/cellhash.h): a hash of the occupied cells of edge h = r over the SELECTED vertices only, the
+// vertices regrouped by cell.  Union: one thread per selected vertex, in cell order, over the cells its radius can reach,
+// into a lock-free union-find whose links always point to a smaller index: every component's root is its smallest member,
+// whatever the scheduling.  Flatten, count (integer atomics), rank the kept roots by a scan in vertex order.  Memory O(M);
+// no float atomics; two runs are bitwise equal.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "misplat.h"
+#include "internal.h"
+#include "cellhash.h"
+
+namespace {
+
+// ---------------------------------------------------------------------------------------------------------- union
+// parent[x] <= x always, and parent[x] is a member of x's component (of the radius graph); x is a root iff parent[x] == x.
+//
+// Inside union_kernel workgroups on different CUs and XCDs talk through parent[] alone, so EVERY access to it there is an
+// agent-scope relaxed atomic (loads and stores that bypass the CU's L1, compare-and-swaps executed at the memory side):
+// no fence is needed per element.  What such a load returns is a value parent[x] held at SOME earlier time, not
+// necessarily the latest.  That is harmless:
+//   * every value parent[x] ever held is a member of x's component and is <= x, and < x once x has stopped being a root
+//     (a root is only ever un-rooted by the compare-and-swap below, which a halving store never undoes: a store to
+//     parent[x] is issued only after x was seen as a non-root, with a value that was parent[parent[x]] < parent[x] < x);
+//   * so a walk along (possibly old) values strictly descends and ends, after finitely many steps, at an index that was a
+//     root of x's component when it was read; links only point downwards: no interleaving can close a cycle;
+//   * a halving store replaces the link x -> p by x -> g, g an earlier parent of p.  g < x is not below x in the tree (a
+//     descendant has a larger index), so it lies in the part that stays connected to p: the trees never split, even when
+//     the stored value is older (larger) than the one it overwrites.  That can only lengthen a later walk;
+//   * a hook compare-and-swap(parent[a], a, b) with b < a succeeds only if a IS a root at that moment: two trees of one
+//     component become one.  If a stale read made a look like a root, the swap fails: a retry, nothing else (unite).
+// When the kernel ends every edge (i, j) has been seen with find(i) == find(j) or hooked, so the trees are exactly the
+// components, and each tree's root, the smallest index on every downward path, is the component's smallest member.
+__device__ __forceinline__ int32_t ld_parent(int32_t* parent, int32_t x) {
+    return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// root of x's tree, with path halving
+__device__ __forceinline__ int32_t find_root(int32_t* parent, int32_t x) {
+    int32_t p = ld_parent(parent, x);
+    while (p != x) {
+        const int32_t g = ld_parent(parent, p);
+        if (g == p) return p;
+        __hip_atomic_store(parent + x, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        x = g;
+        p = ld_parent(parent, x);
+    }
+    return x;
+}
+
+// joins the trees of a and b (both members of what must become one component); returns a root of the joined tree as seen
+// by this thread (the caller's next starting point).  A failed swap returns the TRUE parent of a, strictly below a, and the
+// walk goes on from there: max(a, b) falls with every failure, so the loop ends even if every load were stale.
+__device__ __forceinline__ int32_t unite(int32_t* parent, int32_t a, int32_t b) {
+    while (true) {
+        a = find_root(parent, a);
+        b = find_root(parent, b);
+        if (a == b) return a;
+        if (a < b) { const int32_t t = a; a = b; b = t; }
+        const int32_t seen = atomicCAS(parent + a, a, b);         // the larger root under the smaller
+        if (seen == a) return b;
+        a = seen;
+    }
+}
+
+// kSub lanes per entry of the cell-ordered list (the selected vertices), each taking every kSub-th candidate of every cell:
+// neighbouring lanes hold vertices of one cell and walk the same candidate lists.  (One lane per vertex left a 106 k-vertex
+// mesh with two waves per CU, each lane a serial chain of some 500 dependent loads: DESIGN.md section 16.)
+//
+// Which cells hold a neighbour.  d2 < r2 implies |x_i - x_j| < r EXACTLY on every axis: rounding is monotone and the
+// terms are non-negative, so fl(dx dx) <= d2 < fl(r r) gives |dx| < r, and dx = fl(x_i - x_j) with |dx| < r (r a float)
+// gives |x_i - x_j| < r.  The cell of a coordinate is floorf(fl(x inv_h)), a non-decreasing function of x, the same for
+// both ends.  It does NOT follow that the two cell indices differ by at most one: at |x| / r near 2^18 the product
+// x inv_h is rounded to a grid of 2^-5, so two coordinates just under r apart can land 1 + 2^-5 apart and straddle two
+// cell boundaries.  The box is therefore taken from the coordinates, as knn_kernel does: cells
+// cell_of(x_i - t) .. cell_of(x_i + t) with t = r + margin.  The rounding errors of t and of the subtraction are together
+// at most 2^-24 (|x_i| + 2 t) < margin / 2 with margin = 2^-22 (amax + r), so fl(x_i - t) <= x_i - r < x_j, and by
+// monotonicity cell_of(fl(x_i - t)) <= cell_of(x_j); likewise above.  Away from the bound that is at most the 27 cells
+// around the vertex's own (more only when the vertex lies within the margin of a cell face).
+// A vertex outside the coordinate bound the host checks (or not finite) is left alone: its box would not be bounded.
+constexpr int kSub = 8;
+
+__global__ __launch_bounds__(256) void union_kernel(Index ix, int64_t cap, float r, float r2, float inv_h,
+                                                    int32_t* __restrict__ parent) {
+    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t t = g / kSub;
+    const int sub = (int)(g % kSub);
+    if (t >= ix.starts[cap]) return;                              // the number of selected vertices
+    const float4 q = ix.pts[t];
+    const int32_t i = __float_as_int(q.w);
+    const float amax = fmaxf(fmaxf(fabsf(q.x), fabsf(q.y)), fabsf(q.z));
+    if (!(amax * inv_h < kCoordCells + 2.f)) return;
+    const float reach = r + 2.3841858e-7f * (amax + r);
+    const float p[3] = {q.x, q.y, q.z};
+    int lo[3], hi[3];
+#pragma unroll
+    for (int a = 0; a < 3; a++) { lo[a] = cell_of(p[a] - reach, inv_h); hi[a] = cell_of(p[a] + reach, inv_h); }
+    int32_t root = i;                                             // a member of i's tree: where the next find starts
+    for (int cz = lo[2]; cz <= hi[2]; cz++)
+        for (int cy = lo[1]; cy <= hi[1]; cy++)
+            for (int cx = lo[0]; cx <= hi[0]; cx++) {
+                const int s = find_cell(ix.keys, ix.mask, cell_key(cx, cy, cz));
+                if (s < 0) continue;
+                const int e1 = ix.starts[s + 1];
+                for (int e = ix.starts[s] + sub; e < e1; e += kSub) {
+                    const float4 c = ix.pts[e];
+                    const int32_t j = __float_as_int(c.w);
+                    const float dx = q.x - c.x, dy = q.y - c.y, dz = q.z - c.z;
+                    const float d2 = (dx * dx + dy * dy) + dz * dz;
+                    if (j < i && d2 < r2) root = unite(parent, root, j);      // each edge once, from its larger end
+                }
+            }
+}
+
+// ------------------------------------------------------------------------------------------------- flatten, sizes
+__global__ __launch_bounds__(256) void init_kernel(int64_t M, int32_t* __restrict__ parent, int32_t* __restrict__ size) {
+    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (v >= M) return;
+    parent[v] = (int32_t)v;
+    size[v] = 0;
+}
+
+// After the kernel boundary parent[] is read-only: plain loads.  root[v] = the root of v's tree (-1: not selected), and
+// size[root] counts its members: integer adds, one per distinct root among a wave's lanes.
+__global__ __launch_bounds__(256) void flatten_kernel(const int32_t* __restrict__ parent, const uint8_t* __restrict__ mask,
+                                                      int64_t M, int32_t* __restrict__ root, int32_t* __restrict__ size) {
+    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    bool pending = v < M && mask[v];
+    int32_t r = -1;
+    if (pending) {
+        r = (int32_t)v;
+        for (int32_t p = parent[r]; p != r; p = parent[r]) r = p;
+    }
+    if (v < M) root[v] = r;
+    while (true) {
+        const unsigned long long todo = __ballot(pending);
+        if (!todo) break;
+        const int leader = __ffsll((long long)todo) - 1;
+        const int32_t r0 = __shfl(r, leader);
+        const bool same = pending && r == r0;
+        const unsigned long long group = __ballot(same);
+        if (lane == leader) atomicAdd(&size[r0], __popcll(group));
+        if (same) pending = false;
+    }
+}
+
+// ----------------------------------------------------------------------------------------------------------- rank
+__global__ __launch_bounds__(256) void keep_kernel(const int32_t* __restrict__ root, const int32_t* __restrict__ size, int64_t M,
+                                                   int32_t min_size, int32_t* __restrict__ keep) {
+    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (v >= M) return;
+    keep[v] = (root[v] == (int32_t)v && size[v] > min_size) ? 1 : 0;
+}
+
+// rank[v] = number of kept roots below v: the kept clusters in ascending order of their smallest member (= their root).
+__global__ __launch_bounds__(256) void label_kernel(const int32_t* __restrict__ root, const int32_t* __restrict__ size,
+                                                    const int32_t* __restrict__ rank, int64_t M, int32_t min_size,
+                                                    int32_t* __restrict__ labels, int32_t* __restrict__ sizes,
+                                                    int32_t* __restrict__ n_clusters) {
+    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (v == 0) *n_clusters = rank[M];
+    if (v >= M) return;
+    const int32_t r = root[v];
+    const bool kept = r >= 0 && size[r] > min_size;
+    labels[v] = kept ? rank[r] : -1;
+    if (kept && r == (int32_t)v) sizes[rank[r]] = size[r];
+}
+
+// ------------------------------------------------------------------------------------------------------- workspace
+struct Layout {
+    int64_t cap;
+    int64_t o_keys, o_counts, o_starts, o_vslot, o_pts, o_scan, o_parent, o_size, o_root, o_keep, o_rank, total;
+};
+
+inline Layout layout(int64_t M) {
+    Layout L;
+    L.cap = hash_capacity(M);
+    const int64_t scan_n = L.cap > M ? L.cap : M;
+    int64_t o = 0;
+    L.o_keys = o;   o += al(8 * L.cap);
+    L.o_counts = o; o += al(4 * L.cap);
+    L.o_starts = o; o += al(4 * (L.cap + 1));
+    L.o_vslot = o;  o += al(4 * M);
+    L.o_pts = o;    o += al(16 * M);
+    L.o_scan = o;   o += al(4 * (2 * ((scan_n + kScanBlock - 1) / kScanBlock) + 2));
+    L.o_parent = o; o += al(4 * M);
+    L.o_size = o;   o += al(4 * M);
+    L.o_root = o;   o += al(4 * M);
+    L.o_keep = o;   o += al(4 * M);
+    L.o_rank = o;   o += al(4 * (M + 1));
+    L.total = o;
+    return L;
+}
+
+inline bool sizes_ok(int64_t M) { return M >= 0 && M < (1ll << 30); }
+
+}  // namespace
+
+extern "C" int64_t misplat_cluster_workspace(int64_t n_vertices) {
+    if (!sizes_ok(n_vertices)) return -1;
+    return layout(n_vertices).total;
+}
+
+extern "C" int misplat_cluster_radius(const float* vertices, int64_t n_vertices, const uint8_t* mask, float radius,
+                                      int32_t min_cluster_size, void* workspace, int64_t workspace_bytes, int32_t* labels,
+                                      int32_t* sizes, int32_t* n_clusters, misplat_stream_t stream) {
+    const int64_t M = n_vertices;
+    const float inv_h = 1.f / radius;
+    if (!sizes_ok(M) || !(radius > 0.f) || !(radius < 3.0e37f) || !(inv_h < 3.0e38f) || min_cluster_size < 0 || !workspace ||
+        !n_clusters || (M > 0 && (!vertices || !mask || !labels || !sizes)))
+        return MISPLAT_EINVAL;
+    const Layout L = layout(M);
+    if (workspace_bytes < L.total) return MISPLAT_EWORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    if (M == 0) {
+        misplat_internal::fill_bytes(n_clusters, 4, 0u, s);
+        return launched();
+    }
+    char* ws = (char*)workspace;
+    unsigned long long* keys = (unsigned long long*)(ws + L.o_keys);
+    int32_t* counts = (int32_t*)(ws + L.o_counts);
+    int32_t* starts = (int32_t*)(ws + L.o_starts);
+    int32_t* vslot = (int32_t*)(ws + L.o_vslot);
+    float4* pts = (float4*)(ws + L.o_pts);
+    int32_t* scr = (int32_t*)(ws + L.o_scan);
+    int32_t* parent = (int32_t*)(ws + L.o_parent);
+    int32_t* size = (int32_t*)(ws + L.o_size);
+    int32_t* root = (int32_t*)(ws + L.o_root);
+    int32_t* keep = (int32_t*)(ws + L.o_keep);
+    int32_t* rank = (int32_t*)(ws + L.o_rank);
+    const unsigned nb = blocks(M, 256);
+    misplat_internal::fill_bytes(keys, 8 * L.cap, 0xffffffffu, s);          // (kernels, not memsets: internal.h)
+    misplat_internal::fill_bytes(counts, 4 * L.cap, 0u, s);
+    hipLaunchKernelGGL(init_kernel, dim3(nb), dim3(256), 0, s, M, parent, size);
+    hipLaunchKernelGGL(index_insert_kernel, dim3(nb), dim3(256), 0, s, vertices, M, mask, inv_h, keys, (uint32_t)(L.cap - 1),
+                       vslot, counts);
+    scan(counts, L.cap, starts, scr, s);
+    hipLaunchKernelGGL(index_fill_kernel, dim3(nb), dim3(256), 0, s, vertices, M, (const int32_t*)vslot, (const int32_t*)starts,
+                       counts, pts);
+    const Index ix{keys, starts, pts, (uint32_t)(L.cap - 1)};
+    hipLaunchKernelGGL(union_kernel, dim3(blocks(M * kSub, 256)), dim3(256), 0, s, ix, L.cap, radius, radius * radius, inv_h, parent);
+    hipLaunchKernelGGL(flatten_kernel, dim3(nb), dim3(256), 0, s, (const int32_t*)parent, mask, M, root, size);
+    hipLaunchKernelGGL(keep_kernel, dim3(nb), dim3(256), 0, s, (const int32_t*)root, (const int32_t*)size, M, min_cluster_size,
+                       keep);
+    scan(keep, M, rank, scr, s);
+    hipLaunchKernelGGL(label_kernel, dim3(nb), dim3(256), 0, s, (const int32_t*)root, (const int32_t*)size, (const int32_t*)rank,
+                       M, min_cluster_size, labels, sizes, n_clusters);
+    return launched();
+}

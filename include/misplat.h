@@ -693,6 +693,20 @@ int misplat_meshmap_aggregate(int64_t n_vertices, int64_t n_points, int32_t k, c
                               const uint8_t* valid, const float* values, int32_t n_channels, int32_t n_unit,
                               void* workspace, int64_t workspace_bytes, float* out, misplat_stream_t stream);
 
+/* ---- radius-graph clustering of selected mesh vertices (csrc/cluster.hip) --------------------------
+ * The reference's mesh_clustering restated in fp32 (the oracle is tests/meshquery_restatement.py).  vertices [M,3] fp32,
+ * mask [M] uint8 (non-zero: selected); every vertex finite with |x| / radius < 2^18 per axis (the caller checks it).
+ * Selected vertices i != j are joined iff d2 < r2, d2 = ((dx dx + dy dy) + dz dz) and r2 = radius radius in fp32; clusters are
+ * the connected components with MORE than min_cluster_size members, numbered in ascending order of their smallest vertex.
+ * Deterministic (integer atomics only); memory O(M). */
+/* workspace bytes for M vertices; -1 for sizes the library refuses. */
+int64_t misplat_cluster_workspace(int64_t n_vertices);
+/* labels [M] int32: the cluster of each vertex, -1 if it is not selected or its component was dropped; sizes (capacity M
+ * int32): sizes[c] = members of cluster c for c < n_clusters, the rest is not written; n_clusters: one int32 on the device. */
+int misplat_cluster_radius(const float* vertices, int64_t n_vertices, const uint8_t* mask, float radius,
+                           int32_t min_cluster_size, void* workspace, int64_t workspace_bytes, int32_t* labels,
+                           int32_t* sizes, int32_t* n_clusters, misplat_stream_t stream);
+
 /* Library identification ("misplat <version> gfx950"). */
 const char* misplat_version(void);
 
