@@ -14,6 +14,9 @@ from .optim import FusedAdam, step_all as fused_adam_step_all  # noqa: F401
 from .tsdf import TSDFVolume, write_ply  # noqa: F401
 from .meshmap import features2vertex, normals2vertex  # noqa: F401
 from .meshquery import cluster_labels, mesh_clustering, query_similarity, similarity_colors  # noqa: F401
+from .pointcloud import (calculate_accuracy, calculate_completeness, clean_pcd, density_filter,  # noqa: F401
+                         knn_mean_distance, radius_count, remove_far_points, remove_statistical_outlier,
+                         statistical_outlier_mask, voxel_down_sample)
 
 __version__ = "0.1.0"
 

@@ -121,6 +121,10 @@ SYMBOLS = {
     "misplat_meshmap_workspace": (C.c_int64, 4), "misplat_meshmap_knn": (C.c_int, 12),
     "misplat_meshmap_aggregate": (C.c_int, 13),
     "misplat_cluster_workspace": (C.c_int64, 1), "misplat_cluster_radius": (C.c_int, 11),
+    "misplat_pointcloud_workspace": (C.c_int64, 2), "misplat_pointcloud_cells": (C.c_int, 7),
+    "misplat_pointcloud_knn": (C.c_int, 12), "misplat_pointcloud_radius_count": (C.c_int, 9),
+    "misplat_pointcloud_outlier_mask": (C.c_int, 7), "misplat_pointcloud_voxel_group": (C.c_int, 12),
+    "misplat_pointcloud_voxel_mean": (C.c_int, 8),
     "misplat_version": (C.c_char_p, 0),
 }
 

@@ -41,6 +41,8 @@ SOURCES = {
     "meshmap.hip": ["-ffp-contract=off"],
     # cluster.hip: the same: the radius graph's edge test d2 < r2 equals the fp32 restatement (tests/) bit for bit
     "cluster.hip": ["-ffp-contract=off"],
+    # pointcloud.hip: the same: the k smallest d2, the radius rule d2 < r2 and the fp64 voxel sums equal the restatement (tests/)
+    "pointcloud.hip": ["-ffp-contract=off"],
 }
 
 
@@ -62,7 +64,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(OBJ, exist_ok=True)
     hipcc = _hipcc()
     headers = [os.path.join(INCLUDE, "misplat.h"), os.path.join(CSRC, "sh_eval.h"), os.path.join(CSRC, "internal.h"),
-               os.path.join(CSRC, "mc_tables.h"), os.path.join(CSRC, "cellhash.h")]
+               os.path.join(CSRC, "mc_tables.h"), os.path.join(CSRC, "cellhash.h"), os.path.join(CSRC, "radixsort.h")]
     jobs = []
     objs = []
     for src, extra in SOURCES.items():

@@ -559,6 +559,13 @@ class RadegsModel(nn.Module):
             res["distill_features"] = out[:, 3:].contiguous()
         return res
 
+    @torch.no_grad()
+    def clean_gaussians(self, **kwargs) -> Tensor:
+        """``pointcloud.clean_pcd`` (the reference's ``clean_pcd``: voxel reduction, statistical outliers, far points) on the
+        Gaussian means, with its keyword arguments: the int64 indices of the Gaussians that survive, on the device."""
+        from .pointcloud import clean_pcd
+        return clean_pcd(self.means.detach(), **kwargs)[1]
+
     def _scale_reg(self, dev) -> Tensor:
         """Splatfacto's scale regularisation: 0.1 * mean(max(max(s) / min(s), max_gauss_ratio) - max_gauss_ratio) of the
         activated scales, every 10th step; 0 otherwise [UNVERIFIED-UPSTREAM]."""

@@ -707,6 +707,44 @@ int misplat_cluster_radius(const float* vertices, int64_t n_vertices, const uint
                            int32_t min_cluster_size, void* workspace, int64_t workspace_bytes, int32_t* labels,
                            int32_t* sizes, int32_t* n_clusters, misplat_stream_t stream);
 
+/* ---- point-cloud cleaning (csrc/pointcloud.hip) ----------------------------------------------------
+ * points [N,3] and queries [Nq,3] fp32, finite (the caller checks it); queries NULL: the points query themselves (n_queries
+ * is then ignored) and a point counts among its own neighbours.  d2 = ((dx dx + dy dy) + dz dz) in fp32.  The oracle is
+ * tests/pointcloud_restatement.py.  Deterministic (integer atomics only): two runs are bitwise equal. */
+/* workspace bytes for n_points and the call `kind` (0 cells, 1 knn, 2 radius_count, 3 outlier_mask, 4 voxel_group); -1 for
+ * sizes the library refuses. */
+int64_t misplat_pointcloud_workspace(int64_t n_points, int32_t kind);
+/* n_cells (one int32 on the device) = the number of occupied cells of edge `edge`: the occupancy measure the caller tunes
+ * the kNN's cell edge with.  |x| / edge < 2^18 per axis. */
+int misplat_pointcloud_cells(const float* points, int64_t n_points, float edge, void* workspace, int64_t workspace_bytes,
+                             int32_t* n_cells, misplat_stream_t stream);
+/* mean [Nq] = (the fp32 sum of sqrtf of the k smallest d2 in ascending order) / float(k), nearest [Nq] = sqrtf of the
+ * smallest; 1 <= k <= min(32, N).  No distance cut-off.  edge: the cell edge of the finest of three hash levels (edge, 8 edge,
+ * 64 edge), |x| / edge < 2^18 per axis for points and queries; lanes: 1 or 8 lanes per query.  Neither changes a result. */
+int misplat_pointcloud_knn(const float* points, int64_t n_points, const float* queries, int64_t n_queries, int32_t k,
+                           float edge, int32_t lanes, void* workspace, int64_t workspace_bytes, float* mean, float* nearest,
+                           misplat_stream_t stream);
+/* counts [Nq] int32 = the number of points with d2 < r2, r2 = radius radius in fp32 (strict).  |x| / radius < 2^18 per axis for
+ * the points; a query beyond that range counts 0. */
+int misplat_pointcloud_radius_count(const float* points, int64_t n_points, const float* queries, int64_t n_queries,
+                                    float radius, void* workspace, int64_t workspace_bytes, int32_t* counts,
+                                    misplat_stream_t stream);
+/* keep [N] uint8 = avg > 0 and double(avg) < mu + std_ratio sigma, mu and sigma (n - 1 in the denominator) over the positive
+ * avg in fp64 in a fixed reduction order; fewer than two positive values: keep = avg > 0. */
+int misplat_pointcloud_outlier_mask(const float* avg, int64_t n_points, double std_ratio, void* workspace,
+                                    int64_t workspace_bytes, uint8_t* keep, misplat_stream_t stream);
+/* Voxel grouping: cell = floor((double(p) - origin) / voxel_size) per axis in fp64, |cell| < 2^20 (the caller checks it).
+ * Voxels are numbered in ascending order of their smallest member.  order [N] int32: the points grouped by voxel, ascending
+ * inside each; offsets [N + 1] int32: voxel v holds order[offsets[v] .. offsets[v + 1]) for v < n_voxels (one int32 on the
+ * device), the entries from n_voxels on hold N. */
+int misplat_pointcloud_voxel_group(const float* points, int64_t n_points, double origin_x, double origin_y, double origin_z,
+                                   double voxel_size, void* workspace, int64_t workspace_bytes, int32_t* order,
+                                   int32_t* offsets, int32_t* n_voxels, misplat_stream_t stream);
+/* out [V,D] = per voxel and channel the fp64 sum of values [N,D] over the members in ascending point index, divided by the
+ * member count in fp64 and rounded to fp32. */
+int misplat_pointcloud_voxel_mean(const float* values, int64_t n_points, int32_t n_channels, const int32_t* order,
+                                  const int32_t* offsets, int64_t n_voxels, float* out, misplat_stream_t stream);
+
 /* Library identification ("misplat <version> gfx950"). */
 const char* misplat_version(void);
 
