@@ -17,6 +17,8 @@ from .meshquery import cluster_labels, mesh_clustering, query_similarity, simila
 from .pointcloud import (calculate_accuracy, calculate_completeness, clean_pcd, density_filter,  # noqa: F401
                          knn_mean_distance, radius_count, remove_far_points, remove_statistical_outlier,
                          statistical_outlier_mask, voxel_down_sample)
+from .meshclean import (align_floor, fill_holes, filter_mesh_components, mesh_components, mesh_edge_stats,  # noqa: F401
+                        mesh_holes, plane_inlier_counts, ransac_planes, sample_surface, segment_plane)
 
 __version__ = "0.1.0"
 

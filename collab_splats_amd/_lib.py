@@ -125,6 +125,10 @@ SYMBOLS = {
     "misplat_pointcloud_knn": (C.c_int, 12), "misplat_pointcloud_radius_count": (C.c_int, 9),
     "misplat_pointcloud_outlier_mask": (C.c_int, 7), "misplat_pointcloud_voxel_group": (C.c_int, 12),
     "misplat_pointcloud_voxel_mean": (C.c_int, 8),
+    "misplat_meshclean_workspace": (C.c_int64, 3), "misplat_meshclean_edge_stats": (C.c_int, 9),
+    "misplat_meshclean_components": (C.c_int, 9), "misplat_meshclean_holes": (C.c_int, 11),
+    "misplat_meshclean_segment_sum": (C.c_int, 6), "misplat_meshclean_plane_build": (C.c_int, 8),
+    "misplat_meshclean_plane_count": (C.c_int, 8), "misplat_meshclean_plane_moments": (C.c_int, 9),
     "misplat_version": (C.c_char_p, 0),
 }
 

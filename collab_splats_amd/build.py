@@ -43,6 +43,8 @@ SOURCES = {
     "cluster.hip": ["-ffp-contract=off"],
     # pointcloud.hip: the same: the k smallest d2, the radius rule d2 < r2 and the fp64 voxel sums equal the restatement (tests/)
     "pointcloud.hip": ["-ffp-contract=off"],
+    # meshclean.hip: the same: edge lengths, plane hypotheses and the inlier rule equal the restatement (tests/) bit for bit
+    "meshclean.hip": ["-ffp-contract=off"],
 }
 
 
@@ -64,7 +66,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(OBJ, exist_ok=True)
     hipcc = _hipcc()
     headers = [os.path.join(INCLUDE, "misplat.h"), os.path.join(CSRC, "sh_eval.h"), os.path.join(CSRC, "internal.h"),
-               os.path.join(CSRC, "mc_tables.h"), os.path.join(CSRC, "cellhash.h"), os.path.join(CSRC, "radixsort.h")]
+               os.path.join(CSRC, "mc_tables.h"), os.path.join(CSRC, "cellhash.h"), os.path.join(CSRC, "radixsort.h"),
+               os.path.join(CSRC, "unionfind.h")]
     jobs = []
     objs = []
     for src, extra in SOURCES.items():

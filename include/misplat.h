@@ -745,6 +745,52 @@ int misplat_pointcloud_voxel_group(const float* points, int64_t n_points, double
 int misplat_pointcloud_voxel_mean(const float* values, int64_t n_points, int32_t n_channels, const int32_t* order,
                                   const int32_t* offsets, int64_t n_voxels, float* out, misplat_stream_t stream);
 
+/* ---- mesh finishing (csrc/meshclean.hip) -----------------------------------------------------------
+ * vertices [M,3] fp32, triangles [T,3] int32 with every index in 0 .. M - 1 (the caller checks it), M < 2^31, T < 2^30; the
+ * calls that number corners or edges in int32 (edge_stats, holes) also need 3 T < 2^31.  Every call builds the edge table in
+ * its workspace: the undirected edges (lo, hi) of all triangles in a hash of capacity the power of two >= max(64, 6 T); an edge
+ * (a, a) of a triangle with a repeated corner is ignored.  The oracle is tests/meshclean_restatement.py.  Deterministic
+ * (integer atomics only, fp64 sums in a fixed order): two runs are bitwise equal. */
+/* workspace bytes for the call `kind` (0 edge_stats, 1 components, 2 holes: n_vertices, n_triangles; 3 plane_moments:
+ * n_vertices = the number of points, n_triangles ignored); -1 for sizes the library refuses. */
+int64_t misplat_meshclean_workspace(int64_t n_vertices, int64_t n_triangles, int32_t kind);
+/* counts [3] int32 on the device: undirected edges, boundary edges (exactly one incident (face, corner)), non-manifold edges
+ * (more than two); mean_length: one double on the device, the fp64 mean over the undirected edges of the fp32 length
+ * sqrtf((dx dx + dy dy) + dz dz), 0 without an edge. */
+int misplat_meshclean_edge_stats(const float* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles,
+                                 void* workspace, int64_t workspace_bytes, int32_t* counts, double* mean_length,
+                                 misplat_stream_t stream);
+/* Components of the faces under "share an undirected edge", numbered in ascending order of their smallest face: labels [T]
+ * int32; sizes (capacity T int32): sizes[c] = faces of component c for c < n_components (one int32 on the device). */
+int misplat_meshclean_components(const int32_t* triangles, int64_t n_vertices, int64_t n_triangles, void* workspace,
+                                 int64_t workspace_bytes, int32_t* labels, int32_t* sizes, int32_t* n_components,
+                                 misplat_stream_t stream);
+/* The boundary edges in ascending (face, corner) order, each directed as its face runs: edges (capacity [3 T,2] int32),
+ * length (capacity 3 T fp32), loop_of_edge (capacity 3 T int32): loops are the boundary edges connected through shared
+ * vertices, numbered in ascending order of their smallest vertex; counts [2] int32 on the device: boundary edges, loops. */
+int misplat_meshclean_holes(const float* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles,
+                            void* workspace, int64_t workspace_bytes, int32_t* edges, int32_t* loop_of_edge, float* length,
+                            int32_t* counts, misplat_stream_t stream);
+/* out [L] double: out[l] = the fp64 sum of values[order[e]] over e = offsets[l] .. offsets[l + 1) - 1, in that order. */
+int misplat_meshclean_segment_sum(const float* values, const int32_t* order, const int32_t* offsets, int64_t n_segments,
+                                  double* out, misplat_stream_t stream);
+/* RANSAC hypotheses over points [N,3] fp32, 3 <= N < 2^30, n_planes <= 2^24.  triples_in NULL: hypothesis i takes three
+ * distinct indices from a counter-based hash of (seed, i, draw) and writes them to triples_out [H,3]; else it takes
+ * triples_in [H,3] (in range: the caller checks it).  planes [H,4] fp32, 16-byte aligned: the unit normal and offset of the
+ * plane through the three points, built in fp32 in a fixed order; four NaN for a triple that spans no plane. */
+int misplat_meshclean_plane_build(const float* points, int64_t n_points, const int32_t* triples_in, uint32_t seed,
+                                  int32_t n_planes, int32_t* triples_out, float* planes, misplat_stream_t stream);
+/* counts [H] int32 = the number of points with |((a x + b y) + c z) + d| < threshold in fp32 (strict).  tile: 8, 16 or 32
+ * hypotheses per workgroup; it changes no result. */
+int misplat_meshclean_plane_count(const float* points, int64_t n_points, const float* planes, int32_t n_planes,
+                                  float threshold, int32_t tile, int32_t* counts, misplat_stream_t stream);
+/* The inliers of one plane ([4] fp32 on the device) by the same rule: mask [N] uint8, and moments [10] double on the device:
+ * n, sum x, sum y, sum z, then the sums of (xx, xy, xz, yy, yz, zz) of the coordinates minus the inliers' mean; fp64, fixed
+ * order. */
+int misplat_meshclean_plane_moments(const float* points, int64_t n_points, const float* plane, float threshold,
+                                    void* workspace, int64_t workspace_bytes, uint8_t* mask, double* moments,
+                                    misplat_stream_t stream);
+
 /* Library identification ("misplat <version> gfx950"). */
 const char* misplat_version(void);
 
