@@ -19,6 +19,7 @@ from .pointcloud import (calculate_accuracy, calculate_completeness, clean_pcd, 
                          statistical_outlier_mask, voxel_down_sample)
 from .meshclean import (align_floor, fill_holes, filter_mesh_components, mesh_components, mesh_edge_stats,  # noqa: F401
                         mesh_holes, plane_inlier_counts, ransac_planes, sample_surface, segment_plane)
+from .depthcloud import backproject, depth_edges, depth_normal_cloud, gaussian_mask_filter, sample_pixels  # noqa: F401
 
 __version__ = "0.1.0"
 

@@ -129,6 +129,9 @@ SYMBOLS = {
     "misplat_meshclean_components": (C.c_int, 9), "misplat_meshclean_holes": (C.c_int, 11),
     "misplat_meshclean_segment_sum": (C.c_int, 6), "misplat_meshclean_plane_build": (C.c_int, 8),
     "misplat_meshclean_plane_count": (C.c_int, 8), "misplat_meshclean_plane_moments": (C.c_int, 9),
+    "misplat_depthcloud_workspace": (C.c_int64, 4), "misplat_depthcloud_edges": (C.c_int, 10),
+    "misplat_depthcloud_candidates": (C.c_int, 7), "misplat_depthcloud_sample": (C.c_int, 15),
+    "misplat_depthcloud_backproject": (C.c_int, 15), "misplat_depthcloud_gaussian_filter": (C.c_int, 10),
     "misplat_version": (C.c_char_p, 0),
 }
 

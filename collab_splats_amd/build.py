@@ -45,6 +45,8 @@ SOURCES = {
     "pointcloud.hip": ["-ffp-contract=off"],
     # meshclean.hip: the same: edge lengths, plane hypotheses and the inlier rule equal the restatement (tests/) bit for bit
     "meshclean.hip": ["-ffp-contract=off"],
+    # depthcloud.hip: the same: edge bits, sampled pixels, back-projected points and normals equal the restatement (tests/)
+    "depthcloud.hip": ["-ffp-contract=off"],
 }
 
 
@@ -67,7 +69,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     hipcc = _hipcc()
     headers = [os.path.join(INCLUDE, "misplat.h"), os.path.join(CSRC, "sh_eval.h"), os.path.join(CSRC, "internal.h"),
                os.path.join(CSRC, "mc_tables.h"), os.path.join(CSRC, "cellhash.h"), os.path.join(CSRC, "radixsort.h"),
-               os.path.join(CSRC, "unionfind.h")]
+               os.path.join(CSRC, "unionfind.h"), os.path.join(CSRC, "hashmix.h")]
     jobs = []
     objs = []
     for src, extra in SOURCES.items():

@@ -16,6 +16,7 @@
 #include "internal.h"
 #include "cellhash.h"
 #include "unionfind.h"
+#include "hashmix.h"
 
 namespace {
 
@@ -268,14 +269,10 @@ __global__ __launch_bounds__(256) void segment_sum_kernel(const float* __restric
 }
 
 // ----------------------------------------------------------------------------------------------------------- planes
-// Draw `draw` of hypothesis i under `seed`: a counter-based integer hash (two rounds of a 32-bit finaliser), reduced to
-// 0 .. N - 1 by the high half of a 64-bit product.  tests/meshclean_restatement.py holds the same arithmetic.
+// Draw `draw` of hypothesis i under `seed`: a counter-based integer hash (two rounds of a 32-bit finaliser, hashmix.h),
+// reduced to 0 .. N - 1 by the high half of a 64-bit product.  tests/meshclean_restatement.py holds the same arithmetic.
 __device__ __forceinline__ uint32_t draw_index(uint32_t seed, uint32_t i, uint32_t draw, uint32_t N) {
-    uint32_t x = seed * 0x9E3779B1u + i * 0x85EBCA77u + draw * 0xC2B2AE3Du + 0x27D4EB2Fu;
-    x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
-    x += i;
-    x ^= x >> 15; x *= 0x2C1B3C6Du; x ^= x >> 12; x *= 0x297A2D39u; x ^= x >> 15;
-    return (uint32_t)(((unsigned long long)x * N) >> 32);
+    return (uint32_t)(((unsigned long long)mix32(seed, i, draw) * N) >> 32);
 }
 
 constexpr uint32_t kMaxDraws = 64;    // after so many draws a repeat is resolved by stepping to the next index (N >= 3)

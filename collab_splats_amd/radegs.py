@@ -597,6 +597,129 @@ class RadegsModel(nn.Module):
         from .pointcloud import clean_pcd
         return clean_pcd(self.means.detach(), **kwargs)[1]
 
+    @staticmethod
+    def _camera_poses(cameras: Sequence, device) -> tuple:
+        """(c2w [V,3,4], intrinsics [V,4] = (fx, fy, cx, cy)) of the cameras' own poses and intrinsics (what the reference's
+        exporters hand to ``get_colored_points_from_depth`` and ``project_pix``), built on the host, one upload each."""
+        c2w = torch.stack([c.camera_to_worlds.reshape(-1, 3, 4)[0].detach().float().cpu() for c in cameras])
+        rows = []
+        for c in cameras:
+            if all(isinstance(getattr(c, k, None), float) for k in ("fx", "fy", "cx", "cy")):
+                rows.append([c.fx, c.fy, c.cx, c.cy])
+            else:
+                K = c.get_intrinsics_matrices().reshape(-1, 3, 3)[0].detach().double().cpu()
+                rows.append([float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])])
+        return c2w.to(device), torch.tensor(rows, dtype=torch.float32).to(device)
+
+    @staticmethod
+    def _finish_cloud(out: Dict, down_sample_voxel, outlier_removal: bool, std_ratio: float) -> Dict:
+        """mesh.py:798-805: ``voxel_down_sample`` (normals and colours averaged with the points), then
+        ``remove_statistical_outlier(nb_neighbors=20, std_ratio)``.  Either drops the per-sample ids: a voxel's mean has none."""
+        from .pointcloud import remove_statistical_outlier, voxel_down_sample
+        if down_sample_voxel is not None and out["points"].shape[0] > 0:
+            names = [k for k in ("normals", "colors") if out.get(k) is not None]
+            pts, att, _, _ = voxel_down_sample(out["points"], down_sample_voxel, tuple(out[k] for k in names))
+            out.update(points=pts, frame_ids=None, pixel_ids=None, **dict(zip(names, att)))
+        if outlier_removal and out["points"].shape[0] > 0:
+            pts, ind = remove_statistical_outlier(out["points"], 20, std_ratio)
+            out["points"] = pts
+            for k in ("normals", "colors", "frame_ids", "pixel_ids"):
+                if out.get(k) is not None:
+                    out[k] = out[k][ind]
+        return out
+
+    @torch.no_grad()
+    def depth_normal_points(self, cameras: Sequence, total_points: int = 2_000_000, depth_name: str = "depth", masks=None,
+                            obb_box=None, filter_edges: bool = False, edge_threshold: float = 0.004, edge_dilation: int = 10,
+                            min_accumulation: Optional[float] = None, down_sample_voxel: Optional[float] = None,
+                            outlier_removal: bool = False, std_ratio: float = 2.0, seed: int = 0, batch_size: int = 4
+                            ) -> Dict[str, Optional[Tensor]]:
+        """The cloud of the reference's ``DepthAndNormalMapsPoisson.main`` (mesh.py:864-1002, ``normal_maps``) on the device:
+        ``samples_per_frame = (total_points + V) // V`` (:879); ``render_views`` batch by batch, nothing goes to the host;
+        ``depthcloud.depth_normal_cloud`` on ``maps[depth_name]``, ``rgb`` and ``normals`` with the cameras' own poses and
+        intrinsics and ``frame_offset`` = the batch's first frame, so ``batch_size`` changes no result; the crop
+        ``obb_box.within(points)`` (:988-994); the batches concatenated; then optionally ``voxel_down_sample`` and
+        ``remove_statistical_outlier(20, std_ratio)``.  ``masks`` ([V,H,W(,1)] bool) and the edge filter narrow the candidates
+        as ``depth_normal_cloud`` says.  ``min_accumulation`` None keeps the reference's behaviour: the depth maps carry the
+        image's maximum depth where alpha is 0, so those pixels are back-projected; a number makes ``accumulation >
+        min_accumulation`` part of the candidate rule.  Returns the dict of ``depth_normal_cloud`` with global ``frame_ids``
+        (``frame_ids`` and ``pixel_ids`` are None after a voxel reduction)."""
+        from .depthcloud import depth_normal_cloud
+        cameras = list(cameras)
+        n_views = len(cameras)
+        if n_views == 0:
+            raise ValueError("depth_normal_points: no cameras")
+        if not isinstance(total_points, int) or isinstance(total_points, bool) or total_points < 0:
+            raise ValueError(f"depth_normal_points: total_points must be a non-negative integer, got {total_points!r}")
+        samples_per_frame = (total_points + n_views) // n_views
+        if masks is not None:
+            masks = torch.as_tensor(masks).to(self.device)
+            if masks.shape[0] != n_views:
+                raise ValueError("depth_normal_points: one mask per camera")
+        c2w, intr = self._camera_poses(cameras, self.device)
+        bs = max(1, int(batch_size))
+        parts: Dict[str, List[Tensor]] = {k: [] for k in ("points", "normals", "colors", "frame_ids", "pixel_ids", "counts")}
+        for b in range(0, n_views, bs):
+            maps = self.render_views(cameras[b:b + bs], batch_size=bs)
+            if depth_name not in maps:
+                raise KeyError(f"depth_normal_points: depth_name {depth_name!r} is not among the rendered maps {sorted(maps)}")
+            valid = None if min_accumulation is None else maps["accumulation"] > float(min_accumulation)
+            out = depth_normal_cloud(maps[depth_name], maps["rgb"], maps["normals"], c2w[b:b + bs], intr[b:b + bs], samples_per_frame,
+                                     seed=seed, frame_offset=b, masks=None if masks is None else masks[b:b + bs], valid=valid,
+                                     filter_edges=filter_edges, edge_threshold=edge_threshold, edge_dilation=edge_dilation)
+            del maps
+            out["frame_ids"] = out["frame_ids"] + b
+            if obb_box is not None:
+                inside = obb_box.within(out["points"]).reshape(-1)
+                out["counts"] = torch.bincount(out["frame_ids"][inside] - b, minlength=out["counts"].shape[0]).to(torch.int32)
+                for k in ("points", "normals", "colors", "frame_ids", "pixel_ids"):
+                    out[k] = out[k][inside]
+            for k in parts:
+                parts[k].append(out[k])
+        cloud = {k: torch.cat(v, dim=0) for k, v in parts.items()}
+        return self._finish_cloud(cloud, down_sample_voxel, outlier_removal, std_ratio)
+
+    @torch.no_grad()
+    def gaussian_points(self, cameras: Optional[Sequence] = None, masks=None, min_opacity: Optional[float] = None,
+                        mask_color: Optional[Sequence[float]] = None, obb_box=None, down_sample_voxel: Optional[float] = None,
+                        outlier_removal: bool = False, std_ratio: float = 2.0) -> Dict[str, Optional[Tensor]]:
+        """The cloud of the reference's ``GaussiansToPoisson.main`` (mesh.py:676-805) on the device: the Gaussians themselves,
+        ``{"points", "normals", "colors", "indices"}`` (``indices`` int64: the Gaussian each point is, None after a voxel
+        reduction).  In order: ``depthcloud.gaussian_mask_filter`` against ``masks`` ([V,H,W(,1)] bool, with ``cameras``);
+        ``sigmoid(opacities) > min_opacity``; the ``mask_color`` test (a Gaussian is dropped unless all three clamped colour
+        channels differ from it, mesh.py:753-760); ``self.normals`` and the colours clamped to [0, 1]; the crop
+        ``obb_box.within``; ``voxel_down_sample`` and ``remove_statistical_outlier(20, std_ratio)``.  The colours are
+        Splatfacto's ``colors`` [UNVERIFIED-UPSTREAM]: 0.28209479177387814 features_dc + 0.5.  ``sh_degree == 0`` raises
+        ValueError where the reference asserts (:680)."""
+        from .depthcloud import gaussian_mask_filter
+        if not self.config.sh_degree > 0:
+            raise ValueError("gaussian_points: the model must have sh_degree > 0")
+        if (cameras is None) != (masks is None):
+            raise ValueError("gaussian_points: masks and cameras go together")
+        means = self.means.detach()
+        colors = torch.clamp(self.features_dc.detach().reshape(-1, 3) * 0.28209479177387814 + 0.5, 0.0, 1.0).float()
+        keep = torch.ones(means.shape[0], dtype=torch.bool, device=means.device)
+        if masks is not None:
+            cameras = list(cameras)
+            masks = torch.as_tensor(masks).to(self.device)
+            if masks.shape[0] != len(cameras):
+                raise ValueError("gaussian_points: one mask per camera")
+            c2w, intr = self._camera_poses(cameras, self.device)
+            keep &= gaussian_mask_filter(means, c2w, intr, masks)
+        if min_opacity is not None:
+            keep &= torch.sigmoid(self.opacities.detach()).reshape(-1) > float(min_opacity)
+        if mask_color is not None:
+            keep &= torch.all(colors != torch.tensor([list(mask_color)], dtype=colors.dtype, device=colors.device), dim=-1)
+        if obb_box is not None:
+            keep &= obb_box.within(means).reshape(-1)
+        ind = torch.nonzero(keep)[:, 0]
+        out = {"points": means[ind].float(), "normals": self.normals.detach()[ind], "colors": colors[ind], "frame_ids": ind,
+               "pixel_ids": None}
+        out = self._finish_cloud(out, down_sample_voxel, outlier_removal, std_ratio)
+        out["indices"] = out.pop("frame_ids")
+        del out["pixel_ids"]
+        return out
+
     def _scale_reg(self, dev) -> Tensor:
         """Splatfacto's scale regularisation: 0.1 * mean(max(max(s) / min(s), max_gauss_ratio) - max_gauss_ratio) of the
         activated scales, every 10th step; 0 otherwise [UNVERIFIED-UPSTREAM]."""

@@ -791,6 +791,42 @@ int misplat_meshclean_plane_moments(const float* points, int64_t n_points, const
                                     void* workspace, int64_t workspace_bytes, uint8_t* mask, double* moments,
                                     misplat_stream_t stream);
 
+/* ---- oriented point clouds from depth and normal maps (csrc/depthcloud.hip) ----------------------------
+ * depth [V,H,W] fp32, rgb and normals [V,H,W,3] fp32, masks / valid / edges / candidates [V,H,W] uint8 (non-zero: true),
+ * c2w [V,3,4] fp32 (nerfstudio's OpenGL pose), intrinsics [V,4] fp32 (fx, fy, cx, cy); V <= 65535, H W < 2^31.  The oracle is
+ * tests/depthcloud_restatement.py.  Every fp32 expression has one written order; integer atomics only: two runs are bitwise
+ * equal. */
+/* workspace bytes for the call `kind` (0 edges, 1 sample); -1 for sizes the library refuses. */
+int64_t misplat_depthcloud_workspace(int64_t n_views, int64_t height, int64_t width, int32_t kind);
+/* edges = the pixels with lap > threshold, lap = ((up + left) + (right + down)) - 4 inv of inv = 1 / (d + 1e-6) (0 outside the
+ * image), dilated by a square of Chebyshev radius `dilation` (0..63) clipped at the border. */
+int misplat_depthcloud_edges(const float* depth, int32_t n_views, int32_t height, int32_t width, float threshold,
+                             int32_t dilation, void* workspace, int64_t workspace_bytes, uint8_t* edges,
+                             misplat_stream_t stream);
+/* candidates = depth > 0 and masks and valid and not edges, over n_pixels = V H W; each of the three may be NULL. */
+int misplat_depthcloud_candidates(const float* depth, const uint8_t* masks, const uint8_t* valid, const uint8_t* edges,
+                                  int64_t n_pixels, uint8_t* candidates, misplat_stream_t stream);
+/* Per frame the min(S, n) candidates with the smallest (key, pixel), key = the 32-bit hash of (seed, frame_offset + v, pixel),
+ * or keys [V,H,W] (uint32 bits) when not NULL.  frame_ids / pixel_ids (capacity V min(S, H W) int32): the taken pixels by
+ * frame, then pixel; counts [V] int32; frame_base [V + 1] int32: the exclusive scan of counts, frame_base[V] the total.  All
+ * on the device. */
+int misplat_depthcloud_sample(const uint8_t* candidates, const int32_t* keys, int32_t n_views, int32_t height, int32_t width,
+                              int32_t samples_per_frame, uint32_t seed, uint32_t frame_offset, void* workspace,
+                              int64_t workspace_bytes, int32_t* frame_ids, int32_t* pixel_ids, int32_t* counts,
+                              int32_t* frame_base, misplat_stream_t stream);
+/* Per sample (frame v, pixel (u, w) = (pixel % W, pixel / W), depth d): R = c2w[:3,:3] diag(1,-1,-1), x = ((u + 0.5) - cx) d / fx,
+ * y likewise, points = ((R0 x + R1 y) + R2 d) + t; out_normals = R n, n = 2 m - 1 with y and z flipped, divided by
+ * max(sqrtf((nx nx + ny ny) + nz nz), 1e-12); colors = rgb there.  normals and out_normals: both or neither. */
+int misplat_depthcloud_backproject(const float* depth, const float* rgb, const float* normals, const float* c2w,
+                                   const float* intrinsics, int32_t n_views, int32_t height, int32_t width,
+                                   const int32_t* frame_ids, const int32_t* pixel_ids, int64_t n_samples, float* points,
+                                   float* out_normals, float* colors, misplat_stream_t stream);
+/* keep [N] uint8 = no view drops the centre: per view c = (p - t) @ R, a centre with c.z <= 0 is not tested, iu = floorf((c.x fx /
+ * c.z + cx) - 0.5) (iv likewise), dropped iff 0 < iu < W, 0 < iv < H and masks is 0 there. */
+int misplat_depthcloud_gaussian_filter(const float* means, int64_t n_gauss, const float* c2w, const float* intrinsics,
+                                       const uint8_t* masks, int32_t n_views, int32_t height, int32_t width, uint8_t* keep,
+                                       misplat_stream_t stream);
+
 /* Library identification ("misplat <version> gfx950"). */
 const char* misplat_version(void);
 
