@@ -2174,6 +2174,47 @@ _FULL_SIZE = FULL_SIZE
     # class, indexed buckets and head-of-grid fills are the DEFAULT path (nothing forced here)
     pytest.param(5_000_000, 1920, 1080, None, 1.0, True, 0.0, marks=_FULL_SIZE)])
 def test_steady_state_training_path_vs_c_port(dev, craster, monkeypatch, N, W, H, view, scale_mul, absgrad, opac_shift, lazy):
+    _steady_state_vs_c_port(dev, craster, monkeypatch, N, W, H, view, scale_mul, absgrad, opac_shift, lazy)
+
+
+@pytest.mark.parametrize("case", ["roll_translate", "combined"])
+def test_steady_state_training_path_cameras_vs_c_port(dev, craster, monkeypatch, case):
+    """The dense machinery -- background fill, rows cleared on touch, front-only pivots, the one-launch per-Gaussian
+    backward: all from 262 144 rows on -- under a rolled, translated, anisotropic camera and under an off-centre one with
+    near / far planes, ``radius_clip`` and ``alpha_max`` off their defaults (tests/camera_cases.py, scaled to 640 x 360).
+    Both cameras leave a sixth to a fifth of the tiles empty and a third below FRONT_MIN_BUCKET entries, and the buckets are
+    half as long as under the scene's own camera, so fewer pixels saturate before the end of their list: the share of tiles
+    that front-only ordering cuts is only asked to be 5 % here -- some tiles, so that the pivots of these cameras are in use;
+    front-only itself is asserted ON for all eight calls either way (152 and 112 of the 920 tiles were cut on the MI355X)."""
+    import camera_cases as cc
+    from collab_splats_amd import ops
+    N, W, H = 300_000, 640, 360
+    K, V, spec = cc.case(case, W, H)
+    # the launch-order records of this tile grid are left as they were found (test_cycling_views_... counts the records of its
+    # own eight views in the same table)
+    mine = lambda k: k[0] == dev.index and k[2:5] == (1, (W + 15) // 16, (H + 15) // 16)
+    saved = {k: (v[0].clone(), v[1].clone()) for k, v in ops._ORDER_TABLES.items() if mine(k)}
+    try:
+        st = _steady_state_vs_c_port(dev, craster, monkeypatch, N, W, H, None, 1.5, True, 0.0, "1", K=torch.from_numpy(K),
+                                     V=torch.from_numpy(V), front_share=0.05, **spec)
+    finally:
+        torch.cuda.synchronize()
+        for k in [k for k in ops._ORDER_TABLES if mine(k)]:
+            if k in saved:
+                ops._ORDER_TABLES[k][0].copy_(saved[k][0])
+                ops._ORDER_TABLES[k][1].copy_(saved[k][1])
+            else:
+                del ops._ORDER_TABLES[k]
+        ops.reset_graph_cache(dev)
+    cond = cc.conditions(case, st)
+    print(cond)
+    assert cond["visible"] > 60_000 and cond["n_isects"] > 200_000, cond     # (half of what the C port measured: 120 593 / 423 435 for combined)
+    if case == "combined":
+        assert cond["outside_planes"] > 30_000 and cond["alpha_share"] >= cc.MIN_ALPHA_SHARE, cond
+
+
+def _steady_state_vs_c_port(dev, craster, monkeypatch, N, W, H, view, scale_mul, absgrad, opac_shift, lazy, K=None, V=None,
+                            front_share=0.5, **spec):
     """What ``bench.py --ext-activations`` and the model mirror run from their second step on -- ONE set of raw leaves
     (log-scales, logits) reused call after call with ``scales_are_log`` / ``opacities_are_logit``, both phases in one
     launch with a speculative capacity, graph replay, the previous step's launch order, on-demand SH colours, ``touched``
@@ -2199,6 +2240,8 @@ def test_steady_state_training_path_vs_c_port(dev, craster, monkeypatch, N, W, H
     sc = random_scene(N, W, H, seed=42)
     if view is not None:
         sc["viewmats"] = view_matrix(view)
+    if K is not None:                                           # a camera of the caller's (and ``spec``: keywords off their defaults)
+        sc["Ks"], sc["viewmats"] = K[None].contiguous(), V[None].contiguous()
     log_s = (sc["log_scales"] + math.log(scale_mul)).contiguous()
     sc["opacity_logits"] = (sc["opacity_logits"] + opac_shift).contiguous()
     mode = "classic" if opac_shift < 0 else "antialiased"
@@ -2219,7 +2262,7 @@ def test_steady_state_training_path_vs_c_port(dev, craster, monkeypatch, N, W, H
             l.grad = None
         del out
         out = rasterization(*leaves, V, K, W, H, sh_degree=3, render_mode="RGB+ED", rasterize_mode=mode,
-                            absgrad=absgrad, return_depth_normal=True, scales_are_log=True, opacities_are_logit=True)
+                            absgrad=absgrad, return_depth_normal=True, scales_are_log=True, opacities_are_logit=True, **spec)
         torch.autograd.backward(list(out[:5]), ups_dev)
     torch.cuda.synchronize()
     took = {k: ops.PATH_STATS[k] - before.get(k, 0) for k in ops.PATH_STATS}
@@ -2246,13 +2289,14 @@ def test_steady_state_training_path_vs_c_port(dev, craster, monkeypatch, N, W, H
         assert meta["_bins"]["partial"] is not None and not meta._has("flatten_ids") and "flatten_ids" in meta
         fn = meta["_bins"]["partial"]["front_n"].cpu().numpy()
         cnt = np.diff(np.concatenate([meta["isect_offsets"].reshape(-1).cpu().numpy(), [meta["n_isects"]]]))
-        assert ((fn >= 0) & (fn < cnt)).sum() > 0.5 * fn.size, "most tiles should have been sorted in front only"
+        # (front_share: 0.5 under the scene's own camera, which fills the frame)
+        assert ((fn >= 0) & (fn < cnt)).sum() > front_share * fn.size, "most tiles should have been sorted in front only"
     # ---- the C restatement on the same raw parameters
     cr = craster.CRaster(np.float32)
     scales_np = torch.exp(leaves[2].detach()).cpu().numpy()
     op_np = torch.sigmoid(leaves[3].detach()).cpu().numpy()
     st = cr.forward(sc["means"].numpy(), sc["quats"].numpy(), scales_np, op_np, sc["sh"].numpy(), sc["viewmats"][0].numpy(),
-                    sc["Ks"][0].numpy(), W, H, sh_degree=3, render_mode="RGB+ED", rasterize_mode=mode)
+                    sc["Ks"][0].numpy(), W, H, sh_degree=3, render_mode="RGB+ED", rasterize_mode=mode, **spec)
     assert np.array_equal(st["proj"]["radii"], meta["radii"][0].cpu().numpy())
     assert np.array_equal(st["proj"]["depths"].view(np.uint32), meta["depths"][0].detach().cpu().numpy().view(np.uint32))
     assert np.array_equal(st["proj"]["means2d"].view(np.uint32), meta["means2d"][0].detach().cpu().numpy().view(np.uint32))
@@ -2275,6 +2319,7 @@ def test_steady_state_training_path_vs_c_port(dev, craster, monkeypatch, N, W, H
     assert_close_flips(meta["means2d"].grad[0], gr["v_means2d"], "v_means2d", proof=proof)
     if absgrad:
         assert_close_flips(meta["means2d"].absgrad[0], gr["v_means2d_abs"], "v_means2d_abs", proof=proof)
+    return st
 
 
 @pytest.mark.parametrize("margin,expect_flags", [(1.05, False), (0.6, True)])
