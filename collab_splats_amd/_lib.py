@@ -132,6 +132,10 @@ SYMBOLS = {
     "misplat_depthcloud_workspace": (C.c_int64, 4), "misplat_depthcloud_edges": (C.c_int, 10),
     "misplat_depthcloud_candidates": (C.c_int, 7), "misplat_depthcloud_sample": (C.c_int, 15),
     "misplat_depthcloud_backproject": (C.c_int, 15), "misplat_depthcloud_gaussian_filter": (C.c_int, 10),
+    "misplat_poisson_workspace": (C.c_int64, 2), "misplat_poisson_splat": (C.c_int, 13),
+    "misplat_poisson_system": (C.c_int, 10), "misplat_poisson_cg_init": (C.c_int, 11),
+    "misplat_poisson_cg_iterate": (C.c_int, 13), "misplat_poisson_sample": (C.c_int, 11),
+    "misplat_poisson_mean": (C.c_int, 6), "misplat_poisson_mc_pool": (C.c_int, 5),
     "misplat_version": (C.c_char_p, 0),
 }
 

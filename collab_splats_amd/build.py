@@ -47,6 +47,8 @@ SOURCES = {
     "meshclean.hip": ["-ffp-contract=off"],
     # depthcloud.hip: the same: edge bits, sampled pixels, back-projected points and normals equal the restatement (tests/)
     "depthcloud.hip": ["-ffp-contract=off"],
+    # poisson.hip: the same: the splat's int64 grids, the right-hand side and the diagonal equal the restatement (tests/)
+    "poisson.hip": ["-ffp-contract=off"],
 }
 
 

@@ -17,7 +17,7 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional, Sequence, Union
+from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import torch
 import torch.nn.functional as F
@@ -719,6 +719,28 @@ class RadegsModel(nn.Module):
         out["indices"] = out.pop("frame_ids")
         del out["pixel_ids"]
         return out
+
+    @torch.no_grad()
+    def poisson_mesh(self, cameras: Optional[Sequence], source: str = "depth_normal", depth: int = 8,
+                     trim_quantile: float = 0.01, min_density: Optional[float] = None, **cloud_kwargs
+                     ) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+        """What the reference's ``DepthAndNormalMapsPoisson.main`` and ``GaussiansToPoisson.main`` end in (mesh.py:809-818,
+        1023-1032) on the device: the oriented cloud of ``depth_normal_points(cameras, **cloud_kwargs)`` (``source``
+        "depth_normal") or ``gaussian_points(cameras, **cloud_kwargs)`` ("gaussians"), ``poisson.poisson_reconstruct`` at
+        ``depth`` and ``poisson.poisson_trim(quantile=trim_quantile, min_density=min_density)`` with the colours carried
+        along.  Returns ``(vertices [M,3], triangles [T,3] int32, colors [M,3], density [M])``: what ``extract_mesh`` returns,
+        plus the sampling density.  The solve is this project's dense-grid restatement, not Open3D's octree solver (DESIGN.md
+        section 20)."""
+        from .poisson import poisson_reconstruct, poisson_trim
+        if source == "depth_normal":
+            cloud = self.depth_normal_points(cameras, **cloud_kwargs)
+        elif source == "gaussians":
+            cloud = self.gaussian_points(cameras, **cloud_kwargs)
+        else:
+            raise ValueError(f"poisson_mesh: source must be 'depth_normal' or 'gaussians', got {source!r}")
+        v, t, c, d, _ = poisson_reconstruct(cloud["points"], cloud["normals"], cloud["colors"], depth=depth)
+        v, t, d, (c,), _ = poisson_trim(v, t, d, quantile=trim_quantile, min_density=min_density, attributes=(c,))
+        return v, t, c, d
 
     def _scale_reg(self, dev) -> Tensor:
         """Splatfacto's scale regularisation: 0.1 * mean(max(max(s) / min(s), max_gauss_ratio) - max_gauss_ratio) of the

@@ -827,6 +827,51 @@ int misplat_depthcloud_gaussian_filter(const float* means, int64_t n_gauss, cons
                                        const uint8_t* masks, int32_t n_views, int32_t height, int32_t width, uint8_t* keep,
                                        misplat_stream_t stream);
 
+/* ---- dense-grid screened Poisson surface reconstruction (csrc/poisson.hip) ---------------------------
+ * A restated uniform-grid solve, neither Kazhdan's adaptive octree nor Open3D's code (the oracle is
+ * tests/poisson_restatement.py; Open3D itself is unpinned).  G = 2^depth cells per axis, MISPLAT_POISSON_MIN_DEPTH <= depth <=
+ * MISPLAT_POISSON_MAX_DEPTH; cell (i, j, k) has its centre at origin + (idx + 0.5) h and the linear index i + G (j + G k).  Every
+ * grid is dense over G^3 cells; the fp32 grids are 16-byte aligned.  One workspace (bytes from misplat_poisson_workspace) serves
+ * every call; its first 8 doubles are the solver's state {r.z, p.Ap, r.r, b.b, alpha, beta, done (0 running, 1 converged, 2
+ * iteration cap, 3 p.Ap or r.z was 0), iterations} and must survive from cg_init to the last cg_iterate.  Every fp32 expression
+ * of the splat, the system and the sampler has one written order; integer atomics only and fixed-shape reductions: two runs are
+ * bitwise equal. */
+#define MISPLAT_POISSON_MIN_DEPTH 4
+#define MISPLAT_POISSON_MAX_DEPTH 9
+/* workspace bytes for (depth, n_points: the most values misplat_poisson_mean will see); -1 for sizes the library refuses. */
+int64_t misplat_poisson_workspace(int32_t depth, int64_t n_points);
+/* splat: per point g = (p - origin) / h - 0.5, i0 = floor(g), f = g - i0; each of the 8 surrounding cells (indices clamped to the
+ * grid) takes w = (wx wy) wz: w_grid += w, v_grid[a] += w n_a, c_grid[c] += w c_c, each as llrint(x 2^30) added with 64-bit integer
+ * atomics.  w_grid [G^3], v_grid and c_grid [3][G^3] int64, zeroed here; colors and c_grid may be NULL together. */
+int misplat_poisson_splat(const float* points, const float* normals, const float* colors, int64_t n_points, int32_t depth,
+                          float origin_x, float origin_y, float origin_z, float h, int64_t* w_grid, int64_t* v_grid,
+                          int64_t* c_grid, misplat_stream_t stream);
+/* system: w = float(w_grid) 2^-30; d = float(in-grid neighbours) + (point_weight w) / wbar, wbar = float((double(sum w_grid) 2^-30)
+ * / double(cells with w_grid > 0)); b = -0.5 ((dVx + dVy) + dVz), dV_a = V_a(i + e_a) - V_a(i - e_a), V = float(v_grid) 2^-30 and 0
+ * outside the grid. */
+int misplat_poisson_system(const int64_t* w_grid, const int64_t* v_grid, int32_t depth, float point_weight, void* workspace,
+                           int64_t workspace_bytes, float* w, float* b, float* d, misplat_stream_t stream);
+/* Jacobi-preconditioned conjugate gradients on (A x)(i) = d(i) x(i) - sum of the in-grid neighbours of x.  cg_init: x = 0, r = b,
+ * z = r / d, p = z and the state.  cg_iterate: n_iters (<= 4096) iterations of {ap = A p, alpha; x += alpha p, r -= alpha ap, z = r /
+ * d, beta; p = z + beta p}; alpha, beta and the done flag stay on the device, and once done is set (r.r <= tol^2 b.b, max_iters
+ * reached, p.Ap or r.z zero) every kernel is a no-op, so overshooting is harmless.  The caller reads the state when it likes. */
+int misplat_poisson_cg_init(const float* b, const float* d, int32_t depth, int32_t max_iters, void* workspace,
+                            int64_t workspace_bytes, float* x, float* r, float* z, float* p, misplat_stream_t stream);
+int misplat_poisson_cg_iterate(const float* d, int32_t depth, int32_t n_iters, double tol, int32_t max_iters, void* workspace,
+                               int64_t workspace_bytes, float* x, float* r, float* z, float* p, float* ap,
+                               misplat_stream_t stream);
+/* sample: out [Nq, n_channels] = the trilinear value of field [n_channels][G^3] (cell-centred) at queries [Nq,3]: g as in splat, i0
+ * clamped to 0 .. G - 2 and f to [0, 1]; v0 (1 - f) + v1 f along x, then y, then z.  1 <= n_channels <= 16. */
+int misplat_poisson_sample(const float* field, int32_t n_channels, int32_t depth, float origin_x, float origin_y, float origin_z,
+                           float h, const float* queries, int64_t n_queries, float* out, misplat_stream_t stream);
+/* mean (one double on the device) = the fp64 sum of values [n] in a fixed two-level order, divided by n. */
+int misplat_poisson_mean(const float* values, int64_t n, void* workspace, int64_t workspace_bytes, double* mean,
+                         misplat_stream_t stream);
+/* mc_pool: pool (5 G^3 fp32) = chi - iso as a fully allocated misplat_tsdf unit map: unit u = ux + U (uy + U uz), U = G / 16, in
+ * slot u; plane 0 chi - iso, plane 1 (weight) 1, planes 2..4 (colour) 0.  misplat_tsdf_mc_count / _emit extract it with
+ * voxel_size 1, lo 0, dims U, slot_map[u] = order[u] = u; a vertex v maps to origin + v h. */
+int misplat_poisson_mc_pool(const float* chi, int32_t depth, float iso, float* pool, misplat_stream_t stream);
+
 /* Library identification ("misplat <version> gfx950"). */
 const char* misplat_version(void);
 
