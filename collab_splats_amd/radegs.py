@@ -806,25 +806,100 @@ class RadegsModel(nn.Module):
 
 @dataclass
 class RadegsFeaturesModelConfig(RadegsModelConfig):
-    """rade_features_model.py: the hot-path field of its config -- the width of the distilled feature vector a Gaussian
-    carries (13 in the reference: 3 + 13 = 16 fused channels)."""
+    """rade_features_model.py:40-75: the fields of its config the model reads -- the width of the distilled feature vector a
+    Gaussian carries (13 in the reference: 3 + 13 = 16 fused channels), the decoder's hidden width and the two weights of
+    the feature loss (the reference's defaults)."""
     features_latent_dim: int = 13
+    mlp_hidden_dim: int = 64
+    features_loss_lambda: float = 1e-3
+    features_regularization_lambda: float = 0.1
 
 
 class RadegsFeaturesModel(RadegsModel):
-    """The rasterizer side of ``RadegsFeaturesModel`` (rade_features_model.py:195-478): every Gaussian carries
-    ``distill_features`` [N, latent_dim] that are composited behind its SH colour; ``get_outputs`` returns them as
-    ``outputs["features"]`` [H, W, latent_dim].  The decoder MLP, the text queries and the feature loss (:545-584) are
-    foundation-model code outside the path."""
+    """``RadegsFeaturesModel`` (rade_features_model.py:78-596): every Gaussian carries ``distill_features`` [N, latent_dim]
+    that are composited behind its SH colour; ``get_outputs`` returns them as ``outputs["features"]`` [H, W, latent_dim].
+    With ``metadata`` (``feature_type``: the main feature model's name, ``feature_dims``: name -> (C, H, W)) the model also
+    owns the decoder MLP (``self.decoder``, an optimizer group), ``decode_features`` (:149-189) and the cosine feature loss
+    of ``get_loss_dict`` (:545-584), all on the kernels of csrc/featloss.hip.  The text encoder and
+    its queries (CLIP) are foundation-model code outside the path."""
 
     def __init__(self, config: RadegsFeaturesModelConfig, means, scales, quats, opacities, features_dc, features_rest,
-                 distill_features: Tensor):
+                 distill_features: Tensor, metadata: Optional[Dict] = None):
         super().__init__(config, means, scales, quats, opacities, features_dc, features_rest)
         if distill_features.shape != (means.shape[0], config.features_latent_dim):
             raise ValueError(f"distill_features must be [N, {config.features_latent_dim}], got {tuple(distill_features.shape)}")
         self.gauss_params["distill_features"] = nn.Parameter(distill_features)
+        self.metadata = None
+        if metadata is not None:
+            from .featureloss import TwoLayerMLP
+            if "feature_type" not in metadata or "feature_dims" not in metadata:
+                raise ValueError("RadegsFeaturesModel: metadata needs 'feature_type' and 'feature_dims'")
+            dims = {name: tuple(int(v) for v in d) for name, d in metadata["feature_dims"].items()}
+            if metadata["feature_type"] not in dims:
+                raise ValueError(f"RadegsFeaturesModel: feature_type {metadata['feature_type']!r} is not among feature_dims "
+                                 f"{sorted(dims)}")
+            self.metadata = {"feature_type": metadata["feature_type"], "feature_dims": dims}
+            self.main_features_name = metadata["feature_type"]
+            self.main_features_dims = dims[self.main_features_name]                 # C, H, W
+            self.decoder = TwoLayerMLP(config.features_latent_dim, config.mlp_hidden_dim, dims)
 
     distill_features = property(lambda self: self.gauss_params["distill_features"])
 
     def _features_for_render(self, pick):
         return pick(self.distill_features)
+
+    def _need_decoder(self, what: str) -> None:
+        if self.metadata is None:
+            raise ValueError(f"{what}: the model was built without metadata (feature_type, feature_dims): it has no decoder")
+
+    @torch.no_grad()
+    def decode_features(self, features: Tensor, resize_factor: float = 1.0) -> Dict[str, Tensor]:
+        """rade_features_model.py:149-189: ``features`` [H, W, latent_dim] -> name -> [C_b, h, w].  The features are resized to
+        (int(H_main * resize_factor), int(W_main * resize_factor)) and decoded; the main branch comes back at that size, every
+        other branch resized to its own (H_b, W_b).  Inference only (no gradient): training goes through ``get_loss_dict``."""
+        from .featureloss import feature_decode
+        self._need_decoder("decode_features")
+        _, Hm, Wm = self.main_features_dims
+        main_hw = (int(Hm * resize_factor), int(Wm * resize_factor))
+        if min(main_hw) < 1:
+            raise ValueError(f"decode_features: resize_factor {resize_factor} leaves an empty map {main_hw}")
+        dims = {name: ((d[0],) + main_hw if name == self.main_features_name else d)
+                for name, d in self.metadata["feature_dims"].items()}
+        return feature_decode(features.detach(), self.decoder, dims, main_hw)
+
+    def get_loss_dict(self, outputs, batch, metrics_dict=None) -> Dict[str, Tensor]:
+        """rade_features_model.py:545-584: the base model's losses plus ``features_loss`` = features_loss_lambda * sum over
+        the feature models of weight * mean(1 - cos(decoded, ground truth)), weight 1 for the main model and
+        features_regularization_lambda for the others.  ``batch["features_dict"]`` (name -> [C, H, W]) may live on any device.
+        One autograd node (``ops.feature_loss``).  A model without metadata returns the base dict, as before."""
+        loss_dict = super().get_loss_dict(outputs, batch, metrics_dict)
+        if self.metadata is None:
+            return loss_dict
+        if batch is None or "features_dict" not in batch:
+            raise ValueError("get_loss_dict: the batch carries no 'features_dict'")
+        features = outputs["features"]
+        dims = self.metadata["feature_dims"]
+        if set(batch["features_dict"]) != set(dims):
+            raise ValueError(f"get_loss_dict: features_dict has {sorted(batch['features_dict'])}, the model's feature_dims "
+                             f"{sorted(dims)}")
+        gt = {}
+        for name, d in dims.items():
+            t = batch["features_dict"][name]
+            if tuple(t.shape) != d:
+                raise ValueError(f"get_loss_dict: features_dict[{name!r}] is {tuple(t.shape)}, feature_dims say {d}")
+            gt[name] = t.to(device=features.device, dtype=torch.float32)
+        loss_dict["features_loss"] = ops.feature_loss(features, self.decoder, gt, self.main_features_name,
+                                                      self.config.features_regularization_lambda,
+                                                      self.config.features_loss_lambda)
+        return loss_dict
+
+    def get_gaussian_param_groups(self) -> Dict[str, List[nn.Parameter]]:
+        """One optimizer group per Gaussian parameter, ``distill_features`` among them (rade_features_model.py:586-589)."""
+        return {name: [self.gauss_params[name]] for name in self.gauss_params.keys()}
+
+    def get_param_groups(self) -> Dict[str, List[nn.Parameter]]:
+        """rade_features_model.py:591-596: the Gaussian groups and, for a model with a decoder, ``decoder``."""
+        groups = self.get_gaussian_param_groups()
+        if self.metadata is not None:
+            groups["decoder"] = list(self.decoder.parameters())
+        return groups

@@ -421,6 +421,41 @@ int misplat_ssim_fwd(int32_t height, int32_t width, const float* rgb, const floa
 int misplat_ssim_bwd(int32_t height, int32_t width, const float* rgb, const float* gt, const float* scratch,
                      const float* g_main, float ssim_lambda, float* v_rgb, misplat_stream_t stream);
 
+/* ---- the features model's decoder and cosine feature loss (rade_features_model.py:149-189, :545-584; utils/features.py:
+ * 408-478): csrc/featloss.hip.
+ *   x = bilinear(features [H,W,L] -> (main_h, main_w)) (align_corners=False, no antialiasing), h = relu(w_hidden x + b_hidden),
+ *   p_b = w_out[b] h_b + b_out[b] with h_b = h resampled bilinearly to the branch's (H_b, W_b) (equal to resizing p_b),
+ *   features_loss = loss_lambda * sum_b weights[b] * mean_q (1 - <p_b, gt_b> / (max(|p_b|, 1e-8) * max(|gt_b|, 1e-8))).
+ * features: pixel (y, x) starts at features[(y * W + x) * pix_stride] (pix_stride >= latent: a channel slice of a wider
+ * image is read in place); w_hidden [hidden, latent], b_hidden [hidden]; dims: HOST array [n_branches][3] = (C_b, H_b, W_b);
+ * w_out / b_out / gt: HOST arrays of n_branches DEVICE pointers ([C_b, hidden], [C_b], [C_b, H_b, W_b]); weights: HOST
+ * array [n_branches].  Limits: latent 1..32, hidden 1..256, 1..4 branches, C_b 1..2^20, every map at most 2^28 pixels.
+ * scratch: misplat_featloss_scratch_floats(...) floats (decode_only != 0: what misplat_feature_decode needs), written by
+ * the forward and read AND written by the backward; -1 for sizes outside the limits.  branch_sums (or NULL): device
+ * [n_branches] sums of 1 - cos over a branch's pixels; features_loss (or NULL): device scalar.  Four or five launches;
+ * no prediction is stored; every sum over pixels runs in a fixed order (final sums in fp64): reproducible bit for bit. */
+int64_t misplat_featloss_scratch_floats(int32_t latent, int32_t hidden, int32_t main_h, int32_t main_w, int32_t n_branches,
+                                        const int32_t* dims, int32_t decode_only);
+int misplat_featloss_fwd(int32_t height, int32_t width, int32_t latent, int32_t pix_stride, const float* features,
+                         int32_t hidden, const float* w_hidden, const float* b_hidden, int32_t main_h, int32_t main_w,
+                         int32_t n_branches, const int32_t* dims, const float* const* w_out, const float* const* b_out,
+                         const float* const* gt, const float* weights, float loss_lambda, float* scratch,
+                         float* branch_sums /* or NULL */, float* features_loss /* or NULL */, misplat_stream_t stream);
+/* g_loss: the upstream gradient of features_loss as a DEVICE scalar (or NULL = 0).  v_features [H,W,latent] (contiguous,
+ * every element written: exact zeros where no tap of the resize lands; W * latent < 2^31), v_w_hidden [hidden, latent], v_b_hidden [hidden];
+ * v_w_out / v_b_out: HOST arrays of n_branches DEVICE pointers.  Six launches, no atomics. */
+int misplat_featloss_bwd(int32_t height, int32_t width, int32_t latent, int32_t hidden, const float* w_hidden, int32_t main_h,
+                         int32_t main_w, int32_t n_branches, const int32_t* dims, const float* const* w_out,
+                         const float* const* b_out, const float* const* gt, const float* weights, float loss_lambda,
+                         float* scratch, const float* g_loss, float* v_features, float* v_w_hidden, float* v_b_hidden,
+                         float* const* v_w_out, float* const* v_b_out, misplat_stream_t stream);
+/* Inference: the predictions themselves.  out: HOST array of n_branches DEVICE pointers, each [C_b, H_b, W_b] or, with
+ * channels_last != 0, [H_b * W_b, C_b].  Two or three launches. */
+int misplat_feature_decode(int32_t height, int32_t width, int32_t latent, int32_t pix_stride, const float* features,
+                           int32_t hidden, const float* w_hidden, const float* b_hidden, int32_t main_h, int32_t main_w,
+                           int32_t n_branches, const int32_t* dims, const float* const* w_out, const float* const* b_out,
+                           float* const* out, int32_t channels_last, float* scratch, misplat_stream_t stream);
+
 /* ---- the whole forward of rasterization() (rade_gs_model.py:439-465) as ONE host entry: csrc/raster.hip.
  * Every pointer is a caller-allocated device buffer of the size the per-stage entry points above document
  * (n_isects_host: 8 bytes of PINNED host memory).
