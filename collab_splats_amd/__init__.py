@@ -23,6 +23,7 @@ from .depthcloud import backproject, depth_edges, depth_normal_cloud, gaussian_m
 from .featureloss import TwoLayerMLP, feature_decode, feature_loss  # noqa: F401
 from .poisson import (poisson_grid, poisson_reconstruct, poisson_solve, poisson_splat, poisson_system,  # noqa: F401
                       poisson_trim)
+from .grouping import FrontGaussians, MemoryBank, convert_matched_mask, front_gaussians, project_gaussians  # noqa: F401
 
 __version__ = "0.1.0"
 

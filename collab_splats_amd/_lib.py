@@ -138,6 +138,11 @@ SYMBOLS = {
     "misplat_poisson_system": (C.c_int, 10), "misplat_poisson_cg_init": (C.c_int, 11),
     "misplat_poisson_cg_iterate": (C.c_int, 13), "misplat_poisson_sample": (C.c_int, 11),
     "misplat_poisson_mean": (C.c_int, 6), "misplat_poisson_mc_pool": (C.c_int, 5),
+    "misplat_grouping_workspace": (C.c_int64, 1), "misplat_grouping_project": (C.c_int, 8),
+    "misplat_grouping_mask_ids": (C.c_int, 7), "misplat_grouping_front": (C.c_int, 15),
+    "misplat_grouping_relabel": (C.c_int, 7), "misplat_grouping_overlap": (C.c_int, 8),
+    "misplat_grouping_assign": (C.c_int, 8), "misplat_grouping_merge_count": (C.c_int, 10),
+    "misplat_grouping_merge_copy": (C.c_int, 12), "misplat_grouping_members": (C.c_int, 6),
     "misplat_version": (C.c_char_p, 0),
 }
 

@@ -51,6 +51,8 @@ SOURCES = {
     "depthcloud.hip": ["-ffp-contract=off"],
     # poisson.hip: the same: the splat's int64 grids, the right-hand side and the diagonal equal the restatement (tests/)
     "poisson.hip": ["-ffp-contract=off"],
+    # grouping.hip: integer work throughout; its one double product (front_percentage n) has nothing to contract with
+    "grouping.hip": [],
 }
 
 

@@ -742,6 +742,41 @@ class RadegsModel(nn.Module):
         v, t, d, (c,), _ = poisson_trim(v, t, d, quantile=trim_quantile, min_density=min_density, attributes=(c,))
         return v, t, c, d
 
+    @torch.no_grad()
+    def associate_masks(self, cameras: Sequence, composite_masks: Sequence, front_percentage: float = 0.5, num_patches: int = 32,
+                        iou_threshold: float = 0.1, bank=None):
+        """The reference's ``GroupingClassifier.associate`` loop (grouping.py:226-282) on the device, for views whose segmentation
+        is given: every camera is rendered in evaluation mode, the front Gaussians of every mask of its ``composite_masks[i]``
+        ([H,W] integer ids, 0 the background) are selected from ``self.info`` (``grouping.front_gaussians``), labelled against the
+        bank and merged into it.  Views are processed in order, ALL of them (the reference's loop ends with a stray ``break`` after
+        the first frame).  ``bank`` (or None: a new ``grouping.MemoryBank`` with ``iou_threshold``) carries labels over from
+        earlier calls.  Returns ``(bank, labels, matched)``: per view the int64 labels [M] of its masks and the int32 image of
+        ``grouping.convert_matched_mask``.  The crop box must be unset: the bank indexes all the model's Gaussians."""
+        from .grouping import MemoryBank, convert_matched_mask, front_gaussians
+        cameras, composite_masks = list(cameras), list(composite_masks)
+        if len(cameras) != len(composite_masks):
+            raise ValueError(f"associate_masks: {len(cameras)} cameras but {len(composite_masks)} composite masks")
+        if self.crop_box is not None:
+            raise ValueError("associate_masks: unset the crop box first (set_crop(None)): the bank indexes all Gaussians")
+        n = int(self.means.shape[0])
+        if bank is None:
+            bank = MemoryBank(n, iou_threshold)
+        elif not isinstance(bank, MemoryBank) or bank.num_gaussians != n:
+            raise ValueError(f"associate_masks: bank must be a MemoryBank over the model's {n} Gaussians")
+        labels: List[Tensor] = []
+        matched: List[Tensor] = []
+        was_training = self.training
+        self.eval()
+        try:
+            for camera, mask in zip(cameras, composite_masks):
+                self.get_outputs(camera.to(self.device) if hasattr(camera, "to") else camera)
+                front = front_gaussians(self.info, mask, front_percentage, num_patches)
+                labels.append(bank.associate(front))
+                matched.append(convert_matched_mask(labels[-1], mask))
+        finally:
+            self.train(was_training)
+        return bank, labels, matched
+
     def _scale_reg(self, dev) -> Tensor:
         """Splatfacto's scale regularisation: 0.1 * mean(max(max(s) / min(s), max_gauss_ratio) - max_gauss_ratio) of the
         activated scales, every 10th step; 0 otherwise [UNVERIFIED-UPSTREAM]."""

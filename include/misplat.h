@@ -907,6 +907,53 @@ int misplat_poisson_mean(const float* values, int64_t n, void* workspace, int64_
  * voxel_size 1, lo 0, dims U, slot_map[u] = order[u] = u; a vertex v maps to origin + v h. */
 int misplat_poisson_mc_pool(const float* chi, int32_t depth, float iso, float* pool, misplat_stream_t stream);
 
+/* ---- Gaussian grouping: mask front sets and cross-view label banks (csrc/grouping.hip) ----------------
+ * The oracle is tests/grouping_restatement.py; everything compared is an integer.  n_gauss < 2^31, width height < 2^31, mask
+ * [H,W] int32 with ids 0..65535 (0: background; other values count as background), 1 <= num_patches <= 128, n_masks n_labels <=
+ * 2^26.  Integer atomics only: two runs are bitwise equal.  No call reads anything back.
+ * One workspace (bytes from misplat_grouping_workspace) serves every call; misplat_grouping_mask_ids leaves the id -> rank table
+ * of its mask image at the front of it, which misplat_grouping_front and misplat_grouping_relabel read. */
+/* workspace bytes for n_gauss Gaussians; -1 for sizes the library refuses. */
+int64_t misplat_grouping_workspace(int64_t n_gauss);
+/* radii [N,2] int32, means2d [N,2] fp32 of one camera: valid = any(radii > 1); flat = x + y W of the pixel rintf(mean) (half to
+ * even) clamped to the image (a NaN lands on 0). */
+int misplat_grouping_project(const int32_t* radii, const float* means2d, int64_t n_gauss, int32_t width, int32_t height,
+                             int32_t* flat, uint8_t* valid, misplat_stream_t stream);
+/* mask_ids (capacity 65535) = the positive ids present in mask, ascending; n_masks [1] = their number M.  On the device. */
+int misplat_grouping_mask_ids(const int32_t* mask, int64_t n_pixels, void* workspace, int64_t workspace_bytes, int32_t* mask_ids,
+                              int32_t* n_masks, misplat_stream_t stream);
+/* mask_of [N] = the rank m of the mask a Gaussian is selected for, -1 for the others; counts [n_masks] = the set sizes.  A valid
+ * Gaussian on a pixel of mask m is in the cell (m, min(y / ceil(H / P), P - 1), min(x / ceil(W / P), P - 1)); a cell of n keeps its
+ * max((int64)(front_percentage n), 1) smallest by (depth, id), the product in double.  n_masks: what misplat_grouping_mask_ids
+ * found for this mask with this workspace.  0 < front_percentage <= 1. */
+int misplat_grouping_front(const int32_t* flat, const uint8_t* valid, const float* depths, int64_t n_gauss, const int32_t* mask,
+                           int32_t width, int32_t height, int32_t num_patches, int32_t n_masks, double front_percentage,
+                           void* workspace, int64_t workspace_bytes, int32_t* mask_of, int32_t* counts, misplat_stream_t stream);
+/* out [n_pixels] = labels[rank of the pixel's id] + 1, 0 on background; labels [M] int64, the table as _front. */
+int misplat_grouping_relabel(const int32_t* mask, int64_t n_pixels, const void* workspace, int64_t workspace_bytes,
+                             const int64_t* labels, int32_t* out, misplat_stream_t stream);
+/* The bank: per Gaussian the ascending list of its labels, bank_labels[bank_off[g] .. bank_off[g + 1]).
+ * overlap: count [n_masks, n_labels] int32 (zeroed here) = the Gaussians with mask_of = m that carry label l. */
+int misplat_grouping_overlap(const int32_t* mask_of, int64_t n_gauss, const int32_t* bank_off, const int32_t* bank_labels,
+                             int32_t n_masks, int32_t n_labels, int32_t* count, misplat_stream_t stream);
+/* labels [n_masks] int64: with n_labels = 0 the masks' own ranks; otherwise per mask the lowest label of maximal q =
+ * float(count / (set_size + count + 1e-8)) (the quotient in double), or, when q < iou_threshold (fp32), the next new label,
+ * numbered from n_labels in mask order.  n_new [1] = the number of new labels.  One workgroup. */
+int misplat_grouping_assign(const int32_t* count, const int32_t* set_sizes, int32_t n_masks, int32_t n_labels, float iou_threshold,
+                            int64_t* labels, int32_t* n_new, misplat_stream_t stream);
+/* Every Gaussian with mask_of = m >= 0 gets labels[m] inserted into its list if absent.  merge_count: new_off [N + 1] = the
+ * offsets of the merged lists (new_off[N]: the new number of pairs, which must stay < 2^31); merge_copy: the merged lists into
+ * new_labels (capacity new_capacity >= new_off[N]) and sizes [n_labels_new] int32 += the Gaussians each label gained. */
+int misplat_grouping_merge_count(const int32_t* mask_of, int64_t n_gauss, const int64_t* labels, int32_t n_masks,
+                                 const int32_t* bank_off, const int32_t* bank_labels, void* workspace, int64_t workspace_bytes,
+                                 int32_t* new_off, misplat_stream_t stream);
+int misplat_grouping_merge_copy(const int32_t* mask_of, int64_t n_gauss, const int64_t* labels, int32_t n_masks,
+                                const int32_t* bank_off, const int32_t* bank_labels, const int32_t* new_off, int64_t new_capacity,
+                                int32_t* new_labels, int32_t* sizes, int32_t n_labels_new, misplat_stream_t stream);
+/* flags [N] uint8 = the Gaussian carries `label`. */
+int misplat_grouping_members(const int32_t* bank_off, const int32_t* bank_labels, int64_t n_gauss, int32_t label, uint8_t* flags,
+                             misplat_stream_t stream);
+
 /* Library identification ("misplat <version> gfx950"). */
 const char* misplat_version(void);
 
