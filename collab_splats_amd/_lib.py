@@ -111,6 +111,8 @@ SYMBOLS = {
     "misplat_ssim_scratch_floats": (C.c_int64, 2), "misplat_ssim_fwd": (C.c_int, 10), "misplat_ssim_bwd": (C.c_int, 9),
     "misplat_featloss_scratch_floats": (C.c_int64, 7), "misplat_featloss_fwd": (C.c_int, 21), "misplat_featloss_bwd": (C.c_int, 22),
     "misplat_feature_decode": (C.c_int, 18),
+    "misplat_textquery_fold": (C.c_int, 9), "misplat_textquery_map": (C.c_int, 18), "misplat_textquery_rows": (C.c_int, 15),
+    "misplat_textquery_upsample": (C.c_int, 7),
     "misplat_bucket_plan": (C.c_int, 3), "misplat_bucket_count": (C.c_int, 10), "misplat_bucket_rows": (C.c_int, 14),
     "misplat_bucket_tiles": (C.c_int, 11),
     "misplat_unit_order": (C.c_int, 4), "misplat_raster_fwd": (C.c_int, 5), "misplat_raster_bwd": (C.c_int, 4), "misplat_raster_bwd_plan": (C.c_int, 2), "misplat_graph_cache_create": (C.c_void_p, 1),

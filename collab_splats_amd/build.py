@@ -36,6 +36,8 @@ SOURCES = {
     "ssim.hip": [],
     # featloss.hip: contraction allowed (the decoder's dot products are multiply-add chains; the test oracle is fp64)
     "featloss.hip": [],
+    # textquery.hip: contraction allowed, as featloss.hip (multiply-add chains; the test oracle is fp64)
+    "textquery.hip": [],
     "optim.hip": [],
     # tsdf.hip: fixed IEEE operation order, as project.hip: the voxel grids equal the fp32 restatement (tests/) bit for bit
     "tsdf.hip": ["-ffp-contract=off"],
@@ -75,7 +77,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     hipcc = _hipcc()
     headers = [os.path.join(INCLUDE, "misplat.h"), os.path.join(CSRC, "sh_eval.h"), os.path.join(CSRC, "internal.h"),
                os.path.join(CSRC, "mc_tables.h"), os.path.join(CSRC, "cellhash.h"), os.path.join(CSRC, "radixsort.h"),
-               os.path.join(CSRC, "unionfind.h"), os.path.join(CSRC, "hashmix.h")]
+               os.path.join(CSRC, "unionfind.h"), os.path.join(CSRC, "hashmix.h"), os.path.join(CSRC, "bilinear.h")]
     jobs = []
     objs = []
     for src, extra in SOURCES.items():

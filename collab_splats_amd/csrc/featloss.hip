@@ -22,6 +22,7 @@
 #include <cmath>
 #include <cstdint>
 
+#include "bilinear.h"
 #include "misplat.h"
 
 namespace {
@@ -60,23 +61,6 @@ struct Plan {
     size_t total;
     int max_tiles, max_S, max_units, max_PS, max_blk;
 };
-
-struct Taps { int i0, i1; float l0, l1; };
-
-// F.interpolate(mode="bilinear", align_corners=False): source coordinate (dst + 0.5) * (n_in / n_out) - 0.5, clamped at 0,
-// the upper tap clamped to the last index.  The coordinate is formed in fp64, the two weights are fp32.
-__device__ __forceinline__ Taps taps(int dst, int n_in, double scale) {
-    double src = ((double)dst + 0.5) * scale - 0.5;
-    if (src < 0.0) src = 0.0;
-    int i0 = (int)src;
-    if (i0 > n_in - 1) i0 = n_in - 1;
-    Taps t;
-    t.i0 = i0;
-    t.i1 = i0 + (i0 < n_in - 1 ? 1 : 0);
-    t.l1 = (float)(src - (double)i0);
-    t.l0 = 1.0f - t.l1;
-    return t;
-}
 
 // the destinations whose taps can touch source index i: source coordinate in (i - 1, i + 1), one more on each side for
 // rounding; every candidate is then tested with taps() itself, so the gather is the exact transpose of the sampling

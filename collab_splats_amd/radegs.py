@@ -843,11 +843,12 @@ class RadegsModel(nn.Module):
 class RadegsFeaturesModelConfig(RadegsModelConfig):
     """rade_features_model.py:40-75: the fields of its config the model reads -- the width of the distilled feature vector a
     Gaussian carries (13 in the reference: 3 + 13 = 16 fused channels), the decoder's hidden width and the two weights of
-    the feature loss (the reference's defaults)."""
+    the feature loss (the reference's defaults), and the method of the text-query similarity map."""
     features_latent_dim: int = 13
     mlp_hidden_dim: int = 64
     features_loss_lambda: float = 1e-3
     features_regularization_lambda: float = 0.1
+    similarity_method: str = "pairwise"          # rade_features_model.py:74: "standard" or "pairwise"
 
 
 class RadegsFeaturesModel(RadegsModel):
@@ -865,6 +866,7 @@ class RadegsFeaturesModel(RadegsModel):
             raise ValueError(f"distill_features must be [N, {config.features_latent_dim}], got {tuple(distill_features.shape)}")
         self.gauss_params["distill_features"] = nn.Parameter(distill_features)
         self.metadata = None
+        self.text_query = None                                          # the folded queries of ``set_text_queries``
         if metadata is not None:
             from .featureloss import TwoLayerMLP
             if "feature_type" not in metadata or "feature_dims" not in metadata:
@@ -901,6 +903,46 @@ class RadegsFeaturesModel(RadegsModel):
         dims = {name: ((d[0],) + main_hw if name == self.main_features_name else d)
                 for name, d in self.metadata["feature_dims"].items()}
         return feature_decode(features.detach(), self.decoder, dims, main_hw)
+
+    SIMILARITY_RESIZE_FACTOR = 8.0                                      # rade_features_model.py:509-511
+
+    @torch.no_grad()
+    def set_text_queries(self, text_embeddings: Optional[Tensor], n_positive: int = 1) -> None:
+        """The text queries of the similarity map (rade_features_model.py:484-491 ``set_text_queries``, with the embeddings
+        in place of the strings: the text encoder is the caller's).  ``text_embeddings`` [Q, C_main] float32 on the model's
+        device, unit-norm rows, the first ``n_positive`` positive and the others negative; they are folded into the main
+        branch of the decoder once (``ops.fold_text_queries``) and kept as ``self.text_query``.  The fold is a SNAPSHOT of the
+        decoder's weights at this call: call it again after the decoder has trained on.  None clears the queries."""
+        if text_embeddings is None:
+            self.text_query = None
+            return
+        self._need_decoder("set_text_queries")
+        self.text_query = ops.fold_text_queries(self.decoder, self.main_features_name, text_embeddings, n_positive)
+
+    @torch.no_grad()
+    def get_outputs_for_camera(self, camera, obb_box=None) -> Dict[str, Union[Tensor, List, None]]:
+        """rade_features_model.py:493-539: the base outputs and, with text queries set, ``outputs["similarity"]`` [H, W, 1]: the
+        similarity (``config.similarity_method``, temperature 0.05) of the main branch at the working size (int(H_main * 8.0),
+        int(W_main * 8.0)), resized bilinearly to the image -- on ``ops.similarity_map``, without the decoded features.  One
+        deliberate difference: the reference assigns ``outs["similarity"]`` inside its "the shapes differ" block (:525-538), so
+        a view already at the working size gets no map; here the map is always set.  Without queries, and for an empty crop
+        (which renders no features): the base outputs."""
+        outs = super().get_outputs_for_camera(camera, obb_box)
+        if self.text_query is not None and "features" in outs:
+            _, Hm, Wm = self.main_features_dims
+            work_hw = (int(Hm * self.SIMILARITY_RESIZE_FACTOR), int(Wm * self.SIMILARITY_RESIZE_FACTOR))
+            outs["similarity"] = ops.similarity_map(outs["features"], self.text_query, work_hw, tuple(outs["rgb"].shape[:2]),
+                                                    method=self.config.similarity_method)
+        return outs
+
+    @torch.no_grad()
+    def gaussian_similarity(self, softmax_temp: float = 0.05) -> Tensor:
+        """The similarity of every Gaussian's ``distill_features`` to the text queries, [N] in 0..1 (the reference's
+        commented-out ``similarity`` property, rade_features_model.py:143-147), ready for a threshold or a
+        ``clean_gaussians``-style mask; no [N, C] decoded tensor is formed."""
+        if self.text_query is None:
+            raise ValueError("gaussian_similarity: no text queries are set (set_text_queries)")
+        return ops.gaussian_similarity(self.distill_features.detach(), self.text_query, self.config.similarity_method, softmax_temp)
 
     def get_loss_dict(self, outputs, batch, metrics_dict=None) -> Dict[str, Tensor]:
         """rade_features_model.py:545-584: the base model's losses plus ``features_loss`` = features_loss_lambda * sum over

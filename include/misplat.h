@@ -456,6 +456,34 @@ int misplat_feature_decode(int32_t height, int32_t width, int32_t latent, int32_
                            int32_t n_branches, const int32_t* dims, const float* const* w_out, const float* const* b_out,
                            float* const* out, int32_t channels_last, float* scratch, misplat_stream_t stream);
 
+/* ---- text-query similarity of rendered views and of Gaussians without the decoded features (rade_features_model.py:493-539,
+ * :143-147; utils/features.py:237-325 compute_similarity): csrc/textquery.hip.  The text embeddings E [Q, C] (unit-norm rows,
+ * the first n_positive positive, the others negative) meet a prediction p = w_out h + b_out only through E p = A h + c with
+ * A = E w_out [Q, hidden] and c = E b_out [Q]; per pixel
+ *   x = bilinear(features -> (work_h, work_w)) (the rule of the feature loss above; the image's own size: the latent as it is),
+ *   hid = relu(w_hidden x + b_hidden), z_q = (A_q . hid + c_q) / softmax_temp,
+ *   method 0 ("standard"): softmax(z)[:n_positive].sum(); method 1 ("pairwise"): exp(p) / (n_neg exp(p) + sum_j exp(n_j)) with
+ *   p the mean of the positive z and n_j the negative ones; the maximum is subtracted before any exp; a NaN result is 0.
+ * Limits: latent 1..32, hidden 1..256, n_queries 2..64, 1 <= n_positive <= n_queries - 1, channels 1..2^20, softmax_temp
+ * finite and > 0, every map at most 2^28 pixels, at most 2^28 rows.  One launch each, no atomics, every sum in index order:
+ * reproducible bit for bit.
+ * fold: A and c from embeddings [Q, channels], w_out [channels, hidden], b_out [channels]; each output is one fp64 sum over the
+ * channels in index order, rounded once.  Once per query set. */
+int misplat_textquery_fold(int32_t n_queries, int32_t channels, int32_t hidden, const float* embeddings, const float* w_out,
+                           const float* b_out, float* A, float* c, misplat_stream_t stream);
+/* similarity [work_h, work_w] of an image features [H,W,latent] read through pix_stride as the feature loss reads it. */
+int misplat_textquery_map(int32_t height, int32_t width, int32_t latent, int32_t pix_stride, const float* features, int32_t hidden,
+                          const float* w_hidden, const float* b_hidden, int32_t n_queries, int32_t n_positive, const float* A,
+                          const float* c, int32_t method, float softmax_temp, int32_t work_h, int32_t work_w, float* similarity,
+                          misplat_stream_t stream);
+/* similarity [n_rows] of latents [n_rows, latent] (row r starts at latents[r * row_stride]): the same body, no resize. */
+int misplat_textquery_rows(int64_t n_rows, int32_t latent, int32_t row_stride, const float* latents, int32_t hidden,
+                           const float* w_hidden, const float* b_hidden, int32_t n_queries, int32_t n_positive, const float* A,
+                           const float* c, int32_t method, float softmax_temp, float* similarity, misplat_stream_t stream);
+/* out [out_h, out_w] = bilinear(in [in_h, in_w]) by the same rule: the reference's F.interpolate of the heat map. */
+int misplat_textquery_upsample(int32_t in_h, int32_t in_w, const float* in, int32_t out_h, int32_t out_w, float* out,
+                               misplat_stream_t stream);
+
 /* ---- the whole forward of rasterization() (rade_gs_model.py:439-465) as ONE host entry: csrc/raster.hip.
  * Every pointer is a caller-allocated device buffer of the size the per-stage entry points above document
  * (n_isects_host: 8 bytes of PINNED host memory).
