@@ -17,8 +17,10 @@
 namespace {
 
 __device__ __forceinline__ void atomic_max_float(float* addr, float v) {
-    // order-preserving integer view: works for any finite float
-    if (v >= 0.f) atomicMax(reinterpret_cast<int*>(addr), __float_as_int(v));
+    // order-preserving integer view: works for any finite float.  The path goes by the SIGN BIT, not by v >= 0: -0.0 compares
+    // >= 0 but carries the bit pattern of INT_MIN, which loses the signed maximum against every negative value and the
+    // -FLT_MAX seed (a map of only -0.0 came out as -FLT_MAX)
+    if (__float_as_int(v) >= 0) atomicMax(reinterpret_cast<int*>(addr), __float_as_int(v));
     else atomicMin(reinterpret_cast<unsigned int*>(addr), __float_as_uint(v));
 }
 
