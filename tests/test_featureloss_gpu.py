@@ -11,7 +11,13 @@ bit by chance, but no fp32 result can be asked to carry less than one rounding o
 MULTIPLE = 8: the kernels sum a prediction's 64 products in two chains, a pixel's channel sums in up to 8 splits x 4 waves and
 the pixel sums in tiles, where the restatement's einsum / sum use yet another order; different orders over n terms differ by
 about sqrt(n) roundings relative to the terms' size, which for the largest sums here (768 channels, 660 pixels) is some 25
-roundings against the restatement's own few.  (The figures of a GPU run belong in DESIGN.md section 21; this test prints them.)"""
+roundings against the restatement's own few.  (The figures of a GPU run belong in DESIGN.md section 21; this test prints them.)
+
+LAUNCH_SCENES (featureloss_scenes.py) go on to 2 064 channels and 17 820 pixels under the same rule: there the kernels' sums
+over pixels are partial sums per 256 pixels and per pixel split that meet in fp64, chains no longer than above, while the
+restatement's own error grows with its longer sums.  Their inputs are built so that no hidden pre-activation lies within fp32
+rounding of zero (asserted in test_featureloss_host.py); without that the restatement's error, and with it the bound, would
+measure one flipped relu and not rounding."""
 import pytest
 import torch
 
@@ -54,7 +60,7 @@ def bound(yard: float) -> float:
     return min(MULTIPLE * max(yard, FLOOR), CAP)
 
 
-@pytest.mark.parametrize("name", list(S.SCENES))
+@pytest.mark.parametrize("name", list(S.SCENES) + list(S.LAUNCH_SCENES))
 def test_loss_and_gradients_against_the_fp64_oracle(dev, name):
     scene, ora, y32 = S.make(name), S.oracle(name), S.yardstick(name)
     got = run_gpu(scene, dev)
@@ -65,7 +71,7 @@ def test_loss_and_gradients_against_the_fp64_oracle(dev, name):
         assert got["grads"][k].shape == ref.shape and bool(torch.isfinite(got["grads"][k]).all()), k
         rows.append((k, S.grad_err(got["grads"][k], ora["grads"], k), S.grad_err(y32["grads"][k], ora["grads"], k)))
     for k, e_gpu, e_32 in rows:
-        print(f"featureloss {name:10s} {k:14s} gpu {e_gpu:.3e}  fp32 restatement {e_32:.3e}  bound {bound(e_32):.3e}")
+        print(f"featureloss {name:16s} {k:14s} gpu {e_gpu:.3e}  fp32 restatement {e_32:.3e}  bound {bound(e_32):.3e}")
     for k, e_gpu, e_32 in rows:
         assert e_gpu <= bound(e_32), (name, k, e_gpu, e_32)
         assert e_gpu <= CAP, (name, k, e_gpu)
@@ -141,8 +147,10 @@ def test_all_zero_ground_truth_pixel_adds_one_and_no_gradient(dev):
     assert float(ora["grads"]["features"][sorted(rows)[0], sorted(cols)[0]].abs().max()) == 0.0
 
 
-@pytest.mark.parametrize("name", ["down_int", "wide"])
+@pytest.mark.parametrize("name", ["down_int", "wide", "pixel_splits", "hidden_256_split"])
 def test_two_runs_are_equal_bit_for_bit(dev, name):
+    """``pixel_splits`` / ``hidden_256_split``: the partial sums per pixel split and per channel split, and the passes over 64
+    hidden units, are in the sums as well."""
     scene = S.make(name)
     a, b = run_gpu(scene, dev), run_gpu(scene, dev)
     assert torch.equal(a["loss"], b["loss"])
@@ -155,9 +163,20 @@ def test_two_runs_are_equal_bit_for_bit(dev, name):
 def test_strided_features_equal_the_contiguous_run(dev):
     """``features`` as the [..., 3:16] slice of a [45, 80, 17] tensor (what ``outputs["features"]`` is): read in place through
     the pixel stride, every result equal to the contiguous run's bit for bit."""
+    _strided_equals_contiguous(dev, "down_int")
+
+
+def test_strided_features_equal_the_contiguous_run_under_pixel_splits(dev):
+    """The same on ``pixel_splits`` ([33, 67, 17]): thousands of main-map pixels, each reading its own render pixel."""
+    _strided_equals_contiguous(dev, "pixel_splits")
+
+
+def _strided_equals_contiguous(dev, name):
     from collab_splats_amd import featureloss
-    scene = S.make("down_int")
-    wide = torch.randn(45, 80, 17, generator=torch.Generator().manual_seed(5))
+    scene = S.make(name)
+    H, W, L = scene["features"].shape
+    assert L == 13
+    wide = torch.randn(H, W, 17, generator=torch.Generator().manual_seed(5))
     wide[..., 3:16] = scene["features"]
     view = wide.to(dev)[..., 3:16]
     assert not view.is_contiguous()
@@ -165,11 +184,13 @@ def test_strided_features_equal_the_contiguous_run(dev):
     assert kept.data_ptr() == view.data_ptr() and stride == 17                      # no copy
     a, b = run_gpu(scene, dev), run_gpu(scene, dev, features=view)
     assert torch.equal(a["loss"], b["loss"])
+    for n in a["sums"]:
+        assert torch.equal(a["sums"][n], b["sums"][n]), n
     for k in a["grads"]:
         assert torch.equal(a["grads"][k], b["grads"][k]), k
 
 
-@pytest.mark.parametrize("name", ["down_int", "enlarge"])
+@pytest.mark.parametrize("name", ["down_int", "enlarge", "hidden_200", "mixed_axes"])
 def test_v_features_is_written_whole(dev, name):
     """Two runs whose gradient buffers start from different garbage (NaN, then a large number, left in the allocator's
     freed blocks): equal results, all finite, and exact zeros on the render rows no tap of the resize touches."""
@@ -182,7 +203,7 @@ def test_v_features_is_written_whole(dev, name):
         outs.append(run_gpu(scene, dev)["grads"]["features"])
     assert bool(torch.isfinite(outs[0]).all()) and torch.equal(outs[0], outs[1])
     untouched = (ora["grads"]["features"] == 0).all(-1).all(-1)                       # rows the oracle leaves at zero
-    if name == "down_int":
+    if name in ("down_int", "mixed_axes"):
         assert int(untouched.sum()) >= H // 2
     assert bool((outs[0].cpu()[untouched] == 0).all())
 
@@ -218,6 +239,30 @@ def test_decode_features_against_the_restatement(dev, name, resize_factor):
         e_gpu, e_32 = S.rel_err(got[n], res[torch.float64][n]), S.rel_err(res[torch.float32][n], res[torch.float64][n])
         print(f"decode {name} x{resize_factor} {n}: gpu {e_gpu:.3e} fp32 restatement {e_32:.3e}")
         assert e_gpu <= bound(e_32), (n, e_gpu, e_32)
+
+
+@pytest.mark.parametrize("name", ["hidden_200", "channel_cap", "four_branches", "pixel_splits"])
+def test_feature_decode_in_both_layouts(dev, name):
+    """``feature_decode`` itself (the generic path with a ragged chunk, 8 channel splits, four branches, thousands of pixels)
+    against the fp64 restatement's decode, the bound as above; ``channels_last`` equals the transposed default bit for bit."""
+    import collab_splats_amd as m
+    scene = S.make(name)
+    dec = (scene["w_hidden"].to(dev), scene["b_hidden"].to(dev), {n: (w.to(dev), b.to(dev)) for n, (w, b) in scene["branches"].items()})
+    main_hw = scene["dims"][scene["main"]][1:]
+    got = m.feature_decode(scene["features"].to(dev), dec, scene["dims"], main_hw)
+    last = m.feature_decode(scene["features"].to(dev), dec, scene["dims"], main_hw, channels_last=True)
+    torch.cuda.synchronize()
+    res = {dt: R.decode(scene["features"].to(dt), scene["w_hidden"].to(dt), scene["b_hidden"].to(dt),
+                        {n: (w.to(dt), b.to(dt)) for n, (w, b) in scene["branches"].items()}, scene["dims"], scene["main"])
+           for dt in (torch.float64, torch.float32)}
+    assert list(got) == list(scene["dims"]) and list(last) == list(scene["dims"])
+    for n, (C, Hb, Wb) in scene["dims"].items():
+        assert got[n].shape == (C, Hb, Wb) and last[n].shape == (Hb * Wb, C)
+        assert bool(torch.isfinite(got[n]).all())
+        assert torch.equal(last[n], got[n].reshape(C, Hb * Wb).t()), n
+        e_gpu, e_32 = S.rel_err(got[n], res[torch.float64][n]), S.rel_err(res[torch.float32][n], res[torch.float64][n])
+        print(f"decode {name:16s} {n:5s} gpu {e_gpu:.3e}  fp32 restatement {e_32:.3e}  bound {bound(e_32):.3e}")
+        assert e_gpu <= bound(e_32), (name, n, e_gpu, e_32)
 
 
 def test_per_gaussian_forward_against_the_linear_form(dev):

@@ -50,10 +50,11 @@ def test_cosine_restatement_matches_torch_at_its_edges():
     assert torch.allclose(tiny.grad, want, rtol=1e-12, atol=0.0)
 
 
-@pytest.mark.parametrize("name", ["down_int", "branch_up", "odd_dims"])
+@pytest.mark.parametrize("name", ["down_int", "branch_up", "odd_dims", "four_branches", "mixed_axes"])
 def test_resizing_the_hidden_layer_equals_resizing_the_predictions(name):
     """fp64: the loss and every gradient agree to 1e-12 (relative to the largest entry) between the model's order (resize
-    p_b) and the kernels' (apply branch b's layer to the resized h)."""
+    p_b) and the kernels' (apply branch b's layer to the resized h).  ``four_branches`` and ``mixed_axes`` hold resizes that
+    shrink one axis and enlarge the other."""
     a, b = S.oracle(name), R.run(S.make(name), torch.float64, resized_hidden=True)
     assert S.rel_err(b["loss"], a["loss"]) <= 1e-12
     for k in a["grads"]:
@@ -110,6 +111,123 @@ def test_scenes_hold_what_they_promise():
         assert float(dead["grads"][k].abs().max()) == 0.0, k
     # the all-zero prediction is the clamped case: d/dp = -g / (1e-8 |g|), which reaches b_out (and only b_out)
     assert float(dead["grads"]["b_out.main"].abs().max()) > 1.0
+
+
+def test_launch_scenes_hold_their_input_conditions():
+    """What makes the fp32 yardstick of a launch scene mean something: no hidden pre-activation on which fp32 and fp64 can
+    disagree about the relu.  Exact-grid scenes: the fp32 pre-activations equal the fp64 ones bit for bit, and some are exact
+    zeros.  Random scenes: every non-zero fp64 pre-activation is at least 2^-18 of the largest (fp32's 2^-24 per operation
+    over the few terms of a dot product stays well inside that), and fp32 agrees on every sign."""
+    assert set(S.EXACT_GRID) <= set(S.LAUNCH_SCENES) and not set(S.LAUNCH_SCENES) & set(S.SCENES)
+    for name in S.LAUNCH_SCENES:
+        sc = S.make(name)
+        for n, t in sc["gt"].items():
+            assert t.shape[1] >= 2 and t.shape[2] >= 3, (name, n)
+            zero = (t == 0).all(0)
+            assert bool(zero[S.ZERO_GT_PIXEL]) and int(zero.sum()) == 1, (name, n)
+        p64, p32 = S.preactivations(name, torch.float64), S.preactivations(name, torch.float32)
+        if name in S.EXACT_GRID:
+            f, wh, bh = sc["features"], sc["w_hidden"], sc["b_hidden"]
+            assert torch.equal(f * 16, (f * 16).round()) and float(f.abs().max()) <= 4.0, name
+            for t in (wh, bh):
+                assert torch.equal(t * 256, (t * 256).round()) and float(t.abs().max()) <= 1.0, name
+            assert torch.equal(p32.double(), p64), name
+            assert int((p64 == 0).sum()) > 0, name
+        else:
+            nonzero = p64[p64 != 0].abs()
+            assert float(nonzero.min()) >= S.PREACT_MARGIN * float(nonzero.max()), (name, float(nonzero.min() / nonzero.max()))
+            assert torch.equal(torch.sign(p32).double(), torch.sign(p64)), name
+
+
+def _plan(name):
+    """The launch shape ``make_plan`` (csrc/featloss.hip) derives from a scene's sizes, restated: per branch the 16-channel
+    units, the channel splits S, the 64-pixel tiles of the per-pixel kernels, the 256-pixel tiles and the pixel splits PS of
+    the weight-gradient kernel, and whether the branch is at the main map's resolution; then the chunks of 64 hidden units.
+    A change of ``make_plan`` has to be restated here, and the regimes below looked at again."""
+    (_, _), L, Hd, main, others, _ = S.ALL_SCENES[name]
+    rows = {}
+    for n, (C, Hb, Wb) in zip(S.branch_names(len(others)), [main] + list(others)):
+        P, units = Hb * Wb, -(-C // 16)
+        tiles256 = -(-P // 256)
+        rows[n] = {"C": C, "P": P, "units": units, "S": min(max(units // 8, 1), 8), "tiles64": -(-P // 64), "tiles256": tiles256,
+                   "PS": min(max(tiles256 // 4, 1), 16), "identity": (Hb, Wb) == tuple(main[1:])}
+    return L, Hd, -(-Hd // 64), rows
+
+
+def _tiles_of_split(row, split):
+    return len(range(split, row["tiles256"], row["PS"]))
+
+
+def test_plan_restatement_on_the_production_shape():
+    """The shape every training step runs (render 1080 x 1920, clip 768 x 64 x 114, dino 384): 7 pixel splits, 6 and 3
+    channel splits -- what LAUNCH_SCENES stands in for at a size a test can afford."""
+    for C, S_want in ((768, 6), (384, 3), (1024, 8)):
+        units = -(-C // 16)
+        assert min(max(units // 8, 1), 8) == S_want
+    assert min(max(-(-64 * 114 // 256) // 4, 1), 16) == 7
+
+
+def test_launch_scenes_reach_their_regimes():
+    """Each row of LAUNCH_SCENES reaches the launch regime it is there for (a later change of ``make_plan`` or of a scene must
+    not un-cover one silently)."""
+    old = [_plan(n) for n in S.SCENES]
+    assert all(r["PS"] == 1 for _, _, _, rows in old for r in rows.values())                 # what SCENES never reaches
+    assert all(Hd <= 64 for _, Hd, _, _ in old) and max(len(rows) for _, _, _, rows in old) == 3
+
+    L, Hd, chunks, rows = _plan("pixel_splits")
+    m, a = rows["main"], rows["aux0"]
+    assert Hd == 64 and (m["P"], m["tiles256"], m["PS"]) == (2211, 9, 2)
+    assert (_tiles_of_split(m, 0), _tiles_of_split(m, 1)) == (5, 4)                          # unequal splits
+    assert m["P"] - 8 * 256 == 163 and 2 * 64 < 163 < 3 * 64                                 # last tile: one wave partial, one empty
+    assert (a["P"], a["tiles256"], a["PS"]) == (3100, 13, 3) and not a["identity"]           # another PS: early exit of blockIdx.y == 2
+
+    L, Hd, chunks, rows = _plan("split_cap")
+    m = rows["main"]
+    assert Hd == 64 and len(rows) == 1 and m["C"] < 16 and (m["P"], m["tiles256"], m["PS"]) == (17820, 70, 16)
+    assert m["tiles256"] // 4 > 16                                                           # the cap binds
+    assert sorted({_tiles_of_split(m, s) for s in range(16)}) == [4, 5]
+    H, W = S.ALL_SCENES["split_cap"][0]
+    assert (2 * H, W) == S.ALL_SCENES["split_cap"][3][1:]                                    # rows enlarge by 2: taps 1/4, 3/4
+
+    L, Hd, chunks, rows = _plan("hidden_256_split")
+    m = rows["main"]
+    assert (L, Hd, chunks) == (32, 256, 4) and (m["units"], m["S"], m["PS"]) == (17, 2, 2) and m["units"] % 8 != 0
+    assert not rows["aux0"]["identity"] and rows["aux0"]["C"] % 16 != 0
+
+    L, Hd, chunks, rows = _plan("hidden_200_split")
+    assert (Hd, chunks, Hd % 64) == (200, 4, 8) and rows["main"]["PS"] == 2
+    assert (rows["aux0"]["tiles256"], rows["aux0"]["PS"]) == (14, 3) and not rows["aux0"]["identity"]
+
+    for name in ("pixel_splits", "hidden_256_split", "hidden_200_split"):                    # exact taps (1, 0)
+        assert S.ALL_SCENES[name][0] == S.ALL_SCENES[name][3][1:], name
+
+    L, Hd, chunks, rows = _plan("hidden_65")
+    assert (Hd, chunks, Hd % 64) == (65, 2, 1)
+
+    L, Hd, chunks, rows = _plan("hidden_200")
+    assert (Hd, chunks, Hd % 64) == (200, 4, 8)
+    (_, hm, wm), (_, hb, wb) = S.ALL_SCENES["hidden_200"][3], S.ALL_SCENES["hidden_200"][4][0]
+    assert hb > hm and wb > wm                                                               # an enlarging branch
+
+    L, Hd, chunks, rows = _plan("hidden_1")
+    assert (L, Hd, chunks) == (1, 1, 1)
+
+    L, Hd, chunks, rows = _plan("channel_cap")
+    assert Hd == 64 and [r["units"] for r in rows.values()] == [73, 129]
+    for r in rows.values():
+        assert r["units"] // 8 > 8 and r["S"] == 8                                           # the cap binds
+        assert r["units"] % 32 != 0 and r["P"] < 64                                          # uneven units a wave, one partial wave
+    assert rows["main"]["C"] % 16 != 0 and rows["aux0"]["C"] % 16 == 0                       # a ragged last unit, and a whole one
+
+    L, Hd, chunks, rows = _plan("four_branches")
+    assert len(rows) == 4 and Hd < 64
+    assert [r["identity"] for r in rows.values()] == [True, True, False, False]
+    assert sorted({r["S"] for r in rows.values()}) == [1, 2]
+    (_, hm, wm), others = S.ALL_SCENES["four_branches"][3], S.ALL_SCENES["four_branches"][4]
+    assert others[1][1] > hm and others[1][2] < wm and others[2][1] < hm and others[2][2] > wm   # one axis each way, both ways
+
+    (H, W), (_, hm, wm), (_, hb, wb) = S.ALL_SCENES["mixed_axes"][0], S.ALL_SCENES["mixed_axes"][3], S.ALL_SCENES["mixed_axes"][4][0]
+    assert H > hm and W < wm and hb > hm and wb < wm
 
 
 def test_two_layer_mlp_has_the_checkpoint_layout():
