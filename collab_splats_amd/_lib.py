@@ -145,6 +145,8 @@ SYMBOLS = {
     "misplat_grouping_relabel": (C.c_int, 7), "misplat_grouping_overlap": (C.c_int, 8),
     "misplat_grouping_assign": (C.c_int, 8), "misplat_grouping_merge_count": (C.c_int, 10),
     "misplat_grouping_merge_copy": (C.c_int, 12), "misplat_grouping_members": (C.c_int, 6),
+    "misplat_bilagrid_scratch_floats": (C.c_int64, 5), "misplat_bilagrid_slice_fwd": (C.c_int, 9),
+    "misplat_bilagrid_slice_bwd": (C.c_int, 14), "misplat_bilagrid_tv_fwd": (C.c_int, 8), "misplat_bilagrid_tv_bwd": (C.c_int, 8),
     "misplat_version": (C.c_char_p, 0),
 }
 

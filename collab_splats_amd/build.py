@@ -55,6 +55,9 @@ SOURCES = {
     "poisson.hip": ["-ffp-contract=off"],
     # grouping.hip: integer work throughout; its one double product (front_percentage n) has nothing to contract with
     "grouping.hip": [],
+    # bilagrid.hip: fixed IEEE operation order: the luma z (black exactly 0, white exactly 1), the interval floor(gz) and the
+    # lerp form a + t (b - a) equal the fp32 restatement (tests/); a locally constant grid is reproduced bit for bit
+    "bilagrid.hip": ["-ffp-contract=off"],
 }
 
 

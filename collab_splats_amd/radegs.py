@@ -218,6 +218,10 @@ class RadegsModelConfig:
     # the factor ``_get_downscale_factor()`` returns and back, :223)
     num_downscales: int = 0
     resolution_schedule: int = 3000
+    # Splatfacto's per-camera bilateral grid [UNVERIFIED-UPSTREAM]: a learned affine colour transform per training camera,
+    # applied to the training render (rade_gs_model.py:231-234), with its TV loss (:284-289); grid_shape = (GW, GH, L)
+    use_bilateral_grid: bool = False
+    grid_shape: Tuple[int, int, int] = (16, 16, 8)
 
 
 class RadegsModel(nn.Module):
@@ -228,9 +232,18 @@ class RadegsModel(nn.Module):
     """
 
     def __init__(self, config: RadegsModelConfig, means: Tensor, scales: Tensor, quats: Tensor,
-                 opacities: Tensor, features_dc: Tensor, features_rest: Tensor):
+                 opacities: Tensor, features_dc: Tensor, features_rest: Tensor, num_train_data: int = 0):
         super().__init__()
         self.config = config
+        if config.use_bilateral_grid:
+            # Splatfacto's ``bil_grids`` [UNVERIFIED-UPSTREAM]: one grid per training image (``num_train_data``)
+            from .bilagrid import BilateralGrid
+            if int(num_train_data) < 1:
+                raise ValueError(f"RadegsModel: use_bilateral_grid needs num_train_data >= 1 (one grid per training camera), "
+                                 f"got {num_train_data}")
+            if len(config.grid_shape) != 3:
+                raise ValueError(f"RadegsModel: grid_shape must be (GW, GH, L), got {tuple(config.grid_shape)}")
+            self.bil_grids = BilateralGrid(int(num_train_data), *(int(v) for v in config.grid_shape))
         self.gauss_params = nn.ParameterDict({
             "means": nn.Parameter(means), "scales": nn.Parameter(scales), "quats": nn.Parameter(quats),
             "opacities": nn.Parameter(opacities.reshape(-1, 1)), "features_dc": nn.Parameter(features_dc),
@@ -424,6 +437,10 @@ class RadegsModel(nn.Module):
             ep = ops.outputs_epilogue(render, alpha, expected_depths, median_depths, expected_normals, bg_list, want_depth_im)
             rgb, expected_depths, median_depths, normals = ep[0], ep[1], ep[2], ep[3]
             depth_im = ep[4].squeeze(0) if want_depth_im else None
+        cam_meta = getattr(camera, "metadata", None)
+        if self.config.use_bilateral_grid and self.training and cam_meta is not None and "cam_idx" in cam_meta:
+            # rade_gs_model.py:231-234: the camera's colour transform, on the composited and clamped training render only
+            rgb = ops.bilagrid_slice(rgb.contiguous(), self.bil_grids.grids, int(cam_meta["cam_idx"]))
         if background.shape[0] == 3 and not self.training:
             background = background.expand(H, W, 3)
         out = {
@@ -825,7 +842,7 @@ class RadegsModel(nn.Module):
                 loss_dict["scale_reg"] = self._scale_reg(rgb.device)
             if with_dn:
                 loss_dict["depth_normal_loss"] = dn_loss
-            return loss_dict
+            return self._add_tv_loss(loss_dict)
         if gt is not None:
             if self.config.ssim_lambda > 0:
                 raise MisplatError(f"get_loss_dict: main_loss (L1 + SSIM) takes float32 images of equal shape on the GPU; got "
@@ -836,7 +853,26 @@ class RadegsModel(nn.Module):
         if with_dn:
             depth_normal_loss = ((1 - self.config.depth_ratio) * e1.mean() + self.config.depth_ratio * e2.mean())
             loss_dict["depth_normal_loss"] = self.config.depth_normal_lambda * depth_normal_loss
+        return self._add_tv_loss(loss_dict)
+
+    def _add_tv_loss(self, loss_dict: Dict[str, Tensor]) -> Dict[str, Tensor]:
+        """Splatfacto's "total variation loss (cameras)" (rade_gs_model.py:284-289) [UNVERIFIED-UPSTREAM]: 10 x the TV of every
+        camera's grid, while training with ``use_bilateral_grid``; otherwise the dict as it is."""
+        if self.config.use_bilateral_grid and self.training:
+            loss_dict["tv_loss"] = 10 * ops.bilagrid_tv_loss(self.bil_grids.grids)
         return loss_dict
+
+    def get_gaussian_param_groups(self) -> Dict[str, List[nn.Parameter]]:
+        """One optimizer group per Gaussian parameter (Splatfacto's ``get_gaussian_param_groups``)."""
+        return {name: [self.gauss_params[name]] for name in self.gauss_params.keys()}
+
+    def get_param_groups(self) -> Dict[str, List[nn.Parameter]]:
+        """The Gaussian groups and, with ``use_bilateral_grid``, ``bilateral_grid`` (configs/rade_gs_method.py:78-83: Adam,
+        lr 2e-3 falling to 1e-4 after 1000 warm-up steps; the schedule is the trainer's)."""
+        groups = self.get_gaussian_param_groups()
+        if self.config.use_bilateral_grid:
+            groups["bilateral_grid"] = list(self.bil_grids.parameters())
+        return groups
 
 
 @dataclass
@@ -860,8 +896,8 @@ class RadegsFeaturesModel(RadegsModel):
     its queries (CLIP) are foundation-model code outside the path."""
 
     def __init__(self, config: RadegsFeaturesModelConfig, means, scales, quats, opacities, features_dc, features_rest,
-                 distill_features: Tensor, metadata: Optional[Dict] = None):
-        super().__init__(config, means, scales, quats, opacities, features_dc, features_rest)
+                 distill_features: Tensor, metadata: Optional[Dict] = None, num_train_data: int = 0):
+        super().__init__(config, means, scales, quats, opacities, features_dc, features_rest, num_train_data=num_train_data)
         if distill_features.shape != (means.shape[0], config.features_latent_dim):
             raise ValueError(f"distill_features must be [N, {config.features_latent_dim}], got {tuple(distill_features.shape)}")
         self.gauss_params["distill_features"] = nn.Parameter(distill_features)
@@ -970,13 +1006,10 @@ class RadegsFeaturesModel(RadegsModel):
                                                       self.config.features_loss_lambda)
         return loss_dict
 
-    def get_gaussian_param_groups(self) -> Dict[str, List[nn.Parameter]]:
-        """One optimizer group per Gaussian parameter, ``distill_features`` among them (rade_features_model.py:586-589)."""
-        return {name: [self.gauss_params[name]] for name in self.gauss_params.keys()}
-
     def get_param_groups(self) -> Dict[str, List[nn.Parameter]]:
-        """rade_features_model.py:591-596: the Gaussian groups and, for a model with a decoder, ``decoder``."""
-        groups = self.get_gaussian_param_groups()
+        """rade_features_model.py:591-596: the Gaussian groups (``distill_features`` among them, :586-589), for a model with a
+        decoder ``decoder``, and with ``use_bilateral_grid`` ``bilateral_grid`` (configs/rade_features_method.py:89-94)."""
+        groups = super().get_param_groups()
         if self.metadata is not None:
             groups["decoder"] = list(self.decoder.parameters())
         return groups

@@ -982,6 +982,36 @@ int misplat_grouping_merge_copy(const int32_t* mask_of, int64_t n_gauss, const i
 int misplat_grouping_members(const int32_t* bank_off, const int32_t* bank_labels, int64_t n_gauss, int32_t label, uint8_t* flags,
                              misplat_stream_t stream);
 
+/* ---- bilateral-grid colour correction of a training view and the grids' total-variation loss (the reference's call sites
+ * rade_gs_model.py:231-234, :284-289; the operation is nerfstudio's, restated from the published method, DESIGN.md section
+ * 24): csrc/bilagrid.hip.  grids [num, 12, L, GH, GW] fp32, channel 4 c + j = entry (c, j) of a 3 x 4 affine; per pixel
+ *   x = px / (W - 1), y = py / (H - 1) (0 for a single column / row), z = 0.299 r + 0.587 g + 0.114 b (fp32, left to right),
+ *   A = trilinear(grid at (z (L - 1), y (GH - 1), x (GW - 1))), border-clamped, in lerp form a + t (b - a) along x, y, z,
+ *   out_c = A[c,0] r + A[c,1] g + A[c,2] b + A[c,3] (not clamped).
+ * Limits: 1 <= GW, GH <= MISPLAT_BILAGRID_MAX_XY, 1 <= L <= MISPLAT_BILAGRID_MAX_L, 1 <= H, W <= 32768.  No atomics, every
+ * sum in a fixed order: reproducible bit for bit.  No call synchronises. */
+#define MISPLAT_BILAGRID_MAX_XY 256
+#define MISPLAT_BILAGRID_MAX_L 16
+#define MISPLAT_BILAGRID_TV_BLOCKS 1024  /* misplat_bilagrid_tv_fwd's partials: 3 * this many doubles */
+/* floats of scratch misplat_bilagrid_slice_bwd needs; -1 for sizes outside the limits. */
+int64_t misplat_bilagrid_scratch_floats(int32_t height, int32_t width, int32_t grid_w, int32_t grid_h, int32_t grid_l);
+/* rgb, out [H, W, 3]; grid: ONE camera's [12, L, GH, GW].  One launch. */
+int misplat_bilagrid_slice_fwd(int32_t height, int32_t width, const float* rgb, const float* grid, int32_t grid_w, int32_t grid_h,
+                               int32_t grid_l, float* out, misplat_stream_t stream);
+/* grids, v_grids: ALL cameras' [num, 12, L, GH, GW]; v_grids is written whole (camera `cam`: the gradient, the others: 0);
+ * v_rgb [H, W, 3] includes the path through z: the slope of the interval floor(gz), 0 where gz <= 0 or gz >= L - 1.  A and the
+ * slope are recomputed from rgb and the grid.  Three launches. */
+int misplat_bilagrid_slice_bwd(int32_t height, int32_t width, const float* rgb, const float* grids, int32_t num, int32_t cam,
+                               int32_t grid_w, int32_t grid_h, int32_t grid_l, const float* v_out, float* v_rgb, float* v_grids,
+                               float* scratch, misplat_stream_t stream);
+/* loss [1] = (1 / num) sum over the axes GW, GH, L of sum (G[i + 1] - G[i])^2 / (12 (n_axis - 1) (the other two sizes)); an
+ * axis of size 1 adds 0.  Partial sums in fp64, met in index order.  Two launches. */
+int misplat_bilagrid_tv_fwd(const float* grids, int32_t num, int32_t grid_w, int32_t grid_h, int32_t grid_l, double* partials,
+                            float* loss, misplat_stream_t stream);
+/* v_grids = v_loss[0] * d loss / d grids (v_loss: DEVICE scalar).  One launch. */
+int misplat_bilagrid_tv_bwd(const float* grids, int32_t num, int32_t grid_w, int32_t grid_h, int32_t grid_l, const float* v_loss,
+                            float* v_grids, misplat_stream_t stream);
+
 /* Library identification ("misplat <version> gfx950"). */
 const char* misplat_version(void);
 
