@@ -80,7 +80,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
     hipcc = _hipcc()
     headers = [os.path.join(INCLUDE, "misplat.h"), os.path.join(CSRC, "sh_eval.h"), os.path.join(CSRC, "internal.h"),
                os.path.join(CSRC, "mc_tables.h"), os.path.join(CSRC, "cellhash.h"), os.path.join(CSRC, "radixsort.h"),
-               os.path.join(CSRC, "unionfind.h"), os.path.join(CSRC, "hashmix.h"), os.path.join(CSRC, "bilinear.h")]
+               os.path.join(CSRC, "unionfind.h"), os.path.join(CSRC, "hashmix.h"), os.path.join(CSRC, "bilinear.h"),
+               os.path.join(CSRC, "wgprims.h")]
     jobs = []
     objs = []
     for src, extra in SOURCES.items():

@@ -26,6 +26,7 @@
 #include <cstdint>
 
 #include "misplat.h"
+#include "wgprims.h"
 
 namespace {
 
@@ -258,15 +259,7 @@ __global__ __launch_bounds__(256) void grid_bwd_finish_kernel(Geo g, const float
     }
 }
 
-// ---- TV.  sums[3] per lane in fp64: the squared forward differences along GW, GH and L.
-__device__ __forceinline__ double block_sum(double v, double* red /* [4] */) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    __syncthreads();                                               // (red is reused from one call to the next)
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
+// ---- TV.  sums[3] per lane in fp64: the squared forward differences along GW, GH and L, each through wgprims.h's block_sum.
 
 __global__ __launch_bounds__(256) void tv_fwd_kernel(Geo g, const float* __restrict__ grids, int64_t total,
                                                      double* __restrict__ partials) {
@@ -290,9 +283,9 @@ __global__ __launch_bounds__(256) void tv_fwd_kernel(Geo g, const float* __restr
             sz += (double)(d * d);
         }
     }
-    sx = block_sum(sx, red);
-    sy = block_sum(sy, red);
-    sz = block_sum(sz, red);
+    sx = block_sum<4>(sx, red);
+    sy = block_sum<4>(sy, red);
+    sz = block_sum<4>(sz, red);
     if (threadIdx.x == 0) {
         partials[3 * blockIdx.x] = sx;
         partials[3 * blockIdx.x + 1] = sy;
@@ -310,7 +303,7 @@ __global__ __launch_bounds__(256) void tv_finish_kernel(Geo g, int num, const do
     double s[3] = {0.0, 0.0, 0.0};
     for (int i = threadIdx.x; i < n_part; i += 256)
         for (int a = 0; a < 3; a++) s[a] += partials[3 * i + a];
-    const double sx = block_sum(s[0], red), sy = block_sum(s[1], red), sz = block_sum(s[2], red);
+    const double sx = block_sum<4>(s[0], red), sy = block_sum<4>(s[1], red), sz = block_sum<4>(s[2], red);
     if (threadIdx.x == 0) {
         double tv = 0.0;
         if (g.GW > 1) tv += sx / axis_count(g.GW, g.GH, g.L);
@@ -355,8 +348,6 @@ int split_count(int H, int W, int GW, int GH) {
 int stream_blocks(int64_t total) {
     return (int)std::max<int64_t>(1, std::min<int64_t>((total + 255) / 256, MISPLAT_BILAGRID_TV_BLOCKS));
 }
-
-int launched() { return hipGetLastError() == hipSuccess ? MISPLAT_OK : MISPLAT_ELAUNCH; }
 
 }  // namespace
 

@@ -12,27 +12,11 @@
 #include <stdint.h>
 #include "misplat.h"
 #include "internal.h"
+#include "wgprims.h"
 
 namespace {
 
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint32_t dpp_take(uint32_t ident, uint32_t x) {
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)ident, (int)x, CTRL, ROW_MASK, 0xF, false);
-}
-// inclusive wave scan: lane i ends with op(x_0 .. x_i); lane 63 holds the wave total
-template <class Op>
-__device__ __forceinline__ uint32_t wave_scan_incl(uint32_t x, uint32_t ident, Op op) {
-    x = op(x, dpp_take<0x111, 0xF>(ident, x));      // row_shr:1
-    x = op(x, dpp_take<0x112, 0xF>(ident, x));      // row_shr:2
-    x = op(x, dpp_take<0x114, 0xF>(ident, x));      // row_shr:4
-    x = op(x, dpp_take<0x118, 0xF>(ident, x));      // row_shr:8
-    x = op(x, dpp_take<0x142, 0xA>(ident, x));      // row_bcast:15 -> rows 1, 3
-    x = op(x, dpp_take<0x143, 0xC>(ident, x));      // row_bcast:31 -> rows 2, 3
-    return x;
-}
-
-
-
+// (the DPP wave scan wave_scan_incl is wgprims.h's)
 
 __global__ __launch_bounds__(256) void pack_kernel(int64_t n_rows, int cd,
                                                    const float* __restrict__ means2d,

@@ -28,6 +28,7 @@
 #include <stdint.h>
 #include "misplat.h"
 #include "internal.h"
+#include "wgprims.h"
 
 namespace {
 
@@ -76,18 +77,8 @@ __device__ __forceinline__ void tile_rect(float mx, float my, int rxi, int ryi, 
     y0 = (int)(fy0 < fth ? fy0 : fth); y1 = (int)(fy1 < fth ? fy1 : fth);
 }
 
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint32_t dpp_take(uint32_t ident, uint32_t x) {
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)ident, (int)x, CTRL, ROW_MASK, 0xF, false);
-}
 __device__ __forceinline__ uint32_t wave_scan_add(uint32_t x) {      // inclusive; lane 63 holds the total
-    x += dpp_take<0x111, 0xF>(0u, x);
-    x += dpp_take<0x112, 0xF>(0u, x);
-    x += dpp_take<0x114, 0xF>(0u, x);
-    x += dpp_take<0x118, 0xF>(0u, x);
-    x += dpp_take<0x142, 0xA>(0u, x);
-    x += dpp_take<0x143, 0xC>(0u, x);
-    return x;
+    return wave_scan_incl(x, 0u, [](uint32_t a, uint32_t b) { return a + b; });
 }
 
 __device__ __forceinline__ int cell_of(uint32_t xy, uint32_t wh, int cam, int shift, int cells_x, int cells_per_cam) {
@@ -386,13 +377,7 @@ __device__ __forceinline__ void tile_wg_prologue(TileWg& L, int64_t n_vis, int n
 }
 
 __device__ __forceinline__ uint32_t wave_scan_max(uint32_t x) {      // inclusive; lane 63 holds the wave maximum
-    x = max(x, dpp_take<0x111, 0xF>(0u, x));
-    x = max(x, dpp_take<0x112, 0xF>(0u, x));
-    x = max(x, dpp_take<0x114, 0xF>(0u, x));
-    x = max(x, dpp_take<0x118, 0xF>(0u, x));
-    x = max(x, dpp_take<0x142, 0xA>(0u, x));
-    x = max(x, dpp_take<0x143, 0xC>(0u, x));
-    return x;
+    return wave_scan_incl(x, 0u, [](uint32_t a, uint32_t b) { return max(a, b); });
 }
 
 __global__ __launch_bounds__(kRowsPerWg) void bucket_tile_count_kernel(

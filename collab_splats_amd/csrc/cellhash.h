@@ -1,6 +1,7 @@
-// cellhash.h -- the spatial index shared by meshmap.hip (kNN vertex map) and cluster.hip (radius-graph
-// clustering, section 16): a hash of the OCCUPIED cells of edge h (open addressing, capacity a power of two >= 2 M, 64-bit
-// keys) and the vertices regrouped by cell (count, scan, fill).  Memory O(M) whatever the extent of the scene.
+// cellhash.h -- the spatial index shared by meshmap.hip (kNN vertex map), cluster.hip (radius-graph
+// clustering, section 16) and pointcloud.hip (section 17): a hash of the OCCUPIED cells of edge h (open addressing, capacity
+// a power of two >= 2 M, 64-bit keys) and the vertices regrouped by cell (count, scan, fill).  Memory O(M) whatever the
+// extent of the scene.  The scan, the claim loop of the insertion and the host helpers are wgprims.h's.
 //
 // Everything sits in an unnamed namespace on purpose: each translation unit that includes this header compiles its own
 // copy of the kernels into its own code object (the library is built without relocatable device code).
@@ -8,12 +9,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "misplat.h"
+#include "wgprims.h"
 
 namespace {
 
-constexpr int kScanBlock = 1024;
 constexpr float kCoordCells = 262144.f;   // |v| / h < 2^18 for every vertex (the host checks it)
-constexpr unsigned long long kEmpty = ~0ull;
 
 __device__ __forceinline__ unsigned long long cell_key(int cx, int cy, int cz) {
     return (unsigned long long)(uint32_t)(cx + (1 << 20)) | ((unsigned long long)(uint32_t)(cy + (1 << 20)) << 21) |
@@ -40,69 +40,6 @@ __device__ __forceinline__ int find_cell(const unsigned long long* __restrict__ 
     }
 }
 
-// ------------------------------------------------------------------------------------------------------------ scan
-// Exclusive scan of n int32 in three launches: per-block sums, one workgroup over the block sums, per-block scans.
-// out[n] = total.  bsum: 2 ceil(n / 1024) + 1 int32.
-__device__ __forceinline__ int32_t block_scan_excl(int32_t x, int32_t* wsum, int32_t& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int32_t incl = x;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int32_t o = __shfl_up(incl, off);
-        if (lane >= off) incl += o;
-    }
-    __syncthreads();
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    int32_t before = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < kScanBlock / 64; w++) { before += (w < wave) ? wsum[w] : 0; total += wsum[w]; }
-    return before + incl - x;
-}
-
-__global__ __launch_bounds__(kScanBlock) void scan_reduce_kernel(const int32_t* __restrict__ in, int64_t n,
-                                                                 int32_t* __restrict__ bsum) {
-    __shared__ int32_t wsum[kScanBlock / 64];
-    const int64_t i = (int64_t)blockIdx.x * kScanBlock + threadIdx.x;
-    int32_t total;
-    (void)block_scan_excl(i < n ? in[i] : 0, wsum, total);
-    if (threadIdx.x == 0) bsum[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(kScanBlock) void scan_top_kernel(const int32_t* __restrict__ bsum, int64_t nb,
-                                                              int32_t* __restrict__ boff) {
-    __shared__ int32_t wsum[kScanBlock / 64];
-    int32_t carry = 0;
-    for (int64_t b0 = 0; b0 < nb; b0 += kScanBlock) {
-        const int64_t b = b0 + threadIdx.x;
-        int32_t total;
-        const int32_t ex = block_scan_excl(b < nb ? bsum[b] : 0, wsum, total);
-        if (b < nb) boff[b] = carry + ex;
-        carry += total;
-    }
-    if (threadIdx.x == 0) boff[nb] = carry;
-}
-
-__global__ __launch_bounds__(kScanBlock) void scan_down_kernel(const int32_t* __restrict__ in, int64_t n,
-                                                               const int32_t* __restrict__ boff, int64_t nb,
-                                                               int32_t* __restrict__ out) {
-    __shared__ int32_t wsum[kScanBlock / 64];
-    const int64_t i = (int64_t)blockIdx.x * kScanBlock + threadIdx.x;
-    int32_t total;
-    const int32_t ex = block_scan_excl(i < n ? in[i] : 0, wsum, total);
-    if (i < n) out[i] = boff[blockIdx.x] + ex;
-    if (i == 0) out[n] = boff[nb];
-}
-
-inline void scan(const int32_t* in, int64_t n, int32_t* out, int32_t* scratch, hipStream_t s) {
-    const int64_t nb = (n + kScanBlock - 1) / kScanBlock;
-    if (nb > 0) hipLaunchKernelGGL(scan_reduce_kernel, dim3((unsigned)nb), dim3(kScanBlock), 0, s, in, n, scratch);
-    hipLaunchKernelGGL(scan_top_kernel, dim3(1), dim3(kScanBlock), 0, s, (const int32_t*)scratch, nb, scratch + nb);
-    hipLaunchKernelGGL(scan_down_kernel, dim3((unsigned)(nb > 0 ? nb : 1)), dim3(kScanBlock), 0, s, in, n,
-                       (const int32_t*)(scratch + nb), nb, out);
-}
-
 // --------------------------------------------------------------------------------------------------------- index
 // Insert every vertex's cell into the hash and count the vertices per slot.  Which slot a cell takes depends on the
 // insertion order; the lookups and every result do not.  select (or NULL: every vertex): only the vertices with a
@@ -115,12 +52,7 @@ __global__ __launch_bounds__(256) void index_insert_kernel(const float* __restri
     if (v >= M) return;
     if (select && !select[v]) { vslot[v] = -1; return; }
     const unsigned long long key = cell_key(cell_of(V[3 * v], inv_h), cell_of(V[3 * v + 1], inv_h), cell_of(V[3 * v + 2], inv_h));
-    uint32_t s = hash_slot(key, mask);
-    while (true) {
-        const unsigned long long prev = atomicCAS(&keys[s], kEmpty, key);
-        if (prev == kEmpty || prev == key) break;
-        s = (s + 1) & mask;
-    }
+    const uint32_t s = claim_slot(keys, mask, hash_slot(key, mask), key);
     vslot[v] = (int32_t)s;
     atomicAdd(&counts[s], 1);
 }
@@ -151,11 +83,5 @@ inline int64_t hash_capacity(int64_t n) {
     while (cap < 2 * n) cap <<= 1;
     return cap;
 }
-
-inline int64_t al(int64_t b) { return (b + 255) & ~(int64_t)255; }
-
-inline int launched() { return hipGetLastError() == hipSuccess ? MISPLAT_OK : MISPLAT_ELAUNCH; }
-
-inline unsigned blocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
 }  // namespace

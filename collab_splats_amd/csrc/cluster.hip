@@ -142,7 +142,7 @@ inline Layout layout(int64_t M) {
     L.o_starts = o; o += al(4 * (L.cap + 1));
     L.o_vslot = o;  o += al(4 * M);
     L.o_pts = o;    o += al(16 * M);
-    L.o_scan = o;   o += al(4 * (2 * ((scan_n + kScanBlock - 1) / kScanBlock) + 2));
+    L.o_scan = o;   o += al(scan_scratch_bytes(scan_n));
     L.o_parent = o; o += al(4 * M);
     L.o_size = o;   o += al(4 * M);
     L.o_root = o;   o += al(4 * M);

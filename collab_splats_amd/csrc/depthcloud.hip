@@ -9,7 +9,7 @@
 #include <stdint.h>
 #include "misplat.h"
 #include "internal.h"
-#include "cellhash.h"
+#include "wgprims.h"
 #include "hashmix.h"
 
 namespace {
@@ -146,19 +146,9 @@ __global__ __launch_bounds__(256) void key_pick_kernel(int pass, int32_t S, Fram
     const int v = blockIdx.x;
     const FrameState st = state[v];
     if (pass > 0 && st.take_all) return;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int32_t c = hist[((int64_t)v * 4 + pass) * 256 + threadIdx.x];
-    int32_t incl = c;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int32_t o = __shfl_up(incl, off);
-        if (lane >= off) incl += o;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    int32_t total = 0;
-#pragma unroll
-    for (int w = 0; w < 4; w++) { incl += (w < wave) ? wsum[w] : 0; total += wsum[w]; }
+    int32_t total;
+    const int32_t incl = block_scan_excl<int32_t, 4>(c, wsum, total) + c;
     int32_t k = st.k, n = st.n;
     if (pass == 0) {
         n = total;
@@ -203,21 +193,6 @@ __global__ __launch_bounds__(256) void select_count_kernel(const uint8_t* __rest
     if (threadIdx.x == 0) {
         part[((int64_t)v) * nb + blockIdx.x] = (wl[0] + wl[1]) + (wl[2] + wl[3]);
         part[((int64_t)V + v) * nb + blockIdx.x] = (we[0] + we[1]) + (we[2] + we[3]);
-    }
-}
-
-// exclusive scan of every row of in [rows, nb] (one workgroup a row)
-__global__ __launch_bounds__(kScanBlock) void row_scan_kernel(const int32_t* __restrict__ in, int64_t nb, int32_t* __restrict__ out) {
-    __shared__ int32_t wsum[kScanBlock / 64];
-    in += (int64_t)blockIdx.x * nb;
-    out += (int64_t)blockIdx.x * nb;
-    int32_t carry = 0;
-    for (int64_t b0 = 0; b0 < nb; b0 += kScanBlock) {
-        const int64_t b = b0 + threadIdx.x;
-        int32_t total;
-        const int32_t ex = block_scan_excl(b < nb ? in[b] : 0, wsum, total);
-        if (b < nb) out[b] = carry + ex;
-        carry += total;
     }
 }
 
@@ -410,9 +385,12 @@ extern "C" int misplat_depthcloud_sample(const uint8_t* candidates, const int32_
         hipLaunchKernelGGL(key_pick_kernel, dim3((unsigned)V), dim3(256), 0, s, pass, samples_per_frame, state, (const int32_t*)hist,
                            counts);
     }
-    hipLaunchKernelGGL(scan_top_kernel, dim3(1), dim3(kScanBlock), 0, s, (const int32_t*)counts, V, frame_base);
+    hipLaunchKernelGGL((carry_scan_kernel<int32_t, int32_t>), dim3(1), dim3(kScanBlock), 0, s, (const int32_t*)counts, V, V, frame_base,
+                       frame_base + V);
     hipLaunchKernelGGL(select_count_kernel, grid, dim3(256), 0, s, candidates, keys, P, seed, frame_offset, (const FrameState*)state, part);
-    hipLaunchKernelGGL(row_scan_kernel, dim3((unsigned)(2 * V)), dim3(kScanBlock), 0, s, (const int32_t*)part, L.nb, offs);
+    // every row of part [2 V, nb]: one workgroup a row
+    hipLaunchKernelGGL((carry_scan_kernel<int32_t, int32_t>), dim3((unsigned)(2 * V)), dim3(kScanBlock), 0, s, (const int32_t*)part,
+                       (int64_t)L.nb, (int64_t)L.nb, offs, (int32_t*)nullptr);
     hipLaunchKernelGGL(select_emit_kernel, grid, dim3(256), 0, s, candidates, keys, P, seed, frame_offset, (const FrameState*)state,
                        (const int32_t*)offs, (const int32_t*)frame_base, frame_ids, pixel_ids);
     return launched();

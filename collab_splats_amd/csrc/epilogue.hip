@@ -13,6 +13,7 @@
 #include <stdint.h>
 #include "misplat.h"
 #include "internal.h"
+#include "wgprims.h"
 
 namespace {
 
@@ -123,12 +124,6 @@ inline int grid_for(int64_t n, int block) {
 // loss values.  Backward: the three constant-magnitude gradient images in one pass.
 constexpr int kLossBlocks = 512;
 
-__device__ __forceinline__ float wave_sum_f(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
-
 __global__ __launch_bounds__(256) void loss_partial_kernel(int64_t n_pix, const float* __restrict__ rgb,
                                                            const float* __restrict__ gt, const float* __restrict__ err_exp,
                                                            const float* __restrict__ err_med, float* __restrict__ partials) {
@@ -147,7 +142,7 @@ __global__ __launch_bounds__(256) void loss_partial_kernel(int64_t n_pix, const 
     }
     if (err_exp)
         for (int64_t i = tid; i < n_pix; i += stride) { s1 += err_exp[i]; s2 += err_med[i]; }
-    s0 = wave_sum_f(s0); s1 = wave_sum_f(s1); s2 = wave_sum_f(s2);
+    s0 = wave_sum_xor(s0); s1 = wave_sum_xor(s1); s2 = wave_sum_xor(s2);
     if ((threadIdx.x & 63) == 0) { sm[0][threadIdx.x >> 6] = s0; sm[1][threadIdx.x >> 6] = s1; sm[2][threadIdx.x >> 6] = s2; }
     __syncthreads();
     if (threadIdx.x < 3)

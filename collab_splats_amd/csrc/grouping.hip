@@ -17,7 +17,7 @@
 #include <stdint.h>
 #include "misplat.h"
 #include "internal.h"
-#include "cellhash.h"
+#include "wgprims.h"
 #include "radixsort.h"
 
 namespace {
@@ -269,7 +269,7 @@ inline Layout layout(int64_t N) {
     int64_t o = 0;
     L.o_present = o; o += al(4 * kIds);
     L.o_rank = o;    o += al(4 * (kIds + 1));
-    L.o_scan = o;    o += al(4 * (2 * ((scan_n + kScanBlock - 1) / kScanBlock) + 2));
+    L.o_scan = o;    o += al(scan_scratch_bytes(scan_n));
     L.o_ka = o;      o += al(4 * N);
     L.o_va = o;      o += al(4 * N);
     L.o_kb = o;      o += al(4 * N);

@@ -14,7 +14,7 @@
 #include <stdint.h>
 #include "misplat.h"
 #include "internal.h"
-#include "cellhash.h"
+#include "wgprims.h"
 #include "unionfind.h"
 #include "hashmix.h"
 
@@ -61,12 +61,7 @@ __global__ __launch_bounds__(256) void edge_insert_kernel(const int32_t* __restr
     corner_edge(tri, f, (int)(h - 3 * f), a, b);
     if (a == b) return;
     const unsigned long long key = edge_key(a, b);
-    unsigned long long s = edge_home(key, E.mask);
-    while (true) {
-        const unsigned long long prev = atomicCAS(&E.keys[s], kEmpty, key);
-        if (prev == kEmpty || prev == key) break;
-        s = (s + 1) & E.mask;
-    }
+    const unsigned long long s = claim_slot(E.keys, E.mask, edge_home(key, E.mask), key);
     atomicAdd(&E.cnt[s], 1);
     atomicMin(&E.face[s], (int32_t)f);
 }
@@ -84,33 +79,7 @@ __global__ __launch_bounds__(256) void edge_count_kernel(EdgeTable E, int64_t ca
 }
 
 // ------------------------------------------------------------------------------------------------- fixed-order sums
-// K doubles per thread: 64 lanes by a shuffle tree, the four waves in order.  The pattern of pointcloud.hip's stat kernels.
-template <int K>
-__device__ __forceinline__ void block_sums(double (&x)[K], double* out) {
-    __shared__ double ws[K][4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < K; k++) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) x[k] += __shfl_down(x[k], off);
-        if (lane == 0) ws[k][wave] = x[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < K) out[threadIdx.x] = ((ws[threadIdx.x][0] + ws[threadIdx.x][1]) + ws[threadIdx.x][2]) + ws[threadIdx.x][3];
-}
-
-// out[k] = the sum over the nb workgroup partials part[b K + k], strided over one workgroup and through the same tree
-template <int K>
-__global__ __launch_bounds__(256) void sum_final_kernel(const double* __restrict__ part, int64_t nb, double* __restrict__ out) {
-    double x[K];
-#pragma unroll
-    for (int k = 0; k < K; k++) x[k] = 0.0;
-    for (int64_t b = threadIdx.x; b < nb; b += 256)
-#pragma unroll
-        for (int k = 0; k < K; k++) x[k] += part[b * K + k];
-    block_sums<K>(x, out);
-}
-
+// wgprims.h's: K doubles per thread through block_sums<K>, the workgroup partials through sum_final_kernel<K, 256>.
 __device__ __forceinline__ float edge_length(const float* __restrict__ V, int32_t a, int32_t b) {
     const float dx = V[3 * (int64_t)b] - V[3 * (int64_t)a], dy = V[3 * (int64_t)b + 1] - V[3 * (int64_t)a + 1],
                 dz = V[3 * (int64_t)b + 2] - V[3 * (int64_t)a + 2];
@@ -436,7 +405,7 @@ inline Layout layout(int64_t M, int64_t T, int kind) {
     L.o_keys = o; o += al(8 * L.cap);
     L.o_cnt = o;  o += al(4 * L.cap);
     L.o_face = o; o += al(4 * L.cap);
-    L.o_scan = o; o += al(4 * (2 * ((scan_n + kScanBlock - 1) / kScanBlock) + 2));
+    L.o_scan = o; o += al(scan_scratch_bytes(scan_n));
     if (kind == kKindStats) {
         L.o_part = o; o += al(8 * ((3 * T + 255) / 256 + 1));
         L.o_sum = o;  o += al(8);
@@ -501,7 +470,7 @@ extern "C" int misplat_meshclean_edge_stats(const float* vertices, int64_t n_ver
     hipLaunchKernelGGL(edge_count_kernel, dim3(blocks(L.cap, 256)), dim3(256), 0, s, E, L.cap, counts);
     const int64_t nb = (3 * T + 255) / 256;
     if (nb > 0) hipLaunchKernelGGL(edge_length_kernel, dim3((unsigned)nb), dim3(256), 0, s, vertices, triangles, T, E, part);
-    hipLaunchKernelGGL(sum_final_kernel<1>, dim3(1), dim3(256), 0, s, (const double*)part, nb, sum);
+    hipLaunchKernelGGL((sum_final_kernel<1, 256>), dim3(1), dim3(256), 0, s, (const double*)part, nb, sum);
     hipLaunchKernelGGL(edge_mean_kernel, dim3(1), dim3(1), 0, s, (const double*)sum, (const int32_t*)counts, mean_length);
     return launched();
 }
@@ -622,9 +591,9 @@ extern "C" int misplat_meshclean_plane_moments(const float* points, int64_t n_po
     double* part = (double*)((char*)workspace + L.o_part);
     const int64_t nb = (N + 255) / 256;
     hipLaunchKernelGGL(moment_mean_kernel, dim3((unsigned)nb), dim3(256), 0, s, points, N, (const float4*)plane, threshold, mask, part);
-    hipLaunchKernelGGL(sum_final_kernel<4>, dim3(1), dim3(256), 0, s, (const double*)part, nb, moments);
+    hipLaunchKernelGGL((sum_final_kernel<4, 256>), dim3(1), dim3(256), 0, s, (const double*)part, nb, moments);
     hipLaunchKernelGGL(moment_cov_kernel, dim3((unsigned)nb), dim3(256), 0, s, points, N, (const uint8_t*)mask,
                        (const double*)moments, part);
-    hipLaunchKernelGGL(sum_final_kernel<6>, dim3(1), dim3(256), 0, s, (const double*)part, nb, moments + 4);
+    hipLaunchKernelGGL((sum_final_kernel<6, 256>), dim3(1), dim3(256), 0, s, (const double*)part, nb, moments + 4);
     return launched();
 }

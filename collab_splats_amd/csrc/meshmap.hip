@@ -132,46 +132,16 @@ __global__ __launch_bounds__(256) void knn_kernel(Index ix, int64_t M, const flo
 // ---------------------------------------------------------------------------------------------------------- sigma
 // stats[0] = sum of the distances of the valid rows (fp64), stats[1] = number of valid rows.  Rows are summed in j order,
 // 256 rows per workgroup in a fixed tree, the workgroup sums in index order by one workgroup: the result does not depend on
-// scheduling.
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off);
-    return x;
-}
-
+// scheduling (wgprims.h: block_sums, then sum_final_kernel<2, 256>).
 __global__ __launch_bounds__(256) void sigma_partial_kernel(const float* __restrict__ dist, const uint8_t* __restrict__ valid,
                                                             int64_t N, int k, double* __restrict__ part) {
-    __shared__ double ws[2][4];
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    double s = 0.0, c = 0.0;
+    double sc[2] = {0.0, 0.0};
     if (i < N && valid[i]) {
-        for (int j = 0; j < k; j++) s += (double)dist[i * k + j];
-        c = 1.0;
+        for (int j = 0; j < k; j++) sc[0] += (double)dist[i * k + j];
+        sc[1] = 1.0;
     }
-    s = wave_sum(s);
-    c = wave_sum(c);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) { ws[0][wave] = s; ws[1][wave] = c; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        part[2 * blockIdx.x] = ((ws[0][0] + ws[0][1]) + ws[0][2]) + ws[0][3];
-        part[2 * blockIdx.x + 1] = ((ws[1][0] + ws[1][1]) + ws[1][2]) + ws[1][3];
-    }
-}
-
-__global__ __launch_bounds__(256) void sigma_final_kernel(const double* __restrict__ part, int64_t nb, double* __restrict__ stats) {
-    __shared__ double ws[2][4];
-    double s = 0.0, c = 0.0;
-    for (int64_t b = threadIdx.x; b < nb; b += 256) { s += part[2 * b]; c += part[2 * b + 1]; }
-    s = wave_sum(s);
-    c = wave_sum(c);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) { ws[0][wave] = s; ws[1][wave] = c; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        stats[0] = ((ws[0][0] + ws[0][1]) + ws[0][2]) + ws[0][3];
-        stats[1] = ((ws[1][0] + ws[1][1]) + ws[1][2]) + ws[1][3];
-    }
+    block_sums<2>(sc, part + 2 * blockIdx.x);
 }
 
 // --------------------------------------------------------------------------------------------------------- weights
@@ -308,7 +278,7 @@ inline Layout layout(int64_t M, int64_t N, int k, int D) {
     L.o_starts = o; o += al(4 * (L.cap + 1));
     L.o_vslot = o;  o += al(4 * M);
     L.o_pts = o;    o += al(16 * M);
-    L.o_scan = o;   o += al(4 * (2 * ((L.scan_n + kScanBlock - 1) / kScanBlock) + 2));
+    L.o_scan = o;   o += al(scan_scratch_bytes(L.scan_n));
     L.o_sig = o;    o += al(8 * (2 * ((N + 255) / 256) + 2));
     L.o_w = o;      o += al(4 * L.E);
     L.o_ka = o;     o += al(4 * L.E);
@@ -406,7 +376,7 @@ extern "C" int misplat_meshmap_aggregate(int64_t n_vertices, int64_t n_points, i
     float* part = (float*)(ws + L.o_part);
     const int64_t nb_sig = (N + 255) / 256;
     hipLaunchKernelGGL(sigma_partial_kernel, dim3((unsigned)nb_sig), dim3(256), 0, s, dist, valid, N, (int)k, sig + 2);
-    hipLaunchKernelGGL(sigma_final_kernel, dim3(1), dim3(256), 0, s, (const double*)(sig + 2), nb_sig, sig);
+    hipLaunchKernelGGL((sum_final_kernel<2, 256>), dim3(1), dim3(256), 0, s, (const double*)(sig + 2), nb_sig, sig);
     hipLaunchKernelGGL(weights_kernel, dim3(blocks(N, 256)), dim3(256), 0, s, idx, dist, valid, N, (int)k, (int32_t)M,
                        (const double*)sig, w, ka, va);
     const int64_t E = L.E;

@@ -7,6 +7,7 @@
 #include <math.h>
 #include <stdint.h>
 #include "misplat.h"
+#include "wgprims.h"
 
 namespace {
 
@@ -152,29 +153,12 @@ __device__ __forceinline__ uint32_t union_byte(const uint8_t* __restrict__ gathe
     return v;
 }
 
-__device__ __forceinline__ uint32_t block_scan_excl(uint32_t x, uint32_t* wsum, uint32_t& total) {   // 256 threads
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t incl = x;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = __shfl_up(incl, off);
-        if (lane >= off) incl += o;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0u;
-    total = 0u;
-#pragma unroll
-    for (int w = 0; w < 4; w++) { before += (w < wave) ? wsum[w] : 0u; total += wsum[w]; }
-    return before + incl - x;
-}
-
 __global__ __launch_bounds__(256) void union_count_kernel(const uint8_t* __restrict__ gathered, int world, int64_t nbytes,
                                                           int32_t* __restrict__ block_counts) {
     __shared__ uint32_t wsum[4];
     const uint32_t v = union_byte(gathered, world, nbytes, (int64_t)blockIdx.x * kBitsBlock + threadIdx.x);
     uint32_t total;
-    (void)block_scan_excl((uint32_t)__popc(v), wsum, total);
+    (void)block_scan_excl<uint32_t, 4>((uint32_t)__popc(v), wsum, total);
     if (threadIdx.x == 0) block_counts[blockIdx.x] = (int32_t)total;
 }
 
@@ -185,45 +169,13 @@ __global__ __launch_bounds__(256) void union_ids_kernel(const uint8_t* __restric
     const int64_t b = (int64_t)blockIdx.x * kBitsBlock + threadIdx.x;
     uint32_t v = union_byte(gathered, world, nbytes, b);
     uint32_t total;
-    int64_t pos = block_offsets[blockIdx.x] + (int64_t)block_scan_excl((uint32_t)__popc(v), wsum, total);
+    int64_t pos = block_offsets[blockIdx.x] + (int64_t)block_scan_excl<uint32_t, 4>((uint32_t)__popc(v), wsum, total);
     while (v) {
         const int k = __ffs((int)v) - 1;
         if (pos < ids_cap) ids[pos] = (int32_t)(b * 8 + k);     // (a speculative capacity may be short: the caller checks the count)
         pos++;
         v &= v - 1u;
     }
-}
-
-// Exclusive scan of the per-block counts (int64 offsets) and their total, by ONE workgroup: a few thousand counts (one per 2 048
-// rows) -- a library scan call here costs the host more than the whole reduce's kernels (measured: the first torch op behind
-// the backward's launch blocked the autograd thread for 0.9 ms per step at 5 M Gaussians).
-__global__ __launch_bounds__(1024) void union_scan_kernel(const int32_t* __restrict__ counts, int64_t n_blocks,
-                                                          int64_t* __restrict__ offsets, int64_t* __restrict__ total) {
-    __shared__ unsigned long long wsum[16];
-    __shared__ unsigned long long carry_s;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) carry_s = 0ull;
-    __syncthreads();
-    for (int64_t base = 0; base < n_blocks; base += 1024) {
-        const int64_t i = base + threadIdx.x;
-        const unsigned long long x = i < n_blocks ? (unsigned long long)(uint32_t)counts[i] : 0ull;
-        unsigned long long incl = x;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const unsigned long long o = __shfl_up(incl, off);
-            if (lane >= off) incl += o;
-        }
-        if (lane == 63) wsum[wave] = incl;
-        __syncthreads();
-        unsigned long long before = carry_s, all = 0ull;
-#pragma unroll
-        for (int w = 0; w < 16; w++) { before += (w < wave) ? wsum[w] : 0ull; all += wsum[w]; }
-        if (i < n_blocks) offsets[i] = (int64_t)(before + incl - x);
-        __syncthreads();
-        if (threadIdx.x == 0) carry_s += all;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total = (int64_t)carry_s;
 }
 
 struct RowTable {
@@ -305,7 +257,11 @@ extern "C" int misplat_union_count(const uint8_t* gathered, int32_t world, int64
 extern "C" int misplat_union_scan(const int32_t* block_counts, int64_t n_blocks, int64_t* block_offsets, int64_t* total,
                                   misplat_stream_t stream) {
     if (n_blocks < 0 || !total || (n_blocks > 0 && (!block_counts || !block_offsets))) return MISPLAT_EINVAL;
-    hipLaunchKernelGGL(union_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, block_counts, n_blocks, block_offsets, total);
+    // Exclusive scan of the per-block counts (int64 offsets) and their total, by ONE workgroup (wgprims.h): a few thousand counts
+    // (one per 2 048 rows) -- a library scan call here costs the host more than the whole reduce's kernels (measured: the first
+    // torch op behind the backward's launch blocked the autograd thread for 0.9 ms per step at 5 M Gaussians).
+    hipLaunchKernelGGL((carry_scan_kernel<int32_t, int64_t>), dim3(1), dim3(kScanBlock), 0, (hipStream_t)stream, block_counts, n_blocks,
+                       n_blocks, block_offsets, total);
     return hipGetLastError() == hipSuccess ? MISPLAT_OK : MISPLAT_ELAUNCH;
 }
 

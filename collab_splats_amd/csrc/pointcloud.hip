@@ -236,42 +236,19 @@ __global__ __launch_bounds__(256) void occupied_kernel(const unsigned long long*
 }
 
 // ---------------------------------------------------------------------------------------------------- outlier stats
-// The pattern of meshmap.hip's sigma kernels: 256 values per workgroup in a fixed tree, the workgroup sums strided over one
-// workgroup and through the same tree.  Pass 0: (sum of the positive avg, their number); pass 1: (sum of (avg - mu)^2, 0).
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off);
-    return x;
-}
-
-__device__ __forceinline__ void block_pair(double s, double c, double* out) {
-    __shared__ double ws[2][4];
-    s = wave_sum(s);
-    c = wave_sum(c);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) { ws[0][wave] = s; ws[1][wave] = c; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        out[0] = ((ws[0][0] + ws[0][1]) + ws[0][2]) + ws[0][3];
-        out[1] = ((ws[1][0] + ws[1][1]) + ws[1][2]) + ws[1][3];
-    }
-}
+// wgprims.h's fixed-order sums: 256 values per workgroup in a fixed tree (block_sums), the workgroup sums strided over one
+// workgroup and through the same tree (sum_final_kernel<2, 256>).  Pass 0: (sum of the positive avg, their number); pass 1:
+// (sum of (avg - mu)^2, 0).
 
 __global__ __launch_bounds__(256) void stat_partial_kernel(const float* __restrict__ avg, int64_t N, int pass,
                                                            const double* __restrict__ stats, double* __restrict__ part) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    double s = 0.0, c = 0.0;
+    double sc[2] = {0.0, 0.0};
     if (i < N && avg[i] > 0.f) {
-        if (pass == 0) { s = (double)avg[i]; c = 1.0; }
-        else { const double d = (double)avg[i] - stats[0] / stats[1]; s = d * d; }
+        if (pass == 0) { sc[0] = (double)avg[i]; sc[1] = 1.0; }
+        else { const double d = (double)avg[i] - stats[0] / stats[1]; sc[0] = d * d; }
     }
-    block_pair(s, c, part + 2 * blockIdx.x);
-}
-
-__global__ __launch_bounds__(256) void stat_final_kernel(const double* __restrict__ part, int64_t nb, double* __restrict__ out) {
-    double s = 0.0, c = 0.0;
-    for (int64_t b = threadIdx.x; b < nb; b += 256) { s += part[2 * b]; c += part[2 * b + 1]; }
-    block_pair(s, c, out);
+    block_sums<2>(sc, part + 2 * blockIdx.x);
 }
 
 // stats: 0 sum, 1 n_valid, 2 sum of squares, 3 (unused), 4 threshold.  n_valid <= 1: no threshold (every positive avg stays).
@@ -301,12 +278,7 @@ __global__ __launch_bounds__(256) void voxel_insert_kernel(const float* __restri
     const unsigned long long key = (unsigned long long)(voxel_cell(P[3 * i], ox, voxel) + 1048576) |
                                    ((unsigned long long)(voxel_cell(P[3 * i + 1], oy, voxel) + 1048576) << 21) |
                                    ((unsigned long long)(voxel_cell(P[3 * i + 2], oz, voxel) + 1048576) << 42);
-    uint32_t s = hash_slot(key, mask);
-    while (true) {
-        const unsigned long long prev = atomicCAS(&keys[s], kEmpty, key);
-        if (prev == kEmpty || prev == key) break;
-        s = (s + 1) & mask;
-    }
+    const uint32_t s = claim_slot(keys, mask, hash_slot(key, mask), key);
     vslot[i] = (int32_t)s;
     atomicMin(&first[s], (int32_t)i);
 }
@@ -386,7 +358,7 @@ inline Layout layout(int64_t N, int kind) {
         L.lv[l].o_pts = o;    o += al(16 * N);
     }
     L.o_vslot = o; o += al(4 * N);
-    L.o_scan = o;  o += al(4 * (2 * ((scan_n + kScanBlock - 1) / kScanBlock) + 2));
+    L.o_scan = o;  o += al(scan_scratch_bytes(scan_n));
     if (kind == kKindOutlier) {
         L.o_part = o;  o += al(8 * (2 * ((N + 255) / 256) + 2));
         L.o_stats = o; o += al(8 * 8);
@@ -511,7 +483,7 @@ extern "C" int misplat_pointcloud_outlier_mask(const float* avg, int64_t n_point
     const int64_t nb = (N + 255) / 256;
     for (int pass = 0; pass < 2; pass++) {
         hipLaunchKernelGGL(stat_partial_kernel, dim3((unsigned)nb), dim3(256), 0, s, avg, N, pass, (const double*)stats, part);
-        hipLaunchKernelGGL(stat_final_kernel, dim3(1), dim3(256), 0, s, (const double*)part, nb, stats + 2 * pass);
+        hipLaunchKernelGGL((sum_final_kernel<2, 256>), dim3(1), dim3(256), 0, s, (const double*)part, nb, stats + 2 * pass);
     }
     hipLaunchKernelGGL(outlier_mask_kernel, dim3(blocks(N, 256)), dim3(256), 0, s, avg, N, std_ratio, stats, keep);
     return launched();

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "misplat.h"
+#include "wgprims.h"
 
 namespace {
 
@@ -24,24 +25,8 @@ constexpr float kInvFix = 1.f / 1073741824.f;
 enum { S_RZ = 0, S_PAP, S_RR, S_BB, S_ALPHA, S_BETA, S_DONE, S_ITERS };
 constexpr int64_t kStateBytes = 64, kSumsBytes = 64;  // state, then {sum of W, cells with W > 0} as uint64
 
-inline int launched() { return hipGetLastError() == hipSuccess ? MISPLAT_OK : MISPLAT_ELAUNCH; }
-
-// sum over the workgroup in a fixed tree: lanes by shuffles, then the waves in ascending order (every thread gets the sum)
-template <int WAVES>
-__device__ __forceinline__ double block_sum(double v, double* sh) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();                                  // sh may still be read by a previous call
-    if (lane == 0) sh[wave] = v;
-    __syncthreads();
-    double s = 0.0;
-#pragma unroll
-    for (int w = 0; w < WAVES; w++) s += sh[w];
-    return s;
-}
-
-// the one-workgroup second level: thread t adds partials t, t + 1024, ... in ascending order, then the tree
+// the one-workgroup second level: thread t adds partials t, t + 1024, ... in ascending order, then wgprims.h's block_sum (the
+// workgroup sum in a fixed tree; every thread gets it).  A device function, not sum_final_kernel: the callers go on computing.
 __device__ __forceinline__ double final_sum(const double* __restrict__ partials, int64_t n, double* sh) {
     double v = 0.0;
 #pragma unroll 8

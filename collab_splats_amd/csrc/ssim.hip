@@ -25,6 +25,7 @@
 #include <cstdint>
 
 #include "misplat.h"
+#include "wgprims.h"
 
 namespace {
 
@@ -45,12 +46,6 @@ Window make_window() {
     }
     for (int i = 0; i < kWin; i++) W.w[i] /= sum;
     return W;
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
 }
 
 // maps: [3][3 channels][OH][OW] (d ssim / d E[x], / d E[xx], / d E[xy]); partials: one float per workgroup.
@@ -174,8 +169,8 @@ __global__ __launch_bounds__(256) void ssim_fwd_kernel(int H, int Wd, const floa
             }
         }
     }
-    s = wave_sum(s);
-    l1 = wave_sum(l1);
+    s = wave_sum_xor(s);
+    l1 = wave_sum_xor(l1);
     if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = s; red[1][threadIdx.x >> 6] = l1; }
     __syncthreads();
     if (threadIdx.x < 2) {

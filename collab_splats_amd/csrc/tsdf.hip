@@ -17,6 +17,7 @@
 
 #define MC_QUAL static __constant__
 #include "mc_tables.h"
+#include "wgprims.h"
 
 namespace {
 
@@ -71,25 +72,6 @@ __device__ __forceinline__ int64_t voxel_ref(const Grid& g, const int32_t* __res
 __device__ __forceinline__ float plane(const float* __restrict__ pool, int64_t ref, int c) {
     const int64_t s = ref >> 12;
     return pool[(s * kPlanes + c) * kUnitVoxels + (ref & 4095)];
-}
-
-// exclusive scan of one value per thread over a 256-thread workgroup; `total` = the workgroup's sum
-__device__ __forceinline__ uint32_t block_scan_excl(uint32_t x, uint32_t* wsum, uint32_t& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t incl = x;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = __shfl_up(incl, off);
-        if (lane >= off) incl += o;
-    }
-    __syncthreads();                                    // wsum may still be read by a previous call
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0u;
-    total = 0u;
-#pragma unroll
-    for (int w = 0; w < 4; w++) { before += (w < wave) ? wsum[w] : 0u; total += wsum[w]; }
-    return before + incl - x;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- mark
@@ -243,39 +225,7 @@ __global__ __launch_bounds__(4096 / kVPL) void tsdf_integrate_kernel(Grid g, con
 }
 
 // ------------------------------------------------------------------------------------------------------ scan / order
-// Exclusive scan by ONE workgroup per array (blockIdx.x selects array b of `in` / `out`, each n long): a few thousand block
-// counts or one count per allocated unit.
-__global__ __launch_bounds__(1024) void tsdf_scan_kernel(const int32_t* __restrict__ in, int64_t n, int32_t* __restrict__ out,
-                                                         int32_t* __restrict__ total) {
-    __shared__ int32_t wsum[16];
-    __shared__ int32_t carry_s;
-    in += blockIdx.x * n;
-    out += blockIdx.x * n;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) carry_s = 0;
-    __syncthreads();
-    for (int64_t b0 = 0; b0 < n; b0 += 1024) {
-        const int64_t i = b0 + threadIdx.x;
-        const int32_t x = i < n ? in[i] : 0;
-        int32_t incl = x;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int32_t o = __shfl_up(incl, off);
-            if (lane >= off) incl += o;
-        }
-        if (lane == 63) wsum[wave] = incl;
-        __syncthreads();
-        int32_t before = carry_s, all = 0;
-#pragma unroll
-        for (int w = 0; w < 16; w++) { before += (w < wave) ? wsum[w] : 0; all += wsum[w]; }
-        if (i < n) out[i] = before + incl - x;
-        __syncthreads();
-        if (threadIdx.x == 0) carry_s += all;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) total[blockIdx.x] = carry_s;
-}
-
+// The scans of the block counts and of the per-unit counts are wgprims.h's carry_scan_kernel (one workgroup per array).
 // allocated units of map block b (4096 map entries, 16 consecutive per lane): count (WRITE = false) or write their map
 // indices, in map order, from offs[b] on (WRITE = true)
 template <bool WRITE>
@@ -289,7 +239,7 @@ __global__ __launch_bounds__(256) void tsdf_order_kernel(int64_t n_map, const in
     for (int k = 0; k < 16; k++)
         if (m0 + k < n_map && slot_map[m0 + k] >= 0) bits |= 1u << k;
     uint32_t total;
-    const uint32_t pre = block_scan_excl((uint32_t)__popc(bits), wsum, total);
+    const uint32_t pre = block_scan_excl<uint32_t, 4>((uint32_t)__popc(bits), wsum, total);
     if (!WRITE) {
         if (threadIdx.x == 0) counts[blockIdx.x] = (int32_t)total;
         return;
@@ -371,8 +321,8 @@ __global__ __launch_bounds__(256) void mc_count_kernel(Grid g, const int32_t* __
         nt += tri;
     }
     uint32_t tv, tt;
-    (void)block_scan_excl(nv, wsum, tv);
-    (void)block_scan_excl(nt, wsum, tt);
+    (void)block_scan_excl<uint32_t, 4>(nv, wsum, tv);
+    (void)block_scan_excl<uint32_t, 4>(nt, wsum, tt);
     if (t == 0) {
         unit_counts[blockIdx.x] = (int32_t)tv;
         unit_counts[n_units + blockIdx.x] = (int32_t)tt;
@@ -399,7 +349,7 @@ __global__ __launch_bounds__(256) void mc_vertices_kernel(Grid g, const int32_t*
 #pragma unroll
     for (int k = 0; k < 16; k++) { c[k] = cnt[v0 + k]; n += __popc(c[k] & 7u); }
     uint32_t total;
-    int32_t idx = voffs[blockIdx.x] + (int32_t)block_scan_excl(n, wsum, total);
+    int32_t idx = voffs[blockIdx.x] + (int32_t)block_scan_excl<uint32_t, 4>(n, wsum, total);
     for (int k = 0; k < 16; k++) {
         const uint32_t mask = c[k] & 7u;
         if (!mask) continue;
@@ -443,7 +393,7 @@ __global__ __launch_bounds__(256) void mc_triangles_kernel(Grid g, const int32_t
 #pragma unroll
     for (int k = 0; k < 16; k++) { c[k] = cnt[v0 + k]; n += c[k] >> 3; }
     uint32_t total;
-    int64_t tri = toffs[blockIdx.x] + (int32_t)block_scan_excl(n, wsum, total);
+    int64_t tri = toffs[blockIdx.x] + (int32_t)block_scan_excl<uint32_t, 4>(n, wsum, total);
     for (int k = 0; k < 16; k++) {
         const int nt = c[k] >> 3;
         if (!nt) continue;
@@ -479,8 +429,6 @@ bool make_grid(const misplat_tsdf_grid* p, Grid& g, int64_t& n_map) {
     g.ulen = p->voxel_size * 16.f;
     return true;
 }
-
-inline int launched() { return hipGetLastError() == hipSuccess ? MISPLAT_OK : MISPLAT_ELAUNCH; }
 
 }  // namespace
 
@@ -533,7 +481,8 @@ extern "C" int misplat_tsdf_order(const misplat_tsdf_grid* grid, const int32_t* 
     const int64_t nb = (n_map + 4095) / 4096;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(tsdf_order_kernel<false>, dim3((unsigned)nb), dim3(256), 0, s, n_map, slot_map, scratch, nullptr, nullptr);
-    hipLaunchKernelGGL(tsdf_scan_kernel, dim3(1), dim3(1024), 0, s, scratch, nb, scratch + nb, scratch + 2 * nb);
+    hipLaunchKernelGGL((carry_scan_kernel<int32_t, int32_t>), dim3(1), dim3(kScanBlock), 0, s, (const int32_t*)scratch, nb, nb,
+                       scratch + nb, scratch + 2 * nb);
     hipLaunchKernelGGL(tsdf_order_kernel<true>, dim3((unsigned)nb), dim3(256), 0, s, n_map, slot_map, nullptr, scratch + nb, order);
     return launched();
 }
@@ -550,7 +499,8 @@ extern "C" int misplat_tsdf_mc_count(const misplat_tsdf_grid* grid, const int32_
     hipLaunchKernelGGL(mc_classify_kernel, dim3((unsigned)n_units), dim3(256), 0, s, g, slot_map, order, pool, code);
     hipLaunchKernelGGL(mc_count_kernel, dim3((unsigned)n_units), dim3(256), 0, s, g, slot_map, order, (int64_t)n_units, pool,
                        (const uint16_t*)code, cnt, unit_counts);
-    hipLaunchKernelGGL(tsdf_scan_kernel, dim3(2), dim3(1024), 0, s, unit_counts, (int64_t)n_units, unit_offs, totals);
+    hipLaunchKernelGGL((carry_scan_kernel<int32_t, int32_t>), dim3(2), dim3(kScanBlock), 0, s, (const int32_t*)unit_counts,
+                       (int64_t)n_units, (int64_t)n_units, unit_offs, totals);
     return launched();
 }
 

@@ -6,10 +6,10 @@ import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 src = sys.argv[1]
 flt = sys.argv[2] if len(sys.argv) > 2 else ""
-extra = ["-ffp-contract=off"] if src == "project.hip" else (["-fno-slp-vectorize"] if src == "blend.hip" else [])
+sys.path.insert(0, ROOT)
+from collab_splats_amd import build as B                     # the flags the library ships with: COMMON and the file's own
 out = os.path.join(tempfile.gettempdir(), src.replace(".hip", ".s"))
-subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-fno-fast-math",
-                *extra, *[a for a in sys.argv[3:]], "-S", "--cuda-device-only", os.path.join(ROOT, "collab_splats_amd", "csrc", src), "-o", out],
+subprocess.run([B._hipcc(), *B.COMMON, *B.SOURCES[src], *sys.argv[3:], "-S", "--cuda-device-only", os.path.join(B.CSRC, src), "-o", out],
                check=True, stderr=subprocess.DEVNULL)
 txt = open(out).read()
 filt = "c++filt"

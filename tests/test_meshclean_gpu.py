@@ -308,8 +308,16 @@ def test_threshold_is_strict():
 
 
 def test_segment_plane():
+    _segment_plane(20000)
+
+
+def test_segment_plane_refit_sums_more_partials_than_the_final_workgroup_has_threads():
+    _segment_plane(65800)                                           # 258 workgroup partials of 256 points through 256 threads
+
+
+def _segment_plane(n):
     import collab_splats_amd as m
-    P, nrm = Q.planted_plane(20000, seed=0)                         # 60 % on the plane (+- t / 4), 40 % uniform clutter
+    P, nrm = Q.planted_plane(n, seed=0)                             # 60 % on the plane (+- t / 4), 40 % uniform clutter
     plane, inliers, index = m.segment_plane(_v(P), 0.02, 3, 300, 11, return_index=True)
     rplane, rinl, rindex = R.segment_plane(P, 0.02, 300, 11)
     assert plane.dtype == torch.float64 and not plane.is_cuda and inliers.dtype == torch.int64 and inliers.is_cuda

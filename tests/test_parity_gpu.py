@@ -2789,6 +2789,33 @@ def test_sparse_reduce_kernels_bitmaps_union_pack_unpack(dev):
             assert torch.equal(o[idt.long()], 2 * t[idt.long()]) and bool((o[torch.from_numpy(keep).to(dev)] == 7.0).all())
 
 
+def test_sparse_reduce_union_scan_takes_a_second_trip(dev):
+    """1 025 block counts (one per 2 048 rows): the one-workgroup scan of 1 024 counts a trip carries its sum into a second
+    trip.  The same chain and the same assertions as the test above, without the packing."""
+    from collab_splats_amd import _lib
+    lib = _lib.load()
+    rng = np.random.default_rng(4)
+    n, world = 1025 * 2048 - 5, 2
+    flags = (rng.random((world, n)) < 0.04).astype(np.uint8)
+    nbytes = (n + 7) // 8
+    gathered = torch.from_numpy(np.stack([np.packbits(flags[w], bitorder="little") for w in range(world)])).to(dev)
+    n_blocks = (nbytes + 255) // 256
+    assert n_blocks == 1025
+    counts = torch.empty(n_blocks, dtype=torch.int32, device=dev)
+    _lib.check(lib.misplat_union_count(_lib.ptr(gathered), C.c_int32(world), C.c_int64(nbytes), _lib.ptr(counts), _lib.stream_ptr()), "count")
+    rows = np.flatnonzero(flags.any(0))
+    incl = torch.cumsum(counts, 0, dtype=torch.int64)
+    assert int(incl[-1]) == rows.size and int(counts[-1]) > 0
+    offs_k = torch.full((n_blocks,), -1, dtype=torch.int64, device=dev)
+    total_k = torch.full((1,), -1, dtype=torch.int64, device=dev)
+    _lib.check(lib.misplat_union_scan(_lib.ptr(counts), C.c_int64(n_blocks), _lib.ptr(offs_k), _lib.ptr(total_k), _lib.stream_ptr()), "scan")
+    assert torch.equal(offs_k, incl - counts) and int(total_k) == rows.size
+    ids = torch.empty(rows.size, dtype=torch.int32, device=dev)
+    _lib.check(lib.misplat_union_ids(_lib.ptr(gathered), C.c_int32(world), C.c_int64(nbytes), _lib.ptr(offs_k), _lib.ptr(ids),
+                                     C.c_int64(ids.numel()), _lib.stream_ptr()), "ids")
+    assert np.array_equal(ids.cpu().numpy(), rows.astype(np.int32))
+
+
 def test_memset_node_in_a_captured_sequence_is_applied_on_every_replay(dev):
     """Round 2 saw a replayed forward return "garbage + n" intersections when its captured sequence began with a 16-byte
     hipMemsetAsync of the counters, and removed every memset from the library without finding out why.  The same construct in
