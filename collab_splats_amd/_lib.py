@@ -147,6 +147,9 @@ SYMBOLS = {
     "misplat_grouping_merge_copy": (C.c_int, 12), "misplat_grouping_members": (C.c_int, 6),
     "misplat_bilagrid_scratch_floats": (C.c_int64, 5), "misplat_bilagrid_slice_fwd": (C.c_int, 9),
     "misplat_bilagrid_slice_bwd": (C.c_int, 14), "misplat_bilagrid_tv_fwd": (C.c_int, 8), "misplat_bilagrid_tv_bwd": (C.c_int, 8),
+    "misplat_density_workspace": (C.c_int64, 2), "misplat_density_records": (C.c_int, 9),
+    "misplat_density_count": (C.c_int, 13), "misplat_density_emit": (C.c_int, 14), "misplat_density_lists": (C.c_int, 12),
+    "misplat_density_accumulate": (C.c_int, 10), "misplat_density_query": (C.c_int, 15),
     "misplat_version": (C.c_char_p, 0),
 }
 

@@ -58,6 +58,9 @@ SOURCES = {
     # bilagrid.hip: fixed IEEE operation order: the luma z (black exactly 0, white exactly 1), the interval floor(gz) and the
     # lerp form a + t (b - a) equal the fp32 restatement (tests/); a locally constant grid is reproduced bit for bit
     "bilagrid.hip": ["-ffp-contract=off"],
+    # density.hip: fixed IEEE operation order: the Gaussians' frames, unit ranges and slab tests, hence the unit lists, equal
+    # the fp32 restatement (tests/) bit for bit; the accumulation's multiply-adds are written as explicit fma
+    "density.hip": ["-ffp-contract=off"],
 }
 
 

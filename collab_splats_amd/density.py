@@ -1,0 +1,372 @@
+"""The density of the Gaussian mixture itself on the MI355X, and marching-cubes meshes of its level sets (csrc/density.hip,
+DESIGN.md section 25).
+
+What the reference's ``MarchingCubesMesh`` and ``LevelSetExtractor`` reach through ``model.get_density`` /
+``get_density_grad`` / ``get_closest_gaussians`` (collab_splats/utils/mesh.py:1234-1359, :1045-1230), restated from the
+published definition (SuGaR's density): with ``A = diag(1 / s) R(q)^T`` and ``m_g(x) = |A_g (x - mu_g)|^2``,
+
+    k_g(x) = o_g (exp(-m_g / 2) - exp(-r^2 / 2))  where m_g < r^2, else 0;      d(x) = sum_g k_g(x)
+
+(continuous at the cut-off ``r``).  ``DensityField`` evaluates ``d`` on the TSDF volume's lattice (voxel ``g`` centred at
+``(g + 0.5) voxel_size``, units of 16^3 voxels, only the units a Gaussian reaches allocated), answers point queries from the
+same per-unit lists and extracts level sets through the TSDF volume's marching cubes.  Everything stays on the device; there is
+no CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+import time
+from typing import Dict, Optional, Tuple
+
+import numpy as np
+import torch
+from torch import Tensor
+
+from ._lib import MisplatError, check, load, ptr, require_gpu, stream_ptr
+from .tsdf import MAX_UNITS, UNIT, UNIT_VOXELS, Grid, _unit_range
+
+REC = 16                             # floats per record (include/misplat.h MISPLAT_DENSITY_REC)
+MAX_CHANNELS = 16                    # channels of query's values (MISPLAT_DENSITY_MAX_CHANNELS)
+MAX_PAIRS = (1 << 31) - 4096
+
+
+def _scalars(name: str, voxel_size, cutoff, min_opacity) -> Tuple[float, float, float]:
+    try:
+        h, r, mo = float(voxel_size), float(cutoff), float(min_opacity)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name}: voxel_size, cutoff and min_opacity must be numbers") from None
+    if not (h > 0 and math.isfinite(h)):
+        raise ValueError(f"{name}: voxel_size must be a finite number > 0, got {voxel_size!r}")
+    if not 0 < r <= 6:
+        raise ValueError(f"{name}: cutoff must be in (0, 6], got {cutoff!r}")
+    if not 0 <= mo <= 1:
+        raise ValueError(f"{name}: min_opacity must be in [0, 1], got {min_opacity!r}")
+    return h, r, mo
+
+
+def _gaussians(name: str, means, quats, scales, opacities) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    for label, t in (("means", means), ("quats", quats), ("scales", scales), ("opacities", opacities)):
+        if not isinstance(t, Tensor) or not t.is_floating_point():
+            raise ValueError(f"{name}: {label} must be a floating-point tensor")
+    if means.dim() != 2 or means.shape[1] != 3:
+        raise ValueError(f"{name}: means must be [N,3], got {tuple(means.shape)}")
+    n = means.shape[0]
+    if tuple(quats.shape) != (n, 4):
+        raise ValueError(f"{name}: quats must be [{n},4], got {tuple(quats.shape)}")
+    if tuple(scales.shape) != (n, 3):
+        raise ValueError(f"{name}: scales must be [{n},3], got {tuple(scales.shape)}")
+    if tuple(opacities.shape) not in ((n,), (n, 1)):
+        raise ValueError(f"{name}: opacities must be [{n}] or [{n},1], got {tuple(opacities.shape)}")
+    if n >= 1 << 31:
+        raise ValueError(f"{name}: at most 2^31 - 1 Gaussians")
+    return means, quats, scales, opacities.reshape(-1)
+
+
+def _points(name: str, points) -> Tensor:
+    if not isinstance(points, Tensor) or not points.is_floating_point() or points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"{name}: points must be a floating-point tensor [P,3], got "
+                         f"{tuple(points.shape) if isinstance(points, Tensor) else type(points).__name__}")
+    if points.shape[0] >= 1 << 31:
+        raise ValueError(f"{name}: at most 2^31 - 1 points")
+    return points
+
+
+def _values(name: str, values, n: int) -> Optional[Tensor]:
+    if values is None:
+        return None
+    if not isinstance(values, Tensor) or not values.is_floating_point() or values.dim() != 2 or values.shape[0] != n:
+        raise ValueError(f"{name}: values must be a floating-point tensor [{n},D], got "
+                         f"{tuple(values.shape) if isinstance(values, Tensor) else type(values).__name__}")
+    if not 1 <= values.shape[1] <= MAX_CHANNELS:
+        raise ValueError(f"{name}: values must have 1..{MAX_CHANNELS} channels, got D = {values.shape[1]}")
+    return values
+
+
+def _f32(t: Tensor) -> Tensor:
+    return t.detach().to(torch.float32).contiguous()
+
+
+class _Stages:
+    """Seconds per build stage into a dict, each stage synchronised; nothing at all without a dict."""
+
+    def __init__(self, out: Optional[dict]):
+        self.out = out
+        if out is not None:
+            torch.cuda.synchronize()
+            self.t = time.perf_counter()
+
+    def __call__(self, stage: str) -> None:
+        if self.out is not None:
+            torch.cuda.synchronize()
+            now = time.perf_counter()
+            self.out[stage] = now - self.t
+            self.t = now
+
+
+class DensityField:
+    """The mixture's density on the lattice of voxel size ``voxel_size``.
+
+    ``means [N,3]``, ``quats [N,4]`` (wxyz, normalised inside), ACTIVATED ``scales [N,3]`` > 0 and ``opacities [N]`` in [0,1]:
+    the arguments of the ``rasterization()`` call.  A Gaussian with opacity below ``min_opacity`` or a non-finite parameter takes
+    no part.  ``bounds`` (``[[min xyz], [max xyz]]``): the unit map covers the units overlapping the box and nothing outside is
+    evaluated; without it the map covers the AABB of ``mu +- E`` over the participating Gaussians, padded by one voxel (``E``: the
+    half sides of the support's box at the cut-off; one host read).  More than ``max_units`` map entries raise ``MisplatError``.
+    Two more host reads give the number of (unit, Gaussian) pairs and of allocated units.  Two builds are bitwise equal."""
+
+    def __init__(self, means: Tensor, quats: Tensor, scales: Tensor, opacities: Tensor, voxel_size: float, cutoff: float = 3.0,
+                 min_opacity: float = 1.0 / 255.0, bounds=None, max_units: int = MAX_UNITS, _flags: int = 0,
+                 _timings: Optional[dict] = None):
+        name = "DensityField"
+        means, quats, scales, opacities = _gaussians(name, means, quats, scales, opacities)
+        h, r, mo = _scalars(name, voxel_size, cutoff, min_opacity)
+        clip = None
+        if bounds is not None:
+            b = np.asarray(bounds.detach().cpu() if isinstance(bounds, Tensor) else bounds, np.float64)
+            if b.shape != (2, 3) or not np.all(np.isfinite(b)) or not np.all(b[1] >= b[0]):
+                raise ValueError(f"{name}: bounds must be finite [[min xyz], [max xyz]] with max >= min")
+            clip = b
+        require_gpu(means, quats, scales, opacities)
+        self.device = means.device
+        self.voxel_size, self.cutoff, self.min_opacity = h, r, mo
+        self.ulen = float(np.float32(h) * np.float32(UNIT))
+        self.max_units = min(int(max_units), MAX_UNITS)
+        self.n_gauss = int(means.shape[0])
+        self.n_units = self.n_pairs = 0
+        self.lo = np.zeros(3, np.int64)
+        self.dims = np.zeros(3, np.int64)
+        self._slot_map = self._pool = self._ids = self._ranges = self._touched = None
+        self._records = torch.empty((self.n_gauss, REC), dtype=torch.float32, device=self.device)
+        if self.n_gauss == 0:
+            return
+        lib = load()
+        dev = self.device
+        mark = _Stages(_timings)                                # (scripts/density_bench.py: seconds per stage, synchronised)
+        mu, q, s, o = _f32(means), _f32(quats), _f32(scales), _f32(opacities)
+        cr, cmo = C.c_float(r), C.c_float(mo)
+        check(lib.misplat_density_records(ptr(mu), ptr(q), ptr(s), ptr(o), C.c_int64(self.n_gauss), cr, cmo, ptr(self._records),
+                                          stream_ptr()), "misplat_density_records")
+        mark("records")
+        if clip is None:
+            e = self._records[:, 13:16]
+            part = e[:, 0] >= 0
+            big = torch.full_like(e, float("inf"))
+            lo_w = torch.where(part[:, None], self._records[:, 0:3] - e, big).amin(0)
+            hi_w = torch.where(part[:, None], self._records[:, 0:3] + e, -big).amax(0)
+            box = torch.stack([lo_w, hi_w]).double().cpu().numpy()                   # host read
+            if not np.all(np.isfinite(box)):
+                return                                                               # no Gaussian takes part
+            clip = np.stack([box[0] - h, box[1] + h])               # (the one-voxel pad of the lists: every unit they reach)
+        lo, hi = _unit_range(clip[0], clip[1], self.ulen)
+        if np.any(np.abs(lo) >= 1 << 19) or np.any(np.abs(hi) >= (1 << 19) - 1):
+            raise MisplatError(f"{name}: the bounds reach unit {max(np.abs(lo).max(), np.abs(hi).max())}, beyond the lattice's "
+                               f"2^19 units per axis: pass bounds= or a larger voxel_size")
+        dims = hi - lo + 1
+        n_map = int(np.prod(dims.astype(object)))
+        if n_map > self.max_units:
+            raise MisplatError(f"{name}: the bounds span {n_map} units of {UNIT}^3 voxels, above the cap of {self.max_units}: "
+                               f"pass bounds= or a larger voxel_size")
+        self.lo, self.dims = lo.astype(np.int64), dims.astype(np.int64)
+        mark("bounds")
+        grid = self._grid()
+        N = C.c_int64(self.n_gauss)
+        ws = torch.empty(int(lib.misplat_density_workspace(N, C.c_int64(0))), dtype=torch.uint8, device=dev)
+        pair_off = torch.empty(self.n_gauss + 1, dtype=torch.int32, device=dev)
+        total = torch.empty(1, dtype=torch.int64, device=dev)
+        check(lib.misplat_density_count(C.byref(grid), ptr(mu), ptr(q), ptr(s), ptr(o), N, cr, cmo, ptr(ws), C.c_int64(ws.numel()),
+                                        ptr(pair_off), ptr(total), stream_ptr()), "misplat_density_count")
+        n_pairs = int(total.item())                                                  # host read
+        self._slot_map = torch.full((n_map,), -1, dtype=torch.int32, device=dev)
+        mark("count")
+        if n_pairs == 0:
+            return
+        if n_pairs >= MAX_PAIRS:
+            raise MisplatError(f"{name}: {n_pairs} (unit, Gaussian) pairs, above the cap of {MAX_PAIRS}: pass bounds= or a larger "
+                               f"voxel_size")
+        E = C.c_int64(n_pairs)
+        keys = torch.empty(n_pairs, dtype=torch.int32, device=dev)
+        ids = torch.empty(n_pairs, dtype=torch.int32, device=dev)
+        words = torch.zeros(n_map, dtype=torch.int64, device=dev)
+        check(lib.misplat_density_emit(C.byref(grid), ptr(mu), ptr(q), ptr(s), ptr(o), N, cr, cmo, ptr(pair_off), E, ptr(keys),
+                                       ptr(ids), ptr(words), stream_ptr()), "misplat_density_emit")
+        counters = torch.zeros(2, dtype=torch.int32, device=dev)
+        touched = torch.empty(2 * min(n_map, n_pairs), dtype=torch.int32, device=dev)
+        tgrid = self._grid()
+        check(lib.misplat_tsdf_alloc(C.byref(tgrid), ptr(words), ptr(self._slot_map), ptr(counters), ptr(touched), stream_ptr()),
+              "misplat_tsdf_alloc")
+        n_units = int(counters[0].item())                                            # host read: the pool's size
+        del words
+        mark("emit_alloc")
+        ws = torch.empty(int(lib.misplat_density_workspace(C.c_int64(0), E)), dtype=torch.uint8, device=dev)
+        keys_sorted = torch.empty(n_pairs, dtype=torch.int32, device=dev)
+        self._ids = torch.empty(n_pairs, dtype=torch.int32, device=dev)
+        self._ranges = torch.zeros((n_units, 2), dtype=torch.int32, device=dev)
+        check(lib.misplat_density_lists(C.byref(grid), ptr(self._slot_map), ptr(keys), ptr(ids), E, n_units, ptr(ws),
+                                        C.c_int64(ws.numel()), ptr(keys_sorted), ptr(self._ids), ptr(self._ranges), stream_ptr()),
+              "misplat_density_lists")
+        mark("lists")
+        del keys, ids, keys_sorted, ws
+        self._touched = touched
+        self._pool = torch.empty((n_units, 5, UNIT_VOXELS), dtype=torch.float32, device=dev)
+        check(lib.misplat_density_accumulate(C.byref(grid), ptr(touched), n_units, ptr(self._records), ptr(self._ids),
+                                             ptr(self._ranges), cr, int(_flags), ptr(self._pool), stream_ptr()),
+              "misplat_density_accumulate")
+        mark("accumulate")
+        self.n_units, self.n_pairs = n_units, n_pairs
+
+    # ------------------------------------------------------------------------------------------------------------ plumbing
+    def _grid(self) -> Grid:
+        g = Grid(self.voxel_size, self.voxel_size, 1.0)       # (sdf_trunc and depth_trunc: unused here, positive for tsdf.hip)
+        g.lo[:] = [int(x) for x in self.lo]
+        g.dims[:] = [int(x) for x in self.dims]
+        return g
+
+    def _map_order(self) -> Tensor:
+        return torch.nonzero(self._slot_map >= 0).squeeze(1)
+
+    # -------------------------------------------------------------------------------------------------------------- public
+    def units(self):
+        """The allocated units in map order, on the host (for tests and inspection): ``(coords [n,3] int64, d [n,4096],
+        (offsets [n + 1] int64, ids int32))``; voxel i = lx + 16 ly + 256 lz; unit k's list is ``ids[offsets[k]:offsets[k + 1]]``,
+        ascending."""
+        if self.n_units == 0:
+            return (np.zeros((0, 3), np.int64), np.zeros((0, UNIT_VOXELS), np.float32),
+                    (np.zeros(1, np.int64), np.zeros(0, np.int32)))
+        m = self._map_order()
+        slots = self._slot_map[m].long()
+        d = self._pool[slots, 0].cpu().numpy()
+        rng = self._ranges[slots].cpu().numpy().astype(np.int64)
+        ids = self._ids.cpu().numpy()
+        m = m.cpu().numpy()
+        nx, ny = int(self.dims[0]), int(self.dims[1])
+        coords = np.stack([m % nx, (m // nx) % ny, m // (nx * ny)], 1) + self.lo[None, :]
+        # (the pairs are sorted by map index: the lists lie in map order, end to end)
+        offsets = np.concatenate([rng[:, 0], rng[-1:, 1]])
+        assert np.array_equal(rng[1:, 0], rng[:-1, 1]) and rng[0, 0] == 0 and rng[-1, 1] == len(ids)
+        return coords, d, (offsets, ids)
+
+    def dense(self) -> Tensor:
+        """``[Dz 16, Dy 16, Dx 16]`` fp32 on the device, 0 in unallocated units: for inspection and small grids (torch ops)."""
+        dx, dy, dz = (int(v) for v in self.dims)
+        out = torch.zeros((dz, dy, dx, UNIT, UNIT, UNIT), dtype=torch.float32, device=self.device)
+        if self.n_units:
+            m = self._map_order()
+            out.view(-1, UNIT, UNIT, UNIT)[m] = self._pool[self._slot_map[m].long(), 0].view(-1, UNIT, UNIT, UNIT)
+        return out.permute(0, 3, 1, 4, 2, 5).reshape(dz * UNIT, dy * UNIT, dx * UNIT).contiguous()
+
+    def query(self, points: Tensor, values: Optional[Tensor] = None) -> Dict[str, Optional[Tensor]]:
+        """``{"density" [P], "grad" [P,3], "dominant" [P] int32, "values" [P,D] or None}`` at ``points [P,3]``, from the list of
+        the unit that holds the point's voxel; ``values [N,D]`` (1 <= D <= 16): per-Gaussian attributes, blended by the terms.
+        A point outside the map or in an unallocated unit gives 0 / 0 / -1 / 0.  One lane per point: points that arrive
+        spatially ordered (marching-cubes vertices) read coherent lists; sorting arbitrary points by unit first is left for
+        later."""
+        name = "DensityField.query"
+        points = _points(name, points)
+        values = _values(name, values, self.n_gauss)
+        require_gpu(points, values)
+        P = int(points.shape[0])
+        dev = self.device
+        out = {"density": torch.zeros(P, dtype=torch.float32, device=dev),
+               "grad": torch.zeros((P, 3), dtype=torch.float32, device=dev),
+               "dominant": torch.full((P,), -1, dtype=torch.int32, device=dev),
+               "values": None if values is None else torch.zeros((P, values.shape[1]), dtype=torch.float32, device=dev)}
+        if P == 0 or self.n_units == 0:
+            return out
+        p32 = _f32(points)
+        v32 = None if values is None else _f32(values)
+        grid = self._grid()
+        check(load().misplat_density_query(C.byref(grid), ptr(self._slot_map), ptr(self._records), ptr(self._ids), ptr(self._ranges),
+                                           C.c_float(self.cutoff), ptr(p32), C.c_int64(P), ptr(v32),
+                                           0 if v32 is None else int(v32.shape[1]), ptr(out["density"]), ptr(out["grad"]),
+                                           ptr(out["dominant"]), ptr(out["values"]), stream_ptr()), "misplat_density_query")
+        return out
+
+    def extract_mesh(self, iso: float = 0.5, values: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Optional[Tensor]]:
+        """Marching cubes of ``iso - d`` through the TSDF volume's extraction (csrc/tsdf.hip), in its deterministic order:
+        ``(vertices [M,3] fp32, triangles [T,3] int32, values at the vertices [M,D] or None)``.  The field is negative inside, so
+        triangles face decreasing density.  The vertex values are ``query(vertices, values)["values"]``.  The field's pool is
+        not changed: any number of level sets may be extracted.  An empty field, or ``iso`` above the maximum, gives the empty
+        triple."""
+        name = "DensityField.extract_mesh"
+        try:
+            iso = float(iso)
+        except (TypeError, ValueError):
+            raise ValueError(f"{name}: iso must be a number") from None
+        if not math.isfinite(iso):
+            raise ValueError(f"{name}: iso must be finite, got {iso!r}")
+        values = _values(name, values, self.n_gauss)
+        require_gpu(values)
+        dev = self.device
+        D = None if values is None else int(values.shape[1])
+        empty = (torch.zeros((0, 3), dtype=torch.float32, device=dev), torch.zeros((0, 3), dtype=torch.int32, device=dev),
+                 None if D is None else torch.zeros((0, D), dtype=torch.float32, device=dev))
+        if self.n_units == 0:
+            return empty
+        lib = load()
+        grid = self._grid()
+        n = self.n_units
+        work = self._pool.clone()                                  # (the extraction takes 5 planes: DESIGN.md section 25)
+        torch.sub(iso, self._pool[:, 0], out=work[:, 0])
+        nb = (int(np.prod(self.dims)) + 4095) // 4096
+        scratch = torch.empty(2 * nb + 1, dtype=torch.int32, device=dev)
+        order = torch.empty(n, dtype=torch.int32, device=dev)
+        check(lib.misplat_tsdf_order(C.byref(grid), ptr(self._slot_map), ptr(scratch), ptr(order), stream_ptr()),
+              "misplat_tsdf_order")
+        code = torch.empty(n * UNIT_VOXELS, dtype=torch.int16, device=dev)
+        cnt = torch.empty(n * UNIT_VOXELS, dtype=torch.uint8, device=dev)
+        unit_counts = torch.empty(2 * n, dtype=torch.int32, device=dev)
+        unit_offs = torch.empty(2 * n, dtype=torch.int32, device=dev)
+        totals = torch.empty(2, dtype=torch.int32, device=dev)
+        check(lib.misplat_tsdf_mc_count(C.byref(grid), ptr(self._slot_map), ptr(order), n, ptr(work), ptr(code), ptr(cnt),
+                                        ptr(unit_counts), ptr(unit_offs), ptr(totals), stream_ptr()), "misplat_tsdf_mc_count")
+        M, T = (int(x) for x in totals.tolist())                   # host read
+        if M == 0:
+            return empty
+        vert_base = torch.empty(n * UNIT_VOXELS, dtype=torch.int32, device=dev)
+        vertices = torch.empty((M, 3), dtype=torch.float32, device=dev)
+        unused = torch.empty((M, 3), dtype=torch.float32, device=dev)       # the pool carries no colour
+        triangles = torch.empty((T, 3), dtype=torch.int32, device=dev)
+        check(lib.misplat_tsdf_mc_emit(C.byref(grid), ptr(self._slot_map), ptr(order), n, ptr(work), ptr(code), ptr(cnt),
+                                       ptr(unit_offs), ptr(vert_base), ptr(vertices), ptr(unused), ptr(triangles), stream_ptr()),
+              "misplat_tsdf_mc_emit")
+        del work, code, cnt, vert_base, unused
+        return vertices, triangles, None if values is None else self.query(vertices, values)["values"]
+
+
+def gaussian_density(points: Tensor, means: Tensor, quats: Tensor, scales: Tensor, opacities: Tensor,
+                     voxel_size: Optional[float] = None, cutoff: float = 3.0, min_opacity: float = 1.0 / 255.0) -> Tensor:
+    """``d`` [P] at ``points [P,3]``: a ``DensityField`` over the points' bounding box, queried once.  ``voxel_size`` only sizes the
+    units the Gaussians are listed in (16 voxels a side): it changes the cost, not the value beyond the order of the sum's
+    roundings.  None: 1/512 of the box's longest side (at most 33 units per axis)."""
+    return _at_points("gaussian_density", points, means, quats, scales, opacities, voxel_size, cutoff, min_opacity)["density"]
+
+
+def gaussian_density_grad(points: Tensor, means: Tensor, quats: Tensor, scales: Tensor, opacities: Tensor,
+                          voxel_size: Optional[float] = None, cutoff: float = 3.0, min_opacity: float = 1.0 / 255.0) -> Tensor:
+    """``grad d`` [P,3] at ``points [P,3]``; see ``gaussian_density``."""
+    return _at_points("gaussian_density_grad", points, means, quats, scales, opacities, voxel_size, cutoff, min_opacity)["grad"]
+
+
+def _at_points(name, points, means, quats, scales, opacities, voxel_size, cutoff, min_opacity) -> Dict[str, Optional[Tensor]]:
+    points = _points(name, points)
+    _gaussians(name, means, quats, scales, opacities)
+    _scalars(name, 1.0 if voxel_size is None else voxel_size, cutoff, min_opacity)
+    require_gpu(points, means, quats, scales, opacities)
+    P = int(points.shape[0])
+    if P == 0:
+        return {"density": torch.zeros(0, dtype=torch.float32, device=points.device),
+                "grad": torch.zeros((0, 3), dtype=torch.float32, device=points.device)}
+    p = points.detach().double()
+    fin = torch.isfinite(p).all(1)
+    big = torch.full_like(p, float("inf"))
+    box = torch.stack([torch.where(fin[:, None], p, big).amin(0), torch.where(fin[:, None], p, -big).amax(0)]).cpu().numpy()
+    if not np.all(np.isfinite(box)):
+        box = np.zeros((2, 3))                                       # no finite point: every answer is 0
+    if voxel_size is None:
+        side = float((box[1] - box[0]).max())
+        voxel_size = side / 512.0 if side > 0 else 1.0
+    field = DensityField(means, quats, scales, opacities, voxel_size, cutoff, min_opacity, bounds=box)
+    return field.query(points)
+
+
+__all__ = ["DensityField", "gaussian_density", "gaussian_density_grad", "MAX_CHANNELS", "MisplatError"]

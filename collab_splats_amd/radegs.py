@@ -759,6 +759,87 @@ class RadegsModel(nn.Module):
         v, t, d, (c,), _ = poisson_trim(v, t, d, quantile=trim_quantile, min_density=min_density, attributes=(c,))
         return v, t, c, d
 
+    # ------------------------------------------------------------------ the mixture's own density
+    @property
+    def colors(self) -> Tensor:
+        """Splatfacto's ``colors`` [UNVERIFIED-UPSTREAM]: ``clamp(0.28209479177387814 features_dc + 0.5, 0, 1)``, or
+        ``sigmoid(features_dc)`` at ``sh_degree == 0``; [N,3]."""
+        dc = self.features_dc.reshape(-1, 3)
+        if self.config.sh_degree > 0:
+            return torch.clamp(dc * 0.28209479177387814 + 0.5, 0.0, 1.0)
+        return torch.sigmoid(dc)
+
+    def _activated(self, keep: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+        pick = (lambda t: t[keep]) if keep is not None else (lambda t: t)
+        return (pick(self.means.detach()).float(), pick(self.quats.detach()).float(),
+                torch.exp(pick(self.scales.detach()).float()), torch.sigmoid(pick(self.opacities.detach()).float()).reshape(-1))
+
+    @torch.no_grad()
+    def density_field(self, voxel_size: float, cutoff: float = 3.0, min_opacity: float = 1.0 / 255.0, bounds=None, obb_box=None):
+        """``density.DensityField`` of the model's Gaussians (activated scales and opacities).  With ``obb_box`` the Gaussians
+        outside it are dropped, as ``set_crop`` drops them from a render, and ``bounds`` default to the box's AABB
+        (``tsdf.obb_bounds``).  The field's Gaussian ids index the kept Gaussians: ``field.kept`` holds their indices in the
+        model (None without a box)."""
+        from .density import DensityField
+        from .tsdf import obb_bounds
+        keep = None
+        if obb_box is not None:
+            keep = torch.nonzero(obb_box.within(self.means.detach()).reshape(-1))[:, 0]
+            if bounds is None:
+                bounds = obb_bounds(obb_box)
+        field = DensityField(*self._activated(keep), voxel_size, cutoff, min_opacity, bounds=bounds)
+        field.kept = keep
+        return field
+
+    @torch.no_grad()
+    def get_density(self, points: Tensor, voxel_size: Optional[float] = None, cutoff: float = 3.0,
+                    min_opacity: float = 1.0 / 255.0) -> Tensor:
+        """The mixture's density [P] at ``points [P,3]`` (what the reference's exporters call, mesh.py:1300):
+        ``density.gaussian_density`` on the activated parameters."""
+        from .density import gaussian_density
+        return gaussian_density(points, *self._activated(), voxel_size, cutoff, min_opacity)
+
+    @torch.no_grad()
+    def get_density_grad(self, points: Tensor, voxel_size: Optional[float] = None, cutoff: float = 3.0,
+                         min_opacity: float = 1.0 / 255.0) -> Tensor:
+        """The density's gradient [P,3] (mesh.py:968): ``density.gaussian_density_grad`` on the activated parameters."""
+        from .density import gaussian_density_grad
+        return gaussian_density_grad(points, *self._activated(), voxel_size, cutoff, min_opacity)
+
+    @torch.no_grad()
+    def marching_cubes_mesh(self, cameras: Optional[Sequence] = None, camera_radius_multiplier: float = 2.0, resolution: int = 512,
+                            isosurface_threshold: float = 0.5, voxel_size: Optional[float] = None, obb_box=None,
+                            cutoff: float = 3.0, min_opacity: float = 1.0 / 255.0) -> Tuple[Tensor, Tensor, Tensor]:
+        """The reference's ``MarchingCubesMesh.main`` (mesh.py:1234-1359) on the device, with no dense grid: the level set
+        ``isosurface_threshold`` of the mixture's density.  With ``cameras``: the reference's cube, centred on the world origin,
+        half side ``camera_radius_multiplier`` x the largest distance of a camera centre from their mean (:1266-1275), sampled
+        at ``h = 2 radius / (resolution - 1)``.  With ``voxel_size`` instead: that ``h`` over the Gaussians' own bounds (the
+        box's AABB with ``obb_box``).  Gaussians outside ``obb_box`` are dropped.  Returns ``(vertices [M,3], triangles [T,3]
+        int32, colors [M,3])``, the colours ``self.colors`` blended by the Gaussians' terms at the vertex (the reference takes the
+        closest Gaussian's): ready for ``finish_mesh`` and ``tsdf.write_ply``."""
+        name = "marching_cubes_mesh"
+        bounds = None
+        if voxel_size is None:
+            if cameras is None:
+                raise ValueError(f"{name}: pass cameras (the reference's cube) or voxel_size")
+            cameras = list(cameras)
+            if not cameras:
+                raise ValueError(f"{name}: no cameras")
+            if not isinstance(resolution, int) or isinstance(resolution, bool) or resolution < 2:
+                raise ValueError(f"{name}: resolution must be an integer >= 2, got {resolution!r}")
+            centres = torch.stack([c.camera_to_worlds.reshape(-1, 3, 4)[0, :, 3].detach().double().cpu() for c in cameras])
+            radius = float(camera_radius_multiplier) * float(torch.linalg.norm(centres - centres.mean(0, keepdim=True), dim=-1).max())
+            if not (radius > 0 and math.isfinite(radius)):
+                raise ValueError(f"{name}: the cameras span no volume (radius {radius!r}): pass voxel_size")
+            voxel_size = 2.0 * radius / (resolution - 1)
+            bounds = [[-radius] * 3, [radius] * 3]
+        field = self.density_field(voxel_size, cutoff, min_opacity, bounds=bounds, obb_box=obb_box)
+        colors = self.colors.detach().float()
+        if field.kept is not None:
+            colors = colors[field.kept]
+        vertices, triangles, vcol = field.extract_mesh(isosurface_threshold, values=colors.contiguous())
+        return vertices, triangles, vcol
+
     @torch.no_grad()
     def associate_masks(self, cameras: Sequence, composite_masks: Sequence, front_percentage: float = 0.5, num_patches: int = 32,
                         iou_threshold: float = 0.1, bank=None):

@@ -1012,6 +1012,55 @@ int misplat_bilagrid_tv_fwd(const float* grids, int32_t num, int32_t grid_w, int
 int misplat_bilagrid_tv_bwd(const float* grids, int32_t num, int32_t grid_w, int32_t grid_h, int32_t grid_l, const float* v_loss,
                             float* v_grids, misplat_stream_t stream);
 
+/* ---- the Gaussian mixture's own density on the TSDF lattice, and its level sets (csrc/density.hip) ----
+ * Restated from the published definition (SuGaR's density); the oracle is tests/density_restatement.py.  means [N,3], quats
+ * [N,4] (wxyz, normalised inside), scales [N,3] > 0 and opacities [N] in [0,1], both ACTIVATED; 0 < cutoff r <= 6.  A Gaussian
+ * with opacity < min_opacity, a non-finite parameter, a non-positive scale or a zero quaternion takes no part.  With R = R(q)
+ * (columns e_a), A = diag(1 / s) R^T and m(x) = |A (x - mu)|^2:
+ *   k_g(x) = o_g (exp(-m_g / 2) - exp(-r^2 / 2)) where m_g < r^2, else 0 (continuous at the cut-off);  d(x) = sum_g k_g(x).
+ * Lattice, unit map and pool are misplat_tsdf's (voxel g centred at (g + 0.5) voxel_size, units of 16^3, 5 planes of 4096 fp32
+ * per slot): of the grid only voxel_size, lo and dims are read.  A Gaussian is listed in a unit by a conservative fp32 test in
+ * a fixed operation order (density.hip's head states it): the integer structures equal the restatement's bit for bit.
+ * Order of calls: records; count (the host reads n_pairs); emit into zeroed words; misplat_tsdf_alloc (slot_map all -1,
+ * counters zero: touched then lists the n_units allocated units); lists; accumulate; then query and misplat_tsdf_mc_* at will. */
+#define MISPLAT_DENSITY_REC 16          /* floats per record: mu[3], A[9] row-major, o, E[3] (E = -1: takes no part) */
+#define MISPLAT_DENSITY_BATCH 64        /* records accumulate stages in LDS at a time */
+#define MISPLAT_DENSITY_MAX_CHANNELS 16 /* channels of query's values */
+/* workspace bytes that serve count (n_pairs = 0) or lists; -1 for sizes the library refuses (n_gauss, n_pairs < 2^31). */
+int64_t misplat_density_workspace(int64_t n_gauss, int64_t n_pairs);
+/* records [N,16] (16-byte aligned); E_i = r sqrt(sum_a (R[i][a] s_a)^2), the half sides of the support's AABB. */
+int misplat_density_records(const float* means, const float* quats, const float* scales, const float* opacities,
+                            int64_t n_gauss, float cutoff, float min_opacity, float* records, misplat_stream_t stream);
+/* count: pair_off [N + 1] = the exclusive scan of the (unit, Gaussian) pairs per Gaussian; n_pairs: DEVICE int64, their number
+ * (exact also where the int32 scan has overflowed: the caller refuses >= 2^31 - 4096). */
+int misplat_density_count(const misplat_tsdf_grid* grid, const float* means, const float* quats, const float* scales,
+                          const float* opacities, int64_t n_gauss, float cutoff, float min_opacity, void* workspace,
+                          int64_t workspace_bytes, int32_t* pair_off, int64_t* n_pairs, misplat_stream_t stream);
+/* emit: keys / ids [n_pairs] = (unit map index, Gaussian) from pair_off[g] on, a Gaussian's units in ascending map order;
+ * words[unit] = 1 for every unit listed (misplat_tsdf_alloc's input; zeroed by the caller). */
+int misplat_density_emit(const misplat_tsdf_grid* grid, const float* means, const float* quats, const float* scales,
+                         const float* opacities, int64_t n_gauss, float cutoff, float min_opacity, const int32_t* pair_off,
+                         int64_t n_pairs, int32_t* keys, int32_t* ids, uint64_t* words, misplat_stream_t stream);
+/* lists: the pairs sorted by unit, stable (keys and ids are used as scratch): every unit's list is ascending in g;
+ * ranges [n_units, 2] = the part [begin, end) of ids_sorted that belongs to the unit in pool slot s. */
+int misplat_density_lists(const misplat_tsdf_grid* grid, const int32_t* slot_map, int32_t* keys, int32_t* ids, int64_t n_pairs,
+                          int32_t n_units, void* workspace, int64_t workspace_bytes, int32_t* keys_sorted, int32_t* ids_sorted,
+                          int32_t* ranges, misplat_stream_t stream);
+/* accumulate: plane 0 of every listed unit = d at its voxel centres, terms added in list order (two runs are bitwise equal);
+ * plane 1 = 1, planes 2..4 = 0.  touched: misplat_tsdf_alloc's {map index, slot} pairs.  flags bit 0: no sub-brick skipping (by
+ * default a wave passes over a record whose slabs miss its 8 x 8 x 16 brick). */
+int misplat_density_accumulate(const misplat_tsdf_grid* grid, const int32_t* touched, int32_t n_units, const float* records,
+                               const int32_t* ids_sorted, const int32_t* ranges, float cutoff, int32_t flags, float* pool,
+                               misplat_stream_t stream);
+/* query: at points [P,3], from the list of the unit that holds the point's voxel floor(p / voxel_size): density [P], grad
+ * [P,3], dominant [P] (the g of the largest term, the lowest at a tie; -1 where d = 0), values_out [P,D] = sum k_g values[g] /
+ * d (0 where d = 0) for values [N,D], 1 <= D <= 16; any output may be NULL (values and values_out go together).  A point
+ * outside the map or in an unallocated unit gives 0 / 0 / -1 / 0. */
+int misplat_density_query(const misplat_tsdf_grid* grid, const int32_t* slot_map, const float* records, const int32_t* ids_sorted,
+                          const int32_t* ranges, float cutoff, const float* points, int64_t n_points, const float* values,
+                          int32_t n_channels, float* density, float* grad, int32_t* dominant, float* values_out,
+                          misplat_stream_t stream);
+
 /* Library identification ("misplat <version> gfx950"). */
 const char* misplat_version(void);
 
