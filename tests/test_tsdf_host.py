@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import tsdf_fields as F_
 import tsdf_scenes as S
 from tsdf_restatement import RestatedTSDF
 from collab_splats_amd import mc_tables as mc
@@ -114,6 +115,63 @@ def test_restatement_sphere_is_closed_and_has_the_right_volume():
     vol = np.einsum("ij,ij->i", a, np.cross(b, cc)).sum() / 6
     assert abs(vol / (4 / 3 * np.pi * radius ** 3) - 1) < 0.03
     assert np.all((c >= 0) & (c <= 1)) and c.std() > 0.05
+
+
+def _restated(field, vs):
+    r = RestatedTSDF(vs, 3 * vs)
+    r.units = {u: d.copy() for u, d in field.items()}
+    return r
+
+
+def test_restated_random_block_against_independent_references():
+    """A closed random field over 2 x 2 x 2 units takes all 256 configurations; the restatement's mesh of it has a vertex at
+    the fp64 rule's place on every sign-changing lattice edge and nowhere else, is closed and consistently oriented, and
+    winds once around every negative voxel centre and not at all around the others."""
+    vs = 0.013
+    field = F_.random_field(F_.block((-1, -2, 3), (2, 2, 2)), seed=11, p_neg=0.5, closed=True)
+    cfg = F_.configurations(field)
+    assert np.all(cfg > 0), f"configurations never taken: {np.flatnonzero(cfg == 0).tolist()}"
+    ntri, _, _ = mc.tables()
+    assert set(np.flatnonzero(ntri == 5)) <= set(np.flatnonzero(cfg)) and int((ntri == 5).sum()) == 32
+    v, f, c = _restated(field, vs).extract_mesh()
+    assert len(f) == F_.triangle_total(field, ntri) and len(f) > 50000
+    F_.check_vertices(field, vs, v, c)
+    F_.check_directed_edges(f, len(v))
+    F_.check_winding(field, vs, v, f, n=600, seed=5)
+
+
+def test_restated_open_fields_follow_the_vertex_rule():
+    """Weight-0 voxels, exact zeros of both signs and unallocated neighbours: the vertices are still those of the rule."""
+    vs = 0.02
+    field = F_.random_field(F_.block((0, 0, 0), (2, 1, 1)), seed=3, p_neg=0.4, w0=0.05, zeros=0.02)
+    plus, minus = F_.zeros_next_to_negatives(field)
+    assert plus > 0 and minus > 0
+    v, f, c = _restated(field, vs).extract_mesh()
+    assert F_.check_vertices(field, vs, v, c) > 1000
+    assert len(f) == F_.triangle_total(field, mc.tables()[0])
+    assert len(np.unique(f)) == len(v)
+
+
+def test_winding_number_of_a_tetrahedron():
+    """The solid-angle sum itself: 1 inside an outward-facing tetrahedron, 0 outside, -1 inside the reversed one."""
+    v = np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0], [0, 0, 1]], np.float64)
+    f = np.array([[0, 2, 1], [0, 1, 3], [0, 3, 2], [1, 2, 3]])
+    q = np.array([[0.1, 0.2, 0.3], [0.6, 0.6, 0.6], [-0.1, 0.2, 0.2]])
+    assert np.allclose(F_.winding_numbers(v, f, q), [1, 0, 0], atol=1e-12)
+    assert np.allclose(F_.winding_numbers(v, f[:, ::-1], q), [-1, 0, 0], atol=1e-12)
+
+
+def test_room_views_reach_what_they_are_for():
+    """Cameras inside the volume: voxels behind every camera and off all four image sides, walls on every image border."""
+    d, vm, K, rgb = S.room_views(7, 33, 21, (30.0, 22.0, 13.3, 12.1), offset=(300.0, -200.0, 150.0))
+    assert d.shape == (7, 21, 33, 1) and rgb.shape == (7, 21, 33, 3) and vm.dtype == np.float32
+    assert np.all(K[:, 0, 0] != K[:, 1, 1]) and np.all(K[:, 0, 2] != 33 / 2)
+    for edge in (d[:, 0], d[:, -1], d[:, :, 0], d[:, :, -1]):
+        assert (edge > 0).all()
+    r = RestatedTSDF(0.02, 0.06, 0.7)
+    reach = S.projection_reach(r, d, vm, K, range(7))
+    assert all(n > 0 for n in reach.values()), reach
+    assert r.touched_units(d[0, ..., 0], vm[0], K[0]).min(0)[0] > 900
 
 
 @pytest.mark.parametrize("scene", ["sphere", "plane"])

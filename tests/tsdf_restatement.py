@@ -63,7 +63,9 @@ class RestatedTSDF:
             return np.zeros((0, 3), np.int64)
         ext = boxes[:, 1] - boxes[:, 0] + 1
         out = []
-        n = int(ext.max()) if ext.size else 0
+        if not np.any(np.all(ext > 0, 1)):                # the bounds leave no sample a unit
+            return np.zeros((0, 3), np.int64)
+        n = int(ext.max())
         for oz in range(n):
             for oy in range(n):
                 for ox in range(n):

@@ -131,6 +131,68 @@ def plane_views(n, W, H, height=0.6, seed=0):
             np.stack(rgbs), np.stack(masks))
 
 
+ROOM = ((-0.5, -0.4, -0.3), (0.6, 0.5, 0.45))
+
+
+def room_views(n, W, H, K, room=ROOM, radius=0.08, offset=(0.0, 0.0, 0.0), eye_radius=0.25, seed=0):
+    """n views from INSIDE an axis-aligned room with a small sphere in it, all shifted by the world ``offset``.  K = (fx, fy,
+    cx, cy) is the caller's (off-centre, fx != fy allowed).  Eyes are drawn within eye_radius of the room's centre (clear of
+    the sphere); each looks at a point drawn anywhere in the room, so walls cross every image border, parts of the volume lie
+    behind every camera and parts project off all four image sides."""
+    rng = np.random.default_rng(seed)
+    off = np.asarray(offset, np.float64)
+    lo, hi = np.asarray(room[0], np.float64) + off, np.asarray(room[1], np.float64) + off
+    mid = 0.5 * (lo + hi)
+    centre = mid + np.array([0.22, -0.17, -0.12])
+    fx, fy, cx, cy = (float(x) for x in K)
+    Km = np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1]])
+    vms, deps, rgbs = [], [], []
+    while len(vms) < n:
+        e = rng.standard_normal(3)
+        eye = mid + eye_radius * rng.random() ** (1 / 3) * e / np.linalg.norm(e)
+        target = lo + (hi - lo) * rng.random(3)
+        if np.linalg.norm(eye - centre) < radius + 0.05 or np.linalg.norm(target - eye) < 0.1:
+            continue
+        z = (target - eye) / np.linalg.norm(target - eye)
+        M = look_at(eye, target, up=(0, 0, 1) if abs(z[2]) < 0.9 else (0, 1, 0))
+        dep, rgb = render_sphere(M, Km, W, H, centre, radius, room=(lo, hi))
+        vms.append(M); deps.append(dep); rgbs.append(rgb)
+    return (np.stack(deps)[..., None], np.stack(vms).astype(np.float32), np.repeat(Km[None], n, 0).astype(np.float32),
+            np.stack(rgbs))
+
+
+def projection_reach(r, depths, vms, Ks, views):
+    """What the integration of ``views`` meets, recomputed from the restatement's formulas over the voxels of the units each
+    view touches (``r``: a RestatedTSDF with the volume's parameters): voxels behind the camera, voxels in front of it that
+    project off each image side, and voxels landing in the first half pixel (0.0001 <= u_f < 0.5)."""
+    from tsdf_restatement import LOCAL
+    F = np.float32
+    H, W = depths.shape[1:3]
+    out = dict(behind=0, left=0, right=0, top=0, bottom=0, first_half_pixel=0, inside=0)
+    for j in views:
+        M, K = np.asarray(vms[j], np.float32), np.asarray(Ks[j], np.float32)
+        U = r.touched_units(np.asarray(depths[j], np.float32).reshape(H, W), M, K)
+        if len(U) == 0:
+            continue
+        g = (U[:, None, :] * 16 + LOCAL[None]).astype(np.float32)
+        x, y, z = [((g[..., a] + F(0.5)) * r.vs) for a in range(3)]
+        with np.errstate(all="ignore"):
+            zc = ((M[2, 0] * x + M[2, 1] * y) + M[2, 2] * z) + M[2, 3]
+            xc = ((M[0, 0] * x + M[0, 1] * y) + M[0, 2] * z) + M[0, 3]
+            yc = ((M[1, 0] * x + M[1, 1] * y) + M[1, 2] * z) + M[1, 3]
+            uf = ((xc * K[0, 0]) / zc + K[0, 2]) + F(0.5)
+            vf = ((yc * K[1, 1]) / zc + K[1, 2]) + F(0.5)
+        front = zc > 0
+        out["behind"] += int((~front).sum())
+        out["left"] += int((front & (uf < F(0.0001))).sum())
+        out["right"] += int((front & (uf >= F(W))).sum())
+        out["top"] += int((front & (vf < F(0.0001))).sum())
+        out["bottom"] += int((front & (vf >= F(H))).sum())
+        out["first_half_pixel"] += int((front & (uf >= F(0.0001)) & (uf < F(0.5))).sum())
+        out["inside"] += int((front & (uf >= F(0.0001)) & (uf < F(W)) & (vf >= F(0.0001)) & (vf < F(H))).sum())
+    return out
+
+
 def pinhole_camera(M, K, W, H):
     """A ``radegs.PinholeCamera`` (nerfstudio conventions: OpenGL c2w) for the OpenCV world -> camera matrix M."""
     import torch
