@@ -127,29 +127,22 @@ __global__ __launch_bounds__(256) void label_kernel(const int32_t* __restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------------------- workspace
-struct Layout {
-    int64_t cap;
-    int64_t o_keys, o_counts, o_starts, o_vslot, o_pts, o_scan, o_parent, o_size, o_root, o_keep, o_rank, total;
+struct Work {
+    IndexBufs ix;
+    int32_t *vslot, *scr, *parent, *size, *root, *keep, *rank;
 };
 
-inline Layout layout(int64_t M) {
-    Layout L;
-    L.cap = hash_capacity(M);
-    const int64_t scan_n = L.cap > M ? L.cap : M;
-    int64_t o = 0;
-    L.o_keys = o;   o += al(8 * L.cap);
-    L.o_counts = o; o += al(4 * L.cap);
-    L.o_starts = o; o += al(4 * (L.cap + 1));
-    L.o_vslot = o;  o += al(4 * M);
-    L.o_pts = o;    o += al(16 * M);
-    L.o_scan = o;   o += al(scan_scratch_bytes(scan_n));
-    L.o_parent = o; o += al(4 * M);
-    L.o_size = o;   o += al(4 * M);
-    L.o_root = o;   o += al(4 * M);
-    L.o_keep = o;   o += al(4 * M);
-    L.o_rank = o;   o += al(4 * (M + 1));
-    L.total = o;
-    return L;
+inline Work carve(Carver& c, int64_t M) {
+    Work W;
+    W.ix = take_index(c, M);
+    W.vslot = c.take<int32_t>(M);
+    W.scr = take_scan(c, W.ix.cap > M ? W.ix.cap : M);              // the index's counts, then M keep flags
+    W.parent = c.take<int32_t>(M);
+    W.size = c.take<int32_t>(M);
+    W.root = c.take<int32_t>(M);
+    W.keep = c.take<int32_t>(M);
+    W.rank = c.take<int32_t>(M + 1);
+    return W;
 }
 
 inline bool sizes_ok(int64_t M) { return M >= 0 && M < (1ll << 30); }
@@ -158,7 +151,9 @@ inline bool sizes_ok(int64_t M) { return M >= 0 && M < (1ll << 30); }
 
 extern "C" int64_t misplat_cluster_workspace(int64_t n_vertices) {
     if (!sizes_ok(n_vertices)) return -1;
-    return layout(n_vertices).total;
+    Carver c{nullptr};
+    carve(c, n_vertices);
+    return c.o;
 }
 
 extern "C" int misplat_cluster_radius(const float* vertices, int64_t n_vertices, const uint8_t* mask, float radius,
@@ -169,41 +164,24 @@ extern "C" int misplat_cluster_radius(const float* vertices, int64_t n_vertices,
     if (!sizes_ok(M) || !(radius > 0.f) || !(radius < 3.0e37f) || !(inv_h < 3.0e38f) || min_cluster_size < 0 || !workspace ||
         !n_clusters || (M > 0 && (!vertices || !mask || !labels || !sizes)))
         return MISPLAT_EINVAL;
-    const Layout L = layout(M);
-    if (workspace_bytes < L.total) return MISPLAT_EWORKSPACE;
+    Carver c{(char*)workspace};
+    const Work W = carve(c, M);
+    if (workspace_bytes < c.o) return MISPLAT_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     if (M == 0) {
         misplat_internal::fill_bytes(n_clusters, 4, 0u, s);
         return launched();
     }
-    char* ws = (char*)workspace;
-    unsigned long long* keys = (unsigned long long*)(ws + L.o_keys);
-    int32_t* counts = (int32_t*)(ws + L.o_counts);
-    int32_t* starts = (int32_t*)(ws + L.o_starts);
-    int32_t* vslot = (int32_t*)(ws + L.o_vslot);
-    float4* pts = (float4*)(ws + L.o_pts);
-    int32_t* scr = (int32_t*)(ws + L.o_scan);
-    int32_t* parent = (int32_t*)(ws + L.o_parent);
-    int32_t* size = (int32_t*)(ws + L.o_size);
-    int32_t* root = (int32_t*)(ws + L.o_root);
-    int32_t* keep = (int32_t*)(ws + L.o_keep);
-    int32_t* rank = (int32_t*)(ws + L.o_rank);
     const unsigned nb = blocks(M, 256);
-    misplat_internal::fill_bytes(keys, 8 * L.cap, 0xffffffffu, s);          // (kernels, not memsets: internal.h)
-    misplat_internal::fill_bytes(counts, 4 * L.cap, 0u, s);
-    hipLaunchKernelGGL(init_kernel, dim3(nb), dim3(256), 0, s, M, parent, size);
-    hipLaunchKernelGGL(index_insert_kernel, dim3(nb), dim3(256), 0, s, vertices, M, mask, inv_h, keys, (uint32_t)(L.cap - 1),
-                       vslot, counts);
-    scan(counts, L.cap, starts, scr, s);
-    hipLaunchKernelGGL(index_fill_kernel, dim3(nb), dim3(256), 0, s, vertices, M, (const int32_t*)vslot, (const int32_t*)starts,
-                       counts, pts);
-    const Index ix{keys, starts, pts, (uint32_t)(L.cap - 1)};
-    hipLaunchKernelGGL(union_kernel, dim3(blocks(M * kSub, 256)), dim3(256), 0, s, ix, L.cap, radius, radius * radius, inv_h, parent);
-    hipLaunchKernelGGL(flatten_kernel, dim3(nb), dim3(256), 0, s, (const int32_t*)parent, mask, M, root, size);
-    hipLaunchKernelGGL(keep_kernel, dim3(nb), dim3(256), 0, s, (const int32_t*)root, (const int32_t*)size, M, min_cluster_size,
-                       keep);
-    scan(keep, M, rank, scr, s);
-    hipLaunchKernelGGL(label_kernel, dim3(nb), dim3(256), 0, s, (const int32_t*)root, (const int32_t*)size, (const int32_t*)rank,
-                       M, min_cluster_size, labels, sizes, n_clusters);
+    const Index ix = build_index(vertices, M, mask, inv_h, W.ix, W.vslot, W.scr, s);
+    hipLaunchKernelGGL(init_kernel, dim3(nb), dim3(256), 0, s, M, W.parent, W.size);
+    hipLaunchKernelGGL(union_kernel, dim3(blocks(M * kSub, 256)), dim3(256), 0, s, ix, W.ix.cap, radius, radius * radius, inv_h,
+                       W.parent);
+    hipLaunchKernelGGL(flatten_kernel, dim3(nb), dim3(256), 0, s, (const int32_t*)W.parent, mask, M, W.root, W.size);
+    hipLaunchKernelGGL(keep_kernel, dim3(nb), dim3(256), 0, s, (const int32_t*)W.root, (const int32_t*)W.size, M, min_cluster_size,
+                       W.keep);
+    scan(W.keep, M, W.rank, W.scr, s);
+    hipLaunchKernelGGL(label_kernel, dim3(nb), dim3(256), 0, s, (const int32_t*)W.root, (const int32_t*)W.size,
+                       (const int32_t*)W.rank, M, min_cluster_size, labels, sizes, n_clusters);
     return launched();
 }

@@ -368,23 +368,23 @@ __global__ __launch_bounds__(256) void density_query_kernel(Grid g, const int32_
 }
 
 // ----------------------------------------------------------------------------------------------------------- workspace
-struct Layout {
-    int64_t o_counts, o_scan, o_total, o_kb, o_vb, o_hist, o_hoff, nblk, total;
+// N Gaussians (misplat_density_count) and E pairs (misplat_density_lists): either may be 0 for the call that does not use it
+struct Work {
+    int32_t *counts, *scr;
+    unsigned long long* total;
+    int32_t *kb, *vb;                 // (not used: the sort runs between the caller's two pairs)
+    SortBufs sort;
 };
-inline Layout layout(int64_t N, int64_t E) {
-    Layout L;
-    int64_t o = 0;
-    L.nblk = (E + kTile - 1) / kTile;
-    const int64_t n_scan = N > 256 * L.nblk ? N : 256 * L.nblk;
-    L.o_counts = o; o += al(4 * (N + 1));
-    L.o_scan = o;   o += al(scan_scratch_bytes(n_scan + 1));
-    L.o_total = o;  o += al(8);
-    L.o_kb = o;     o += al(4 * E);
-    L.o_vb = o;     o += al(4 * E);
-    L.o_hist = o;   o += al(4 * 256 * L.nblk);
-    L.o_hoff = o;   o += al(4 * (256 * L.nblk + 1));
-    L.total = o;
-    return L;
+inline Work carve(Carver& c, int64_t N, int64_t E) {
+    Work W;
+    const int64_t n_hist = 256 * ((E + kTile - 1) / kTile);
+    W.counts = c.take<int32_t>(N + 1);
+    W.scr = take_scan(c, (N > n_hist ? N : n_hist) + 1);
+    W.total = c.take<unsigned long long>(1);
+    W.kb = c.take<int32_t>(E);
+    W.vb = c.take<int32_t>(E);
+    W.sort = take_sort(c, E);
+    return W;
 }
 inline bool sizes_ok(int64_t N, int64_t E) { return N >= 0 && N < (1ll << 31) && E >= 0 && E < (1ll << 31) - kTile; }
 
@@ -395,7 +395,9 @@ __global__ void density_copy_total_kernel(const unsigned long long* total, int64
 
 extern "C" int64_t misplat_density_workspace(int64_t n_gauss, int64_t n_pairs) {
     if (!sizes_ok(n_gauss, n_pairs)) return -1;
-    return layout(n_gauss, n_pairs).total;
+    Carver c{nullptr};
+    carve(c, n_gauss, n_pairs);
+    return c.o;
 }
 
 extern "C" int misplat_density_records(const float* means, const float* quats, const float* scales, const float* opacities,
@@ -417,18 +419,16 @@ extern "C" int misplat_density_count(const misplat_tsdf_grid* grid, const float*
     if (!make_grid(grid, g, n_map) || !sizes_ok(n_gauss, 0) || n_gauss < 1 || !cutoff_ok(cutoff) || !(min_opacity == min_opacity) ||
         !means || !quats || !scales || !opacities || !workspace || !pair_off || !n_pairs)
         return MISPLAT_EINVAL;
-    const Layout L = layout(n_gauss, 0);
-    if (workspace_bytes < L.total) return MISPLAT_EWORKSPACE;
+    Carver c{(char*)workspace};
+    const Work W = carve(c, n_gauss, 0);
+    if (workspace_bytes < c.o) return MISPLAT_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    int32_t* counts = (int32_t*)(ws + L.o_counts);
-    unsigned long long* total = (unsigned long long*)(ws + L.o_total);
-    hipLaunchKernelGGL(density_clear_total_kernel, dim3(1), dim3(1), 0, s, total);
+    hipLaunchKernelGGL(density_clear_total_kernel, dim3(1), dim3(1), 0, s, W.total);
     hipLaunchKernelGGL(density_pairs_kernel<false>, dim3(blocks(n_gauss, 256)), dim3(256), 0, s, g, means, quats, scales, opacities,
-                       n_gauss, cutoff, min_opacity, counts, total, (const int32_t*)nullptr, (int64_t)0, (int32_t*)nullptr,
+                       n_gauss, cutoff, min_opacity, W.counts, W.total, (const int32_t*)nullptr, (int64_t)0, (int32_t*)nullptr,
                        (int32_t*)nullptr, (unsigned long long*)nullptr);
-    scan(counts, n_gauss, pair_off, (int32_t*)(ws + L.o_scan), s);
-    hipLaunchKernelGGL(density_copy_total_kernel, dim3(1), dim3(1), 0, s, (const unsigned long long*)total, n_pairs);
+    scan(W.counts, n_gauss, pair_off, W.scr, s);
+    hipLaunchKernelGGL(density_copy_total_kernel, dim3(1), dim3(1), 0, s, (const unsigned long long*)W.total, n_pairs);
     return launched();
 }
 
@@ -456,28 +456,17 @@ extern "C" int misplat_density_lists(const misplat_tsdf_grid* grid, const int32_
     if (!make_grid(grid, g, n_map) || !sizes_ok(0, E) || E < 1 || n_units < 1 || n_units > n_map || !slot_map || !keys || !ids ||
         !workspace || !keys_sorted || !ids_sorted || !ranges)
         return MISPLAT_EINVAL;
-    const Layout L = layout(0, E);
-    if (workspace_bytes < L.total) return MISPLAT_EWORKSPACE;
+    Carver c{(char*)workspace};
+    const Work W = carve(c, 0, E);
+    if (workspace_bytes < c.o) return MISPLAT_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    int32_t* hist = (int32_t*)(ws + L.o_hist);
-    int32_t* hoff = (int32_t*)(ws + L.o_hoff);
-    int32_t* scr = (int32_t*)(ws + L.o_scan);
     // passes over the bits of the largest map index; one more over zero digits (the identity, the sort being stable) where
-    // that makes their number odd: the result then lies in keys_sorted / ids_sorted
-    int passes = 1;
-    while (passes < 4 && ((n_map - 1) >> (8 * passes)) > 0) passes++;
+    // that makes their number odd: the result then lies in keys_sorted / ids_sorted.  (A fifth pass repeats the top byte:
+    // the identity again.)
+    int passes = radix_passes(n_map - 1);
     if (passes % 2 == 0) passes++;
     int32_t *ka = keys, *va = ids, *kb = keys_sorted, *vb = ids_sorted;
-    for (int pass = 0; pass < passes; pass++) {
-        const int shift = 8 * pass < 24 ? 8 * pass : 24;   // (a fifth pass repeats the top byte: the identity again)
-        hipLaunchKernelGGL(radix_hist_kernel, dim3((unsigned)L.nblk), dim3(256), 0, s, (const int32_t*)ka, E, shift, L.nblk, hist);
-        scan(hist, 256 * L.nblk, hoff, scr, s);
-        hipLaunchKernelGGL(radix_scatter_kernel, dim3((unsigned)L.nblk), dim3(256), 0, s, (const int32_t*)ka, (const int32_t*)va, E,
-                           shift, L.nblk, (const int32_t*)hoff, kb, vb);
-        int32_t* t = ka; ka = kb; kb = t;
-        t = va; va = vb; vb = t;
-    }
+    radix_sort(ka, va, kb, vb, E, passes, W.sort, W.scr, s);
     hipLaunchKernelGGL(density_ranges_kernel, dim3(blocks(E, 256)), dim3(256), 0, s, (const int32_t*)keys_sorted, E, slot_map, ranges);
     return launched();
 }

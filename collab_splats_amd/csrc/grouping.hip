@@ -255,46 +255,41 @@ __global__ __launch_bounds__(256) void members_kernel(const int32_t* __restrict_
 }
 
 // --------------------------------------------------------------------------------------------------------- workspace
-struct Layout {
-    int64_t nblk, o_present, o_rank, o_scan, o_ka, o_va, o_kb, o_vb, o_hist, o_hoff, total;
+// the mask table (present, rank) and the scan's scratch come first: they are what misplat_grouping_mask_ids leaves for
+// _front and _relabel.  _mask_ids and _relabel carve for N = 1 and ask for `table_bytes`: the table sits at the same offsets for every N,
+// and the scan of kIds flags needs no more scratch than N = 1 gives
+struct Work {
+    int32_t *present, *rank, *scr;
+    int64_t table_bytes;
+    int32_t *ka, *va, *kb, *vb;
+    SortBufs sort;
 };
 
-// the mask table (present, rank) comes first: it is what misplat_grouping_mask_ids leaves for _front and _relabel
-inline Layout layout(int64_t N) {
-    Layout L = {};
-    L.nblk = (N + kTile - 1) / kTile;
+inline Work carve(Carver& c, int64_t N) {
+    Work W;
+    const int64_t n_hist = 256 * ((N + kTile - 1) / kTile);
     int64_t scan_n = N;                                             // the bank's merge scans N counts
-    if (256 * L.nblk > scan_n) scan_n = 256 * L.nblk;
+    if (n_hist > scan_n) scan_n = n_hist;
     if (kIds > scan_n) scan_n = kIds;
-    int64_t o = 0;
-    L.o_present = o; o += al(4 * kIds);
-    L.o_rank = o;    o += al(4 * (kIds + 1));
-    L.o_scan = o;    o += al(scan_scratch_bytes(scan_n));
-    L.o_ka = o;      o += al(4 * N);
-    L.o_va = o;      o += al(4 * N);
-    L.o_kb = o;      o += al(4 * N);
-    L.o_vb = o;      o += al(4 * N);
-    L.o_hist = o;    o += al(4 * 256 * L.nblk);
-    L.o_hoff = o;    o += al(4 * (256 * L.nblk + 1));
-    L.total = o;
-    return L;
-}
-
-inline void sort_pass(int32_t*& ka, int32_t*& va, int32_t*& kb, int32_t*& vb, int64_t N, int shift, const Layout& L, int32_t* hist,
-                      int32_t* hoff, int32_t* scr, hipStream_t s) {
-    hipLaunchKernelGGL(radix_hist_kernel, dim3((unsigned)L.nblk), dim3(256), 0, s, (const int32_t*)ka, N, shift, L.nblk, hist);
-    scan(hist, 256 * L.nblk, hoff, scr, s);
-    hipLaunchKernelGGL(radix_scatter_kernel, dim3((unsigned)L.nblk), dim3(256), 0, s, (const int32_t*)ka, (const int32_t*)va, N, shift,
-                       L.nblk, (const int32_t*)hoff, kb, vb);
-    int32_t* t = ka; ka = kb; kb = t;
-    t = va; va = vb; vb = t;
+    W.present = c.take<int32_t>(kIds);
+    W.rank = c.take<int32_t>(kIds + 1);
+    W.scr = take_scan(c, scan_n);
+    W.table_bytes = c.o;
+    W.ka = c.take<int32_t>(N);
+    W.va = c.take<int32_t>(N);
+    W.kb = c.take<int32_t>(N);
+    W.vb = c.take<int32_t>(N);
+    W.sort = take_sort(c, N);
+    return W;
 }
 
 }  // namespace
 
 extern "C" int64_t misplat_grouping_workspace(int64_t n_gauss) {
     if (!gauss_ok(n_gauss)) return -1;
-    return layout(n_gauss).total;
+    Carver c{nullptr};
+    carve(c, n_gauss);
+    return c.o;
 }
 
 extern "C" int misplat_grouping_project(const int32_t* radii, const float* means2d, int64_t n_gauss, int32_t width, int32_t height,
@@ -308,19 +303,17 @@ extern "C" int misplat_grouping_project(const int32_t* radii, const float* means
 extern "C" int misplat_grouping_mask_ids(const int32_t* mask, int64_t n_pixels, void* workspace, int64_t workspace_bytes,
                                          int32_t* mask_ids, int32_t* n_masks, misplat_stream_t stream) {
     if (n_pixels < 1 || n_pixels >= (1ll << 31) || !mask || !workspace || !mask_ids || !n_masks) return MISPLAT_EINVAL;
-    const Layout L = layout(1);
-    if (workspace_bytes < L.o_ka) return MISPLAT_EWORKSPACE;        // the table and the scan's scratch: what every N has
+    Carver c{(char*)workspace};
+    const Work W = carve(c, 1);
+    if (workspace_bytes < W.table_bytes) return MISPLAT_EWORKSPACE;  // the table and the scan's scratch: what every N has
     hipStream_t s = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    int32_t* present = (int32_t*)(ws + L.o_present);
-    int32_t* rank = (int32_t*)(ws + L.o_rank);
-    misplat_internal::fill_bytes(present, 4 * kIds, 0u, s);
+    misplat_internal::fill_bytes(W.present, 4 * kIds, 0u, s);
     unsigned nb = blocks(n_pixels, 256);
     if (nb > 2048) nb = 2048;
-    hipLaunchKernelGGL(presence_kernel, dim3(nb), dim3(256), 0, s, mask, n_pixels, present);
-    scan(present, kIds, rank, (int32_t*)(ws + L.o_scan), s);
-    hipLaunchKernelGGL(mask_ids_kernel, dim3(kIds / 256), dim3(256), 0, s, (const int32_t*)present, (const int32_t*)rank, mask_ids,
-                       n_masks);
+    hipLaunchKernelGGL(presence_kernel, dim3(nb), dim3(256), 0, s, mask, n_pixels, W.present);
+    scan(W.present, kIds, W.rank, W.scr, s);
+    hipLaunchKernelGGL(mask_ids_kernel, dim3(kIds / 256), dim3(256), 0, s, (const int32_t*)W.present, (const int32_t*)W.rank,
+                       mask_ids, n_masks);
     return launched();
 }
 
@@ -334,28 +327,25 @@ extern "C" int misplat_grouping_front(const int32_t* flat, const uint8_t* valid,
         !(front_percentage > 0.0) || !(front_percentage <= 1.0) || !flat || !valid || !depths || !mask || !workspace || !mask_of ||
         (M > 0 && !counts))
         return MISPLAT_EINVAL;
-    const Layout L = layout(N);
-    if (workspace_bytes < L.total) return MISPLAT_EWORKSPACE;
+    Carver c{(char*)workspace};
+    const Work W = carve(c, N);
+    if (workspace_bytes < c.o) return MISPLAT_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     const unsigned nb = blocks(N, 256);
     if (M == 0) {
         hipLaunchKernelGGL(fill_i32_kernel, dim3(nb), dim3(256), 0, s, mask_of, N, -1);
         return launched();
     }
-    char* ws = (char*)workspace;
-    const int32_t* rank = (const int32_t*)(ws + L.o_rank);
-    int32_t* scr = (int32_t*)(ws + L.o_scan);
-    int32_t *ka = (int32_t*)(ws + L.o_ka), *va = (int32_t*)(ws + L.o_va), *kb = (int32_t*)(ws + L.o_kb), *vb = (int32_t*)(ws + L.o_vb);
-    int32_t* hist = (int32_t*)(ws + L.o_hist);
-    int32_t* hoff = (int32_t*)(ws + L.o_hoff);
+    int32_t *ka = W.ka, *va = W.va, *kb = W.kb, *vb = W.vb;
     misplat_internal::fill_bytes(counts, 4 * (size_t)M, 0u, s);
     hipLaunchKernelGGL(depth_keys_kernel, dim3(nb), dim3(256), 0, s, depths, N, ka, va, mask_of);
-    for (int shift = 0; shift < 32; shift += 8) sort_pass(ka, va, kb, vb, N, shift, L, hist, hoff, scr, s);
-    const int32_t none = M * P * P;                                 // < 2^30: M < 2^16, P <= 2^7
+    radix_sort(ka, va, kb, vb, N, 4, W.sort, W.scr, s);             // (the depth's bits: all 32)
+    const int32_t none = M * P * P;                                 // 1 <= none < 2^30: 1 <= M < 2^16, 1 <= P <= 2^7
     const int pw = (width + P - 1) / P, ph = (height + P - 1) / P;
-    hipLaunchKernelGGL(cell_keys_kernel, dim3(nb), dim3(256), 0, s, (const int32_t*)va, N, flat, valid, mask, rank, (int)width,
-                       (int32_t)(width * height), pw, ph, P, none, ka);
-    for (int shift = 0; shift < 32 && (none >> shift) > 0; shift += 8) sort_pass(ka, va, kb, vb, N, shift, L, hist, hoff, scr, s);
+    hipLaunchKernelGGL(cell_keys_kernel, dim3(nb), dim3(256), 0, s, (const int32_t*)va, N, flat, valid, mask, (const int32_t*)W.rank,
+                       (int)width, (int32_t)(width * height), pw, ph, P, none, ka);
+    // the keys are 0 .. none.  none >= 1 here (M == 0 has returned above, P >= 1 is checked), so at least one pass runs
+    radix_sort(ka, va, kb, vb, N, radix_passes(none), W.sort, W.scr, s);
     hipLaunchKernelGGL(select_kernel, dim3(nb), dim3(256), 0, s, (const int32_t*)ka, (const int32_t*)va, N, none, P * P, front_percentage,
                        mask_of, counts);
     return launched();
@@ -364,10 +354,11 @@ extern "C" int misplat_grouping_front(const int32_t* flat, const uint8_t* valid,
 extern "C" int misplat_grouping_relabel(const int32_t* mask, int64_t n_pixels, const void* workspace, int64_t workspace_bytes,
                                         const int64_t* labels, int32_t* out, misplat_stream_t stream) {
     if (n_pixels < 1 || n_pixels >= (1ll << 31) || !mask || !workspace || !labels || !out) return MISPLAT_EINVAL;
-    const Layout L = layout(1);
-    if (workspace_bytes < L.o_ka) return MISPLAT_EWORKSPACE;
+    Carver c{(char*)workspace};
+    const Work W = carve(c, 1);
+    if (workspace_bytes < W.table_bytes) return MISPLAT_EWORKSPACE;
     hipLaunchKernelGGL(relabel_kernel, dim3(blocks(n_pixels, 256)), dim3(256), 0, (hipStream_t)stream, mask, n_pixels,
-                       (const int32_t*)((const char*)workspace + L.o_rank), labels, out);
+                       (const int32_t*)W.rank, labels, out);
     return launched();
 }
 
@@ -398,14 +389,13 @@ extern "C" int misplat_grouping_merge_count(const int32_t* mask_of, int64_t n_ga
                                             int64_t workspace_bytes, int32_t* new_off, misplat_stream_t stream) {
     const int64_t N = n_gauss;
     if (!gauss_ok(N) || n_masks < 1 || !mask_of || !labels || !bank_off || !bank_labels || !workspace || !new_off) return MISPLAT_EINVAL;
-    const Layout L = layout(N);
-    if (workspace_bytes < L.total) return MISPLAT_EWORKSPACE;
+    Carver c{(char*)workspace};
+    const Work W = carve(c, N);
+    if (workspace_bytes < c.o) return MISPLAT_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    int32_t* cnt = (int32_t*)(ws + L.o_ka);
     hipLaunchKernelGGL(merge_count_kernel, dim3(blocks(N, 256)), dim3(256), 0, s, mask_of, N, labels, (int)n_masks, bank_off, bank_labels,
-                       cnt);
-    scan(cnt, N, new_off, (int32_t*)(ws + L.o_scan), s);
+                       W.ka);                                        // (the counts borrow the sort's first key buffer)
+    scan(W.ka, N, new_off, W.scr, s);
     return launched();
 }
 

@@ -385,48 +385,47 @@ inline int64_t edge_capacity(int64_t T) {
     return cap;
 }
 
-struct Layout {
+// what a kind does not use stays null
+struct Work {
     int64_t cap;
-    int64_t o_keys, o_cnt, o_face, o_scan, o_part, o_sum, o_parent, o_size, o_root, o_keep, o_rank, o_flag, o_pos, o_eroot, total;
+    unsigned long long* keys;         // the edge table: keys, cnt, face [cap]
+    int32_t *cnt, *face, *scr;
+    double *part, *sum;
+    int32_t *parent, *size, *root, *keep, *rank, *flag, *pos, *eroot;
 };
 
-// M vertices, T triangles (mesh kinds) or N points (kKindMoments, passed as n)
-inline Layout layout(int64_t M, int64_t T, int kind) {
-    Layout L = {};
-    int64_t o = 0;
+// M vertices, T triangles (mesh kinds) or N points (kKindMoments, passed as M)
+inline Work carve(Carver& c, int64_t M, int64_t T, int kind) {
+    Work W = {};
     if (kind == kKindMoments) {
-        const int64_t nb = (M + 255) / 256;
-        L.o_part = o; o += al(8 * 6 * (nb + 1));
-        L.total = o;
-        return L;
+        W.part = c.take<double>(6 * ((M + 255) / 256 + 1));
+        return W;
     }
-    L.cap = edge_capacity(T);
-    int64_t scan_n = 3 * T > M ? 3 * T : M;
-    L.o_keys = o; o += al(8 * L.cap);
-    L.o_cnt = o;  o += al(4 * L.cap);
-    L.o_face = o; o += al(4 * L.cap);
-    L.o_scan = o; o += al(scan_scratch_bytes(scan_n));
+    W.cap = edge_capacity(T);
+    W.keys = c.take<unsigned long long>(W.cap);
+    W.cnt = c.take<int32_t>(W.cap);
+    W.face = c.take<int32_t>(W.cap);
+    W.scr = take_scan(c, 3 * T > M ? 3 * T : M);
     if (kind == kKindStats) {
-        L.o_part = o; o += al(8 * ((3 * T + 255) / 256 + 1));
-        L.o_sum = o;  o += al(8);
+        W.part = c.take<double>((3 * T + 255) / 256 + 1);
+        W.sum = c.take<double>(1);
     }
     if (kind == kKindComponents) {
-        L.o_parent = o; o += al(4 * T);
-        L.o_size = o;   o += al(4 * T);
-        L.o_root = o;   o += al(4 * T);
-        L.o_keep = o;   o += al(4 * T);
-        L.o_rank = o;   o += al(4 * (T + 1));
+        W.parent = c.take<int32_t>(T);
+        W.size = c.take<int32_t>(T);
+        W.root = c.take<int32_t>(T);
+        W.keep = c.take<int32_t>(T);
+        W.rank = c.take<int32_t>(T + 1);
     }
     if (kind == kKindHoles) {
-        L.o_flag = o;   o += al(4 * 3 * T);
-        L.o_pos = o;    o += al(4 * (3 * T + 1));
-        L.o_eroot = o;  o += al(4 * 3 * T);
-        L.o_parent = o; o += al(4 * M);
-        L.o_keep = o;   o += al(4 * M);
-        L.o_rank = o;   o += al(4 * (M + 1));
+        W.flag = c.take<int32_t>(3 * T);
+        W.pos = c.take<int32_t>(3 * T + 1);
+        W.eroot = c.take<int32_t>(3 * T);
+        W.parent = c.take<int32_t>(M);
+        W.keep = c.take<int32_t>(M);
+        W.rank = c.take<int32_t>(M + 1);
     }
-    L.total = o;
-    return L;
+    return W;
 }
 
 inline bool mesh_ok(int64_t M, int64_t T) { return M >= 0 && M < (1ll << 31) && T >= 0 && T < (1ll << 30); }
@@ -434,12 +433,11 @@ inline bool mesh_ok(int64_t M, int64_t T) { return M >= 0 && M < (1ll << 31) && 
 inline bool corners_ok(int64_t T) { return 3 * T < (1ll << 31); }
 inline bool cloud_ok(int64_t N) { return N >= 0 && N < (1ll << 30); }
 
-inline EdgeTable build_edges(const int32_t* tri, int64_t T, char* ws, const Layout& L, hipStream_t s) {
-    EdgeTable E{(unsigned long long*)(ws + L.o_keys), (int32_t*)(ws + L.o_cnt), (int32_t*)(ws + L.o_face),
-                (unsigned long long)(L.cap - 1)};
-    misplat_internal::fill_bytes(E.keys, 8 * L.cap, 0xffffffffu, s);          // (kernels, not memsets: internal.h)
-    misplat_internal::fill_bytes(E.cnt, 4 * L.cap, 0u, s);
-    misplat_internal::fill_bytes(E.face, 4 * L.cap, 0x7fffffffu, s);
+inline EdgeTable build_edges(const int32_t* tri, int64_t T, const Work& W, hipStream_t s) {
+    EdgeTable E{W.keys, W.cnt, W.face, (unsigned long long)(W.cap - 1)};
+    misplat_internal::fill_bytes(E.keys, 8 * W.cap, 0xffffffffu, s);          // (kernels, not memsets: internal.h)
+    misplat_internal::fill_bytes(E.cnt, 4 * W.cap, 0u, s);
+    misplat_internal::fill_bytes(E.face, 4 * W.cap, 0x7fffffffu, s);
     if (T > 0) hipLaunchKernelGGL(edge_insert_kernel, dim3(blocks(3 * T, 256)), dim3(256), 0, s, tri, T, E);
     return E;
 }
@@ -448,9 +446,12 @@ inline EdgeTable build_edges(const int32_t* tri, int64_t T, char* ws, const Layo
 
 extern "C" int64_t misplat_meshclean_workspace(int64_t n_vertices, int64_t n_triangles, int32_t kind) {
     if (kind < kKindStats || kind > kKindMoments) return -1;
-    if (kind == kKindMoments) return cloud_ok(n_vertices) ? layout(n_vertices, 0, kind).total : -1;
-    if (!mesh_ok(n_vertices, n_triangles) || (kind != kKindComponents && !corners_ok(n_triangles))) return -1;
-    return layout(n_vertices, n_triangles, kind).total;
+    if (kind == kKindMoments ? !cloud_ok(n_vertices)
+                             : !mesh_ok(n_vertices, n_triangles) || (kind != kKindComponents && !corners_ok(n_triangles)))
+        return -1;
+    Carver c{nullptr};
+    carve(c, n_vertices, kind == kKindMoments ? 0 : n_triangles, kind);
+    return c.o;
 }
 
 extern "C" int misplat_meshclean_edge_stats(const float* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles,
@@ -459,19 +460,17 @@ extern "C" int misplat_meshclean_edge_stats(const float* vertices, int64_t n_ver
     const int64_t M = n_vertices, T = n_triangles;
     if (!mesh_ok(M, T) || !corners_ok(T) || !workspace || !counts || !mean_length || (T > 0 && (!vertices || !triangles)))
         return MISPLAT_EINVAL;
-    const Layout L = layout(M, T, kKindStats);
-    if (workspace_bytes < L.total) return MISPLAT_EWORKSPACE;
+    Carver c{(char*)workspace};
+    const Work W = carve(c, M, T, kKindStats);
+    if (workspace_bytes < c.o) return MISPLAT_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    const EdgeTable E = build_edges(triangles, T, ws, L, s);
-    double* part = (double*)(ws + L.o_part);
-    double* sum = (double*)(ws + L.o_sum);
+    const EdgeTable E = build_edges(triangles, T, W, s);
     misplat_internal::fill_bytes(counts, 12, 0u, s);
-    hipLaunchKernelGGL(edge_count_kernel, dim3(blocks(L.cap, 256)), dim3(256), 0, s, E, L.cap, counts);
+    hipLaunchKernelGGL(edge_count_kernel, dim3(blocks(W.cap, 256)), dim3(256), 0, s, E, W.cap, counts);
     const int64_t nb = (3 * T + 255) / 256;
-    if (nb > 0) hipLaunchKernelGGL(edge_length_kernel, dim3((unsigned)nb), dim3(256), 0, s, vertices, triangles, T, E, part);
-    hipLaunchKernelGGL((sum_final_kernel<1, 256>), dim3(1), dim3(256), 0, s, (const double*)part, nb, sum);
-    hipLaunchKernelGGL(edge_mean_kernel, dim3(1), dim3(1), 0, s, (const double*)sum, (const int32_t*)counts, mean_length);
+    if (nb > 0) hipLaunchKernelGGL(edge_length_kernel, dim3((unsigned)nb), dim3(256), 0, s, vertices, triangles, T, E, W.part);
+    hipLaunchKernelGGL((sum_final_kernel<1, 256>), dim3(1), dim3(256), 0, s, (const double*)W.part, nb, W.sum);
+    hipLaunchKernelGGL(edge_mean_kernel, dim3(1), dim3(1), 0, s, (const double*)W.sum, (const int32_t*)counts, mean_length);
     return launched();
 }
 
@@ -480,29 +479,23 @@ extern "C" int misplat_meshclean_components(const int32_t* triangles, int64_t n_
                                             misplat_stream_t stream) {
     const int64_t M = n_vertices, T = n_triangles;
     if (!mesh_ok(M, T) || !workspace || !n_components || (T > 0 && (!triangles || !labels || !sizes))) return MISPLAT_EINVAL;
-    const Layout L = layout(M, T, kKindComponents);
-    if (workspace_bytes < L.total) return MISPLAT_EWORKSPACE;
+    Carver c{(char*)workspace};
+    const Work W = carve(c, M, T, kKindComponents);
+    if (workspace_bytes < c.o) return MISPLAT_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     if (T == 0) {
         misplat_internal::fill_bytes(n_components, 4, 0u, s);
         return launched();
     }
-    char* ws = (char*)workspace;
-    const EdgeTable E = build_edges(triangles, T, ws, L, s);
-    int32_t* scr = (int32_t*)(ws + L.o_scan);
-    int32_t* parent = (int32_t*)(ws + L.o_parent);
-    int32_t* size = (int32_t*)(ws + L.o_size);
-    int32_t* root = (int32_t*)(ws + L.o_root);
-    int32_t* keep = (int32_t*)(ws + L.o_keep);
-    int32_t* rank = (int32_t*)(ws + L.o_rank);
+    const EdgeTable E = build_edges(triangles, T, W, s);
     const unsigned nb = blocks(T, 256);
-    hipLaunchKernelGGL(iota_kernel, dim3(nb), dim3(256), 0, s, T, parent, size);
-    hipLaunchKernelGGL(face_union_kernel, dim3(blocks(3 * T, 256)), dim3(256), 0, s, triangles, T, E, parent);
-    hipLaunchKernelGGL(flatten_kernel, dim3(nb), dim3(256), 0, s, (const int32_t*)parent, T, root, size);
-    hipLaunchKernelGGL(is_root_kernel, dim3(nb), dim3(256), 0, s, (const int32_t*)root, T, keep);
-    scan(keep, T, rank, scr, s);
-    hipLaunchKernelGGL(face_label_kernel, dim3(nb), dim3(256), 0, s, (const int32_t*)root, (const int32_t*)size,
-                       (const int32_t*)rank, T, labels, sizes, n_components);
+    hipLaunchKernelGGL(iota_kernel, dim3(nb), dim3(256), 0, s, T, W.parent, W.size);
+    hipLaunchKernelGGL(face_union_kernel, dim3(blocks(3 * T, 256)), dim3(256), 0, s, triangles, T, E, W.parent);
+    hipLaunchKernelGGL(flatten_kernel, dim3(nb), dim3(256), 0, s, (const int32_t*)W.parent, T, W.root, W.size);
+    hipLaunchKernelGGL(is_root_kernel, dim3(nb), dim3(256), 0, s, (const int32_t*)W.root, T, W.keep);
+    scan(W.keep, T, W.rank, W.scr, s);
+    hipLaunchKernelGGL(face_label_kernel, dim3(nb), dim3(256), 0, s, (const int32_t*)W.root, (const int32_t*)W.size,
+                       (const int32_t*)W.rank, T, labels, sizes, n_components);
     return launched();
 }
 
@@ -513,22 +506,17 @@ extern "C" int misplat_meshclean_holes(const float* vertices, int64_t n_vertices
     if (!mesh_ok(M, T) || !corners_ok(T) || !workspace || !counts ||
         (T > 0 && (M < 1 || !vertices || !triangles || !edges || !loop_of_edge || !length)))
         return MISPLAT_EINVAL;
-    const Layout L = layout(M, T, kKindHoles);
-    if (workspace_bytes < L.total) return MISPLAT_EWORKSPACE;
+    Carver c{(char*)workspace};
+    const Work W = carve(c, M, T, kKindHoles);
+    if (workspace_bytes < c.o) return MISPLAT_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     if (T == 0) {
         misplat_internal::fill_bytes(counts, 8, 0u, s);
         return launched();
     }
-    char* ws = (char*)workspace;
-    const EdgeTable E = build_edges(triangles, T, ws, L, s);
-    int32_t* scr = (int32_t*)(ws + L.o_scan);
-    int32_t* flag = (int32_t*)(ws + L.o_flag);
-    int32_t* pos = (int32_t*)(ws + L.o_pos);
-    int32_t* eroot = (int32_t*)(ws + L.o_eroot);
-    int32_t* vparent = (int32_t*)(ws + L.o_parent);
-    int32_t* on = (int32_t*)(ws + L.o_keep);
-    int32_t* vrank = (int32_t*)(ws + L.o_rank);
+    const EdgeTable E = build_edges(triangles, T, W, s);
+    int32_t *scr = W.scr, *flag = W.flag, *pos = W.pos, *eroot = W.eroot;
+    int32_t *vparent = W.parent, *on = W.keep, *vrank = W.rank;     // (over the vertices here)
     const unsigned nh = blocks(3 * T, 256);
     hipLaunchKernelGGL(iota_kernel, dim3(blocks(M, 256)), dim3(256), 0, s, M, vparent, on);
     hipLaunchKernelGGL(boundary_flag_kernel, dim3(nh), dim3(256), 0, s, triangles, T, E, flag);
@@ -585,10 +573,10 @@ extern "C" int misplat_meshclean_plane_moments(const float* points, int64_t n_po
                                                misplat_stream_t stream) {
     const int64_t N = n_points;
     if (!cloud_ok(N) || N < 1 || !(threshold > 0.f) || !points || !plane || !workspace || !mask || !moments) return MISPLAT_EINVAL;
-    const Layout L = layout(N, 0, kKindMoments);
-    if (workspace_bytes < L.total) return MISPLAT_EWORKSPACE;
+    Carver c{(char*)workspace};
+    double* part = carve(c, N, 0, kKindMoments).part;
+    if (workspace_bytes < c.o) return MISPLAT_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    double* part = (double*)((char*)workspace + L.o_part);
     const int64_t nb = (N + 255) / 256;
     hipLaunchKernelGGL(moment_mean_kernel, dim3((unsigned)nb), dim3(256), 0, s, points, N, (const float4*)plane, threshold, mask, part);
     hipLaunchKernelGGL((sum_final_kernel<4, 256>), dim3(1), dim3(256), 0, s, (const double*)part, nb, moments);

@@ -23,28 +23,9 @@ constexpr int kMaxRings = 6;          // rings beyond the sdf_trunc box before t
 constexpr int kChunk = 512;           // contributions per partial sum (longer lists are split, cdna guide Appendix B)
 
 // ----------------------------------------------------------------------------------------------------------- query
-// k best of (d2 bits, vertex index) as one 64-bit key, ascending in best[KC - k .. KC - 1]; the KC - k slots in front hold 0
-// and never move (a real key is never below them).  Unset slots hold kEmpty.
+// k best of (d2 bits, vertex index) as one 64-bit key (cellhash.h's KBest); unset slots hold kEmpty
 template <int KC>
-struct Best {
-    unsigned long long b[KC];
-    __device__ __forceinline__ void reset(int k) {
-#pragma unroll
-        for (int j = 0; j < KC; j++) b[j] = (j >= KC - k) ? kEmpty : 0ull;
-    }
-    __device__ __forceinline__ unsigned long long nearest(int k) const {      // b[KC - k] without a dynamic register index
-        unsigned long long r = 0ull;
-#pragma unroll
-        for (int j = 0; j < KC; j++) r = (j == KC - k) ? b[j] : r;
-        return r;
-    }
-    __device__ __forceinline__ void offer(unsigned long long key) {
-        if (key >= b[KC - 1]) return;
-#pragma unroll
-        for (int j = KC - 1; j > 0; j--) b[j] = (b[j - 1] > key) ? b[j - 1] : (b[j] > key ? key : b[j]);
-        b[0] = b[0] > key ? key : b[0];
-    }
-};
+using Best = KBest<unsigned long long, KC>;
 
 __device__ __forceinline__ unsigned long long cand_key(float px, float py, float pz, float4 q) {
     const float dx = px - q.x, dy = py - q.y, dz = pz - q.z;
@@ -257,43 +238,45 @@ __global__ __launch_bounds__(256) void vertex_sum_kernel(const int32_t* __restri
 }
 
 // ------------------------------------------------------------------------------------------------------- workspace
-struct Layout {
-    int64_t cap, nblk, E, q_cap, scan_n;
-    int64_t o_keys, o_counts, o_starts, o_vslot, o_pts, o_scan, o_sig, o_w, o_ka, o_va, o_kb, o_vb, o_hist, o_hoff, o_offs,
-        o_nch, o_choff, o_owner, o_part, total;
+// the query's part first: misplat_meshmap_knn asks for no more than `knn_bytes`
+struct Work {
+    IndexBufs ix;
+    int32_t *vslot, *scr;
+    double* sig;
+    int64_t knn_bytes;
+    float* w;
+    int32_t *ka, *va, *kb, *vb;
+    SortBufs sort;
+    int32_t *offs, *nch, *choff, *owner;
+    float* part;
+    int64_t E, q_cap;
 };
 
-inline Layout layout(int64_t M, int64_t N, int k, int D) {
-    Layout L;
-    L.cap = hash_capacity(M);
-    L.E = N * k;
-    L.nblk = (L.E + kTile - 1) / kTile;
-    L.q_cap = M + L.E / kChunk + 1;
-    L.scan_n = L.cap;
-    if (256 * L.nblk > L.scan_n) L.scan_n = 256 * L.nblk;
-    if (M + 1 > L.scan_n) L.scan_n = M + 1;
-    int64_t o = 0;
-    L.o_keys = o;   o += al(8 * L.cap);
-    L.o_counts = o; o += al(4 * L.cap);
-    L.o_starts = o; o += al(4 * (L.cap + 1));
-    L.o_vslot = o;  o += al(4 * M);
-    L.o_pts = o;    o += al(16 * M);
-    L.o_scan = o;   o += al(scan_scratch_bytes(L.scan_n));
-    L.o_sig = o;    o += al(8 * (2 * ((N + 255) / 256) + 2));
-    L.o_w = o;      o += al(4 * L.E);
-    L.o_ka = o;     o += al(4 * L.E);
-    L.o_va = o;     o += al(4 * L.E);
-    L.o_kb = o;     o += al(4 * L.E);
-    L.o_vb = o;     o += al(4 * L.E);
-    L.o_hist = o;   o += al(4 * 256 * L.nblk);
-    L.o_hoff = o;   o += al(4 * (256 * L.nblk + 1));
-    L.o_offs = o;   o += al(4 * (M + 1));
-    L.o_nch = o;    o += al(4 * M);
-    L.o_choff = o;  o += al(4 * (M + 1));
-    L.o_owner = o;  o += al(4 * L.q_cap);
-    L.o_part = o;   o += al(4 * L.q_cap * (D + 1));
-    L.total = o;
-    return L;
+inline Work carve(Carver& c, int64_t M, int64_t N, int k, int D) {
+    Work W;
+    W.E = N * k;
+    W.q_cap = M + W.E / kChunk + 1;
+    const int64_t n_hist = 256 * ((W.E + kTile - 1) / kTile);
+    int64_t scan_n = hash_capacity(M);                              // the index's counts, the sort's histograms, M chunk counts
+    if (n_hist > scan_n) scan_n = n_hist;
+    if (M + 1 > scan_n) scan_n = M + 1;
+    W.ix = take_index(c, M);
+    W.vslot = c.take<int32_t>(M);
+    W.scr = take_scan(c, scan_n);
+    W.sig = c.take<double>(2 * ((N + 255) / 256) + 2);
+    W.knn_bytes = c.o;
+    W.w = c.take<float>(W.E);
+    W.ka = c.take<int32_t>(W.E);
+    W.va = c.take<int32_t>(W.E);
+    W.kb = c.take<int32_t>(W.E);
+    W.vb = c.take<int32_t>(W.E);
+    W.sort = take_sort(c, W.E);
+    W.offs = c.take<int32_t>(M + 1);
+    W.nch = c.take<int32_t>(M);
+    W.choff = c.take<int32_t>(M + 1);
+    W.owner = c.take<int32_t>(W.q_cap);
+    W.part = c.take<float>(W.q_cap * (D + 1));
+    return W;
 }
 
 inline bool sizes_ok(int64_t M, int64_t N, int k, int D) {
@@ -310,7 +293,9 @@ void launch_knn(const Index& ix, int64_t M, const float* P, int64_t N, int k, fl
 
 extern "C" int64_t misplat_meshmap_workspace(int64_t n_vertices, int64_t n_points, int32_t k, int32_t n_channels) {
     if (!sizes_ok(n_vertices, n_points, k, n_channels)) return -1;
-    return layout(n_vertices, n_points, k, n_channels).total;
+    Carver c{nullptr};
+    carve(c, n_vertices, n_points, k, n_channels);
+    return c.o;
 }
 
 extern "C" int misplat_meshmap_knn(const float* vertices, int64_t n_vertices, const float* points, int64_t n_points, int32_t k,
@@ -320,27 +305,13 @@ extern "C" int misplat_meshmap_knn(const float* vertices, int64_t n_vertices, co
     if (!sizes_ok(M, N, k, 0) || !(sdf_trunc > 0.f) || !(sdf_trunc < 3.0e37f) || !vertices || !workspace ||
         (N > 0 && (!points || !idx || !dist || !valid)))
         return MISPLAT_EINVAL;
-    const Layout L = layout(M, N, k, 0);
-    if (workspace_bytes < L.o_w) return MISPLAT_EWORKSPACE;
+    Carver c{(char*)workspace};
+    const Work W = carve(c, M, N, k, 0);
+    if (workspace_bytes < W.knn_bytes) return MISPLAT_EWORKSPACE;
     if (N == 0) return MISPLAT_OK;
-    char* ws = (char*)workspace;
     hipStream_t s = (hipStream_t)stream;
-    unsigned long long* keys = (unsigned long long*)(ws + L.o_keys);
-    int32_t* counts = (int32_t*)(ws + L.o_counts);
-    int32_t* starts = (int32_t*)(ws + L.o_starts);
-    int32_t* vslot = (int32_t*)(ws + L.o_vslot);
-    float4* pts = (float4*)(ws + L.o_pts);
-    int32_t* scr = (int32_t*)(ws + L.o_scan);
     const float h = sdf_trunc, inv_h = 1.f / sdf_trunc;
-    misplat_internal::fill_bytes(keys, 8 * L.cap, 0xffffffffu, s);          // (kernels, not memsets: internal.h)
-    misplat_internal::fill_bytes(counts, 4 * L.cap, 0u, s);
-    hipLaunchKernelGGL(index_insert_kernel, dim3(blocks(M, 256)), dim3(256), 0, s, vertices, M,
-                       (const uint8_t*)nullptr, inv_h, keys,
-                       (uint32_t)(L.cap - 1), vslot, counts);
-    scan(counts, L.cap, starts, scr, s);
-    hipLaunchKernelGGL(index_fill_kernel, dim3(blocks(M, 256)), dim3(256), 0, s, vertices, M, (const int32_t*)vslot,
-                       (const int32_t*)starts, counts, pts);
-    const Index ix{keys, starts, pts, (uint32_t)(L.cap - 1)};
+    const Index ix = build_index(vertices, M, nullptr, inv_h, W.ix, W.vslot, W.scr, s);
     if (k <= 4) launch_knn<4>(ix, M, points, N, k, sdf_trunc, h, inv_h, idx, dist, valid, s);
     else if (k <= 8) launch_knn<8>(ix, M, points, N, k, sdf_trunc, h, inv_h, idx, dist, valid, s);
     else launch_knn<16>(ix, M, points, N, k, sdf_trunc, h, inv_h, idx, dist, valid, s);
@@ -355,47 +326,29 @@ extern "C" int misplat_meshmap_aggregate(int64_t n_vertices, int64_t n_points, i
     if (!sizes_ok(M, N, k, D) || D < 1 || !(n_unit == 0 || (n_unit == 3 && D >= 3)) || !workspace || !out ||
         (N > 0 && (!idx || !dist || !valid || !values)))
         return MISPLAT_EINVAL;
-    const Layout L = layout(M, N, k, D);
-    if (workspace_bytes < L.total) return MISPLAT_EWORKSPACE;
-    char* ws = (char*)workspace;
+    Carver c{(char*)workspace};
+    const Work W = carve(c, M, N, k, D);
+    if (workspace_bytes < c.o) return MISPLAT_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     if (N == 0) {
         misplat_internal::fill_bytes(out, 4 * M * D, 0u, s);
         return launched();
     }
-    int32_t* scr = (int32_t*)(ws + L.o_scan);
-    double* sig = (double*)(ws + L.o_sig);
-    float* w = (float*)(ws + L.o_w);
-    int32_t *ka = (int32_t*)(ws + L.o_ka), *va = (int32_t*)(ws + L.o_va), *kb = (int32_t*)(ws + L.o_kb), *vb = (int32_t*)(ws + L.o_vb);
-    int32_t* hist = (int32_t*)(ws + L.o_hist);
-    int32_t* hoff = (int32_t*)(ws + L.o_hoff);
-    int32_t* offs = (int32_t*)(ws + L.o_offs);
-    int32_t* nch = (int32_t*)(ws + L.o_nch);
-    int32_t* choff = (int32_t*)(ws + L.o_choff);
-    int32_t* owner = (int32_t*)(ws + L.o_owner);
-    float* part = (float*)(ws + L.o_part);
     const int64_t nb_sig = (N + 255) / 256;
-    hipLaunchKernelGGL(sigma_partial_kernel, dim3((unsigned)nb_sig), dim3(256), 0, s, dist, valid, N, (int)k, sig + 2);
-    hipLaunchKernelGGL((sum_final_kernel<2, 256>), dim3(1), dim3(256), 0, s, (const double*)(sig + 2), nb_sig, sig);
+    hipLaunchKernelGGL(sigma_partial_kernel, dim3((unsigned)nb_sig), dim3(256), 0, s, dist, valid, N, (int)k, W.sig + 2);
+    hipLaunchKernelGGL((sum_final_kernel<2, 256>), dim3(1), dim3(256), 0, s, (const double*)(W.sig + 2), nb_sig, W.sig);
+    int32_t *ka = W.ka, *va = W.va, *kb = W.kb, *vb = W.vb;
     hipLaunchKernelGGL(weights_kernel, dim3(blocks(N, 256)), dim3(256), 0, s, idx, dist, valid, N, (int)k, (int32_t)M,
-                       (const double*)sig, w, ka, va);
-    const int64_t E = L.E;
-    for (int shift = 0; shift == 0 || (M >> shift) > 0; shift += 8) {
-        hipLaunchKernelGGL(radix_hist_kernel, dim3((unsigned)L.nblk), dim3(256), 0, s, (const int32_t*)ka, E, shift, L.nblk, hist);
-        scan(hist, 256 * L.nblk, hoff, scr, s);
-        hipLaunchKernelGGL(radix_scatter_kernel, dim3((unsigned)L.nblk), dim3(256), 0, s, (const int32_t*)ka, (const int32_t*)va, E,
-                           shift, L.nblk, (const int32_t*)hoff, kb, vb);
-        int32_t* t = ka; ka = kb; kb = t;
-        t = va; va = vb; vb = t;
-    }
-    hipLaunchKernelGGL(list_offsets_kernel, dim3(blocks(M + 1, 256)), dim3(256), 0, s, (const int32_t*)ka, E, (int32_t)M, offs);
-    hipLaunchKernelGGL(chunk_count_kernel, dim3(blocks(M, 256)), dim3(256), 0, s, (const int32_t*)offs, (int32_t)M, nch);
-    scan(nch, M, choff, scr, s);
-    hipLaunchKernelGGL(chunk_owner_kernel, dim3(blocks(M, 256)), dim3(256), 0, s, (const int32_t*)choff, (int32_t)M, owner);
-    hipLaunchKernelGGL(chunk_sum_kernel, dim3(blocks(L.q_cap * (D + 1), 256)), dim3(256), 0, s, (const int32_t*)owner,
-                       (const int32_t*)choff, (const int32_t*)offs, (int32_t)M, (const int32_t*)va, (const float*)w, values, D,
-                       (int)k, L.q_cap, part);
-    hipLaunchKernelGGL(vertex_sum_kernel, dim3(blocks(M, 256)), dim3(256), 0, s, (const int32_t*)choff, (int32_t)M,
-                       (const float*)part, D, (int)n_unit, out);
+                       (const double*)W.sig, W.w, ka, va);
+    radix_sort(ka, va, kb, vb, W.E, radix_passes(M), W.sort, W.scr, s);       // (the keys are 0 .. M)
+    hipLaunchKernelGGL(list_offsets_kernel, dim3(blocks(M + 1, 256)), dim3(256), 0, s, (const int32_t*)ka, W.E, (int32_t)M, W.offs);
+    hipLaunchKernelGGL(chunk_count_kernel, dim3(blocks(M, 256)), dim3(256), 0, s, (const int32_t*)W.offs, (int32_t)M, W.nch);
+    scan(W.nch, M, W.choff, W.scr, s);
+    hipLaunchKernelGGL(chunk_owner_kernel, dim3(blocks(M, 256)), dim3(256), 0, s, (const int32_t*)W.choff, (int32_t)M, W.owner);
+    hipLaunchKernelGGL(chunk_sum_kernel, dim3(blocks(W.q_cap * (D + 1), 256)), dim3(256), 0, s, (const int32_t*)W.owner,
+                       (const int32_t*)W.choff, (const int32_t*)W.offs, (int32_t)M, (const int32_t*)va, (const float*)W.w, values, D,
+                       (int)k, W.q_cap, W.part);
+    hipLaunchKernelGGL(vertex_sum_kernel, dim3(blocks(M, 256)), dim3(256), 0, s, (const int32_t*)W.choff, (int32_t)M,
+                       (const float*)W.part, D, (int)n_unit, out);
     return launched();
 }

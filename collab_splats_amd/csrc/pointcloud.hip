@@ -26,22 +26,10 @@ constexpr uint32_t kUnset = 0xffffffffu;
 constexpr int kSubR = 8;              // lanes per query of the radius count (as cluster.hip's union)
 
 // --------------------------------------------------------------------------------------------------------- best list
-// The k smallest d2 seen, as the bits of the (non-negative) floats: ascending in b[KC - k .. KC - 1]; the KC - k slots in
-// front hold 0 and never move.  Unset slots hold kUnset (above +inf's bits).  An equal key is inserted behind its equals.
+// The k smallest d2 seen, as the bits of the (non-negative) floats (cellhash.h's KBest).  Unset slots hold kUnset (above
+// +inf's bits).
 template <int KC>
-struct Best {
-    uint32_t b[KC];
-    __device__ __forceinline__ void reset(int k) {
-#pragma unroll
-        for (int j = 0; j < KC; j++) b[j] = (j >= KC - k) ? kUnset : 0u;
-    }
-    __device__ __forceinline__ void offer(uint32_t key) {
-        if (key >= b[KC - 1]) return;
-#pragma unroll
-        for (int j = KC - 1; j > 0; j--) b[j] = (b[j - 1] > key) ? b[j - 1] : (b[j] > key ? key : b[j]);
-        b[0] = b[0] > key ? key : b[0];
-    }
-};
+using Best = KBest<uint32_t, KC>;
 
 // the k smallest of what the L lanes of a query hold together (every lane gets the same list): a butterfly over disjoint sets
 template <int KC, int L>
@@ -329,72 +317,45 @@ __global__ __launch_bounds__(256) void voxel_mean_kernel(const float* __restrict
 }
 
 // ------------------------------------------------------------------------------------------------------- workspace
-struct LevelLayout {
-    int64_t o_keys, o_counts, o_starts, o_pts;
-};
-
-struct Layout {
-    int64_t cap, nblk;
-    LevelLayout lv[kLevels];
-    int64_t o_vslot, o_scan, o_part, o_stats, o_first, o_flag, o_rank, o_ka, o_va, o_kb, o_vb, o_hist, o_hoff, total;
-};
-
 enum { kKindCells = 0, kKindKnn = 1, kKindRadius = 2, kKindOutlier = 3, kKindVoxel = 4 };
 
 inline bool sizes_ok(int64_t N) { return N >= 0 && N < (1ll << 30); }
 
-inline Layout layout(int64_t N, int kind) {
-    Layout L = {};
-    L.cap = hash_capacity(N);
-    L.nblk = (N + kTile - 1) / kTile;
-    int64_t scan_n = L.cap;
-    if (256 * L.nblk > scan_n) scan_n = 256 * L.nblk;
-    int64_t o = 0;
+// what a kind does not use stays null
+struct Work {
+    IndexBufs lv[kLevels];            // kKindKnn: all of them; kKindCells, kKindRadius: lv[0]
+    int32_t *vslot, *scr;
+    double *part, *stats;             // kKindOutlier
+    unsigned long long* vkeys;        // kKindVoxel: the voxel hash (capacity cap), ...
+    int32_t *first, *flag, *rank, *ka, *va, *kb, *vb;
+    SortBufs sort;                    // ... and the sort of the points by voxel
+    int64_t cap;
+};
+
+inline Work carve(Carver& c, int64_t N, int kind) {
+    Work W = {};
+    W.cap = hash_capacity(N);
+    const int64_t n_hist = 256 * ((N + kTile - 1) / kTile);
     const int levels = kind == kKindKnn ? kLevels : (kind == kKindCells || kind == kKindRadius) ? 1 : 0;
-    for (int l = 0; l < levels; l++) {
-        L.lv[l].o_keys = o;   o += al(8 * L.cap);
-        L.lv[l].o_counts = o; o += al(4 * L.cap);
-        L.lv[l].o_starts = o; o += al(4 * (L.cap + 1));
-        L.lv[l].o_pts = o;    o += al(16 * N);
-    }
-    L.o_vslot = o; o += al(4 * N);
-    L.o_scan = o;  o += al(scan_scratch_bytes(scan_n));
+    for (int l = 0; l < levels; l++) W.lv[l] = take_index(c, N);
+    W.vslot = c.take<int32_t>(N);
+    W.scr = take_scan(c, W.cap > n_hist ? W.cap : n_hist);
     if (kind == kKindOutlier) {
-        L.o_part = o;  o += al(8 * (2 * ((N + 255) / 256) + 2));
-        L.o_stats = o; o += al(8 * 8);
+        W.part = c.take<double>(2 * ((N + 255) / 256) + 2);
+        W.stats = c.take<double>(8);
     }
     if (kind == kKindVoxel) {
-        L.lv[0].o_keys = o; o += al(8 * L.cap);
-        L.o_first = o; o += al(4 * L.cap);
-        L.o_flag = o;  o += al(4 * N);
-        L.o_rank = o;  o += al(4 * (N + 1));
-        L.o_ka = o;    o += al(4 * N);
-        L.o_va = o;    o += al(4 * N);
-        L.o_kb = o;    o += al(4 * N);
-        L.o_vb = o;    o += al(4 * N);
-        L.o_hist = o;  o += al(4 * 256 * L.nblk);
-        L.o_hoff = o;  o += al(4 * (256 * L.nblk + 1));
+        W.vkeys = c.take<unsigned long long>(W.cap);
+        W.first = c.take<int32_t>(W.cap);
+        W.flag = c.take<int32_t>(N);
+        W.rank = c.take<int32_t>(N + 1);
+        W.ka = c.take<int32_t>(N);
+        W.va = c.take<int32_t>(N);
+        W.kb = c.take<int32_t>(N);
+        W.vb = c.take<int32_t>(N);
+        W.sort = take_sort(c, N);
     }
-    L.total = o;
-    return L;
-}
-
-// the hash of the occupied cells of edge 1 / inv_h and the points regrouped by cell
-inline Index build_level(const float* P, int64_t N, float inv_h, char* ws, const Layout& L, int l, hipStream_t s) {
-    unsigned long long* keys = (unsigned long long*)(ws + L.lv[l].o_keys);
-    int32_t* counts = (int32_t*)(ws + L.lv[l].o_counts);
-    int32_t* starts = (int32_t*)(ws + L.lv[l].o_starts);
-    float4* pts = (float4*)(ws + L.lv[l].o_pts);
-    int32_t* vslot = (int32_t*)(ws + L.o_vslot);
-    int32_t* scr = (int32_t*)(ws + L.o_scan);
-    misplat_internal::fill_bytes(keys, 8 * L.cap, 0xffffffffu, s);          // (kernels, not memsets: internal.h)
-    misplat_internal::fill_bytes(counts, 4 * L.cap, 0u, s);
-    hipLaunchKernelGGL(index_insert_kernel, dim3(blocks(N, 256)), dim3(256), 0, s, P, N, (const uint8_t*)nullptr, inv_h, keys,
-                       (uint32_t)(L.cap - 1), vslot, counts);
-    scan(counts, L.cap, starts, scr, s);
-    hipLaunchKernelGGL(index_fill_kernel, dim3(blocks(N, 256)), dim3(256), 0, s, P, N, (const int32_t*)vslot,
-                       (const int32_t*)starts, counts, pts);
-    return Index{keys, starts, pts, (uint32_t)(L.cap - 1)};
+    return W;
 }
 
 inline bool edge_ok(float h) { return h > 0.f && h < 3.0e35f && 1.f / h < 3.0e38f; }
@@ -412,19 +373,22 @@ void launch_knn(const Levels& lv, int64_t N, const float* Q, int64_t Nq, int k, 
 
 extern "C" int64_t misplat_pointcloud_workspace(int64_t n_points, int32_t kind) {
     if (!sizes_ok(n_points) || kind < kKindCells || kind > kKindVoxel) return -1;
-    return layout(n_points, kind).total;
+    Carver c{nullptr};
+    carve(c, n_points, kind);
+    return c.o;
 }
 
 extern "C" int misplat_pointcloud_cells(const float* points, int64_t n_points, float edge, void* workspace,
                                         int64_t workspace_bytes, int32_t* n_cells, misplat_stream_t stream) {
     const int64_t N = n_points;
     if (!sizes_ok(N) || N < 1 || !edge_ok(edge) || !points || !workspace || !n_cells) return MISPLAT_EINVAL;
-    const Layout L = layout(N, kKindCells);
-    if (workspace_bytes < L.total) return MISPLAT_EWORKSPACE;
+    Carver c{(char*)workspace};
+    const Work W = carve(c, N, kKindCells);
+    if (workspace_bytes < c.o) return MISPLAT_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    const Index ix = build_level(points, N, 1.f / edge, (char*)workspace, L, 0, s);
+    const Index ix = build_index(points, N, nullptr, 1.f / edge, W.lv[0], W.vslot, W.scr, s);
     misplat_internal::fill_bytes(n_cells, 4, 0u, s);
-    hipLaunchKernelGGL(occupied_kernel, dim3(blocks(L.cap, 256)), dim3(256), 0, s, ix.keys, L.cap, n_cells);
+    hipLaunchKernelGGL(occupied_kernel, dim3(blocks(W.cap, 256)), dim3(256), 0, s, ix.keys, W.cap, n_cells);
     return launched();
 }
 
@@ -435,8 +399,9 @@ extern "C" int misplat_pointcloud_knn(const float* points, int64_t n_points, con
     if (!sizes_ok(N) || !sizes_ok(Nq) || N < 1 || k < 1 || k > 32 || k > N || !(lanes == 1 || lanes == 8) || !edge_ok(edge) ||
         !points || !workspace || (Nq > 0 && (!mean || !nearest)))
         return MISPLAT_EINVAL;
-    const Layout L = layout(N, kKindKnn);
-    if (workspace_bytes < L.total) return MISPLAT_EWORKSPACE;
+    Carver c{(char*)workspace};
+    const Work W = carve(c, N, kKindKnn);
+    if (workspace_bytes < c.o) return MISPLAT_EWORKSPACE;
     if (Nq == 0) return MISPLAT_OK;
     hipStream_t s = (hipStream_t)stream;
     Levels lv;
@@ -444,7 +409,7 @@ extern "C" int misplat_pointcloud_knn(const float* points, int64_t n_points, con
     for (int l = 0; l < kLevels; l++, h *= kCoarser) {
         lv.h[l] = h;
         lv.inv_h[l] = 1.f / h;
-        lv.ix[l] = build_level(points, N, lv.inv_h[l], (char*)workspace, L, l, s);
+        lv.ix[l] = build_index(points, N, nullptr, lv.inv_h[l], W.lv[l], W.vslot, W.scr, s);
     }
     if (k <= 4) launch_knn<4>(lv, N, queries, Nq, k, lanes, mean, nearest, s);
     else if (k <= 8) launch_knn<8>(lv, N, queries, Nq, k, lanes, mean, nearest, s);
@@ -460,12 +425,13 @@ extern "C" int misplat_pointcloud_radius_count(const float* points, int64_t n_po
     if (!sizes_ok(N) || !sizes_ok(Nq) || N < 1 || !(radius > 0.f) || !(radius < 3.0e37f) || !(1.f / radius < 3.0e38f) || !points ||
         !workspace || (Nq > 0 && !counts))
         return MISPLAT_EINVAL;
-    const Layout L = layout(N, kKindRadius);
-    if (workspace_bytes < L.total) return MISPLAT_EWORKSPACE;
+    Carver c{(char*)workspace};
+    const Work W = carve(c, N, kKindRadius);
+    if (workspace_bytes < c.o) return MISPLAT_EWORKSPACE;
     if (Nq == 0) return MISPLAT_OK;
     hipStream_t s = (hipStream_t)stream;
     const float inv_h = 1.f / radius;
-    const Index ix = build_level(points, N, inv_h, (char*)workspace, L, 0, s);
+    const Index ix = build_index(points, N, nullptr, inv_h, W.lv[0], W.vslot, W.scr, s);
     hipLaunchKernelGGL(radius_count_kernel, dim3(blocks(Nq * kSubR, 256)), dim3(256), 0, s, ix, queries, Nq, radius,
                        radius * radius, inv_h, counts);
     return launched();
@@ -475,17 +441,16 @@ extern "C" int misplat_pointcloud_outlier_mask(const float* avg, int64_t n_point
                                                int64_t workspace_bytes, uint8_t* keep, misplat_stream_t stream) {
     const int64_t N = n_points;
     if (!sizes_ok(N) || N < 1 || !(std_ratio == std_ratio) || !avg || !workspace || !keep) return MISPLAT_EINVAL;
-    const Layout L = layout(N, kKindOutlier);
-    if (workspace_bytes < L.total) return MISPLAT_EWORKSPACE;
+    Carver c{(char*)workspace};
+    const Work W = carve(c, N, kKindOutlier);
+    if (workspace_bytes < c.o) return MISPLAT_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    double* part = (double*)((char*)workspace + L.o_part);
-    double* stats = (double*)((char*)workspace + L.o_stats);
     const int64_t nb = (N + 255) / 256;
     for (int pass = 0; pass < 2; pass++) {
-        hipLaunchKernelGGL(stat_partial_kernel, dim3((unsigned)nb), dim3(256), 0, s, avg, N, pass, (const double*)stats, part);
-        hipLaunchKernelGGL((sum_final_kernel<2, 256>), dim3(1), dim3(256), 0, s, (const double*)part, nb, stats + 2 * pass);
+        hipLaunchKernelGGL(stat_partial_kernel, dim3((unsigned)nb), dim3(256), 0, s, avg, N, pass, (const double*)W.stats, W.part);
+        hipLaunchKernelGGL((sum_final_kernel<2, 256>), dim3(1), dim3(256), 0, s, (const double*)W.part, nb, W.stats + 2 * pass);
     }
-    hipLaunchKernelGGL(outlier_mask_kernel, dim3(blocks(N, 256)), dim3(256), 0, s, avg, N, std_ratio, stats, keep);
+    hipLaunchKernelGGL(outlier_mask_kernel, dim3(blocks(N, 256)), dim3(256), 0, s, avg, N, std_ratio, W.stats, keep);
     return launched();
 }
 
@@ -496,36 +461,21 @@ extern "C" int misplat_pointcloud_voxel_group(const float* points, int64_t n_poi
     if (!sizes_ok(N) || N < 1 || !(voxel_size > 0.0) || !(voxel_size < 1e300) || !points || !workspace || !order || !offsets ||
         !n_voxels)
         return MISPLAT_EINVAL;
-    const Layout L = layout(N, kKindVoxel);
-    if (workspace_bytes < L.total) return MISPLAT_EWORKSPACE;
+    Carver c{(char*)workspace};
+    const Work W = carve(c, N, kKindVoxel);
+    if (workspace_bytes < c.o) return MISPLAT_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    unsigned long long* keys = (unsigned long long*)(ws + L.lv[0].o_keys);
-    int32_t* vslot = (int32_t*)(ws + L.o_vslot);
-    int32_t* scr = (int32_t*)(ws + L.o_scan);
-    int32_t* first = (int32_t*)(ws + L.o_first);
-    int32_t* flag = (int32_t*)(ws + L.o_flag);
-    int32_t* rank = (int32_t*)(ws + L.o_rank);
-    int32_t *ka = (int32_t*)(ws + L.o_ka), *va = (int32_t*)(ws + L.o_va), *kb = (int32_t*)(ws + L.o_kb), *vb = (int32_t*)(ws + L.o_vb);
-    int32_t* hist = (int32_t*)(ws + L.o_hist);
-    int32_t* hoff = (int32_t*)(ws + L.o_hoff);
     const unsigned nb = blocks(N, 256);
-    misplat_internal::fill_bytes(keys, 8 * L.cap, 0xffffffffu, s);
-    misplat_internal::fill_bytes(first, 4 * L.cap, 0x7fffffffu, s);
-    hipLaunchKernelGGL(voxel_insert_kernel, dim3(nb), dim3(256), 0, s, points, N, origin_x, origin_y, origin_z, voxel_size, keys,
-                       (uint32_t)(L.cap - 1), vslot, first);
-    hipLaunchKernelGGL(voxel_flag_kernel, dim3(nb), dim3(256), 0, s, (const int32_t*)vslot, (const int32_t*)first, N, flag);
-    scan(flag, N, rank, scr, s);
-    hipLaunchKernelGGL(voxel_key_kernel, dim3(nb), dim3(256), 0, s, (const int32_t*)vslot, (const int32_t*)first,
-                       (const int32_t*)rank, N, ka, va, n_voxels);
-    for (int shift = 0; shift == 0 || ((N - 1) >> shift) > 0; shift += 8) {
-        hipLaunchKernelGGL(radix_hist_kernel, dim3((unsigned)L.nblk), dim3(256), 0, s, (const int32_t*)ka, N, shift, L.nblk, hist);
-        scan(hist, 256 * L.nblk, hoff, scr, s);
-        hipLaunchKernelGGL(radix_scatter_kernel, dim3((unsigned)L.nblk), dim3(256), 0, s, (const int32_t*)ka, (const int32_t*)va, N,
-                           shift, L.nblk, (const int32_t*)hoff, kb, vb);
-        int32_t* t = ka; ka = kb; kb = t;
-        t = va; va = vb; vb = t;
-    }
+    misplat_internal::fill_bytes(W.vkeys, 8 * W.cap, 0xffffffffu, s);
+    misplat_internal::fill_bytes(W.first, 4 * W.cap, 0x7fffffffu, s);
+    hipLaunchKernelGGL(voxel_insert_kernel, dim3(nb), dim3(256), 0, s, points, N, origin_x, origin_y, origin_z, voxel_size, W.vkeys,
+                       (uint32_t)(W.cap - 1), W.vslot, W.first);
+    hipLaunchKernelGGL(voxel_flag_kernel, dim3(nb), dim3(256), 0, s, (const int32_t*)W.vslot, (const int32_t*)W.first, N, W.flag);
+    scan(W.flag, N, W.rank, W.scr, s);
+    int32_t *ka = W.ka, *va = W.va, *kb = W.kb, *vb = W.vb;
+    hipLaunchKernelGGL(voxel_key_kernel, dim3(nb), dim3(256), 0, s, (const int32_t*)W.vslot, (const int32_t*)W.first,
+                       (const int32_t*)W.rank, N, ka, va, n_voxels);
+    radix_sort(ka, va, kb, vb, N, radix_passes(N - 1), W.sort, W.scr, s);      // (the keys are voxel numbers: 0 .. N - 1)
     hipLaunchKernelGGL(voxel_finish_kernel, dim3(blocks(N + 1, 256)), dim3(256), 0, s, (const int32_t*)ka, (const int32_t*)va, N,
                        order, offsets);
     return launched();

@@ -1,9 +1,11 @@
-// radixsort.h -- the stable radix sort shared by meshmap.hip (contributions by vertex) and
-// pointcloud.hip (points by voxel, section 17).  In an unnamed namespace, as cellhash.h: each translation unit that includes
-// this header compiles its own copy of the kernels into its own code object.
+// radixsort.h -- the stable radix sort of (int32 key, int32 value) pairs and its host driver.  Used by meshmap.hip
+// (contributions by vertex), pointcloud.hip (points by voxel, section 17), grouping.hip (Gaussians by
+// depth, then by cell, section 22) and density.hip (pairs by unit, section 25).  In an unnamed namespace, as cellhash.h: each
+// translation unit that includes this header compiles its own copy of the kernels into its own code object.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "wgprims.h"
 
 namespace {
 
@@ -62,6 +64,51 @@ __global__ __launch_bounds__(256) void radix_scatter_kernel(const int32_t* __res
         __syncthreads();
         run[threadIdx.x] += ((wcnt[0][threadIdx.x] + wcnt[1][threadIdx.x]) + wcnt[2][threadIdx.x]) + wcnt[3][threadIdx.x];
         __syncthreads();
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------- host
+// What a sort of E items needs besides its two (key, value) pairs and a scan scratch for 256 nblk counts
+// (take_scan(c, 256 * nblk) or longer).
+struct SortBufs {
+    int32_t *hist, *hoff;
+    int64_t nblk;
+};
+
+inline SortBufs take_sort(Carver& c, int64_t E) {
+    SortBufs b;
+    b.nblk = (E + kTile - 1) / kTile;
+    b.hist = c.take<int32_t>(256 * b.nblk);
+    b.hoff = c.take<int32_t>(256 * b.nblk + 1);
+    return b;
+}
+
+// The number of 8-bit passes that cover every key in 0 .. max_key: at least 1, at most 4 (an int32 key).  Pass p >= 1 is
+// needed iff some key has a bit at or above 8 p, i.e. iff (max_key >> 8 p) > 0, and these conditions are nested: the count
+// is 1 + the number of p in 1 .. 3 with (max_key >> 8 p) > 0.  That is what the loop
+//     for (shift = 0; shift == 0 || (max_key >> shift) > 0; shift += 8)
+// runs for 0 <= max_key < 2^31 (it stops at shift 32 at the latest, max_key being held in 64 bits), and what
+//     for (shift = 0; shift < 32 && (max_key >> shift) > 0; shift += 8)
+// runs for 1 <= max_key < 2^31 (for max_key = 0 that loop runs no pass: a caller that can see 0 must ask for itself).
+inline int radix_passes(int64_t max_key) {
+    int passes = 1;
+    while (passes < 4 && (max_key >> (8 * passes)) > 0) passes++;
+    return passes;
+}
+
+// `passes` passes over E items, pass p on the digit at shift min(8 p, 24) (a pass beyond the fourth repeats the top byte: the
+// sort being stable, the identity).  Every pass reads (ka, va), writes (kb, vb) and swaps the two pairs: on return (ka, va)
+// name the sorted pair -- the caller's second pair if `passes` is odd, its first if even -- and (kb, vb) the other.
+inline void radix_sort(int32_t*& ka, int32_t*& va, int32_t*& kb, int32_t*& vb, int64_t E, int passes, const SortBufs& b,
+                       int32_t* scan_scratch, hipStream_t s) {
+    for (int pass = 0; pass < passes; pass++) {
+        const int shift = 8 * pass < 24 ? 8 * pass : 24;
+        hipLaunchKernelGGL(radix_hist_kernel, dim3((unsigned)b.nblk), dim3(256), 0, s, (const int32_t*)ka, E, shift, b.nblk, b.hist);
+        scan(b.hist, 256 * b.nblk, b.hoff, scan_scratch, s);
+        hipLaunchKernelGGL(radix_scatter_kernel, dim3((unsigned)b.nblk), dim3(256), 0, s, (const int32_t*)ka, (const int32_t*)va, E,
+                           shift, b.nblk, (const int32_t*)b.hoff, kb, vb);
+        int32_t* t = ka; ka = kb; kb = t;
+        t = va; va = vb; vb = t;
     }
 }
 

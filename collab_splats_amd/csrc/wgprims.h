@@ -189,6 +189,23 @@ __device__ __forceinline__ I claim_slot(unsigned long long* __restrict__ keys, I
 // ------------------------------------------------------------------------------------------------------------- host
 inline int64_t al(int64_t b) { return (b + 255) & ~(int64_t)255; }
 
+// A scratch buffer handed out piece by piece, each piece 256-byte aligned.  A file describes its workspace ONCE, as a function
+// that takes its pieces from a Carver: run over the caller's buffer it yields the pointers, run over a null base it yields
+// null pointers and, in `o`, the bytes the buffer must have -- the *_workspace entry points return that.
+struct Carver {
+    char* base;
+    int64_t o = 0;
+    template <class T>
+    T* take(int64_t n) {
+        T* p = base ? (T*)(base + o) : nullptr;
+        o += al((int64_t)sizeof(T) * n);
+        return p;
+    }
+};
+
+// the scratch of scan() over up to n values
+inline int32_t* take_scan(Carver& c, int64_t n) { return c.take<int32_t>(scan_scratch_bytes(n) / 4); }
+
 inline int launched() { return hipGetLastError() == hipSuccess ? MISPLAT_OK : MISPLAT_ELAUNCH; }
 
 inline unsigned blocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }

@@ -128,6 +128,20 @@ def random_scene(seed=None):
                   bounds=[[0.0, 0.0, 0.0], [1.27, 1.27, 1.27]], isos=(0.5,))
 
 
+def wide_map(dims):
+    """Seven small Gaussians in a map of dims units (the bounds give it): in the first unit, in the last and in the middle one,
+    interleaved, so that every unit's list must be brought into ascending g and the map indices reach from 0 to the last.  Not
+    in NAMES: the map is far too large for the oracle, only the integer structures are compared."""
+    L = float(F(H) * F(16))
+    d = np.asarray(dims, np.float64)
+    first, mid, last = 0.5 * L * np.ones(3), (d // 2 + 0.5) * L, (d - 0.5) * L
+    rng = np.random.default_rng(int(np.prod(dims)) % 1000)
+    centres = np.stack([last, first, last, mid, first, last, mid])
+    means = centres + rng.uniform(-0.05, 0.05, (7, 3))
+    return _scene(means, rng.standard_normal((7, 4)), np.exp(rng.uniform(np.log(0.01), np.log(0.03), (7, 3))),
+                  rng.uniform(0.3, 1.0, 7), bounds=[[0.0, 0.0, 0.0], ((d - 0.5) * L).tolist()])
+
+
 @functools.lru_cache(maxsize=None)
 def scene(name):
     if name.startswith("batches_"):

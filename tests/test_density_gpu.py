@@ -66,6 +66,26 @@ def test_integer_structures_bit_for_bit(name):
         assert f.n_units == 0 and f.n_pairs == 0 and d.shape == (0, 4096) and f.dense().numel() == 0
 
 
+@pytest.mark.parametrize("dims", [(8, 8, 4), (257, 1, 1), (41, 41, 41), (257, 257, 257)])
+def test_lists_at_the_sort_pass_counts(dims):
+    """The pairs are sorted by map index, 8 bits a pass, in an odd number of passes: 256 map entries take one pass, 257 two and
+    a third over zero digits, 68 921 three, 257^3 > 2^24 four and a fifth that repeats the top byte.  (Every scene of S.NAMES
+    has a map of at most 64 units: one pass.)"""
+    from collab_splats_amd import DensityField
+    from density_restatement import Restated
+    sc = S.wide_map(dims)
+    f = DensityField(_t(sc["means"]), _t(sc["quats"]), _t(sc["scales"]), _t(sc["opacities"]), sc["h"], bounds=sc["bounds"])
+    R = Restated(sc["means"], sc["quats"], sc["scales"], sc["opacities"], sc["h"], bounds=sc["bounds"])
+    assert np.array_equal(f.dims, dims) and np.array_equal(R.dims, dims) and np.array_equal(f.lo, R.lo)
+    coords, _, (offsets, ids) = f.units()
+    assert np.array_equal(coords, R.unit_coords())
+    ro, ri = R.unit_lists()
+    assert np.array_equal(offsets, ro) and np.array_equal(ids, ri)
+    assert f.n_units == len(R.lists) and f.n_pairs == R.n_pairs
+    m = sorted(R.lists)
+    assert m[0] == 0 and m[-1] == int(np.prod(dims)) - 1 and max(len(v) for v in R.lists.values()) >= 3
+
+
 # -------------------------------------------------------------------------------------------------------------- field
 @pytest.mark.parametrize("name", S.NAMES)
 def test_field_against_the_oracle(name):

@@ -80,6 +80,20 @@ def test_front_at_wave_and_radix_tile_boundaries(N):
     _front(radii, means, depths, mask, 0.2)
 
 
+@pytest.mark.parametrize("ids,P,passes", [([3, 7, 8], 4, 1), ([3, 7, 8, 200, 4097], 128, 3)])
+def test_front_cell_count_at_the_sort_pass_counts(ids, P, passes):
+    """The second sort's keys are the cells 0 .. M P P (M P P: no cell), 8 bits a pass: 48 cells take one pass, 81 920 three
+    (one-pixel patches, most of the 128 x 128 empty).  Two and four passes: the cases above and test_front_mask_ids_up_to_65535."""
+    W, H, N = 70, 45, 3000
+    radii, means, depths = Q.random_view(len(ids), N, W, H)
+    mask = Q.blocks_mask(4, W, H, ids, 9, 7)
+    none = len(ids) * P * P
+    assert (none < 256, 65536 < none < 1 << 24) == (passes == 1, passes == 3)
+    for fp in (0.5, 0.2):
+        front, (got_ids, mask_of, _) = _front(radii, means, depths, mask, fp, P)
+        assert got_ids.tolist() == ids and set(np.unique(mask_of)) == set(range(-1, len(ids)))
+
+
 @pytest.mark.parametrize("W,H,P", [(70, 45, 32), (12, 20, 32), (33, 65, 7)])
 def test_front_image_sizes_and_fractions(W, H, P):
     """45 x 70 with P = 32; 20 x 12 with P = 32 (one-pixel patches, most of the 32 x 32 empty); 65 x 33 with P = 7."""

@@ -149,6 +149,23 @@ def test_map_values(k):
     _check_map(V, P, N3, k, 0.03, normals=True)
 
 
+@pytest.mark.parametrize("n_v", [255, 256, 257, 65537])
+def test_map_values_at_the_sort_pass_counts(n_v):
+    """The contributions are sorted by vertex with keys 0 .. M (M for an invalid row), 8 bits a pass: one pass up to M = 255,
+    two from 256 on, three at 65 537.  Points sit on vertices from the first to the last index, so every digit of the key
+    decides some list, and a few far points bring the key M."""
+    rng = np.random.default_rng(n_v)
+    V = (rng.random((n_v, 3)) * 0.4).astype(np.float32)
+    at = np.concatenate([[0, 1, n_v - 2, n_v - 1], rng.integers(0, n_v, 296)])
+    P = V[at] + np.float32(0.002) * rng.standard_normal((300, 3)).astype(np.float32)
+    P[7::25] += 5.0                                            # 12 invalid rows
+    F = rng.standard_normal((300, 3)).astype(np.float32)
+    out, covered = _check_map(V, P, F, 5, 0.03)
+    assert covered[0] and covered[n_v - 1]
+    _, _, valid = _knn_gpu(V, P, 5, 0.03)
+    assert not valid[7::25].any() and valid.sum() == 300 - 12
+
+
 def test_long_lists_deterministic():
     """1 M points near a sphere onto 2 k vertices on it: about 2 500 contributions per vertex, split into chunks."""
     import collab_splats_amd as m

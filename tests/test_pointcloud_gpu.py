@@ -243,6 +243,18 @@ def test_voxel_down_sample_equals_fp64_evaluation(name, voxel):
     _check_voxel(P, voxel, [], min_bound=(P.min(0).astype(np.float64) - np.array([0.3, 0.001, 7.0])).tolist())
 
 
+@pytest.mark.parametrize("n", [256, 257, 65537])
+def test_voxel_down_sample_at_the_sort_pass_counts(n):
+    """The points are sorted by voxel number, 0 .. N - 1, 8 bits a pass: one pass at N = 256, two at 257, three at 65 537.  A
+    voxel holds 4 points on average, so the order of the fp64 sums shows whether the sort kept the points of a voxel in
+    ascending index."""
+    P = S.uniform(n, 60 + n % 7)
+    voxel = 0.4 / round((n / 4) ** (1 / 3))
+    feats = np.random.default_rng(n).random((n, 5)).astype(np.float32)
+    counts = _check_voxel(P, voxel, [feats])
+    assert counts.sum() == n and counts.max() >= 4 and n / 8 < len(counts) < n / 2
+
+
 # ---------------------------------------------------------------------------------------------- full size, end to end
 def test_full_size():
     """10^6 points (a shell with its far 1 %): the kNN and the radius count against the restatement at 3000 sampled points
