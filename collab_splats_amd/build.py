@@ -6,6 +6,7 @@ hipcc cross-compiles without a GPU.
 """
 from __future__ import annotations
 
+import glob
 import os
 import subprocess
 import sys
@@ -78,20 +79,21 @@ def _stale(target: str, deps) -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+def headers() -> list:
+    """What every object depends on: the public header and every header next to the sources."""
+    return [os.path.join(INCLUDE, "misplat.h")] + sorted(glob.glob(os.path.join(CSRC, "*.h")))
+
+
 def build(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(OBJ, exist_ok=True)
     hipcc = _hipcc()
-    headers = [os.path.join(INCLUDE, "misplat.h"), os.path.join(CSRC, "sh_eval.h"), os.path.join(CSRC, "internal.h"),
-               os.path.join(CSRC, "mc_tables.h"), os.path.join(CSRC, "cellhash.h"), os.path.join(CSRC, "radixsort.h"),
-               os.path.join(CSRC, "unionfind.h"), os.path.join(CSRC, "hashmix.h"), os.path.join(CSRC, "bilinear.h"),
-               os.path.join(CSRC, "wgprims.h")]
     jobs = []
     objs = []
     for src, extra in SOURCES.items():
         s = os.path.join(CSRC, src)
         o = os.path.join(OBJ, src.replace(".hip", ".o"))
         objs.append(o)
-        if force or _stale(o, [s, __file__] + headers):
+        if force or _stale(o, [s, __file__] + headers()):
             jobs.append([hipcc] + COMMON + extra + ["-c", s, "-o", o])
 
     def run(cmd):

@@ -6,9 +6,8 @@
 //   k_g(x) = o_g (exp(-m_g / 2) - exp(-r^2 / 2))  where m_g < r^2, else 0      (continuous at the cut-off r)
 //   d(x) = sum_g k_g(x) in ascending g,   grad d(x) = -sum_{m_g < r^2} o_g exp(-m_g / 2) A_g^T A_g (x - mu_g),  A = diag(1 / s) R^T.
 //
-// Lattice: the TSDF volume's (csrc/tsdf.hip): voxel g has its centre at (g + 0.5) h, units of 16^3 voxels, L = fl32(16 h), a
-// dense unit map (lo, dims, slot_map) and a pool of 5 planes of 4096 fp32 per slot; plane 0 takes d, plane 1 the weight 1,
-// planes 2..4 zero, so misplat_tsdf_mc_count / _emit extract level sets of it unchanged.
+// Lattice: the TSDF volume's (csrc/unitgrid.h), h its voxel size and L = fl32(16 h) its unit length; plane 0 of the pool takes
+// d, plane 1 the weight 1, planes 2..4 zero, so misplat_tsdf_mc_count / _emit extract level sets of it unchanged.
 //
 // Lists: a Gaussian reaches a unit by a conservative test evaluated in fp32 in the written order (compiled with
 // -ffp-contract=off, as every binning-like file), so the integer structures equal the restatement's bit for bit:
@@ -22,34 +21,15 @@
 #include "misplat.h"
 #include "wgprims.h"
 #include "radixsort.h"
+#include "unitgrid.h"
 
 namespace {
 
-constexpr int kUnitVoxels = 4096;
-constexpr int kPlanes = 5;
 constexpr int kRec = MISPLAT_DENSITY_REC;
 constexpr int kBatch = MISPLAT_DENSITY_BATCH;
+using Grid = UnitGrid;
 
-struct Grid {
-    float vs, ulen;
-    int lo[3], dims[3];
-};
-
-bool make_grid(const misplat_tsdf_grid* p, Grid& g, int64_t& n_map) {
-    if (!p || !(p->voxel_size > 0.f) || !(p->voxel_size < 1e30f)) return false;
-    n_map = 1;
-    for (int a = 0; a < 3; a++) {
-        if (p->dims[a] < 1) return false;
-        if (p->lo[a] < -(1 << 19) || (int64_t)p->lo[a] + p->dims[a] > (1 << 19)) return false;   // (as tsdf.hip: exact in fp32)
-        g.lo[a] = p->lo[a];
-        g.dims[a] = p->dims[a];
-        n_map *= p->dims[a];
-    }
-    if (n_map > MISPLAT_TSDF_MAX_UNITS) return false;
-    g.vs = p->voxel_size;
-    g.ulen = p->voxel_size * 16.f;
-    return true;
-}
+bool make_grid(const misplat_tsdf_grid* p, Grid& g, int64_t& n) { return make_unit_grid(p, g, n) && p->voxel_size < 1e30f; }
 
 inline bool cutoff_ok(float r) { return r > 0.f && r <= 6.f; }
 
@@ -126,8 +106,7 @@ __device__ __forceinline__ bool unit_range(const Grid& g, const Geom& G, int (&l
         // (clamped before the conversion: a far Gaussian must not overflow the int)
         int l = (int)fminf(fmaxf(floorf(((G.mu[a] - G.E[a]) - g.vs) / g.ulen), -1e6f), 1e6f);
         int h = (int)fminf(fmaxf(floorf(((G.mu[a] + G.E[a]) + g.vs) / g.ulen), -1e6f), 1e6f);
-        l = l > g.lo[a] ? l : g.lo[a];
-        h = h < g.lo[a] + g.dims[a] - 1 ? h : g.lo[a] + g.dims[a] - 1;
+        clamp_units(g, a, l, h);
         lo[a] = l; hi[a] = h;
         any = any && l <= h;
     }
@@ -180,8 +159,7 @@ __global__ __launch_bounds__(256) void density_pairs_kernel(Grid g, const float*
                 for (int ux = lo[0]; ux <= hi[0]; ux++) {
                     if (!slab_keep(g, G, S, ux, uy, uz)) continue;
                     if (EMIT) {
-                        const int64_t m = (int64_t)(ux - g.lo[0]) +
-                                          (int64_t)g.dims[0] * ((int64_t)(uy - g.lo[1]) + (int64_t)g.dims[1] * (uz - g.lo[2]));
+                        const int64_t m = map_index(g, ux, uy, uz);     // (inside the map: the range is clipped to it)
                         if (pos + n < n_pairs) {           // (always: the offsets are the scan of the same test's counts)
                             keys[pos + n] = (int32_t)m;
                             ids[pos + n] = (int32_t)i;
@@ -225,10 +203,8 @@ __global__ __launch_bounds__(256) void density_accumulate_kernel(Grid g, const i
     __shared__ float4 stage[kBatch * 4];
     const int64_t m = touched[2 * blockIdx.x];
     const int64_t slot = touched[2 * blockIdx.x + 1];
-    const int64_t nxy = (int64_t)g.dims[0] * g.dims[1];
-    const int uz = (int)(m / nxy) + g.lo[2];
-    const int64_t rem = m % nxy;
-    const int uy = (int)(rem / g.dims[0]) + g.lo[1], ux = (int)(rem % g.dims[0]) + g.lo[0];
+    int ux, uy, uz;
+    unit_coords(g, m, ux, uy, uz);
     const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
     const int lx = 8 * (wave & 1) + (lane & 7), ly = 8 * (wave >> 1) + (lane >> 3);
     const float x = ((float)(ux * 16 + lx) + 0.5f) * g.vs;
@@ -283,7 +259,7 @@ __global__ __launch_bounds__(256) void density_accumulate_kernel(Grid g, const i
             }
         }
     }
-    float* base = pool + slot * kPlanes * kUnitVoxels + lx + 16 * ly;
+    float* base = pool + pool_index(slot, 0, 0) + lx + 16 * ly;
 #pragma unroll
     for (int k = 0; k < 16; k++) {
         base[0 * kUnitVoxels + 256 * k] = acc[k];
@@ -328,11 +304,9 @@ __global__ __launch_bounds__(256) void density_query_kernel(Grid g, const int32_
         const int vx = (int)fminf(fmaxf(floorf(px / g.vs), -3e7f), 3e7f);
         const int vy = (int)fminf(fmaxf(floorf(py / g.vs), -3e7f), 3e7f);
         const int vz = (int)fminf(fmaxf(floorf(pz / g.vs), -3e7f), 3e7f);
-        const int mx = (vx >> 4) - g.lo[0], my = (vy >> 4) - g.lo[1], mz = (vz >> 4) - g.lo[2];
-        if (mx >= 0 && my >= 0 && mz >= 0 && mx < g.dims[0] && my < g.dims[1] && mz < g.dims[2]) {
-            const int s = slot_map[(int64_t)mx + (int64_t)g.dims[0] * ((int64_t)my + (int64_t)g.dims[1] * mz)];
-            if (s >= 0) { e0 = ranges[2 * s]; e1 = ranges[2 * s + 1]; }
-        }
+        const int64_t m = map_index(g, vx >> 4, vy >> 4, vz >> 4);
+        const int s = m < 0 ? -1 : slot_map[m];
+        if (s >= 0) { e0 = ranges[2 * s]; e1 = ranges[2 * s + 1]; }
     }
     const float r2 = r * r, ecut = expf(-0.5f * r2);
     float d = 0.f, gx = 0.f, gy = 0.f, gz = 0.f, best = 0.f;

@@ -12,6 +12,7 @@
 #include <stdint.h>
 #include "misplat.h"
 #include "wgprims.h"
+#include "unitgrid.h"
 
 namespace {
 
@@ -340,18 +341,17 @@ __global__ __launch_bounds__(kFinal) void mean_final_kernel(const double* __rest
 // lz), weight 1, colour 0: the layout misplat_tsdf_mc_count / _emit read.  One thread per voxel in pool order.
 __global__ __launch_bounds__(kBlock) void poisson_pool_kernel(const float* __restrict__ chi, int depth, float iso, float* __restrict__ pool) {
     const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    const int64_t slot = t >> 12;
-    const int i = (int)(t & 4095);
+    const int64_t slot = t / kUnitVoxels;
+    const int i = (int)(t % kUnitVoxels);
     const int U = 1 << (depth - 4);
     const int ux = (int)(slot % U), uy = (int)((slot / U) % U), uz = (int)(slot / ((int64_t)U * U));
     const int64_t x = ux * 16 + (i & 15), y = uy * 16 + ((i >> 4) & 15), z = uz * 16 + (i >> 8);
     const float v = chi[x + (y << depth) + (z << (2 * depth))] - iso;
-    float* __restrict__ base = pool + slot * 5 * 4096 + i;
+    float* __restrict__ base = pool + pool_index(slot, 0, 0) + i;
     base[0] = v;
-    base[4096] = 1.f;
-    base[2 * 4096] = 0.f;
-    base[3 * 4096] = 0.f;
-    base[4 * 4096] = 0.f;
+    base[kUnitVoxels] = 1.f;
+#pragma unroll
+    for (int c = 2; c < kPlanes; c++) base[c * kUnitVoxels] = 0.f;
 }
 
 inline bool depth_ok(int32_t depth) { return depth >= MISPLAT_POISSON_MIN_DEPTH && depth <= MISPLAT_POISSON_MAX_DEPTH; }

@@ -4,10 +4,8 @@
 // -ffp-contract=off; every expression below is evaluated in the written order, so the voxel grids equal the restatement's
 // bit for bit.
 //
-// Volume: units of 16^3 voxels; voxel g (global integer coordinate) has its centre at (g + 0.5) * voxel_size.  A DENSE unit
-// map over the grid's bounds (grid->lo, grid->dims, x fastest) holds per unit the pool slot (int32, -1 = unallocated) and, for
-// the batch being integrated, a 64-bit word with bit j set iff view j of the batch touches the unit.  The pool holds per slot
-// 5 planes of 4096 fp32 (tsdf, w, r, g, b), voxel index i = lx + 16 ly + 256 lz.
+// Volume: unitgrid.h's (units of 16^3 voxels, a dense unit map of pool slots, 5 planes of 4096 fp32 per slot); for the batch
+// being integrated the map also holds a 64-bit word per unit, with bit j set iff view j of the batch touches the unit.
 //
 // Pipeline per batch of <= 64 views: mark (words) -> alloc (slots, touched list; the host reads two counts) -> integrate.
 // Extraction: order (allocated units in map order) -> classify + count + unit scan (the host reads two totals) -> emit.
@@ -18,13 +16,11 @@
 #define MC_QUAL static __constant__
 #include "mc_tables.h"
 #include "wgprims.h"
+#include "unitgrid.h"
 
 namespace {
 
-constexpr int kUnitVoxels = 4096;
-constexpr int kPlanes = 5;
-
-struct Grid {
+struct Grid {                                           // UnitGrid's members and the two truncations
     float vs, trunc, dtrunc, ulen;
     int lo[3], dims[3];
 };
@@ -43,35 +39,6 @@ __device__ __forceinline__ float to_u8(float x) {       // uint8(rgb * 255) with
     c = c > 0.f ? c : 0.f;                              // (NaN -> 0)
     c = c < 255.f ? c : 255.f;
     return (float)(int)c;
-}
-
-// map index of unit (ux, uy, uz), or -1 outside the map
-__device__ __forceinline__ int64_t map_index(const Grid& g, int ux, int uy, int uz) {
-    const int mx = ux - g.lo[0], my = uy - g.lo[1], mz = uz - g.lo[2];
-    if (mx < 0 || my < 0 || mz < 0 || mx >= g.dims[0] || my >= g.dims[1] || mz >= g.dims[2]) return -1;
-    return (int64_t)mx + (int64_t)g.dims[0] * ((int64_t)my + (int64_t)g.dims[1] * mz);
-}
-
-__device__ __forceinline__ void unit_coords(const Grid& g, int64_t m, int& ux, int& uy, int& uz) {
-    const int64_t nxy = (int64_t)g.dims[0] * g.dims[1];
-    uz = (int)(m / nxy) + g.lo[2];
-    const int64_t r = m % nxy;
-    uy = (int)(r / g.dims[0]) + g.lo[1];
-    ux = (int)(r % g.dims[0]) + g.lo[0];
-}
-
-// voxel reference slot * 4096 + i of global voxel (gx, gy, gz), or -1 if its unit is not allocated
-__device__ __forceinline__ int64_t voxel_ref(const Grid& g, const int32_t* __restrict__ slot_map, int gx, int gy, int gz) {
-    const int64_t m = map_index(g, gx >> 4, gy >> 4, gz >> 4);
-    if (m < 0) return -1;
-    const int s = slot_map[m];
-    if (s < 0) return -1;
-    return (int64_t)s * kUnitVoxels + ((gx & 15) | ((gy & 15) << 4) | ((gz & 15) << 8));
-}
-
-__device__ __forceinline__ float plane(const float* __restrict__ pool, int64_t ref, int c) {
-    const int64_t s = ref >> 12;
-    return pool[(s * kPlanes + c) * kUnitVoxels + (ref & 4095)];
 }
 
 // ---------------------------------------------------------------------------------------------------------------- mark
@@ -105,8 +72,7 @@ __global__ __launch_bounds__(256) void tsdf_mark_kernel(Grid g, const float* __r
                 // (clamped before the conversion: a far or non-finite point must not overflow the int)
                 int lo = (int)fminf(fmaxf(floorf((p[a] - g.trunc) / g.ulen), -1e6f), 1e6f);
                 int hi = (int)fminf(fmaxf(floorf((p[a] + g.trunc) / g.ulen), -1e6f), 1e6f);
-                lo = lo > g.lo[a] ? lo : g.lo[a];
-                hi = hi < g.lo[a] + g.dims[a] - 1 ? hi : g.lo[a] + g.dims[a] - 1;
+                clamp_units(g, a, lo, hi);
                 box[2 * a] = lo; box[2 * a + 1] = hi;
             }
         }
@@ -163,7 +129,7 @@ __global__ __launch_bounds__(4096 / kVPL) void tsdf_integrate_kernel(Grid g, con
     int ux, uy, uz;
     unit_coords(g, m, ux, uy, uz);
     const int t = threadIdx.x & 255, z0 = kVPL * (threadIdx.x >> 8);
-    float* base = pool + slot * kPlanes * kUnitVoxels + 256 * z0 + t;
+    float* base = pool + pool_index(slot, 0, 0) + 256 * z0 + t;
     float ts[kVPL], ws[kVPL], cr[kVPL], cg[kVPL], cb[kVPL];
 #pragma unroll
     for (int k = 0; k < kVPL; k++) {
@@ -412,21 +378,9 @@ __global__ __launch_bounds__(256) void mc_triangles_kernel(Grid g, const int32_t
 }
 
 bool make_grid(const misplat_tsdf_grid* p, Grid& g, int64_t& n_map) {
-    if (!p || !(p->voxel_size > 0.f) || !(p->sdf_trunc > 0.f) || !(p->depth_trunc > 0.f)) return false;
-    n_map = 1;
-    for (int a = 0; a < 3; a++) {
-        if (p->dims[a] < 1) return false;
-        // global voxel coordinates (unit * 16 + 15 + 1) stay inside int32 and exact in fp32
-        if (p->lo[a] < -(1 << 19) || (int64_t)p->lo[a] + p->dims[a] > (1 << 19)) return false;
-        g.lo[a] = p->lo[a];
-        g.dims[a] = p->dims[a];
-        n_map *= p->dims[a];
-    }
-    if (n_map > MISPLAT_TSDF_MAX_UNITS) return false;
-    g.vs = p->voxel_size;
+    if (!make_unit_grid(p, g, n_map) || !(p->sdf_trunc > 0.f) || !(p->depth_trunc > 0.f)) return false;
     g.trunc = p->sdf_trunc;
     g.dtrunc = p->depth_trunc;
-    g.ulen = p->voxel_size * 16.f;
     return true;
 }
 

@@ -24,7 +24,8 @@ import torch
 from torch import Tensor
 
 from ._lib import MisplatError, check, load, ptr, require_gpu, stream_ptr
-from .tsdf import MAX_UNITS, UNIT, UNIT_VOXELS, Grid, _unit_range
+from .meshmap import _prep
+from .unitvolume import MAX_UNITS, UNIT, UNIT_VOXELS, Grid, _unit_range, make_grid, map_span, marching_cubes, unit_coords
 
 REC = 16                             # floats per record (include/misplat.h MISPLAT_DENSITY_REC)
 MAX_CHANNELS = 16                    # channels of query's values (MISPLAT_DENSITY_MAX_CHANNELS)
@@ -83,10 +84,6 @@ def _values(name: str, values, n: int) -> Optional[Tensor]:
     return values
 
 
-def _f32(t: Tensor) -> Tensor:
-    return t.detach().to(torch.float32).contiguous()
-
-
 class _Stages:
     """Seconds per build stage into a dict, each stage synchronised; nothing at all without a dict."""
 
@@ -142,7 +139,7 @@ class DensityField:
         lib = load()
         dev = self.device
         mark = _Stages(_timings)                                # (scripts/density_bench.py: seconds per stage, synchronised)
-        mu, q, s, o = _f32(means), _f32(quats), _f32(scales), _f32(opacities)
+        mu, q, s, o = _prep(means), _prep(quats), _prep(scales), _prep(opacities)
         cr, cmo = C.c_float(r), C.c_float(mo)
         check(lib.misplat_density_records(ptr(mu), ptr(q), ptr(s), ptr(o), C.c_int64(self.n_gauss), cr, cmo, ptr(self._records),
                                           stream_ptr()), "misplat_density_records")
@@ -158,15 +155,8 @@ class DensityField:
                 return                                                               # no Gaussian takes part
             clip = np.stack([box[0] - h, box[1] + h])               # (the one-voxel pad of the lists: every unit they reach)
         lo, hi = _unit_range(clip[0], clip[1], self.ulen)
-        if np.any(np.abs(lo) >= 1 << 19) or np.any(np.abs(hi) >= (1 << 19) - 1):
-            raise MisplatError(f"{name}: the bounds reach unit {max(np.abs(lo).max(), np.abs(hi).max())}, beyond the lattice's "
-                               f"2^19 units per axis: pass bounds= or a larger voxel_size")
-        dims = hi - lo + 1
-        n_map = int(np.prod(dims.astype(object)))
-        if n_map > self.max_units:
-            raise MisplatError(f"{name}: the bounds span {n_map} units of {UNIT}^3 voxels, above the cap of {self.max_units}: "
-                               f"pass bounds= or a larger voxel_size")
-        self.lo, self.dims = lo.astype(np.int64), dims.astype(np.int64)
+        dims, n_map = map_span(name, "the bounds", lo, hi, self.max_units, "pass bounds= or a larger voxel_size")
+        self.lo, self.dims = lo.astype(np.int64), dims
         mark("bounds")
         grid = self._grid()
         N = C.c_int64(self.n_gauss)
@@ -216,10 +206,8 @@ class DensityField:
 
     # ------------------------------------------------------------------------------------------------------------ plumbing
     def _grid(self) -> Grid:
-        g = Grid(self.voxel_size, self.voxel_size, 1.0)       # (sdf_trunc and depth_trunc: unused here, positive for tsdf.hip)
-        g.lo[:] = [int(x) for x in self.lo]
-        g.dims[:] = [int(x) for x in self.dims]
-        return g
+        # (sdf_trunc and depth_trunc: unused here, positive for tsdf.hip)
+        return make_grid(self.voxel_size, self.voxel_size, 1.0, self.lo, self.dims)
 
     def _map_order(self) -> Tensor:
         return torch.nonzero(self._slot_map >= 0).squeeze(1)
@@ -237,9 +225,7 @@ class DensityField:
         d = self._pool[slots, 0].cpu().numpy()
         rng = self._ranges[slots].cpu().numpy().astype(np.int64)
         ids = self._ids.cpu().numpy()
-        m = m.cpu().numpy()
-        nx, ny = int(self.dims[0]), int(self.dims[1])
-        coords = np.stack([m % nx, (m // nx) % ny, m // (nx * ny)], 1) + self.lo[None, :]
+        coords = unit_coords(m.cpu().numpy(), self.lo, self.dims)
         # (the pairs are sorted by map index: the lists lie in map order, end to end)
         offsets = np.concatenate([rng[:, 0], rng[-1:, 1]])
         assert np.array_equal(rng[1:, 0], rng[:-1, 1]) and rng[0, 0] == 0 and rng[-1, 1] == len(ids)
@@ -272,8 +258,8 @@ class DensityField:
                "values": None if values is None else torch.zeros((P, values.shape[1]), dtype=torch.float32, device=dev)}
         if P == 0 or self.n_units == 0:
             return out
-        p32 = _f32(points)
-        v32 = None if values is None else _f32(values)
+        p32 = _prep(points)
+        v32 = None if values is None else _prep(values)
         grid = self._grid()
         check(load().misplat_density_query(C.byref(grid), ptr(self._slot_map), ptr(self._records), ptr(self._ids), ptr(self._ranges),
                                            C.c_float(self.cutoff), ptr(p32), C.c_int64(P), ptr(v32),
@@ -302,34 +288,14 @@ class DensityField:
                  None if D is None else torch.zeros((0, D), dtype=torch.float32, device=dev))
         if self.n_units == 0:
             return empty
-        lib = load()
-        grid = self._grid()
-        n = self.n_units
         work = self._pool.clone()                                  # (the extraction takes 5 planes: DESIGN.md section 25)
         torch.sub(iso, self._pool[:, 0], out=work[:, 0])
-        nb = (int(np.prod(self.dims)) + 4095) // 4096
-        scratch = torch.empty(2 * nb + 1, dtype=torch.int32, device=dev)
-        order = torch.empty(n, dtype=torch.int32, device=dev)
-        check(lib.misplat_tsdf_order(C.byref(grid), ptr(self._slot_map), ptr(scratch), ptr(order), stream_ptr()),
-              "misplat_tsdf_order")
-        code = torch.empty(n * UNIT_VOXELS, dtype=torch.int16, device=dev)
-        cnt = torch.empty(n * UNIT_VOXELS, dtype=torch.uint8, device=dev)
-        unit_counts = torch.empty(2 * n, dtype=torch.int32, device=dev)
-        unit_offs = torch.empty(2 * n, dtype=torch.int32, device=dev)
-        totals = torch.empty(2, dtype=torch.int32, device=dev)
-        check(lib.misplat_tsdf_mc_count(C.byref(grid), ptr(self._slot_map), ptr(order), n, ptr(work), ptr(code), ptr(cnt),
-                                        ptr(unit_counts), ptr(unit_offs), ptr(totals), stream_ptr()), "misplat_tsdf_mc_count")
-        M, T = (int(x) for x in totals.tolist())                   # host read
-        if M == 0:
+        mesh = marching_cubes(self._grid(), self._slot_map, self.n_units, work)
+        del work
+        if mesh is None:
             return empty
-        vert_base = torch.empty(n * UNIT_VOXELS, dtype=torch.int32, device=dev)
-        vertices = torch.empty((M, 3), dtype=torch.float32, device=dev)
-        unused = torch.empty((M, 3), dtype=torch.float32, device=dev)       # the pool carries no colour
-        triangles = torch.empty((T, 3), dtype=torch.int32, device=dev)
-        check(lib.misplat_tsdf_mc_emit(C.byref(grid), ptr(self._slot_map), ptr(order), n, ptr(work), ptr(code), ptr(cnt),
-                                       ptr(unit_offs), ptr(vert_base), ptr(vertices), ptr(unused), ptr(triangles), stream_ptr()),
-              "misplat_tsdf_mc_emit")
-        del work, code, cnt, vert_base, unused
+        vertices, triangles = mesh[:2]                             # (the pool carries no colour)
+        del mesh
         return vertices, triangles, None if values is None else self.query(vertices, values)["values"]
 
 

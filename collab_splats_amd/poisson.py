@@ -22,6 +22,7 @@ from ._lib import MisplatError, check, load, ptr, require_gpu, stream_ptr
 from .meshclean import _attributes, _mesh
 from .meshmap import _prep
 from .pointcloud import _cloud, _finite, _positive32
+from .unitvolume import UNIT, UNIT_VOXELS, make_grid, marching_cubes
 
 MIN_DEPTH, MAX_DEPTH = 4, 9          # include/misplat.h MISPLAT_POISSON_MIN_DEPTH / MAX_DEPTH: 2^27 cells, 7 int64 grids of them
 FIX = 2.0 ** 30                      # the fixed point of the splat (csrc/poisson.hip kFix)
@@ -236,35 +237,19 @@ def _extract(chi: Tensor, iso: float, depth: int, o: np.ndarray, h, Wf: Tensor, 
              ) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
     """Marching cubes of chi - float32(iso) over the cell centres, through the TSDF volume's extraction (csrc/tsdf.hip) on a fully
     allocated unit map with voxel_size 1; then world = origin + v h and the trilinear density and colour."""
-    from .tsdf import UNIT_VOXELS, Grid
-    lib = load()
     dev = chi.device
-    U = (1 << depth) // 16
+    U = (1 << depth) // UNIT
     n = U ** 3
     pool = torch.empty((n, 5, UNIT_VOXELS), dtype=torch.float32, device=dev)
-    check(lib.misplat_poisson_mc_pool(ptr(chi), depth, C.c_float(iso), ptr(pool), stream_ptr()), "misplat_poisson_mc_pool")
-    grid = Grid(1.0, 1.0, 1.0)
-    grid.lo[:] = [0, 0, 0]
-    grid.dims[:] = [U, U, U]
-    slot_map = torch.arange(n, dtype=torch.int32, device=dev)       # every unit allocated, in map order
-    code = torch.empty(n * UNIT_VOXELS, dtype=torch.int16, device=dev)
-    cnt = torch.empty(n * UNIT_VOXELS, dtype=torch.uint8, device=dev)
-    unit_counts = torch.empty(2 * n, dtype=torch.int32, device=dev)
-    unit_offs = torch.empty(2 * n, dtype=torch.int32, device=dev)
-    totals = torch.empty(2, dtype=torch.int32, device=dev)
-    check(lib.misplat_tsdf_mc_count(C.byref(grid), ptr(slot_map), ptr(slot_map), n, ptr(pool), ptr(code), ptr(cnt), ptr(unit_counts),
-                                    ptr(unit_offs), ptr(totals), stream_ptr()), "misplat_tsdf_mc_count")
-    M, T = (int(x) for x in totals.tolist())                        # host read
-    if M == 0:
+    check(load().misplat_poisson_mc_pool(ptr(chi), depth, C.c_float(iso), ptr(pool), stream_ptr()), "misplat_poisson_mc_pool")
+    slot_map = torch.arange(n, dtype=torch.int32, device=dev)       # every unit allocated, in map order: the order too
+    mesh = marching_cubes(make_grid(1.0, 1.0, 1.0, (0, 0, 0), (U, U, U)), slot_map, n, pool, order=slot_map)
+    del pool
+    if mesh is None:
         z3 = torch.zeros((0, 3), dtype=torch.float32, device=dev)
         return z3, torch.zeros((0, 3), dtype=torch.int32, device=dev), z3.clone(), torch.zeros(0, dtype=torch.float32, device=dev)
-    vert_base = torch.empty(n * UNIT_VOXELS, dtype=torch.int32, device=dev)
-    v = torch.empty((M, 3), dtype=torch.float32, device=dev)
-    unused = torch.empty((M, 3), dtype=torch.float32, device=dev)   # the pool carries no colour
-    triangles = torch.empty((T, 3), dtype=torch.int32, device=dev)
-    check(lib.misplat_tsdf_mc_emit(C.byref(grid), ptr(slot_map), ptr(slot_map), n, ptr(pool), ptr(code), ptr(cnt), ptr(unit_offs),
-                                   ptr(vert_base), ptr(v), ptr(unused), ptr(triangles), stream_ptr()), "misplat_tsdf_mc_emit")
-    del pool, code, cnt, vert_base, unused
+    v, triangles = mesh[:2]                                         # (the pool carries no colour)
+    del mesh
     vertices = torch.as_tensor(o, device=dev)[None, :] + v * float(h)
     density = _sample(Wf[None], depth, o, h, vertices).reshape(-1)
     if Cq is None:

@@ -15,24 +15,10 @@ import torch
 from torch import Tensor
 
 from ._lib import MisplatError, check, load, ptr, require_gpu, stream_ptr
+from .unitvolume import (MAX_UNITS, UNIT, UNIT_VOXELS, Grid, _unit_range, make_grid, map_span, marching_cubes,  # noqa: F401
+                         unit_coords)
 
-UNIT = 16
-UNIT_VOXELS = UNIT ** 3
 MAX_VIEWS = 64                       # views per kernel batch (bits of a unit's view word)
-MAX_UNITS = 1 << 26                  # dense unit map cap (include/misplat.h MISPLAT_TSDF_MAX_UNITS)
-
-
-class Grid(C.Structure):
-    """Mirror of ``misplat_tsdf_grid`` (include/misplat.h)."""
-    _fields_ = [("voxel_size", C.c_float), ("sdf_trunc", C.c_float), ("depth_trunc", C.c_float),
-                ("lo", C.c_int32 * 3), ("dims", C.c_int32 * 3), ("reserved", C.c_int32)]
-
-
-def _unit_range(lo_world, hi_world, ulen: float) -> Tuple[np.ndarray, np.ndarray]:
-    """Inclusive unit-coordinate range of the units overlapping the world box [lo, hi]."""
-    lo = np.floor(np.asarray(lo_world, np.float64) / ulen).astype(np.int64)
-    hi = np.floor(np.asarray(hi_world, np.float64) / ulen).astype(np.int64)
-    return lo, hi
 
 
 class TSDFVolume:
@@ -68,10 +54,7 @@ class TSDFVolume:
 
     # ------------------------------------------------------------------------------------------------------------ plumbing
     def _grid(self) -> Grid:
-        g = Grid(self.voxel_size, self.sdf_trunc, self.depth_trunc)
-        g.lo[:] = [int(x) for x in self.lo]
-        g.dims[:] = [int(x) for x in self.dims]
-        return g
+        return make_grid(self.voxel_size, self.sdf_trunc, self.depth_trunc, self.lo, self.dims)
 
     def _cover(self, lo: np.ndarray, hi: np.ndarray) -> bool:
         """Make the unit map cover units lo..hi (inclusive, clipped to the bounds); False if nothing is left."""
@@ -84,11 +67,8 @@ class TSDFVolume:
             if np.all(lo >= self.lo) and np.all(hi <= old_hi):
                 return True
             lo, hi = np.minimum(lo, self.lo), np.maximum(hi, old_hi)
-        dims = hi - lo + 1
-        n = int(np.prod(dims))
-        if n > self.max_units:
-            raise MisplatError(f"TSDFVolume: the views' frusta span {n} units of {UNIT}^3 voxels, above the cap of "
-                               f"{self.max_units}: pass bounds=, a smaller depth_trunc or a larger voxel_size")
+        dims, n = map_span("TSDFVolume", "the views' frusta", lo, hi, self.max_units,
+                           "pass bounds=, a smaller depth_trunc or a larger voxel_size")
         slot_map = torch.full((n,), -1, dtype=torch.int32, device=self.device)
         if self.n_units:                           # re-linearise the allocated units into the grown map
             m = torch.nonzero(self._slot_map >= 0).squeeze(1)
@@ -197,33 +177,7 @@ class TSDFVolume:
                  torch.zeros((0, 3), dtype=torch.float32, device=dev))
         if self.n_units == 0:
             return empty
-        lib = load()
-        grid = self._grid()
-        n = self.n_units
-        nb = (int(np.prod(self.dims)) + 4095) // 4096
-        scratch = torch.empty(2 * nb + 1, dtype=torch.int32, device=dev)
-        order = torch.empty(n, dtype=torch.int32, device=dev)
-        check(lib.misplat_tsdf_order(C.byref(grid), ptr(self._slot_map), ptr(scratch), ptr(order), stream_ptr()),
-              "misplat_tsdf_order")
-        code = torch.empty(n * UNIT_VOXELS, dtype=torch.int16, device=dev)
-        cnt = torch.empty(n * UNIT_VOXELS, dtype=torch.uint8, device=dev)
-        unit_counts = torch.empty(2 * n, dtype=torch.int32, device=dev)
-        unit_offs = torch.empty(2 * n, dtype=torch.int32, device=dev)
-        totals = torch.empty(2, dtype=torch.int32, device=dev)
-        check(lib.misplat_tsdf_mc_count(C.byref(grid), ptr(self._slot_map), ptr(order), n, ptr(self._pool), ptr(code),
-                                        ptr(cnt), ptr(unit_counts), ptr(unit_offs), ptr(totals), stream_ptr()),
-              "misplat_tsdf_mc_count")
-        M, T = (int(x) for x in totals.tolist())
-        if M == 0:
-            return empty
-        vert_base = torch.empty(n * UNIT_VOXELS, dtype=torch.int32, device=dev)
-        vertices = torch.empty((M, 3), dtype=torch.float32, device=dev)
-        colors = torch.empty((M, 3), dtype=torch.float32, device=dev)
-        triangles = torch.empty((T, 3), dtype=torch.int32, device=dev)
-        check(lib.misplat_tsdf_mc_emit(C.byref(grid), ptr(self._slot_map), ptr(order), n, ptr(self._pool), ptr(code), ptr(cnt),
-                                       ptr(unit_offs), ptr(vert_base), ptr(vertices), ptr(colors), ptr(triangles),
-                                       stream_ptr()), "misplat_tsdf_mc_emit")
-        return vertices, triangles, colors
+        return marching_cubes(self._grid(), self._slot_map, self.n_units, self._pool) or empty
 
     def units(self):
         """The allocated units in map order, on the host (for tests and inspection): (coords [n,3] int64, tsdf [n,4096],
@@ -234,9 +188,7 @@ class TSDFVolume:
         m = torch.nonzero(self._slot_map >= 0).squeeze(1)
         slots = self._slot_map[m].long()
         data = self._pool[slots].cpu().numpy()
-        m = m.cpu().numpy()
-        nx, ny = int(self.dims[0]), int(self.dims[1])
-        coords = np.stack([m % nx, (m // nx) % ny, m // (nx * ny)], 1) + self.lo[None, :]
+        coords = unit_coords(m.cpu().numpy(), self.lo, self.dims)
         return coords, data[:, 0], data[:, 1], np.ascontiguousarray(data[:, 2:5].transpose(0, 2, 1))
 
 

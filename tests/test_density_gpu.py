@@ -214,6 +214,19 @@ def test_two_builds_and_two_queries_are_bitwise_equal_and_extraction_leaves_the_
     assert v.shape == (0, 3) and t.shape == (0, 3) and c is None
 
 
+@pytest.mark.parametrize("D", [None, 1, 5])
+def test_iso_above_the_maximum_gives_the_empty_triple(D):
+    """Allocated units but no crossed edge: the driver's M = 0 path, without values and with them (shape (0, D))."""
+    f = _field("random")
+    assert f.n_units > 0
+    top = float(f._pool[:f.n_units, 0].max())
+    vals = None if D is None else torch.rand((f.n_gauss, D), device=DEV)
+    v, t, c = f.extract_mesh(2.0 * top + 1.0, values=vals)
+    assert v.shape == (0, 3) and v.dtype == torch.float32 and t.shape == (0, 3) and t.dtype == torch.int32
+    assert c is None if D is None else (c.shape == (0, D) and c.dtype == torch.float32)
+    assert f.extract_mesh(0.5 * top)[0].shape[0] > 0                                    # (below it there is a surface)
+
+
 # --------------------------------------------------------------------------------------------------------------- mesh
 def _edges(tri):
     e = np.concatenate([tri[:, [0, 1]], tri[:, [1, 2]], tri[:, [2, 0]]])

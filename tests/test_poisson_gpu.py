@@ -141,6 +141,17 @@ def test_iso_and_mesh_equal_the_restatement_on_the_gpus_chi(name):
     assert _close(_np(v), rv) and _close(_np(c), rc) and _close(_np(d), rd)
 
 
+@pytest.mark.parametrize("value, iso", [(1.0, 0.0), (-1.0, 0.0), (0.25, 0.25)])
+def test_extract_of_a_constant_chi_is_the_four_empty_tensors(value, iso):
+    """No crossed edge (one unit at depth 4, all positive, all negative or all zero): the driver's M = 0 path."""
+    from collab_splats_amd import poisson
+    chi = torch.full((16, 16, 16), value, dtype=torch.float32, device=DEV)
+    v, t, c, d = poisson._extract(chi, iso, 4, np.zeros(3, np.float32), np.float32(1.0), torch.ones_like(chi), None)
+    assert v.shape == (0, 3) and v.dtype == torch.float32 and t.shape == (0, 3) and t.dtype == torch.int32
+    assert c.shape == (0, 3) and c.dtype == torch.float32 and d.shape == (0,) and d.dtype == torch.float32
+    assert all(x.device == chi.device for x in (v, t, c, d))
+
+
 # ----------------------------------------------------------------------------------------------------------- 5 sphere
 @pytest.mark.parametrize("name", ["sphere5", "sphere6"])
 def test_sphere_end_to_end(name):

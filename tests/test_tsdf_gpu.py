@@ -272,6 +272,25 @@ def test_slot_order_reaches_no_result():
     assert _same_bits(a[0], b[0]) and np.array_equal(a[1], b[1]) and _same_bits(a[2], b[2])
 
 
+def test_tsdf_and_poisson_front_ends_extract_the_same_mesh():
+    """One closed 8-unit field through both callers of unitvolume.marching_cubes: TSDFVolume (the order found by
+    misplat_tsdf_order under a random slot permutation) and poisson._extract (chi laid into the pool by misplat_poisson_mc_pool,
+    order = the identity slot map).  Voxel size 1, origin 0, h 1 and iso 0.0 make both lattices the same: voxel g at g + 0.5
+    (0 + v * 1.0 and chi - 0.0 are exact), so vertices and triangles are equal bit for bit; colours are not compared (the
+    Poisson pool carries none)."""
+    from collab_splats_amd import poisson
+    field = F_.random_field(F_.block((0, 0, 0), (2, 2, 2)), p_neg=0.5, closed=True)
+    for d in field.values():
+        d[1] = 1.0
+    v, f, _ = _mesh(_inject(field, 1.0, perm=np.random.default_rng(3).permutation(8), lo=(0, 0, 0)))
+    chi = _t(F_.Dense(field).tsdf.transpose(2, 1, 0))                              # [z, y, x]
+    assert chi.shape == (32, 32, 32)
+    pv, pf, _, _ = poisson._extract(chi, 0.0, 5, np.zeros(3, np.float32), np.float32(1.0), torch.zeros_like(chi), None)
+    assert len(f) > 1000
+    assert pf.dtype == torch.int32 and np.array_equal(pf.cpu().numpy(), f)
+    assert _same_bits(pv.cpu().numpy(), v)
+
+
 def test_marching_cubes_over_more_than_1024_units():
     """A slab of 41 x 25 x 1 units: the per-unit vertex and triangle counts take a second trip of the one-workgroup scan.
     (Restating the slab takes 5 s and 2.6 GB of host memory, so the mesh is held against the independent references: the

@@ -24,8 +24,7 @@ def test_committed_header_equals_generator_output():
 def test_header_is_listed_as_a_build_dependency():
     from collab_splats_amd import build
     src = open(build.__file__).read()
-    assert '"mc_tables.h"' in src and '"tsdf.hip": ["-ffp-contract=off"]' in src
-
+    assert os.path.join(build.CSRC, "mc_tables.h") in build.headers() and '"tsdf.hip": ["-ffp-contract=off"]' in src
 
 def _cases():
     ntri, tri, _ = mc.tables()
