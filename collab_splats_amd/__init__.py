@@ -18,14 +18,14 @@ from .pointcloud import (calculate_accuracy, calculate_completeness, clean_pcd, 
                          knn_mean_distance, radius_count, remove_far_points, remove_statistical_outlier,
                          statistical_outlier_mask, voxel_down_sample)
 from .meshclean import (align_floor, fill_holes, filter_mesh_components, mesh_components, mesh_edge_stats,  # noqa: F401
-                        mesh_holes, plane_inlier_counts, ransac_planes, sample_surface, segment_plane)
+                        mesh_holes, plane_inlier_counts, ransac_planes, sample_surface, segment_plane, smooth_laplacian)
 from .depthcloud import backproject, depth_edges, depth_normal_cloud, gaussian_mask_filter, sample_pixels  # noqa: F401
 from .featureloss import TwoLayerMLP, feature_decode, feature_loss  # noqa: F401
 from .bilagrid import BilateralGrid, bilagrid_slice, bilagrid_tv_loss  # noqa: F401
 from .textquery import TextQuery, fold_text_queries, gaussian_similarity, similarity_map  # noqa: F401
 from .poisson import (poisson_grid, poisson_reconstruct, poisson_solve, poisson_splat, poisson_system,  # noqa: F401
                       poisson_trim)
-from .density import DensityField, gaussian_density, gaussian_density_grad  # noqa: F401
+from .density import DensityField, gaussian_density, gaussian_density_grad, level_surface_points  # noqa: F401
 from .grouping import FrontGaussians, MemoryBank, convert_matched_mask, front_gaussians, project_gaussians  # noqa: F401
 
 __version__ = "0.1.0"

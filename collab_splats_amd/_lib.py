@@ -131,7 +131,8 @@ SYMBOLS = {
     "misplat_pointcloud_voxel_mean": (C.c_int, 8),
     "misplat_meshclean_workspace": (C.c_int64, 3), "misplat_meshclean_edge_stats": (C.c_int, 9),
     "misplat_meshclean_components": (C.c_int, 9), "misplat_meshclean_holes": (C.c_int, 11),
-    "misplat_meshclean_segment_sum": (C.c_int, 6), "misplat_meshclean_plane_build": (C.c_int, 8),
+    "misplat_meshclean_segment_sum": (C.c_int, 6), "misplat_meshclean_smooth": (C.c_int, 15),
+    "misplat_meshclean_plane_build": (C.c_int, 8),
     "misplat_meshclean_plane_count": (C.c_int, 8), "misplat_meshclean_plane_moments": (C.c_int, 9),
     "misplat_depthcloud_workspace": (C.c_int64, 4), "misplat_depthcloud_edges": (C.c_int, 10),
     "misplat_depthcloud_candidates": (C.c_int, 7), "misplat_depthcloud_sample": (C.c_int, 15),
@@ -150,6 +151,7 @@ SYMBOLS = {
     "misplat_density_workspace": (C.c_int64, 2), "misplat_density_records": (C.c_int, 9),
     "misplat_density_count": (C.c_int, 13), "misplat_density_emit": (C.c_int, 14), "misplat_density_lists": (C.c_int, 12),
     "misplat_density_accumulate": (C.c_int, 10), "misplat_density_query": (C.c_int, 15),
+    "misplat_density_raycast": (C.c_int, 19),
     "misplat_version": (C.c_char_p, 0),
 }
 

@@ -1,5 +1,5 @@
 // density.hip -- the density of the Gaussian mixture itself on the TSDF volume's lattice, and at arbitrary points (DESIGN.md
-// section 25).
+// section 25), and the search for its level sets along rays (section 26).
 //
 // Field (restated from the published definition, SuGaR's density; tests/density_restatement.py holds the fp64 oracle and the
 // fp32 restatement of everything integer here): with R = R(q / |q|) (columns e_a), m_g(x) = sum_a ((e_a . (x - mu)) / s_a)^2,
@@ -288,6 +288,18 @@ __device__ __forceinline__ bool gauss_term(const float* __restrict__ rec, float 
     return true;
 }
 
+// the pool slot of the unit that holds the point's voxel floor(p / h); -1: a non-finite point, outside the map, or an
+// unallocated unit.  Shared by query and raycast.
+__device__ __forceinline__ int point_slot(const Grid& g, const int32_t* __restrict__ slot_map, float px, float py, float pz) {
+    if (!(is_fin(px) && is_fin(py) && is_fin(pz))) return -1;
+    // (clamped before the conversion, as the ranges)
+    const int vx = (int)fminf(fmaxf(floorf(px / g.vs), -3e7f), 3e7f);
+    const int vy = (int)fminf(fmaxf(floorf(py / g.vs), -3e7f), 3e7f);
+    const int vz = (int)fminf(fmaxf(floorf(pz / g.vs), -3e7f), 3e7f);
+    const int64_t m = map_index(g, vx >> 4, vy >> 4, vz >> 4);
+    return m < 0 ? -1 : slot_map[m];
+}
+
 __global__ __launch_bounds__(256) void density_query_kernel(Grid g, const int32_t* __restrict__ slot_map,
                                                             const float* __restrict__ records, const int32_t* __restrict__ ids,
                                                             const int32_t* __restrict__ ranges, float r,
@@ -299,15 +311,8 @@ __global__ __launch_bounds__(256) void density_query_kernel(Grid g, const int32_
     if (p >= P) return;
     const float px = points[3 * p], py = points[3 * p + 1], pz = points[3 * p + 2];
     int e0 = 0, e1 = 0;
-    if (is_fin(px) && is_fin(py) && is_fin(pz)) {
-        // (clamped before the conversion, as the ranges)
-        const int vx = (int)fminf(fmaxf(floorf(px / g.vs), -3e7f), 3e7f);
-        const int vy = (int)fminf(fmaxf(floorf(py / g.vs), -3e7f), 3e7f);
-        const int vz = (int)fminf(fmaxf(floorf(pz / g.vs), -3e7f), 3e7f);
-        const int64_t m = map_index(g, vx >> 4, vy >> 4, vz >> 4);
-        const int s = m < 0 ? -1 : slot_map[m];
-        if (s >= 0) { e0 = ranges[2 * s]; e1 = ranges[2 * s + 1]; }
-    }
+    const int s = point_slot(g, slot_map, px, py, pz);
+    if (s >= 0) { e0 = ranges[2 * s]; e1 = ranges[2 * s + 1]; }
     const float r2 = r * r, ecut = expf(-0.5f * r2);
     float d = 0.f, gx = 0.f, gy = 0.f, gz = 0.f, best = 0.f;
     int32_t dom = -1;
@@ -338,6 +343,99 @@ __global__ __launch_bounds__(256) void density_query_kernel(Grid g, const int32_
                 for (int c = 0; c < nc; c++) v[c] += k * values[(int64_t)D * id + c0 + c];
             }
         for (int c = 0; c < nc; c++) values_out[(int64_t)D * p + c0 + c] = d > 0.f ? v[c] / d : 0.f;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------- raycast
+// The level-set search along rays.  One wave per ray, four rays per workgroup; lane k owns sample k.
+// d at the wave's 64 points, bit for bit what query gives at each: the wave walks its distinct units one at a time (the slot
+// of the first pending lane, the lanes that share it), the unit's list with a wave-uniform index, so the id and the record
+// are uniform loads that serve the whole group; each lane adds its terms in its own unit's list order.  need: the lanes
+// whose sample is evaluated (the others return 0).
+__device__ __forceinline__ float wave_density(const Grid& g, const int32_t* __restrict__ slot_map, const float* __restrict__ records,
+                                              const int32_t* __restrict__ ids, const int32_t* __restrict__ ranges, float r2,
+                                              float ecut, bool need, float px, float py, float pz) {
+    const int slot = need ? point_slot(g, slot_map, px, py, pz) : -1;
+    bool pending = slot >= 0;
+    float d = 0.f;
+    while (true) {
+        const unsigned long long todo = __ballot(pending);
+        if (!todo) break;
+        const int leader = __builtin_amdgcn_readfirstlane(__ffsll((long long)todo) - 1);
+        const int s = __builtin_amdgcn_readlane(slot, leader);
+        const bool mine = pending && slot == s;
+        const int e0 = __builtin_amdgcn_readfirstlane(ranges[2 * s]), e1 = __builtin_amdgcn_readfirstlane(ranges[2 * s + 1]);
+        for (int e = e0; e < e1; e++) {
+            const float* rec = records + (int64_t)kRec * __builtin_amdgcn_readfirstlane(ids[e]);
+            float k, ex, tv[3];
+            if (mine && gauss_term(rec, px, py, pz, r2, ecut, k, ex, tv)) d += k;
+        }
+        if (mine) pending = false;
+    }
+    return d;
+}
+
+struct Levels {
+    float v[4];
+};
+
+// lane k's value (k wave-uniform)
+__device__ __forceinline__ float read_lane(float x, int k) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), k)); }
+
+// t_out [L, M], hit_out [L, M]: per level the first crossing from below, front to back: a coarse pass of 64 samples over
+// [t0, t1] shared by the levels, then per level 64 samples over its bracket (the ends reuse the coarse values), then the
+// linear interpolation inside the fine bracket.  Every expression in the one order DESIGN.md section 26 writes.
+__global__ __launch_bounds__(256) void density_raycast_kernel(Grid g, const int32_t* __restrict__ slot_map,
+                                                              const float* __restrict__ records, const int32_t* __restrict__ ids,
+                                                              const int32_t* __restrict__ ranges, float r,
+                                                              const float* __restrict__ origins, const float* __restrict__ dirs,
+                                                              const float* __restrict__ t0s, const float* __restrict__ t1s, int64_t M,
+                                                              Levels levels, int L, float* __restrict__ t_out,
+                                                              uint8_t* __restrict__ hit_out) {
+    const int lane = threadIdx.x & 63;
+    const int64_t ray = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (ray >= M) return;                                  // (the whole wave)
+    const float ox = origins[3 * ray], oy = origins[3 * ray + 1], oz = origins[3 * ray + 2];
+    const float vx = dirs[3 * ray], vy = dirs[3 * ray + 1], vz = dirs[3 * ray + 2];
+    const float t0 = t0s[ray], t1 = t1s[ray];
+    const bool ok = is_fin(ox) && is_fin(oy) && is_fin(oz) && is_fin(vx) && is_fin(vy) && is_fin(vz) && is_fin(t0) && is_fin(t1) &&
+                    t1 > t0;
+    if (!ok) {
+        if (lane < L) { t_out[(int64_t)lane * M + ray] = 0.f; hit_out[(int64_t)lane * M + ray] = 0; }
+        return;
+    }
+    const float r2 = r * r, ecut = expf(-0.5f * r2);
+    const float step = (t1 - t0) / 63.f;
+    const float tk = t0 + (float)lane * step;
+    const float D = wave_density(g, slot_map, records, ids, ranges, r2, ecut, true, ox + tk * vx, oy + tk * vy, oz + tk * vz);
+    const float Dn = __shfl_down(D, 1);
+    for (int l = 0; l < L; l++) {
+        const float lev = l == 0 ? levels.v[0] : l == 1 ? levels.v[1] : l == 2 ? levels.v[2] : levels.v[3];
+        float t = 0.f;
+        int hit_lane = 0;                                  // (without a bracket: lane 0 writes the miss)
+        bool hit = false;
+        const unsigned long long bracket = __ballot(lane < 63 && D < lev && lev <= Dn);
+        if (bracket) {
+            const int k = __builtin_amdgcn_readfirstlane(__ffsll((long long)bracket) - 1);
+            const float a = read_lane(tk, k), b = read_lane(tk, k + 1);
+            const float Da = read_lane(D, k), Db = read_lane(D, k + 1);
+            const float fstep = (b - a) / 63.f;
+            const float u = lane == 0 ? a : lane == 63 ? b : a + (float)lane * fstep;
+            float F = wave_density(g, slot_map, records, ids, ranges, r2, ecut, lane > 0 && lane < 63, ox + u * vx, oy + u * vy,
+                                   oz + u * vz);
+            F = lane == 0 ? Da : lane == 63 ? Db : F;
+            const float un = __shfl_down(u, 1), Fn = __shfl_down(F, 1);
+            const unsigned long long fine = __ballot(lane < 63 && F < lev && lev <= Fn);
+            if (fine) {                                    // (always: F_0 < lev <= F_63)
+                hit = true;
+                hit_lane = __builtin_amdgcn_readfirstlane(__ffsll((long long)fine) - 1);
+                t = u + (un - u) * ((lev - F) / (Fn - F));
+            }
+        }
+        if (lane == hit_lane) {
+            t_out[(int64_t)l * M + ray] = t;
+            hit_out[(int64_t)l * M + ray] = hit ? 1 : 0;
+        }
     }
 }
 
@@ -476,5 +574,24 @@ extern "C" int misplat_density_query(const misplat_tsdf_grid* grid, const int32_
                                                            //  every unit is then unallocated and no list is read)
     hipLaunchKernelGGL(density_query_kernel, dim3(blocks(n_points, 256)), dim3(256), 0, (hipStream_t)stream, g, slot_map, records,
                        ids_sorted, ranges, cutoff, points, n_points, values, (int)n_channels, density, grad, dominant, values_out);
+    return launched();
+}
+
+extern "C" int misplat_density_raycast(const misplat_tsdf_grid* grid, const int32_t* slot_map, const float* records,
+                                       const int32_t* ids_sorted, const int32_t* ranges, float cutoff, const float* origins,
+                                       const float* dirs, const float* t0, const float* t1, int64_t n_rays, float level0,
+                                       float level1, float level2, float level3, int32_t n_levels, float* t_out, uint8_t* hit_out,
+                                       misplat_stream_t stream) {
+    Grid g;
+    int64_t n_map;
+    if (!make_grid(grid, g, n_map) || n_rays < 0 || n_rays >= (1ll << 31) || !cutoff_ok(cutoff) || n_levels < 1 || n_levels > 4)
+        return MISPLAT_EINVAL;
+    const Levels levels = {{level0, level1, level2, level3}};
+    for (int l = 0; l < n_levels; l++)
+        if (!(levels.v[l] > 0.f && levels.v[l] < __builtin_inff())) return MISPLAT_EINVAL;
+    if (n_rays == 0) return MISPLAT_OK;
+    if (!slot_map || !origins || !dirs || !t0 || !t1 || !t_out || !hit_out) return MISPLAT_EINVAL;   // (records / ids / ranges: as query)
+    hipLaunchKernelGGL(density_raycast_kernel, dim3(blocks(n_rays, 4)), dim3(256), 0, (hipStream_t)stream, g, slot_map, records,
+                       ids_sorted, ranges, cutoff, origins, dirs, t0, t1, n_rays, levels, (int)n_levels, t_out, hit_out);
     return launched();
 }

@@ -1,6 +1,6 @@
 // meshclean.hip -- mesh finishing: the edge table of a triangle mesh and what reads it (edge
-// statistics, edge-connected components, boundary loops), and the RANSAC plane fit (hypotheses, inlier counts, the fp64
-// moments of the refit).
+// statistics, edge-connected components, boundary loops), the RANSAC plane fit (hypotheses, inlier counts, the fp64
+// moments of the refit), and Laplacian smoothing over a sorted CSR of the directed edges.
 //
 // Semantics: tests/meshclean_restatement.py is the oracle.  Compiled with -ffp-contract=off: every fp32 expression is
 // evaluated in the written order.  Integer atomics only; every fp64 sum runs in a fixed order; two runs are bitwise equal.
@@ -15,6 +15,7 @@
 #include "misplat.h"
 #include "internal.h"
 #include "wgprims.h"
+#include "radixsort.h"
 #include "unionfind.h"
 #include "hashmix.h"
 
@@ -376,8 +377,58 @@ __global__ __launch_bounds__(256) void moment_cov_kernel(const float* __restrict
     block_sums<6>(x, part + 6 * (int64_t)blockIdx.x);
 }
 
+// ------------------------------------------------------------------------------------------------------- smoothing
+// Laplacian smoothing.  The directed edges of all corners, both ways, as (key = target, value =
+// source): sorted by target, then stably by source, they form a CSR over the sources with every row ascending in its target.
+__global__ __launch_bounds__(256) void smooth_edges_kernel(const int32_t* __restrict__ tri, int64_t T, int32_t* __restrict__ tgt,
+                                                           int32_t* __restrict__ src) {
+    const int64_t h = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (h >= 3 * T) return;
+    const int64_t f = h / 3;
+    int32_t a, b;
+    corner_edge(tri, f, (int)(h - 3 * f), a, b);
+    tgt[2 * h] = b; src[2 * h] = a;
+    tgt[2 * h + 1] = a; src[2 * h + 1] = b;
+}
+
+// rows[2 i], rows[2 i + 1] = vertex i's part of the sorted edges (zeroed by the caller: a vertex without an edge keeps 0, 0)
+__global__ __launch_bounds__(256) void smooth_rows_kernel(const int32_t* __restrict__ src, int64_t E, int32_t* __restrict__ rows) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= E) return;
+    const int32_t s = src[e];
+    if (e == 0 || src[e - 1] != s) rows[2 * (int64_t)s] = (int32_t)e;
+    if (e == E - 1 || src[e + 1] != s) rows[2 * (int64_t)s + 1] = (int32_t)(e + 1);
+}
+
+// One lane per (vertex i, channel c) of values [M, D]: out = x + lam (sum_j w_ij x_j / sum_j w_ij - x) over the distinct
+// neighbours j != i in ascending order, w_ij = 1 / (|p_i - p_j| + 1e-12) from the positions pos; fp64 throughout in this one
+// order, stored fp32.  A repeated edge is met once (the row is sorted: a repeat follows its twin); no neighbour: unchanged.
+__global__ __launch_bounds__(256) void smooth_gather_kernel(const float* __restrict__ pos, int64_t M, const int32_t* __restrict__ rows,
+                                                            const int32_t* __restrict__ tgt, const float* __restrict__ values, int D,
+                                                            double lam, float* __restrict__ out) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= M * D) return;
+    const int64_t i = idx / D;
+    const int c = (int)(idx - i * D);
+    const double px = (double)pos[3 * i], py = (double)pos[3 * i + 1], pz = (double)pos[3 * i + 2];
+    double W = 0.0, S = 0.0;
+    int32_t prev = -1;
+    for (int32_t e = rows[2 * i]; e < rows[2 * i + 1]; e++) {
+        const int32_t j = tgt[e];
+        if (j == prev || j == (int32_t)i) continue;
+        prev = j;
+        const double dx = (double)pos[3 * (int64_t)j] - px, dy = (double)pos[3 * (int64_t)j + 1] - py,
+                     dz = (double)pos[3 * (int64_t)j + 2] - pz;
+        const double w = 1.0 / (sqrt((dx * dx + dy * dy) + dz * dz) + 1e-12);
+        W += w;
+        S += w * (double)values[(int64_t)j * D + c];
+    }
+    const double x = (double)values[idx];
+    out[idx] = W > 0.0 ? (float)(x + lam * (S / W - x)) : values[idx];
+}
+
 // ------------------------------------------------------------------------------------------------------- workspace
-enum { kKindStats = 0, kKindComponents = 1, kKindHoles = 2, kKindMoments = 3 };
+enum { kKindStats = 0, kKindComponents = 1, kKindHoles = 2, kKindMoments = 3, kKindSmooth = 4 };
 
 inline int64_t edge_capacity(int64_t T) {
     int64_t cap = 64;
@@ -392,6 +443,8 @@ struct Work {
     int32_t *cnt, *face, *scr;
     double *part, *sum;
     int32_t *parent, *size, *root, *keep, *rank, *flag, *pos, *eroot;
+    int32_t *ka, *va, *kb, *vb, *rows;    // smoothing: the two pairs of the sort over the 6 T directed edges, the CSR rows [2 M]
+    SortBufs sort;
 };
 
 // M vertices, T triangles (mesh kinds) or N points (kKindMoments, passed as M)
@@ -399,6 +452,17 @@ inline Work carve(Carver& c, int64_t M, int64_t T, int kind) {
     Work W = {};
     if (kind == kKindMoments) {
         W.part = c.take<double>(6 * ((M + 255) / 256 + 1));
+        return W;
+    }
+    if (kind == kKindSmooth) {                             // (no edge table: the sorted directed edges serve)
+        const int64_t E = 6 * T;
+        W.ka = c.take<int32_t>(E);
+        W.va = c.take<int32_t>(E);
+        W.kb = c.take<int32_t>(E);
+        W.vb = c.take<int32_t>(E);
+        W.rows = c.take<int32_t>(2 * M);
+        W.scr = take_scan(c, 256 * ((E + kTile - 1) / kTile) + 1);
+        W.sort = take_sort(c, E);
         return W;
     }
     W.cap = edge_capacity(T);
@@ -432,6 +496,8 @@ inline bool mesh_ok(int64_t M, int64_t T) { return M >= 0 && M < (1ll << 31) && 
 // the calls that number the 3 T corners (or the edges) in int32
 inline bool corners_ok(int64_t T) { return 3 * T < (1ll << 31); }
 inline bool cloud_ok(int64_t N) { return N >= 0 && N < (1ll << 30); }
+// smoothing sorts the 6 T directed edges
+inline bool smooth_ok(int64_t T) { return 6 * T < (1ll << 31) - kTile; }
 
 inline EdgeTable build_edges(const int32_t* tri, int64_t T, const Work& W, hipStream_t s) {
     EdgeTable E{W.keys, W.cnt, W.face, (unsigned long long)(W.cap - 1)};
@@ -445,10 +511,11 @@ inline EdgeTable build_edges(const int32_t* tri, int64_t T, const Work& W, hipSt
 }  // namespace
 
 extern "C" int64_t misplat_meshclean_workspace(int64_t n_vertices, int64_t n_triangles, int32_t kind) {
-    if (kind < kKindStats || kind > kKindMoments) return -1;
+    if (kind < kKindStats || kind > kKindSmooth) return -1;
     if (kind == kKindMoments ? !cloud_ok(n_vertices)
                              : !mesh_ok(n_vertices, n_triangles) || (kind != kKindComponents && !corners_ok(n_triangles)))
         return -1;
+    if (kind == kKindSmooth && !smooth_ok(n_triangles)) return -1;
     Carver c{nullptr};
     carve(c, n_vertices, kind == kKindMoments ? 0 : n_triangles, kind);
     return c.o;
@@ -538,6 +605,43 @@ extern "C" int misplat_meshclean_segment_sum(const float* values, const int32_t*
     if (n_segments == 0) return MISPLAT_OK;
     hipLaunchKernelGGL(segment_sum_kernel, dim3(blocks(n_segments, 256)), dim3(256), 0, (hipStream_t)stream, values, order, offsets,
                        n_segments, out);
+    return launched();
+}
+
+extern "C" int misplat_meshclean_smooth(const float* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles,
+                                        const float* attributes, int32_t n_channels, int32_t iterations, double lam,
+                                        void* workspace, int64_t workspace_bytes, float* vertices_out, float* attributes_out,
+                                        float* vertices_tmp, float* attributes_tmp, misplat_stream_t stream) {
+    const int64_t M = n_vertices, T = n_triangles, E = 6 * T;
+    const int D = n_channels;
+    if (!mesh_ok(M, T) || !corners_ok(T) || !smooth_ok(T) || M < 1 || T < 1 || D < 0 || D > 4096 || M * (D > 3 ? D : 3) >= (1ll << 39) ||
+        iterations < 1 || !(lam == lam) || !vertices || !triangles || !workspace || !vertices_out ||
+        (D > 0 && (!attributes || !attributes_out)) || (iterations > 1 && (!vertices_tmp || (D > 0 && !attributes_tmp))))
+        return MISPLAT_EINVAL;
+    Carver c{(char*)workspace};
+    const Work W = carve(c, M, T, kKindSmooth);
+    if (workspace_bytes < c.o) return MISPLAT_EWORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    int32_t *ka = W.ka, *va = W.va, *kb = W.kb, *vb = W.vb;
+    hipLaunchKernelGGL(smooth_edges_kernel, dim3(blocks(3 * T, 256)), dim3(256), 0, s, triangles, T, ka, va);
+    const int passes = radix_passes(M - 1);
+    radix_sort(ka, va, kb, vb, E, passes, W.sort, W.scr, s);           // by target; (ka, va) name the sorted pair
+    radix_sort(va, ka, vb, kb, E, passes, W.sort, W.scr, s);           // stably by source: va the sources, ka the targets
+    misplat_internal::fill_bytes(W.rows, 8 * (size_t)M, 0u, s);
+    hipLaunchKernelGGL(smooth_rows_kernel, dim3(blocks(E, 256)), dim3(256), 0, s, (const int32_t*)va, E, W.rows);
+    const float *pos = vertices, *att = attributes;
+    for (int it = 0; it < iterations; it++) {
+        const bool last_parity = (iterations - 1 - it) % 2 == 0;        // the last iteration writes the outputs
+        float* pos_to = last_parity ? vertices_out : vertices_tmp;
+        float* att_to = last_parity ? attributes_out : attributes_tmp;
+        hipLaunchKernelGGL(smooth_gather_kernel, dim3(blocks(M * 3, 256)), dim3(256), 0, s, pos, M, (const int32_t*)W.rows,
+                           (const int32_t*)ka, pos, 3, lam, pos_to);
+        if (D > 0)
+            hipLaunchKernelGGL(smooth_gather_kernel, dim3(blocks(M * D, 256)), dim3(256), 0, s, pos, M, (const int32_t*)W.rows,
+                               (const int32_t*)ka, att, D, lam, att_to);
+        pos = pos_to;
+        att = att_to;
+    }
     return launched();
 }
 

@@ -9,8 +9,10 @@ published definition (SuGaR's density): with ``A = diag(1 / s) R(q)^T`` and ``m_
 
 (continuous at the cut-off ``r``).  ``DensityField`` evaluates ``d`` on the TSDF volume's lattice (voxel ``g`` centred at
 ``(g + 0.5) voxel_size``, units of 16^3 voxels, only the units a Gaussian reaches allocated), answers point queries from the
-same per-unit lists and extracts level sets through the TSDF volume's marching cubes.  Everything stays on the device; there is
-no CPU fallback.
+same per-unit lists and extracts level sets through the TSDF volume's marching cubes.  ``DensityField.raycast`` and
+``level_surface_points`` are the level-set search along rays that ``LevelSetExtractor`` asks of
+``model.compute_level_surface_points`` (a dn-splatter / SuGaR method the reference's models lack).
+Everything stays on the device; there is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -30,6 +32,7 @@ from .unitvolume import MAX_UNITS, UNIT, UNIT_VOXELS, Grid, _unit_range, make_gr
 REC = 16                             # floats per record (include/misplat.h MISPLAT_DENSITY_REC)
 MAX_CHANNELS = 16                    # channels of query's values (MISPLAT_DENSITY_MAX_CHANNELS)
 MAX_PAIRS = (1 << 31) - 4096
+MAX_LEVELS = 4                       # levels of one raycast (passed to the kernel by value)
 
 
 def _scalars(name: str, voxel_size, cutoff, min_opacity) -> Tuple[float, float, float]:
@@ -82,6 +85,37 @@ def _values(name: str, values, n: int) -> Optional[Tensor]:
     if not 1 <= values.shape[1] <= MAX_CHANNELS:
         raise ValueError(f"{name}: values must have 1..{MAX_CHANNELS} channels, got D = {values.shape[1]}")
     return values
+
+
+def _rays(name: str, origins, dirs, t_near, t_far) -> int:
+    for label, t in (("origins", origins), ("dirs", dirs)):
+        if not isinstance(t, Tensor) or not t.is_floating_point() or t.dim() != 2 or t.shape[1] != 3:
+            raise ValueError(f"{name}: {label} must be a floating-point tensor [M,3], got "
+                             f"{tuple(t.shape) if isinstance(t, Tensor) else type(t).__name__}")
+    m = int(origins.shape[0])
+    if dirs.shape[0] != m:
+        raise ValueError(f"{name}: dirs must be [{m},3], got {tuple(dirs.shape)}")
+    for label, t in (("t_near", t_near), ("t_far", t_far)):
+        if not isinstance(t, Tensor) or not t.is_floating_point() or tuple(t.shape) != (m,):
+            raise ValueError(f"{name}: {label} must be a floating-point tensor [{m}], got "
+                             f"{tuple(t.shape) if isinstance(t, Tensor) else type(t).__name__}")
+    if m >= 1 << 31:
+        raise ValueError(f"{name}: at most 2^31 - 1 rays")
+    return m
+
+
+def _levels(name: str, levels) -> Tuple[float, ...]:
+    try:
+        lv = tuple(float(x) for x in levels)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name}: levels must be a sequence of numbers, got {levels!r}") from None
+    if not 1 <= len(lv) <= MAX_LEVELS:
+        raise ValueError(f"{name}: 1..{MAX_LEVELS} levels, got {len(lv)}")
+    for x in lv:
+        x32 = float(torch.tensor(x, dtype=torch.float32)) if math.isfinite(x) else x
+        if not (x > 0 and math.isfinite(x) and x32 > 0 and math.isfinite(x32)):
+            raise ValueError(f"{name}: every level must be a finite number > 0 (in fp32), got {x!r}")
+    return lv
 
 
 class _Stages:
@@ -267,6 +301,32 @@ class DensityField:
                                            ptr(out["dominant"]), ptr(out["values"]), stream_ptr()), "misplat_density_query")
         return out
 
+    def raycast(self, origins: Tensor, dirs: Tensor, t_near: Tensor, t_far: Tensor, levels) -> Dict[str, Tensor]:
+        """The level-set search along rays: ``{"t": [L,M] fp32, "hit": [L,M] bool}`` for the rays
+        ``origins + t dirs`` (``dirs`` used as given, not normalised) over ``t_near <= t <= t_far`` and 1..4 ``levels``, each
+        finite and > 0.  Per ray: the density at 64 evenly spaced samples (each exactly what ``query`` gives there); per level the
+        first pair of neighbours with ``d_k < level <= d_{k+1}``, 64 more samples inside it, and the linear interpolation in the
+        first such pair of those.  A ray with no such pair, with a non-finite input or with ``t_far <= t_near`` misses (``hit``
+        False, ``t`` 0); a ray that starts inside a level hits only after the density has dipped below it.  One wave per ray:
+        a unit's list is read once for all the samples in it.  Two calls are bitwise equal."""
+        name = "DensityField.raycast"
+        M = _rays(name, origins, dirs, t_near, t_far)
+        lv = _levels(name, levels)
+        require_gpu(origins, dirs, t_near, t_far)
+        dev = self.device
+        t = torch.zeros((len(lv), M), dtype=torch.float32, device=dev)
+        hit = torch.zeros((len(lv), M), dtype=torch.uint8, device=dev)
+        if M == 0 or self.n_units == 0:
+            return {"t": t, "hit": hit.view(torch.bool)}
+        o32, v32, a32, b32 = _prep(origins), _prep(dirs), _prep(t_near), _prep(t_far)
+        grid = self._grid()
+        lv4 = lv + (lv[-1],) * (MAX_LEVELS - len(lv))
+        check(load().misplat_density_raycast(C.byref(grid), ptr(self._slot_map), ptr(self._records), ptr(self._ids),
+                                             ptr(self._ranges), C.c_float(self.cutoff), ptr(o32), ptr(v32), ptr(a32), ptr(b32),
+                                             C.c_int64(M), C.c_float(lv4[0]), C.c_float(lv4[1]), C.c_float(lv4[2]), C.c_float(lv4[3]),
+                                             len(lv), ptr(t), ptr(hit), stream_ptr()), "misplat_density_raycast")
+        return {"t": t, "hit": hit.view(torch.bool)}
+
     def extract_mesh(self, iso: float = 0.5, values: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Optional[Tensor]]:
         """Marching cubes of ``iso - d`` through the TSDF volume's extraction (csrc/tsdf.hip), in its deterministic order:
         ``(vertices [M,3] fp32, triangles [T,3] int32, values at the vertices [M,D] or None)``.  The field is negative inside, so
@@ -297,6 +357,30 @@ class DensityField:
         vertices, triangles = mesh[:2]                             # (the pool carries no colour)
         del mesh
         return vertices, triangles, None if values is None else self.query(vertices, values)["values"]
+
+
+def level_surface_points(field: DensityField, origins: Tensor, dirs: Tensor, t_near: Tensor, t_far: Tensor, levels,
+                         values: Optional[Tensor] = None) -> Dict[float, Dict[str, Optional[Tensor]]]:
+    """What the reference's ``LevelSetExtractor`` asks of ``model.compute_level_surface_points`` (mesh.py:1110), on the device:
+    ``field.raycast``, the hit points ``origins + t dirs`` (a multiply, then an add, in fp32) and one ``field.query(points,
+    values)`` per level.  ``{level: {"points" [P,3], "t" [P], "ray_ids" [P] int64, "density", "grad", "dominant", "values"}}``,
+    the rays of a level in ascending order.  One host read per level (the number of hits)."""
+    name = "level_surface_points"
+    if not isinstance(field, DensityField):
+        raise ValueError(f"{name}: field must be a DensityField, got {type(field).__name__}")
+    _rays(name, origins, dirs, t_near, t_far)
+    lv = _levels(name, levels)
+    values = _values(name, values, field.n_gauss)
+    cast = field.raycast(origins, dirs, t_near, t_far, lv)
+    o32, v32 = _prep(origins), _prep(dirs)
+    out: Dict[float, Dict[str, Optional[Tensor]]] = {}
+    for i, level in enumerate(lv):
+        ray_ids = torch.nonzero(cast["hit"][i])[:, 0]
+        t = cast["t"][i][ray_ids]
+        points = o32[ray_ids] + t[:, None] * v32[ray_ids]
+        res = field.query(points, values)
+        out[level] = {"points": points, "t": t, "ray_ids": ray_ids, **res}
+    return out
 
 
 def gaussian_density(points: Tensor, means: Tensor, quats: Tensor, scales: Tensor, opacities: Tensor,
@@ -335,4 +419,5 @@ def _at_points(name, points, means, quats, scales, opacities, voxel_size, cutoff
     return field.query(points)
 
 
-__all__ = ["DensityField", "gaussian_density", "gaussian_density_grad", "MAX_CHANNELS", "MisplatError"]
+__all__ = ["DensityField", "gaussian_density", "gaussian_density_grad", "level_surface_points", "MAX_CHANNELS", "MAX_LEVELS",
+           "MisplatError"]

@@ -5,7 +5,8 @@ MeshLib (``clean_repair_mesh``, mesh.py:227-407: drop floating components, measu
 floor with Open3D (``align_geometry_floor``, mesh.py:410-515: sample the surface, RANSAC plane, rotate, translate).  Here the
 same steps run on device tensors: the edge table of the welded mesh, the edge-connected components, the boundary loops, the
 RANSAC hypotheses, their inlier counts and the refit's moments are HIP kernels; the rest is thin torch on the device and a
-3x3 eigenproblem on the host.  There is no CPU fallback.
+3x3 eigenproblem on the host.  ``smooth_laplacian`` is the Laplacian smoothing that ends the reference's ``LevelSetExtractor``
+(mesh.py:1217-1223, Open3D's ``filter_smooth_laplacian``).  There is no CPU fallback.
 
 What is NOT restated: MeshLib's ``fillHoleNicely`` (and the subdivision and smoothing of the standard fill).  ``fill_holes``
 is the reference's *fallback*, ``fillHoleTrivially``: one new vertex per hole and a fan of triangles to it.  Nothing about it
@@ -27,7 +28,7 @@ from .pointcloud import _cloud, _positive32
 # Hypotheses per workgroup of the inlier count: 8, 16 or 32.  It changes no result (DESIGN.md section 18.3 holds the measurement).
 PLANE_TILE = 16
 
-_STATS, _COMPONENTS, _HOLES, _MOMENTS = range(4)
+_STATS, _COMPONENTS, _HOLES, _MOMENTS, _SMOOTH = range(5)
 MAX_PLANES = 1 << 24
 
 
@@ -238,6 +239,48 @@ def fill_holes(vertices: Tensor, triangles: Tensor, max_hole_size: float = 3.0, 
     return outs[0], torch.cat([t.long(), fans]).to(triangles.dtype), tuple(outs[1:]), n_fill
 
 
+# -------------------------------------------------------------------------------------------------------- smoothing
+def smooth_laplacian(vertices: Tensor, triangles: Tensor, iterations: int = 1, lam: float = 0.5, attributes: Sequence[Tensor] = ()
+                     ) -> Tuple[Tensor, Tuple[Tensor, ...]]:
+    """Open3D's ``filter_smooth_laplacian`` restated [UNVERIFIED-UPSTREAM], what the reference's ``LevelSetExtractor`` ends
+    with (mesh.py:1217-1223): ``(vertices', attributes')``.  Per iteration, from the previous iteration's positions: with
+    ``N(i)`` the distinct vertices that share a triangle edge with ``i`` and ``w_ij = 1 / (|x_i - x_j| + 1e-12)``,
+    ``x_i' = x_i + lam (sum_j w_ij x_j / sum_j w_ij - x_i)``; every row of ``attributes`` ([M,D] float32) is smoothed with the
+    same weights; a vertex without a neighbour is unchanged.  The neighbours are gathered in ascending order from a CSR built
+    once per call (the directed edges sorted by source, then target); sums in fp64 in that order, stores in fp32: two runs are
+    bitwise equal."""
+    name = "smooth_laplacian"
+    v, t = _mesh(name, vertices, triangles)
+    attributes = _attributes(name, attributes, v.shape[0], True)
+    if not isinstance(iterations, int) or isinstance(iterations, bool) or iterations < 0:
+        raise ValueError(f"{name}: iterations must be a non-negative integer, got {iterations!r}")
+    try:
+        lam = float(lam)
+    except (TypeError, ValueError):
+        lam = math.nan
+    if not math.isfinite(lam):
+        raise ValueError(f"{name}: lam must be a finite number")
+    if 6 * t.shape[0] >= (1 << 31) - 4096:
+        raise ValueError(f"{name}: {t.shape[0]} triangles are beyond the library's limits (6 T < 2^31 - 4096)")
+    require_gpu(vertices, triangles, *attributes)
+    attributes = tuple(_prep(a) for a in attributes)
+    m, n = v.shape[0], t.shape[0]
+    if iterations == 0 or m == 0 or n == 0:
+        return v.clone(), tuple(a.clone() for a in attributes)
+    dev = v.device
+    widths = [a.shape[1] for a in attributes]
+    d = sum(widths)
+    att = torch.cat(attributes, 1).contiguous() if d else None
+    v_out, a_out = torch.empty_like(v), None if att is None else torch.empty_like(att)
+    v_tmp = torch.empty_like(v) if iterations > 1 else None
+    a_tmp = torch.empty_like(att) if iterations > 1 and att is not None else None
+    ws = _workspace(m, n, _SMOOTH, dev)
+    check(load().misplat_meshclean_smooth(ptr(v), C.c_int64(m), ptr(t), C.c_int64(n), ptr(att), d, iterations, C.c_double(lam),
+                                          ptr(ws), C.c_int64(ws.numel()), ptr(v_out), ptr(a_out), ptr(v_tmp), ptr(a_tmp),
+                                          stream_ptr()), "misplat_meshclean_smooth")
+    return v_out, (tuple(x.contiguous() for x in torch.split(a_out, widths, 1)) if d else ())
+
+
 # ------------------------------------------------------------------------------------------------------------ plane
 def _threshold(name: str, v) -> float:
     return _positive32(name, "distance_threshold", v)
@@ -444,4 +487,5 @@ def align_floor(points_or_mesh: Union[Tensor, Tuple[Tensor, Tensor]], dist_thres
 
 
 __all__ = ["mesh_edge_stats", "mesh_components", "filter_mesh_components", "mesh_holes", "fill_holes", "plane_inlier_counts",
-           "ransac_planes", "segment_plane", "sample_surface", "floor_rotation", "apply_rigid", "align_floor", "MisplatError"]
+           "ransac_planes", "segment_plane", "sample_surface", "floor_rotation", "apply_rigid", "align_floor", "smooth_laplacian",
+           "MisplatError"]

@@ -840,6 +840,155 @@ class RadegsModel(nn.Module):
         vertices, triangles, vcol = field.extract_mesh(isosurface_threshold, values=colors.contiguous())
         return vertices, triangles, vcol
 
+    # ------------------------------------------------------------------ level-set surface points
+    _NORMAL_MODES = ("analytical", "closest_gaussian", "average")
+
+    @staticmethod
+    def _level_set_args(name: str, cameras, total_points, surface_levels, return_normal, search_radius, voxel_size) -> tuple:
+        from .density import _levels, _scalars
+        cameras = list(cameras)
+        if not cameras:
+            raise ValueError(f"{name}: no cameras")
+        if return_normal not in RadegsModel._NORMAL_MODES:
+            raise ValueError(f"{name}: return_normal must be one of {RadegsModel._NORMAL_MODES}, got {return_normal!r}")
+        if not isinstance(total_points, int) or isinstance(total_points, bool) or total_points < 0:
+            raise ValueError(f"{name}: total_points must be a non-negative integer, got {total_points!r}")
+        levels = _levels(name, surface_levels)
+        h = _scalars(name, voxel_size, 3.0, 0.0)[0]
+        radius = 8.0 * h if search_radius is None else search_radius
+        try:
+            radius = float(radius)
+        except (TypeError, ValueError):
+            radius = math.nan
+        if not (radius > 0 and math.isfinite(radius)):
+            raise ValueError(f"{name}: search_radius must be a finite number > 0, got {search_radius!r}")
+        return cameras, levels, radius
+
+    @torch.no_grad()
+    def level_set_points(self, cameras: Sequence, voxel_size: float, total_points: int = 2_000_000,
+                         surface_levels: Sequence[float] = (0.1, 0.3, 0.5), return_normal: str = "closest_gaussian",
+                         depth_name: str = "depth", search_radius: Optional[float] = None, masks=None, obb_box=None,
+                         outlier_removal: bool = True, nb_neighbors: int = 20, std_ratio: float = 20.0, seed: int = 0,
+                         batch_size: int = 4, cutoff: float = 3.0, min_opacity: float = 1.0 / 255.0) -> Dict[float, Dict[str, Tensor]]:
+        """The cloud of the reference's ``LevelSetExtractor.main`` (mesh.py:1077-1144, cleaned as :1171) on the device:
+        ``{level: {"points", "normals", "colors", "frame_ids", "pixel_ids"}}``.  One ``density_field(voxel_size, ...,
+        obb_box=obb_box)``; ``samples_per_frame = (total_points + V) // V``; per batch ``render_views``, the candidates
+        ``accumulation > 0`` with a finite positive ``depth_name`` (and a true mask), ``depthcloud.sample_pixels`` with
+        ``frame_offset`` = the batch's first frame (so ``batch_size`` changes no result) and ``backproject`` to the depth point
+        ``P``.  The ray of a sample starts at the camera centre ``o``, ``v = (P - o) / |P - o|``, and is searched over
+        ``[max(t_c - search_radius, 0), t_c + search_radius]`` around ``t_c = |P - o|`` (``search_radius`` None: 8 voxels,
+        half a unit) by ``density.level_surface_points`` with the kept Gaussians' ``colors`` and normals as values.
+        ``return_normal``: ``"analytical"`` = ``-grad / |grad|``; ``"closest_gaussian"`` = the dominant Gaussian's normal, flipped
+        where ``n . v > 0``; ``"average"`` = the Gaussians' normals, each first flipped to face the view's camera centre, blended
+        by the terms and normalised (one query per frame), flipped where the blend still has ``n . v > 0``.  A normal of zero
+        length drops its point.  Then the crop ``obb_box.within``, the batches concatenated and, per level,
+        ``remove_statistical_outlier(nb_neighbors, std_ratio)``."""
+        from .density import level_surface_points
+        from .depthcloud import backproject, sample_pixels
+        from .pointcloud import remove_statistical_outlier
+        name = "level_set_points"
+        cameras, levels, radius = self._level_set_args(name, cameras, total_points, surface_levels, return_normal, search_radius,
+                                                       voxel_size)
+        n_views = len(cameras)
+        samples_per_frame = (total_points + n_views) // n_views
+        field = self.density_field(voxel_size, cutoff, min_opacity, obb_box=obb_box)
+        pick = (lambda x: x[field.kept]) if field.kept is not None else (lambda x: x)
+        colors = pick(self.colors.detach().float())
+        normals = pick(self.normals.detach().float())
+        means = pick(self.means.detach().float())
+        if masks is not None:
+            masks = torch.as_tensor(masks).to(self.device)
+            if masks.shape[0] != n_views:
+                raise ValueError(f"{name}: one mask per camera")
+        c2w, intr = self._camera_poses(cameras, self.device)
+        bs = max(1, int(batch_size))
+        keys = ("points", "normals", "colors", "frame_ids", "pixel_ids")
+        parts: Dict[float, Dict[str, List[Tensor]]] = {lv: {k: [] for k in keys} for lv in levels}
+        for b in range(0, n_views, bs):
+            maps = self.render_views(cameras[b:b + bs], batch_size=bs, crop_box=obb_box)
+            if depth_name not in maps:
+                raise KeyError(f"{name}: depth_name {depth_name!r} is not among the rendered maps {sorted(maps)}")
+            depth = maps[depth_name]
+            cand = (maps["accumulation"] > 0) & torch.isfinite(depth) & (depth > 0)
+            if masks is not None:
+                cand &= masks[b:b + bs].reshape(cand.shape).bool()
+            f, p, _ = sample_pixels(cand.squeeze(-1), samples_per_frame, seed=seed, frame_offset=b)
+            P = backproject(depth, maps["rgb"], None, c2w[b:b + bs], intr[b:b + bs], f, p)[0]
+            del maps, depth, cand
+            fl = f.long()
+            o = c2w[b:b + bs][:, :, 3].contiguous()[fl]
+            diff = P - o
+            t_c = torch.linalg.norm(diff, dim=1)
+            v = diff / t_c[:, None]
+            t0, t1 = torch.clamp(t_c - radius, min=0.0), t_c + radius
+            # ("average" blends per-view normals: one search per frame; the rays of a frame are contiguous)
+            groups = [torch.nonzero(fl == i)[:, 0] for i in range(min(bs, n_views - b))] if return_normal == "average" else [None]
+            for i, sel in enumerate(groups):
+                take = (lambda x: x) if sel is None else (lambda x, sel=sel: x[sel])
+                nrm = normals
+                if sel is not None:
+                    away = ((means - c2w[b + i, :, 3]) * normals).sum(1) > 0
+                    nrm = torch.where(away[:, None], -normals, normals)
+                found = level_surface_points(field, take(o), take(v), take(t0), take(t1), levels,
+                                             values=torch.cat([colors, nrm], 1).contiguous())
+                for lv in levels:
+                    r = found[lv]
+                    rays = r["ray_ids"]
+                    vv = take(v)[rays]
+                    if return_normal == "analytical":
+                        n = -r["grad"]
+                    elif return_normal == "closest_gaussian":
+                        n = normals[r["dominant"].long().clamp(min=0)]
+                    else:
+                        n = r["values"][:, 3:6]
+                    length = torch.linalg.norm(n, dim=1)
+                    n = n / length[:, None]
+                    if return_normal != "analytical":
+                        n = torch.where(((n * vv).sum(1) > 0)[:, None], -n, n)
+                    keep = (length > 0) & torch.isfinite(n).all(1) & (r["dominant"] >= 0)
+                    if obb_box is not None:
+                        keep &= obb_box.within(r["points"]).reshape(-1)
+                    out = {"points": r["points"], "normals": n, "colors": r["values"][:, 0:3].contiguous(),
+                           "frame_ids": take(fl)[rays] + b, "pixel_ids": take(p)[rays]}
+                    for k in keys:
+                        parts[lv][k].append(out[k][keep])
+        cloud: Dict[float, Dict[str, Tensor]] = {}
+        for lv in levels:
+            c = {k: torch.cat(parts[lv][k], dim=0) for k in keys}
+            if outlier_removal and c["points"].shape[0] > 0:
+                pts, ind = remove_statistical_outlier(c["points"], nb_neighbors, std_ratio)
+                c = {k: (pts if k == "points" else c[k][ind]) for k in keys}
+            cloud[lv] = c
+        return cloud
+
+    @torch.no_grad()
+    def level_set_mesh(self, cameras: Sequence, voxel_size: float, surface_level: float = 0.3, poisson_depth: int = 9,
+                       trim_quantile: float = 0.01, smooth_iterations: int = 2, **points_kwargs
+                       ) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+        """What the reference's ``LevelSetExtractor.main`` ends in (mesh.py:1194-1223) on the device: the cloud of
+        ``level_set_points(cameras, voxel_size, surface_levels=(surface_level,), **points_kwargs)``,
+        ``poisson.poisson_reconstruct`` at ``poisson_depth``, ``poisson.poisson_trim(quantile=trim_quantile)`` and
+        ``meshclean.smooth_laplacian(iterations=smooth_iterations)`` with the colours carried along (the reference calls
+        ``filter_smooth_laplacian`` twice with one iteration each).  Returns ``(vertices [M,3], triangles [T,3] int32, colors
+        [M,3], density [M])``.  The solve is this project's dense-grid restatement, not Open3D's octree solver (DESIGN.md section
+        20)."""
+        from .meshclean import smooth_laplacian
+        from .poisson import poisson_reconstruct, poisson_trim
+        name = "level_set_mesh"
+        if "surface_levels" in points_kwargs:
+            raise ValueError(f"{name}: pass surface_level, not surface_levels")
+        try:
+            level = float(surface_level)
+        except (TypeError, ValueError):
+            raise ValueError(f"{name}: surface_level must be a number, got {surface_level!r}") from None
+        if not isinstance(smooth_iterations, int) or isinstance(smooth_iterations, bool) or smooth_iterations < 0:
+            raise ValueError(f"{name}: smooth_iterations must be a non-negative integer, got {smooth_iterations!r}")
+        cloud = self.level_set_points(cameras, voxel_size, surface_levels=(level,), **points_kwargs)[level]
+        v, t, c, d, _ = poisson_reconstruct(cloud["points"], cloud["normals"], cloud["colors"], depth=poisson_depth)
+        v, t, d, (c,), _ = poisson_trim(v, t, d, quantile=trim_quantile, min_density=None, attributes=(c,))
+        v, (c,) = smooth_laplacian(v, t, smooth_iterations, attributes=(c,))
+        return v, t, c, d
+
     @torch.no_grad()
     def associate_masks(self, cameras: Sequence, composite_masks: Sequence, front_percentage: float = 0.5, num_patches: int = 32,
                         iou_threshold: float = 0.1, bank=None):

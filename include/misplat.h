@@ -814,7 +814,7 @@ int misplat_pointcloud_voxel_mean(const float* values, int64_t n_points, int32_t
  * its workspace: the undirected edges (lo, hi) of all triangles in a hash of capacity the power of two >= max(64, 6 T); an edge
  * (a, a) of a triangle with a repeated corner is ignored.  The oracle is tests/meshclean_restatement.py.  Deterministic
  * (integer atomics only, fp64 sums in a fixed order): two runs are bitwise equal. */
-/* workspace bytes for the call `kind` (0 edge_stats, 1 components, 2 holes: n_vertices, n_triangles; 3 plane_moments:
+/* workspace bytes for the call `kind` (0 edge_stats, 1 components, 2 holes, 4 smooth: n_vertices, n_triangles; 3 plane_moments:
  * n_vertices = the number of points, n_triangles ignored); -1 for sizes the library refuses. */
 int64_t misplat_meshclean_workspace(int64_t n_vertices, int64_t n_triangles, int32_t kind);
 /* counts [3] int32 on the device: undirected edges, boundary edges (exactly one incident (face, corner)), non-manifold edges
@@ -837,6 +837,17 @@ int misplat_meshclean_holes(const float* vertices, int64_t n_vertices, const int
 /* out [L] double: out[l] = the fp64 sum of values[order[e]] over e = offsets[l] .. offsets[l + 1) - 1, in that order. */
 int misplat_meshclean_segment_sum(const float* values, const int32_t* order, const int32_t* offsets, int64_t n_segments,
                                   double* out, misplat_stream_t stream);
+/* Laplacian smoothing: `iterations` >= 1 rounds, each from the round before: with N(i) the distinct
+ * vertices j != i that share a triangle edge with i, in ascending order, and w_ij = 1 / (|x_i - x_j| + 1e-12),
+ * x_i' = x_i + lam (sum_j w_ij x_j / sum_j w_ij - x_i); every row of attributes [M, n_channels] (or NULL with 0 channels) takes
+ * the same weights; a vertex without a neighbour keeps its row.  fp64 sums in that fixed order, fp32 stores.  The CSR of the
+ * neighbours is built once: the 6 T directed edges sorted by (source, target); 6 T < 2^31 - 4096; workspace of kind 4
+ * (misplat_meshclean_workspace).  The result lands in vertices_out / attributes_out; vertices_tmp / attributes_tmp (the same
+ * shapes; may be NULL with one iteration) hold every other round. */
+int misplat_meshclean_smooth(const float* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles,
+                             const float* attributes, int32_t n_channels, int32_t iterations, double lam, void* workspace,
+                             int64_t workspace_bytes, float* vertices_out, float* attributes_out, float* vertices_tmp,
+                             float* attributes_tmp, misplat_stream_t stream);
 /* RANSAC hypotheses over points [N,3] fp32, 3 <= N < 2^30, n_planes <= 2^24.  triples_in NULL: hypothesis i takes three
  * distinct indices from a counter-based hash of (seed, i, draw) and writes them to triples_out [H,3]; else it takes
  * triples_in [H,3] (in range: the caller checks it).  planes [H,4] fp32, 16-byte aligned: the unit normal and offset of the
@@ -1060,6 +1071,15 @@ int misplat_density_query(const misplat_tsdf_grid* grid, const int32_t* slot_map
                           const int32_t* ranges, float cutoff, const float* points, int64_t n_points, const float* values,
                           int32_t n_channels, float* density, float* grad, int32_t* dominant, float* values_out,
                           misplat_stream_t stream);
+/* raycast: per ray (origins, dirs [M,3], used as given; t0, t1 [M]) and level (1 <= n_levels <= 4, each
+ * finite and > 0, passed by value; the levels beyond n_levels are ignored) the first crossing of d from below the level to at
+ * or above it, front to back: 64 samples over [t0, t1], per level 64 more over its bracket, then linear interpolation; d at a
+ * sample is bit for bit what query gives there.  t_out [n_levels, M] fp32 and hit_out [n_levels, M] uint8 (0 / 0 for a miss,
+ * and for a ray with a non-finite input or t1 <= t0).  One launch, one wave per ray. */
+int misplat_density_raycast(const misplat_tsdf_grid* grid, const int32_t* slot_map, const float* records, const int32_t* ids_sorted,
+                            const int32_t* ranges, float cutoff, const float* origins, const float* dirs, const float* t0,
+                            const float* t1, int64_t n_rays, float level0, float level1, float level2, float level3,
+                            int32_t n_levels, float* t_out, uint8_t* hit_out, misplat_stream_t stream);
 
 /* Library identification ("misplat <version> gfx950"). */
 const char* misplat_version(void);
