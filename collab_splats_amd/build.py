@@ -62,6 +62,8 @@ SOURCES = {
     # density.hip: fixed IEEE operation order: the Gaussians' frames, unit ranges and slab tests, hence the unit lists, equal
     # the fp32 restatement (tests/) bit for bit; the accumulation's multiply-adds are written as explicit fma
     "density.hip": ["-ffp-contract=off"],
+    # decimate.hip: the same: quadrics, collapse targets and cost bits (the selection's priority) equal the fp64 restatement (tests/)
+    "decimate.hip": ["-ffp-contract=off"],
 }
 
 

@@ -809,15 +809,21 @@ class RadegsModel(nn.Module):
     @torch.no_grad()
     def marching_cubes_mesh(self, cameras: Optional[Sequence] = None, camera_radius_multiplier: float = 2.0, resolution: int = 512,
                             isosurface_threshold: float = 0.5, voxel_size: Optional[float] = None, obb_box=None,
-                            cutoff: float = 3.0, min_opacity: float = 1.0 / 255.0) -> Tuple[Tensor, Tensor, Tensor]:
+                            cutoff: float = 3.0, min_opacity: float = 1.0 / 255.0,
+                            target_triangles: Optional[int] = None) -> Tuple[Tensor, Tensor, Tensor]:
         """The reference's ``MarchingCubesMesh.main`` (mesh.py:1234-1359) on the device, with no dense grid: the level set
         ``isosurface_threshold`` of the mixture's density.  With ``cameras``: the reference's cube, centred on the world origin,
         half side ``camera_radius_multiplier`` x the largest distance of a camera centre from their mean (:1266-1275), sampled
         at ``h = 2 radius / (resolution - 1)``.  With ``voxel_size`` instead: that ``h`` over the Gaussians' own bounds (the
         box's AABB with ``obb_box``).  Gaussians outside ``obb_box`` are dropped.  Returns ``(vertices [M,3], triangles [T,3]
         int32, colors [M,3])``, the colours ``self.colors`` blended by the Gaussians' terms at the vertex (the reference takes the
-        closest Gaussian's): ready for ``finish_mesh`` and ``tsdf.write_ply``."""
+        closest Gaussian's): ready for ``finish_mesh`` and ``tsdf.write_ply``.  With ``target_triangles`` the mesh is then
+        simplified to at most that many triangles (``decimate.simplify_quadric_decimation``, the colours averaged along), the
+        reference's last step (mesh.py:1350-1352); its default there is 1 000 000, here ``None``: the raw mesh."""
         name = "marching_cubes_mesh"
+        if target_triangles is not None and (not isinstance(target_triangles, int) or isinstance(target_triangles, bool)
+                                             or target_triangles < 0):
+            raise ValueError(f"{name}: target_triangles must be None or a non-negative integer, got {target_triangles!r}")
         bounds = None
         if voxel_size is None:
             if cameras is None:
@@ -838,6 +844,9 @@ class RadegsModel(nn.Module):
         if field.kept is not None:
             colors = colors[field.kept]
         vertices, triangles, vcol = field.extract_mesh(isosurface_threshold, values=colors.contiguous())
+        if target_triangles is not None:
+            from .decimate import simplify_quadric_decimation
+            vertices, triangles, (vcol,), _, _ = simplify_quadric_decimation(vertices, triangles, target_triangles, attributes=(vcol,))
         return vertices, triangles, vcol
 
     # ------------------------------------------------------------------ level-set surface points

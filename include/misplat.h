@@ -865,6 +865,30 @@ int misplat_meshclean_plane_moments(const float* points, int64_t n_points, const
                                     void* workspace, int64_t workspace_bytes, uint8_t* mask, double* moments,
                                     misplat_stream_t stream);
 
+/* ---- quadric-error mesh simplification (csrc/decimate.hip) ---------------------------------------------
+ * Edge collapses in rounds over state the caller owns: vertices [M,3] fp32, triangles [T,3] int32 (every index in 0 .. M - 1),
+ * alive [T] int32 (1 for a live face; no live face has a repeated corner), quadrics [M,10] fp64, into [M] int32 (-1, or the
+ * vertex a dead vertex collapsed into), attributes [M, n_channels] fp32 (or NULL with 0 channels).  1 <= M < 2^31,
+ * 1 <= T, 6 T < 2^31 - 4096, n_alive = the number of live faces (>= 1).  The oracle is tests/decimate_restatement.py.
+ * Deterministic (integer atomics only, fp64 in a written order): two runs are bitwise equal. */
+/* workspace bytes for both calls; -1 for sizes the library refuses. */
+int64_t misplat_decimate_workspace(int64_t n_vertices, int64_t n_triangles);
+/* One round up to the selection: the CSRs of the live faces, (first != 0) the vertices' quadrics, every edge's target, cost and
+ * validity, the two levels of minima, the selected edges (kept in the workspace for misplat_decimate_apply).  counts [3] int32
+ * on the device: live faces found (equal to n_alive for a consistent caller), selected edges, the faces their collapses remove. */
+int misplat_decimate_round(const float* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles,
+                           const int32_t* alive, int64_t n_alive, double* quadrics, int32_t first, void* workspace,
+                           int64_t workspace_bytes, int32_t* counts, misplat_stream_t stream);
+/* Apply what the round call before it selected (same sizes, same workspace, n_selected = its counts[1]): need < 0 every selected
+ * edge, else the shortest prefix in ascending (cost bits, edge key) whose removed faces reach `need`.  The lower end takes the
+ * target, 0.5f (x_lo + x_hi) of every attribute and the sum of the quadrics; the higher end dies (into), its corners are rewired,
+ * the faces of the edge die (alive). */
+int misplat_decimate_apply(float* vertices, int64_t n_vertices, int32_t* triangles, int64_t n_triangles, int32_t* alive,
+                           int64_t n_alive, float* attributes, int32_t n_channels, double* quadrics, int32_t* into,
+                           int64_t n_selected, int64_t need, void* workspace, int64_t workspace_bytes, misplat_stream_t stream);
+/* root [M] int32: the live vertex each vertex ended in (itself if it never collapsed). */
+int misplat_decimate_resolve(const int32_t* into, int64_t n_vertices, int32_t* root, misplat_stream_t stream);
+
 /* ---- oriented point clouds from depth and normal maps (csrc/depthcloud.hip) ----------------------------
  * depth [V,H,W] fp32, rgb and normals [V,H,W,3] fp32, masks / valid / edges / candidates [V,H,W] uint8 (non-zero: true),
  * c2w [V,3,4] fp32 (nerfstudio's OpenGL pose), intrinsics [V,4] fp32 (fx, fy, cx, cy); V <= 65535, H W < 2^31.  The oracle is
