@@ -47,6 +47,8 @@ def simplify_quadric_decimation(vertices: Tensor, triangles: Tensor, target_tria
     for what, x in (("target_triangles", target_triangles), ("max_rounds", max_rounds)):
         if not isinstance(x, int) or isinstance(x, bool) or x < 0:
             raise ValueError(f"{name}: {what} must be a non-negative integer, got {x!r}")
+    if sum(a.shape[1] for a in attributes) > 4096:
+        raise ValueError(f"{name}: {sum(a.shape[1] for a in attributes)} attribute channels in all, the limit is 4096")
     m, n_slots = v.shape[0], t.shape[0]
     if 6 * n_slots >= (1 << 31) - 4096:
         raise ValueError(f"{name}: {n_slots} triangles are beyond the library's limits (6 T < 2^31 - 4096)")

@@ -161,7 +161,8 @@ def evaluate(st, tb):
     q = eb[owner] * M + tb.ut[idx]
     p = np.minimum(np.searchsorted(tb.ukey, q), max(len(tb.ukey) - 1, 0))
     common = np.bincount(owner[tb.ukey[p] == q], minlength=E) if E else np.zeros(0, np.int64)
-    valid = (ec <= 2) & (common == ec) & ~((ec == 2) & tb.vbnd[ea] & tb.vbnd[eb])
+    few, link, free = ec <= 2, common == ec, ~((ec == 2) & tb.vbnd[ea] & tb.vbnd[eb])
+    valid = few & link & free
     # target and cost
     with np.errstate(all="ignore"):
         Qs = st.Q[ea] + st.Q[eb]
@@ -183,11 +184,13 @@ def evaluate(st, tb):
         best[m], bc[m] = pm[m], cm[m]
         target = np.where(solved[:, None], tsol, best)
         cost = _cost(Qs, target)
-    valid &= np.isfinite(target).all(1)
+    finite = np.isfinite(target).all(1)
+    valid &= finite
     # (4) no surviving face around an end turns over; (5) no two surviving faces end with the same vertex set
     P = st.pos.astype(D)
     T64 = target.astype(D)
     sets = []
+    upright, distinct = np.ones(E, bool), np.ones(E, bool)
     for u, o in ((ea, eb), (eb, ea)):
         owner, idx = _expand(tb.crow[u], tb.crow[u + 1])
         g = tb.corder[idx] // 3
@@ -202,12 +205,15 @@ def evaluate(st, tb):
             dots.append(_cross(e1[:, 0], e1[:, 1], e1[:, 2], e2[:, 0], e2[:, 1], e2[:, 2]))
         (ox, oy, oz), (nx, ny, nz) = dots
         dot = (ox * nx + oy * ny) + oz * nz
-        valid[owner[~(dot > 0)]] = False
+        upright[owner[~(dot > 0)]] = False
         rest = np.sort(np.where(tv == u[owner][:, None], -1, tv), 1)[:, 1:]      # the two other corners, ascending
         sets.append((owner, (owner * M + rest[:, 0]) * M + rest[:, 1]))
     (oa, ka), (_, kb) = sets
-    valid[oa[np.isin(ka, kb)]] = False
+    distinct[oa[np.isin(ka, kb)]] = False
+    valid &= upright & distinct
     ev.valid, ev.target = valid, target
+    # for the host tests' account of the refusals: rules (1), (2), (3), a finite target, (4), (5), and the target's branch
+    ev.rules, ev.solved = (few, link, free, finite, upright, distinct), solved
     ev.bits = np.where(valid, cost.view(np.uint64), NONE)
     ev.key = (ea.astype(np.uint64) << np.uint64(32)) | eb.astype(np.uint64)
     ev.tie = np.where(valid, _mix(ev.key), NONE)
@@ -263,8 +269,10 @@ def finish(st, index_dtype=np.int64):
 
 
 # ------------------------------------------------------------------------------------------------------------ drivers
-def simplify(vertices, triangles, target_triangles, attributes=(), max_rounds=256):
-    """(vertices, triangles, attributes, vertex_map, rounds) of the round-based simplifier."""
+def simplify(vertices, triangles, target_triangles, attributes=(), max_rounds=256, on_round=None):
+    """(vertices, triangles, attributes, vertex_map, rounds) of the round-based simplifier.  ``on_round(st, tb, ev, selected,
+    applied)`` sees every round before it is applied (a round's selection and what the landing keeps of it); it changes no
+    result."""
     st = State(vertices, triangles, attributes)
     rounds = 0
     while rounds < max_rounds:
@@ -280,12 +288,15 @@ def simplify(vertices, triangles, target_triangles, attributes=(), max_rounds=25
         if not sel.any():
             break
         rounds += 1
+        selected = sel
         if int(ev.faces[sel].sum()) > need:                         # the last round: the shortest prefix in ascending priority
             ids = np.nonzero(sel)[0]
             ids = ids[np.lexsort((ev.key[ids], ev.bits[ids]))]
             before = np.cumsum(ev.faces[ids]) - ev.faces[ids]
             sel = np.zeros_like(sel)
             sel[ids[before < need]] = True
+        if on_round is not None:
+            on_round(st, tb, ev, selected, sel)
         apply(st, tb, ev, sel)
     return finish(st, np.asarray(triangles).dtype if np.asarray(triangles).size else np.int64) + (rounds,)
 

@@ -43,7 +43,7 @@ def _same(got, ref):
 
 def _check(key, V, T, target, **kw):
     got = _run(V, T, target, **kw)
-    _same(got, _ref(key, V, T, target, **kw))
+    _same(got, _ref(key, V, T, target, **{k: x for k, x in kw.items() if k != "dtype"}))
     return got
 
 
@@ -168,15 +168,19 @@ def test_attributes_dtypes_and_determinism():
         assert all(torch.equal(x.view(torch.int32), y.view(torch.int32)) for x, y in zip(other[2], got[2]))
 
 
-def test_model_mesh_with_target_triangles():
+def _model():
     from collab_splats_amd import radegs
     from collab_splats_amd.synthetic import random_scene
     sc = random_scene(600, 64, 48, seed=3)                                  # the scene of test_density_gpu.py::test_model_surface
     sc["means"][:, :2] *= 0.2
     sc["means"][:, 2] = (sc["means"][:, 2] - 2.0) * 0.2 + 1.0
     sc["log_scales"] += 1.2
-    model = radegs.RadegsModel(radegs.RadegsModelConfig(), sc["means"], sc["log_scales"], sc["quats"], sc["opacity_logits"],
-                               sc["sh"][:, 0], sc["sh"][:, 1:]).to(DEV).eval()
+    return radegs.RadegsModel(radegs.RadegsModelConfig(), sc["means"], sc["log_scales"], sc["quats"], sc["opacity_logits"],
+                              sc["sh"][:, 0], sc["sh"][:, 1:]).to(DEV).eval()
+
+
+def test_model_mesh_with_target_triangles():
+    model = _model()
     raw = model.marching_cubes_mesh(voxel_size=0.04)
     same = model.marching_cubes_mesh(voxel_size=0.04, target_triangles=None)
     assert all(x.dtype == y.dtype and torch.equal(x.view(torch.int32), y.view(torch.int32)) for x, y in zip(raw, same))
@@ -188,3 +192,166 @@ def test_model_mesh_with_target_triangles():
     assert c.shape == v.shape and float(c.min()) >= 0 and float(c.max()) <= 1 and bool(torch.isfinite(v).all())
     with pytest.raises(ValueError, match="target_triangles"):
         model.marching_cubes_mesh(voxel_size=0.04, target_triangles=-1)
+
+
+# ------------------------------------------------------------------------- irregular, defective and workload-sized scenes
+# S.CASES; what each reaches in the restatement (three-pass tables, both target branches, every refusal, a landing sort over
+# two radix tiles) is asserted in test_decimate_host.py::test_restatement_on_the_irregular_scenes.
+def _case(name, dtype=torch.int64):
+    V, T, att, target, max_rounds = S.case(name)
+    _REF[("case", name)] = S.reference(name)[0]
+    return _check(("case", name), V, T, target, attributes=att, max_rounds=max_rounds, dtype=dtype)
+
+
+@pytest.mark.parametrize("name", S.SMALL)
+def test_irregular_and_defective_scenes(name):
+    _case(name)                                                     # (positions compare as bits: defects' NaN rows too)
+
+
+@pytest.mark.parametrize("name", ["high_behind", "high_scattered", "jitter272 3 rounds"])
+def test_three_pass_tables_from_int32_triangles(name):
+    _case(name, torch.int32)
+
+
+def test_three_rounds_at_a_workload_size():
+    got = _case("jitter272 3 rounds")
+    assert got[4] == 3
+
+
+def test_landing_sort_over_two_tiles_twice():
+    got = _case("jitter272 landing")
+    again = _run(*S.case("jitter272 landing")[:2], S.case("jitter272 landing")[3])
+    assert again[4] == got[4] == 1 and torch.equal(again[0].view(torch.int32), got[0].view(torch.int32))
+    assert torch.equal(again[1], got[1]) and torch.equal(again[3], got[3])
+
+
+# ------------------------------------------------------------------------------------------ marching-cubes meshes, whole
+def _against_the_restatement(v, t, c, target):
+    from collab_splats_amd import simplify_quadric_decimation
+    ref = R.simplify(v.cpu().numpy(), t.cpu().numpy(), target, (c.cpu().numpy(),))
+    got = simplify_quadric_decimation(v, t, target, attributes=(c,))
+    assert got[1].dtype == t.dtype
+    _same(got, ref)
+    return got, ref
+
+
+def test_model_mesh_equals_the_restatement():
+    """The marching-cubes mesh of test_model_mesh_with_target_triangles (287 closed blobs, slivers where the level set grazes
+    a lattice point) to half its faces, the colours as the attribute: the exporter's call, and the plain call on its raw mesh."""
+    model = _model()
+    v, t, c = model.marching_cubes_mesh(voxel_size=0.04)
+    n = t.shape[0] // 2
+    got, ref = _against_the_restatement(v, t, c, n)
+    mv, mt, mc = model.marching_cubes_mesh(voxel_size=0.04, target_triangles=n)
+    assert mt.dtype == t.dtype and np.array_equal(mt.cpu().numpy(), ref[1])
+    assert np.array_equal(mv.cpu().numpy().view(np.int32), ref[0].view(np.int32))
+    assert np.array_equal(mc.cpu().numpy().view(np.int32), ref[2][0].view(np.int32))
+
+
+def test_open_level_set_mesh_equals_the_restatement():
+    """density_scenes.clipped at 0.5: the bounds cut through the wide Gaussian's level set, and marching cubes emits no cell
+    beyond them, so the mesh ends in boundary loops."""
+    import density_scenes as DS
+    from collab_splats_amd import DensityField
+    sc = DS.scene("clipped")
+    dev = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(DEV)      # noqa: E731
+    f = DensityField(dev(sc["means"]), dev(sc["quats"]), dev(sc["scales"]), dev(sc["opacities"]), sc["h"], bounds=sc["bounds"])
+    vals = np.random.default_rng(3).uniform(0, 1, (f.n_gauss, 3)).astype(np.float32)
+    v, t, c = f.extract_mesh(0.5, values=dev(vals))
+    _, boundary, nonmanifold = S.edge_counts(t.cpu().numpy())
+    print("clipped at 0.5:", tuple(v.shape), tuple(t.shape), "boundary edges", boundary, "non-manifold", nonmanifold)
+    assert t.shape[0] > 200 and boundary > 0
+    _against_the_restatement(v, t, c, t.shape[0] // 2)
+
+
+# ------------------------------------------------------------------------------------------------------- entry points
+def _entry_state(dead=()):
+    import ctypes as C
+    from collab_splats_amd._lib import load
+    V, T = S.icosphere(1)
+    st = dict(lib=load(), M=len(V), T=len(T), pos=torch.from_numpy(V).to(DEV),
+              tri=torch.from_numpy(T).to(DEV).to(torch.int32).contiguous(), alive=torch.ones(len(T), dtype=torch.int32, device=DEV),
+              quadrics=torch.zeros((len(V), 10), dtype=torch.float64, device=DEV),
+              into=torch.full((len(V),), -1, dtype=torch.int32, device=DEV),
+              counts=torch.full((3,), -7, dtype=torch.int32, device=DEV))
+    for f in dead:
+        st["alive"][f] = 0
+    st["bytes"] = int(st["lib"].misplat_decimate_workspace(C.c_int64(st["M"]), C.c_int64(st["T"])))
+    assert st["bytes"] > 0
+    st["ws"] = torch.full((st["bytes"] + 4096,), 0xA5, dtype=torch.uint8, device=DEV)      # the last 4 KiB: a guard
+    return st
+
+
+def _round(st, n_alive, ws_bytes=None, null=None, first=1):
+    import ctypes as C
+    from collab_splats_amd._lib import ptr, stream_ptr
+    p = {k: (C.c_void_p(0) if k == null else ptr(st[k])) for k in ("pos", "tri", "alive", "quadrics", "ws", "counts")}
+    return st["lib"].misplat_decimate_round(p["pos"], C.c_int64(st["M"]), p["tri"], C.c_int64(st["T"]), p["alive"], C.c_int64(n_alive),
+                                            p["quadrics"], first, p["ws"], C.c_int64(st["bytes"] if ws_bytes is None else ws_bytes),
+                                            p["counts"], stream_ptr())
+
+
+def _apply(st, n_alive, n_selected, channels=0, att=None, ws_bytes=None):
+    import ctypes as C
+    from collab_splats_amd._lib import ptr, stream_ptr
+    return st["lib"].misplat_decimate_apply(ptr(st["pos"]), C.c_int64(st["M"]), ptr(st["tri"]), C.c_int64(st["T"]), ptr(st["alive"]),
+                                            C.c_int64(n_alive), ptr(att), channels, ptr(st["quadrics"]), ptr(st["into"]),
+                                            C.c_int64(n_selected), C.c_int64(-1), ptr(st["ws"]),
+                                            C.c_int64(st["bytes"] if ws_bytes is None else ws_bytes), stream_ptr())
+
+
+def _snapshot(st):
+    torch.cuda.synchronize()
+    return {k: st[k].clone() for k in ("pos", "tri", "alive", "quadrics", "into", "counts", "ws")}
+
+
+def _unchanged(st, before, keys):
+    torch.cuda.synchronize()
+    for k in keys:
+        assert torch.equal(st[k].view(torch.uint8), before[k].view(torch.uint8)), k
+
+
+def test_entry_points_refuse_what_the_header_excludes():
+    """MISPLAT_EINVAL (-1) and MISPLAT_EWORKSPACE (-3) before any launch: no tensor of the state and no byte of the workspace
+    changes."""
+    import ctypes as C
+    st = _entry_state()
+    lib, M, T = st["lib"], st["M"], st["T"]
+    limit = ((1 << 31) - 4096 + 5) // 6                             # the smallest T with 6 T >= 2^31 - 4096
+    assert 6 * limit >= (1 << 31) - 4096 > 6 * (limit - 1)
+    assert lib.misplat_decimate_workspace(C.c_int64(M), C.c_int64(0)) == -1
+    assert lib.misplat_decimate_workspace(C.c_int64(3), C.c_int64(limit)) == -1
+    assert lib.misplat_decimate_workspace(C.c_int64(3), C.c_int64(limit - 1)) > 0
+    before = _snapshot(st)
+    everything = tuple(before)
+    for null in ("pos", "tri", "alive", "quadrics", "ws", "counts"):
+        assert _round(st, T, null=null) == -1, null
+    assert _round(st, T + 1) == -1 and _round(st, 0) == -1
+    assert _round(st, T, ws_bytes=st["bytes"] - 1) == -3
+    att = torch.zeros((M, 4097), dtype=torch.float32, device=DEV)
+    assert _apply(st, T, 0) == -1 and _apply(st, T, T + 1) == -1
+    assert _apply(st, T, 1, channels=4097, att=att) == -1
+    assert _apply(st, T, 1, channels=3, att=None) == -1              # channels without attributes
+    assert _apply(st, T, 1, ws_bytes=st["bytes"] - 1) == -3
+    _unchanged(st, before, everything)
+
+
+@pytest.mark.parametrize("off", [-1, 0, 1])
+def test_round_with_a_wrong_live_count(off):
+    """decimate.hip: "a wrong n_alive reads face 0, never beyond the list".  Every access of live_list_kernel, emit_kernel and
+    what follows them is bounded by the n passed in (the list is zeroed first and only positions below n are written), so a count
+    one too small leaves the last live face out and one too large lists face 0 twice: counts[0] still reports the true
+    count (what the wrapper checks), the mesh is untouched, nothing is written past the declared workspace."""
+    st = _entry_state(dead=(17,))
+    true = st["T"] - 1
+    before = _snapshot(st)
+    assert _round(st, true + off) == 0
+    _unchanged(st, before, ("pos", "tri", "alive", "into"))
+    counts = st["counts"].tolist()
+    assert counts[0] == true and 0 < counts[1] <= counts[2] <= 2 * counts[1]
+    assert bool((st["ws"][st["bytes"]:] == 0xA5).all())
+    if off == 0:                                                    # the consistent call: the restatement's first round
+        V, T = S.icosphere(1)
+        rounds = []
+        R.simplify(V, np.delete(T, 17, 0), 0, max_rounds=1, on_round=lambda *a: rounds.append(S.round_account(*a)))
+        assert counts[1:] == [rounds[0]["selected"], rounds[0]["selected_faces"]]

@@ -31,8 +31,12 @@ def test_argument_validation():
         f(V, T, 10, attributes=(torch.zeros(M, 3, dtype=torch.float64),))
     with pytest.raises(ValueError, match="float32"):
         f(V, T, 10, attributes=(torch.zeros(M),))
+    with pytest.raises(ValueError, match="limit is 4096"):           # 4 097 channels in all: refused before any device work
+        f(V, T, 10, attributes=(torch.zeros(M, 4000), torch.zeros(M, 97)))
     with pytest.raises(MisplatError, match="no CPU fallback"):       # valid arguments on the CPU: there is no other path
         f(V, T, 10, attributes=(torch.zeros(M, 3),))
+    with pytest.raises(MisplatError, match="no CPU fallback"):       # (4 096 channels are within the limit)
+        f(V, T, 10, attributes=(torch.zeros(M, 4000), torch.zeros(M, 96)))
 
 
 @pytest.mark.parametrize("level,target", [(3, 320), (2, 80)])
@@ -76,6 +80,145 @@ def test_restatement_launch_edges():
     V, T = S.merge(S.icosphere(2), S.icosphere(1, 0.3, (3.0, 0.0, 0.0)))
     v, t, _, _, _ = R.simplify(V, T, 120)
     assert S.n_components(t) == 2 and S.edge_counts(t)[1:] == (0, 0)
+
+
+# ------------------------------------------------------------------------------- the scenes cover what they are there for
+# Everything below runs on the restatement alone (S.reference: its result and one account per round, S.round_account).  The
+# GPU tests compare the device with these results for equality; here is the proof that the results pass through the code the
+# scenes are named for.  The figures in the comments were measured on the restatement.
+def _reached(name):
+    (_, t, _, _, _), _ = S.reference(name)
+    target = S.case(name)[3]
+    assert target - 2 < len(t) <= target, (name, len(t), target)
+
+
+def _three_passes(M):
+    """The CSR sorts run radix_passes(M - 1) = 3 passes of 8 bits, an odd count: the sorted pair is the sort's second."""
+    assert M > 65536 and (M - 1) >> 16 > 0 and (M - 1) >> 24 == 0
+
+
+def _jitter24(V, T, rounds):
+    # 24 rounds; refused over the run: 239 by (2), 42 by (3), 1 204 by (4) or (5); 20 269 Cramer targets, 27 fallbacks
+    assert S.total(rounds, "r2") >= 1 and S.total(rounds, "flip_or_pillow") >= 1
+    assert S.total(rounds, "cramer") >= 1 and S.total(rounds, "fallback") >= 1
+    assert any(r["cramer"] and r["fallback"] for r in rounds)               # both branches inside one launch
+    assert S.n_boundary_loops(T) == 2 and not (V[:, 2] == 0).all()
+
+
+def _noisy(V, T, rounds):
+    # -> 100: 37 rounds, 240 refused by (2), 3 079 by (4) or (5); -> 0: 64 rounds, down to the tetrahedron
+    assert S.total(rounds, "r2") >= 1 and S.total(rounds, "flip_or_pillow") >= 1
+    assert S.edge_counts(T)[1:] == (0, 0)
+
+
+def _all_fallback(V, T, rounds):
+    # |det| <= 1e-10 on all 480 edges of the first round and on every edge of every later one
+    assert rounds[0]["fallback"] == 480 and S.total(rounds, "cramer") == 0
+
+
+def _all_cramer(V, T, rounds):
+    assert rounds[0]["cramer"] == 480 and S.total(rounds, "fallback") == 0
+
+
+def _high_behind(V, T, rounds):
+    _three_passes(len(V))
+    assert T.min() >= 1 << 16 and len(T) == 320                             # every key has a third byte
+
+
+def _high_scattered(V, T, rounds):
+    _three_passes(len(V))
+    assert T.max() == len(V) - 1 and T.min() < 1 << 16 and len(np.unique(T)) == 162
+
+
+def _defects(V, T, rounds):
+    # 20 rounds; refused over the run: 87 by (1), 48 by (2), 118 by (3), 120 for a target that is not finite
+    for what in ("r1", "r2", "r3", "nonfinite"):
+        assert S.total(rounds, what) >= 1, what
+    assert S.edge_counts(T)[2] >= 1 and np.isnan(V).any() and np.isinf(V).any()
+    P = V.astype(np.float64)
+    with np.errstate(all="ignore"):
+        area = np.linalg.norm(np.cross(P[T[:, 1]] - P[T[:, 0]], P[T[:, 2]] - P[T[:, 0]]), axis=1)
+    assert (area == 0).any() and (T[area == 0][:, 0] != T[area == 0][:, 1]).all()       # no area, three distinct corners
+    assert len(np.unique(np.sort(T, 1), axis=0)) == len(T) - 2                          # two faces are listed twice
+
+
+def _inf_vertex(V, T, rounds):
+    # in defects every target that is not finite also fails (4) (a NaN normal); here 24 edges over the run are refused for
+    # their target alone, and 88 by (2) alone
+    assert S.total(rounds, "only_finite") >= 1 and S.total(rounds, "only_link") >= 1 and np.isinf(V).sum() == 1
+
+
+def _tube(V, T, rounds):
+    # 5 rounds, then no valid edge is left at 58 faces: 153 refusals by (2) alone, the ring edges (in the sheets and the
+    # spheres an edge that fails (2) has a valence-3 end and fails (5) as well)
+    assert S.total(rounds, "only_link") >= 1 and S.n_boundary_loops(T) == 2 and S.edge_counts(T)[1:] == (6, 0)
+
+
+def _bowtie(V, T, rounds):
+    # one vertex with two closed fans: a single component under "share a vertex", two under "share an edge"
+    assert len(V) == 2 * 42 - 1 and S.n_components(T) == 1 and S.edge_counts(T)[1:] == (0, 0)
+    fans = np.bincount(T.reshape(-1), minlength=len(V))
+    assert fans.max() == 12 and (fans == 12).sum() == 1                     # 6 + 6 faces around the shared vertex
+
+
+def _strip(V, T, rounds):
+    # every vertex is on the boundary: each interior edge is refused by (3), each target is an end or the midpoint
+    assert S.total(rounds, "cramer") == 0 and S.total(rounds, "r3") >= 1 and S.edge_counts(T)[1] == len(V)
+
+
+def _wide(V, T, rounds):
+    assert sum(a.shape[1] for a in S.case("wide")[2]) == 518
+
+
+def _landing(V, T, rounds):
+    # 887 808 directed entries (217 radix tiles); the one round selects 4 629 edges that remove 9 135 faces where 9 050 are
+    # asked for: the landing sorts two tiles of keys (2 860 distinct top digits, 4 622 middle) and applies a prefix of 4 585
+    _three_passes(len(V))
+    assert len(rounds) == 1 and rounds[0]["selected"] > 4096 and rounds[0]["entries"] > 200 * 4096
+    assert 4096 < rounds[0]["applied"] < rounds[0]["selected"]              # the prefix ends inside the second tile
+    assert rounds[0]["top_digits"] > 256 and rounds[0]["middle_digits"] > 256
+
+
+def _three_rounds(V, T, rounds):
+    _three_passes(len(V))
+    # 4 629, 4 189 and 3 974 edges: three plain rounds (no landing), each apply call naming its tables by the odd pass count
+    assert len(rounds) == 3 and all(r["selected"] > 1000 and r["applied"] == r["selected"] for r in rounds)
+
+
+_COVERS = {"jitter24": _jitter24, "noisy3->100": _noisy, "noisy3->0": _noisy, "scale1e-3": _all_fallback, "scale1e-2": _all_fallback,
+           "scale30": _all_cramer, "scale1e4": _all_cramer, "high_behind": _high_behind, "high_scattered": _high_scattered,
+           "defects": _defects, "inf_vertex": _inf_vertex, "tube": _tube, "bowtie": _bowtie, "strip400": _strip, "wide": _wide, "jitter272 landing": _landing,
+           "jitter272 3 rounds": _three_rounds}
+_STOPS_SHORT = ("noisy3->0", "tube", "jitter272 3 rounds")                       # every other case reaches its target
+
+
+@pytest.mark.parametrize("name", list(S.CASES))
+def test_restatement_on_the_irregular_scenes(name):
+    assert set(_COVERS) == set(S.CASES)
+    V, T, att, target, max_rounds = S.case(name)
+    (v, t, a, vm, n_rounds), rounds = S.reference(name)
+    print(name, len(V), len(T), "->", len(t), "rounds", n_rounds,
+          {k: S.total(rounds, k) for k in ("r1", "r2", "r3", "nonfinite", "flip_or_pillow", "cramer", "fallback")})
+    assert n_rounds == len(rounds) and 0 < n_rounds <= max_rounds
+    _COVERS[name](V, T, rounds)
+    # independence, every round: no vertex ends two selected edges, no end of one is adjacent to an end of another
+    assert all(r["shared_ends"] == 0 and r["adjacent_ends"] == 0 for r in rounds)
+    assert all(r["selected"] > 0 and r["removed"] > 0 for r in rounds)
+    # the result
+    if name in _STOPS_SHORT:
+        assert len(t) > target and len(t) >= 4
+    else:
+        _reached(name)
+    _, b0, nm0 = S.edge_counts(T)
+    _, b1, nm1 = S.edge_counts(t)
+    if nm0 == 0:
+        assert nm1 == 0
+    if b0 == 0 and nm0 == 0:
+        assert b1 == 0                                                      # closed stays closed
+    elif nm0 == 0:
+        assert S.n_boundary_loops(t) == S.n_boundary_loops(T)               # the sheets and the strip keep their loops
+    assert len(a) == len(att) and all(x.shape == (len(v), y.shape[1]) for x, y in zip(a, att))
+    assert t.min() == 0 and t.max() == len(v) - 1 and vm.shape == (len(V),) and vm.max() == len(v) - 1
 
 
 def test_rounds_of_local_minima_against_the_greedy_order():
