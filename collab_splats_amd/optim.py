@@ -89,12 +89,13 @@ def _launch(entries: List[tuple]) -> None:
                 if g.dtype != torch.float32 or g.shape != p.shape:
                     raise _lib.MisplatError("FusedAdam: gradient must be float32 with the parameter's shape")
                 keep.append(g)
-                st["step"] += 1
                 ps.append(p.data_ptr()); gs.append(g.data_ptr())
                 ms.append(st["exp_avg"].data_ptr()); vs.append(st["exp_avg_sq"].data_ptr())
-                numel.append(p.numel()); lrs.append(lr); steps.append(int(st["step"].item()))
+                numel.append(p.numel()); lrs.append(lr); steps.append(int(st["step"].item()) + 1)
             vp = C.c_void_p * n
             check(lib.misplat_adam_step(C.c_int32(n), vp(*ps), vp(*gs), vp(*ms), vp(*vs), (C.c_int64 * n)(*numel),
                                         (C.c_float * n)(*lrs), (C.c_int64 * n)(*steps), C.c_double(b1), C.c_double(b2),
                                         C.c_double(eps), stream_ptr()), "misplat_adam_step")
+            for _, st, _, _, _, _ in chunk:              # a refused launch has stepped nothing: the counts stay too
+                st["step"] += 1
             del keep

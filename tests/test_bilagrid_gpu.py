@@ -14,7 +14,11 @@ shuffle tree over 64 lanes, four waves and up to 16 row slices: two different or
 roundings of the sum's size relative to each other, which for n = 42 000 spread over 256 lanes x 11 slices (chains of ~15) is
 a handful of roundings against the restatement's own chain of n; 8 covers it with the margin the feature loss uses.  The TV
 sums meet in fp64 in the kernels, which can only be closer to the oracle than the fp32 restatement's fp32 sum.  (The
-figures of a GPU run belong in DESIGN.md section 24; this test prints them.)"""
+figures of a GPU run belong in DESIGN.md section 24; this test prints them.)
+
+``S.REGIME_SCENES`` / ``S.REGIME_TV_SHAPES`` take the same tests, under the same bound, to the launch regimes a training run
+reaches: several trips of the three grid-stride loops, a middle camera among 23, empty row slices, the sizes at the header's
+limits, a 1 x 1 image and colours outside 0..1 (test_bilagrid_host.py asserts from the launch arithmetic what each reaches)."""
 import pytest
 import torch
 
@@ -56,10 +60,10 @@ def run_tv_gpu(grids, dev):
     return {"loss": loss.detach(), "v_grids": g.grad}
 
 
-@pytest.mark.parametrize("name", list(S.SCENES))
+@pytest.mark.parametrize("name", S.ALL_SCENES)
 def test_slice_and_gradients_against_the_fp64_oracle(dev, name):
     scene = S.make(name)
-    for cam in (0, scene["num"] - 1):
+    for cam in S.cameras(name):
         ora, y32 = S.oracle(name, cam), S.yardstick(name, cam)
         got = run_gpu(scene, cam, dev)
         rows = [(k, S.rel_err(got[k], ora[k]), S.rel_err(y32[k], ora[k])) for k in ("out", "v_rgb", "v_grids")]
@@ -84,7 +88,7 @@ def test_identity_grid_returns_rgb_bit_for_bit(dev, name):
     assert batched.shape == (1,) + tuple(scene["rgb"].shape) and torch.equal(batched[0].cpu(), scene["rgb"])
 
 
-@pytest.mark.parametrize("name", list(S.TV_SHAPES))
+@pytest.mark.parametrize("name", S.ALL_TV_SHAPES)
 def test_tv_loss_and_gradient_against_the_fp64_oracle(dev, name):
     ora, y32 = S.tv_oracle(name), S.tv_yardstick(name)
     got = run_tv_gpu(S.tv_grids(name), dev)
@@ -104,15 +108,103 @@ def test_tv_gradient_scales_with_the_incoming_scalar(dev):
         S.rel_err(S.tv_yardstick("odd_3")["v_grids"], S.tv_oracle("odd_3")["v_grids"]))
 
 
-@pytest.mark.parametrize("name", ["blocks", "split", "deep"])
+@pytest.mark.parametrize("name", ["blocks", "split", "deep"] + list(S.REGIME_SCENES))
 def test_two_runs_are_equal_bit_for_bit(dev, name):
-    """``split`` / ``deep``: the row slices of a support and the two level chunks are in the sums as well."""
+    """``split`` / ``deep``: the row slices of a support and the two level chunks are in the sums as well.  The regime scenes:
+    the cameras they list beyond camera 0 (``many_cams``: 11 and 22, with the finish kernel's second trip in the result)."""
     scene = S.make(name)
-    a, b = run_gpu(scene, 1, dev), run_gpu(scene, 1, dev)
-    for k in a:
-        assert torch.equal(a[k], b[k]), k
+    for cam in S.cameras(name)[1:]:
+        a, b = run_gpu(scene, cam, dev), run_gpu(scene, cam, dev)
+        for k in a:
+            assert torch.equal(a[k], b[k]), (cam, k)
     ta, tb = run_tv_gpu(scene["grids"], dev), run_tv_gpu(scene["grids"], dev)
     assert torch.equal(ta["loss"], tb["loss"]) and torch.equal(ta["v_grids"], tb["v_grids"])
+
+
+def test_empty_row_slices_write_their_zeros_into_dirty_scratch(dev):
+    """The grid-side backward's scratch comes from ``torch.empty``: a row slice without rows must still write its zeros, or
+    the second pass adds whatever lay there.  Fresh device memory is often zero, so the comparison on ``empty_slices`` alone
+    can pass by luck; here the block the scratch will take is filled with NaN first (freed blocks of the caching allocator
+    are handed out again for a request of the same size -- checked with a probe, so the test cannot pass without its premise)."""
+    import ctypes as C
+    import collab_splats_amd as m
+    from collab_splats_amd import _lib
+    scene = S.make("empty_slices")
+    (H, W), (GW, GH, L) = scene["rgb"].shape[:2], scene["shape"]
+    n = int(_lib.load().misplat_bilagrid_scratch_floats(C.c_int32(H), C.c_int32(W), C.c_int32(GW), C.c_int32(GH), C.c_int32(L)))
+    assert n == 11 * GW * GH * 8 * 12                                                  # 11 row slices, L padded to 8 levels
+    for cam in S.cameras("empty_slices"):
+        ora, y32 = S.oracle("empty_slices", cam), S.yardstick("empty_slices", cam)
+        torch.cuda.empty_cache()
+        rgb = scene["rgb"].to(dev).requires_grad_(True)
+        g = scene["grids"].to(dev).requires_grad_(True)
+        out = m.bilagrid_slice(rgb, g, cam)
+        v_out = scene["v_out"].to(dev)
+        junk = [torch.full((n,), float("nan"), device=dev) for _ in range(3)]
+        torch.cuda.synchronize()
+        del junk
+        probe = torch.empty(n, device=dev)
+        assert bool(torch.isnan(probe).all()), "the allocator did not hand the dirtied block out again: the test has no premise"
+        del probe
+        out.backward(v_out)
+        torch.cuda.synchronize()
+        assert bool(torch.isfinite(g.grad).all()), cam
+        e_gpu, e_32 = S.rel_err(g.grad, ora["v_grids"]), S.rel_err(y32["v_grids"], ora["v_grids"])
+        assert e_gpu <= bound(e_32), (cam, e_gpu, e_32)
+        assert bool((g.grad[1 - cam] == 0).all())
+
+
+@pytest.mark.parametrize("name", list(S.REGIME_TV_SHAPES))
+def test_two_tv_runs_are_equal_bit_for_bit(dev, name):
+    """The partials of several trips and all 1024 of them in tv_finish_kernel meet in a fixed order."""
+    ta, tb = run_tv_gpu(S.tv_grids(name), dev), run_tv_gpu(S.tv_grids(name), dev)
+    assert torch.equal(ta["loss"], tb["loss"]) and torch.equal(ta["v_grids"], tb["v_grids"])
+
+
+@pytest.mark.parametrize("name,cams", [("one_pixel", (0, 1)), ("max_depth", (0, 1)), ("many_cams", (11,)), ("beyond", (0, 1))])
+def test_identity_grid_returns_rgb_bit_for_bit_on_regime_scenes(dev, name, cams):
+    """``beyond``: the identity affine is constant along z, so colours outside 0..1 come back bit for bit as well."""
+    import collab_splats_amd as m
+    scene = S.make(name)
+    grids = m.BilateralGrid(scene["num"], *scene["shape"]).grids.detach()
+    if name == "beyond":
+        assert float(scene["rgb"].min()) < 0.0 and float(scene["rgb"].max()) > 1.0
+    for cam in cams:
+        got = run_gpu(scene, cam, dev, grids=grids)
+        assert torch.equal(got["out"].cpu(), scene["rgb"]), (name, cam)
+
+
+def test_upstream_gradient_layouts(dev):
+    """The layouts of ``v_out`` the autograd node meets: ``sum().backward()`` hands it an expanded, stride-0 tensor of ones, and
+    a [1, H, W, 3] image gets its gradient in that shape.  Both must give the gradients of the explicit, dense [H, W, 3] run."""
+    import collab_splats_amd as m
+    scene = S.make("blocks")
+    cam = 1
+
+    def run(batched: bool, how: str):
+        rgb = (scene["rgb"][None] if batched else scene["rgb"]).to(dev).requires_grad_(True)
+        g = scene["grids"].to(dev).requires_grad_(True)
+        out = m.bilagrid_slice(rgb, g, cam)
+        if how == "sum":
+            out.sum().backward()
+        else:
+            v = torch.ones_like(out) if how == "ones" else scene["v_out"].to(dev).view(out.shape)
+            out.backward(v)
+        torch.cuda.synchronize()
+        assert rgb.grad.shape == rgb.shape and g.grad.shape == g.shape
+        return rgb.grad.reshape(scene["rgb"].shape), g.grad
+
+    ones = run(False, "ones")
+    for batched, how in ((False, "sum"), (True, "sum"), (True, "ones")):
+        got = run(batched, how)
+        assert torch.equal(got[0], ones[0]) and torch.equal(got[1], ones[1]), (batched, how)
+    assert float(ones[1][cam].abs().sum()) > 0 and bool((ones[1][0] == 0).all())
+    dense, dense_b = run(False, "v_out"), run(True, "v_out")
+    assert torch.equal(dense[0], dense_b[0]) and torch.equal(dense[1], dense_b[1])
+    ora = S.oracle("blocks", cam)
+    y32 = S.yardstick("blocks", cam)
+    for k, got in (("v_rgb", dense_b[0]), ("v_grids", dense_b[1])):
+        assert S.rel_err(got, ora[k]) <= bound(S.rel_err(y32[k], ora[k])), k
 
 
 def _model(dev, flag: bool, features: bool = False):
