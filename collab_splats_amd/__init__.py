@@ -23,6 +23,7 @@ from .decimate import simplify_quadric_decimation  # noqa: F401
 from .depthcloud import backproject, depth_edges, depth_normal_cloud, gaussian_mask_filter, sample_pixels  # noqa: F401
 from .featureloss import TwoLayerMLP, feature_decode, feature_loss  # noqa: F401
 from .bilagrid import BilateralGrid, bilagrid_slice, bilagrid_tv_loss  # noqa: F401
+from .camera_opt import CameraOptimizer  # noqa: F401
 from .textquery import TextQuery, fold_text_queries, gaussian_similarity, similarity_map  # noqa: F401
 from .poisson import (poisson_grid, poisson_reconstruct, poisson_solve, poisson_splat, poisson_system,  # noqa: F401
                       poisson_trim)

@@ -97,6 +97,7 @@ def make_params(n_gauss: int, n_cams: int, width: int, height: int, tile_size: i
 # name -> (restype, n_args); every symbol include/misplat.h declares
 SYMBOLS = {
     "misplat_project_fwd": (C.c_int, 16), "misplat_project_bwd": (C.c_int, 18),
+    "misplat_project_bwd_pose_workspace": (C.c_int64, 2), "misplat_project_bwd_pose": (C.c_int, 17),
     "misplat_project_pack_fwd": (C.c_int, 17), "misplat_color_fwd": (C.c_int, 16),
     "misplat_color_bwd": (C.c_int, 16), "misplat_project_pack_bwd": (C.c_int, 20),
     "misplat_sh_fwd": (C.c_int, 9), "misplat_sh_bwd": (C.c_int, 11),

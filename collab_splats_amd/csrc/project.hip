@@ -16,6 +16,7 @@
 #include "misplat.h"
 #include "sh_eval.h"
 #include "internal.h"
+#include "wgprims.h"
 
 namespace {
 
@@ -228,9 +229,12 @@ struct ProjGrads {
 };
 
 // Backward of project_one + rade_extras for ONE (camera, Gaussian); ACCUMULATES into o_m/o_q/o_s.
+// pose (or absent): receives v_mu[3] -- the gradient of the camera-space mean -- and the final v_Rc[9] -- that of
+// Rc = Rw Rg(q) --, the two quantities through which the view matrix acts (project_bwd_pose_kernel); untouched when the
+// row is culled.  The function is inlined into every caller: with pose absent nothing of it is left in their code.
 __device__ __forceinline__ void project_bwd_one(const float* mean, const float* quat, const float* sc,
                                                 const Cam& cam, const misplat_params& P, ProjGrads& G,
-                                                float* o_m, float* o_q, float* o_s) {
+                                                float* o_m, float* o_q, float* o_s, float* pose = nullptr) {
     ProjState S;
     if (!project_one(mean, quat, sc, cam, P, S)) {
         if (G.m2d_sums) { G.v_m2d[0] = 0.f; G.v_m2d[1] = 0.f; }
@@ -353,6 +357,12 @@ __device__ __forceinline__ void project_bwd_one(const float* mean, const float* 
             v_Rc[i * 3 + k] += acc * sc[k];
             v_s[k] += acc * S.Rc[i * 3 + k];
         }
+    if (pose) {
+#pragma unroll
+        for (int i = 0; i < 3; i++) pose[i] = v_mu[i];
+#pragma unroll
+        for (int i = 0; i < 9; i++) pose[3 + i] = v_Rc[i];
+    }
     float w_[9];
 #pragma unroll
     for (int i = 0; i < 3; i++)
@@ -407,6 +417,92 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(
 #pragma unroll
         for (int k = 0; k < 4; k++) v_quats[4 * g + k] = o_q[k];
     }
+}
+
+// ------------------------------------------------------------------ view-matrix gradient
+// The forward depends on V[c] only through mu = Rw m + t and Rc = Rw Rg(q), so
+//   v_V[c,:3,:3] = sum_g (v_mu (x) m + v_Rc Rg^T),   v_V[c,:3,3] = sum_g v_mu,   v_V[c,3,:] = 0
+// over the Gaussians visible in camera c (project_bwd_kernel's test).  One thread per Gaussian in a grid-stride loop,
+// blockIdx.y = camera; the 12 terms are formed in fp32 like the rest of the file and summed in fp64 in a fixed order:
+// thread (its Gaussians in ascending order), block_sums<12>, then one workgroup per camera over the partials in
+// sum_final_kernel's order.  The grid depends on N only (pose_blocks), so two runs give the same bits; no atomics.
+// Registers: 24 VGPRs of accumulators next to ProjState; the kernel streams (about 100 B per visible row) and one wave
+// per SIMD's budget (launch bounds 256) is never approached -- see DESIGN.md section 28 for the measured allocation.
+constexpr int kPoseBlock = 256;
+constexpr int kPoseMaxBlocks = 1024;
+inline int pose_blocks(int64_t n) {
+    int64_t b = (n + kPoseBlock - 1) / kPoseBlock;
+    return (int)(b < 1 ? 1 : (b > kPoseMaxBlocks ? kPoseMaxBlocks : b));
+}
+
+__global__ __launch_bounds__(kPoseBlock) void project_bwd_pose_kernel(
+    misplat_params P, const float* __restrict__ means, const float* __restrict__ quats,
+    const float* __restrict__ scales, const float* __restrict__ viewmats,
+    const float* __restrict__ Ks, const int32_t* __restrict__ radii,
+    const float* __restrict__ v_means2d, const float* __restrict__ v_depths,
+    const float* __restrict__ v_conics, const float* __restrict__ v_comps,
+    const float* __restrict__ v_ray_ts, const float* __restrict__ v_ray_planes,
+    const float* __restrict__ v_normals, double* __restrict__ part) {
+    const int ci = blockIdx.y;
+    const Cam cam = load_cam(viewmats + 16 * ci, Ks + 9 * ci);
+    double acc[12];
+#pragma unroll
+    for (int k = 0; k < 12; k++) acc[k] = 0.0;
+    for (int64_t g = (int64_t)blockIdx.x * kPoseBlock + threadIdx.x; g < P.n_gauss; g += (int64_t)gridDim.x * kPoseBlock) {
+        const int64_t idx = (int64_t)ci * P.n_gauss + g;
+        if (radii[2 * idx] <= 0 && radii[2 * idx + 1] <= 0) continue;
+        float mean[3] = {means[3 * g], means[3 * g + 1], means[3 * g + 2]};
+        float quat[4] = {quats[4 * g], quats[4 * g + 1], quats[4 * g + 2], quats[4 * g + 3]};
+        float sc[3] = {scales[3 * g], scales[3 * g + 1], scales[3 * g + 2]};
+        ProjGrads G;
+        G.v_m2d[0] = v_means2d[2 * idx]; G.v_m2d[1] = v_means2d[2 * idx + 1];
+        G.v_depth = v_depths[idx];
+        G.v_conic[0] = v_conics[3 * idx]; G.v_conic[1] = v_conics[3 * idx + 1]; G.v_conic[2] = v_conics[3 * idx + 2];
+        G.v_comp = v_comps[idx]; G.v_rt = v_ray_ts[idx];
+        G.v_rp[0] = v_ray_planes[2 * idx]; G.v_rp[1] = v_ray_planes[2 * idx + 1];
+        G.v_nr[0] = v_normals[3 * idx]; G.v_nr[1] = v_normals[3 * idx + 1]; G.v_nr[2] = v_normals[3 * idx + 2];
+        float o_m[3] = {0.f, 0.f, 0.f}, o_q[4] = {0.f, 0.f, 0.f, 0.f}, o_s[3] = {0.f, 0.f, 0.f};
+        float pose[12];
+#pragma unroll
+        for (int k = 0; k < 12; k++) pose[k] = 0.f;
+        project_bwd_one(mean, quat, sc, cam, P, G, o_m, o_q, o_s, pose);
+        // Rg(q) as project_one forms it
+        const float n = sqrtf(quat[0] * quat[0] + quat[1] * quat[1] + quat[2] * quat[2] + quat[3] * quat[3]);
+        const float r = quat[0] / n, x = quat[1] / n, y = quat[2] / n, z = quat[3] / n;
+        float Rg[9];
+        Rg[0] = 1.0f - 2.0f * (y * y + z * z); Rg[1] = 2.0f * (x * y - r * z); Rg[2] = 2.0f * (x * z + r * y);
+        Rg[3] = 2.0f * (x * y + r * z); Rg[4] = 1.0f - 2.0f * (x * x + z * z); Rg[5] = 2.0f * (y * z - r * x);
+        Rg[6] = 2.0f * (x * z - r * y); Rg[7] = 2.0f * (y * z + r * x); Rg[8] = 1.0f - 2.0f * (x * x + y * y);
+        const float* v_mu = pose;
+        const float* v_Rc = pose + 3;
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+                const float t = v_mu[i] * mean[j] + (v_Rc[i * 3 + 0] * Rg[j * 3 + 0] + v_Rc[i * 3 + 1] * Rg[j * 3 + 1] + v_Rc[i * 3 + 2] * Rg[j * 3 + 2]);
+                acc[i * 4 + j] += (double)t;
+            }
+            acc[i * 4 + 3] += (double)v_mu[i];
+        }
+    }
+    block_sums<12, kPoseBlock / 64>(acc, part + ((int64_t)ci * gridDim.x + blockIdx.x) * 12);
+}
+
+// One workgroup per camera: its nb partials in sum_final_kernel's order, written as the fp32 rows of v_viewmats[c]
+// (row 3 = 0).  nb == 0 (no Gaussians): zeros.
+__global__ __launch_bounds__(kPoseBlock) void project_bwd_pose_final_kernel(const double* __restrict__ part, int nb,
+                                                                           float* __restrict__ v_viewmats) {
+    __shared__ double out[12];
+    part += (int64_t)blockIdx.x * nb * 12;
+    double x[12];
+#pragma unroll
+    for (int k = 0; k < 12; k++) x[k] = 0.0;
+    for (int b = threadIdx.x; b < nb; b += kPoseBlock)
+#pragma unroll
+        for (int k = 0; k < 12; k++) x[k] += part[(int64_t)b * 12 + k];
+    block_sums<12, kPoseBlock / 64>(x, out);
+    // (thread k < 12 wrote out[k] itself)
+    if (threadIdx.x < 16) v_viewmats[16 * blockIdx.x + threadIdx.x] = threadIdx.x < 12 ? (float)out[threadIdx.x] : 0.f;
 }
 
 // ------------------------------------------------------------------ spherical harmonics
@@ -1678,6 +1774,31 @@ extern "C" int misplat_project_bwd(const misplat_params* p, const float* means, 
     hipLaunchKernelGGL(project_bwd_kernel, dim3(grid_for(p->n_gauss, 256)), dim3(256), 0, (hipStream_t)stream,
                        *p, means, quats, scales, viewmats, Ks, radii, v_means2d, v_depths, v_conics,
                        v_compensations, v_ray_ts, v_ray_planes, v_normals, v_means, v_quats, v_scales);
+    return check_launch();
+}
+
+extern "C" int64_t misplat_project_bwd_pose_workspace(int32_t n_gauss, int32_t n_cams) {
+    if (n_gauss < 0 || n_cams < 1) return 0;
+    return al((int64_t)n_cams * pose_blocks(n_gauss) * 12 * (int64_t)sizeof(double));
+}
+
+extern "C" int misplat_project_bwd_pose(const misplat_params* p, const float* means, const float* quats,
+                                        const float* scales, const float* viewmats, const float* Ks,
+                                        const int32_t* radii, const float* v_means2d, const float* v_depths,
+                                        const float* v_conics, const float* v_compensations,
+                                        const float* v_ray_ts, const float* v_ray_planes,
+                                        const float* v_normals, void* workspace, float* v_viewmats,
+                                        misplat_stream_t stream) {
+    if (!p || p->n_gauss < 0 || p->n_cams < 1 || p->activations || !workspace || !v_viewmats) return MISPLAT_EINVAL;
+    const int nb = p->n_gauss > 0 ? pose_blocks(p->n_gauss) : 0;
+    if (nb > 0) {
+        hipLaunchKernelGGL(project_bwd_pose_kernel, dim3(nb, p->n_cams), dim3(kPoseBlock), 0, (hipStream_t)stream,
+                           *p, means, quats, scales, viewmats, Ks, radii, v_means2d, v_depths, v_conics,
+                           v_compensations, v_ray_ts, v_ray_planes, v_normals, (double*)workspace);
+        if (check_launch() != MISPLAT_OK) return MISPLAT_ELAUNCH;
+    }
+    hipLaunchKernelGGL(project_bwd_pose_final_kernel, dim3(p->n_cams), dim3(kPoseBlock), 0, (hipStream_t)stream,
+                       (const double*)workspace, nb, v_viewmats);
     return check_launch();
 }
 

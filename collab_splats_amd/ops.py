@@ -735,6 +735,13 @@ def fused_node_ok() -> bool:
     return FUSED_NODE and fused_entry_ok()
 
 
+# The packed nodes (_RasterFused, _ProjectPack, _ProjectPackX) form no gradient for ``viewmats``: entered with one asked
+# for they refuse instead of dropping it
+POSE_GRAD_MESSAGE = ("{node} forms no gradient for viewmats: a camera pose gradient takes the staged path -- call "
+                     "rasterization() (it routes there when viewmats.requires_grad) or ops.project() / "
+                     "fully_fused_projection(), whose backward runs misplat_project_bwd_pose")
+
+
 # A steady-state call is a function of its inputs' addresses: the arena hands the same slot to the same call, so the ~30 views
 # carved from it and the ~90 fields of the argument block come out identical every time.  They are kept ON THE SLOT
 # (arena.Slot.plan) keyed by everything that went into them; a call that finds its plan resets the pinned count, makes the one
@@ -759,6 +766,8 @@ class _RasterFused(torch.autograd.Function):
     def forward(ctx, means, quats, scales, opacities, colors, colors_rest, features, viewmats, Ks, P: Params, sh_degree,
                 depth_channel: bool, cd: int, absgrad: bool, extra: dict):
         import weakref
+        if ctx.needs_input_grad[7]:
+            raise NotImplementedError(POSE_GRAD_MESSAGE.format(node="_RasterFused"))
         require_gpu(means, quats, scales, opacities, colors, viewmats, Ks, features)
         if sh_degree is not None:
             kd = colors.shape[1] if colors_rest is None else 1 + colors_rest.shape[1]

@@ -58,7 +58,16 @@ class _Project(torch.autograd.Function):
         check(lib.misplat_project_bwd(C.byref(P), ptr(means), ptr(quats), ptr(scales), ptr(viewmats), ptr(Ks),
                                       ptr(radii), *[ptr(t) for t in g], ptr(v_means), ptr(v_quats),
                                       ptr(v_scales), stream_ptr()), "misplat_project_bwd")
-        return v_means, v_quats, v_scales, None, None, None, None
+        v_viewmats = None
+        if ctx.needs_input_grad[4]:
+            # camera pose gradient (csrc/project.hip: project_bwd_pose_kernel): the same gradient rows once more, summed per camera
+            nbytes = int(lib.misplat_project_bwd_pose_workspace(C.c_int32(P.n_gauss), C.c_int32(P.n_cams)))
+            work = torch.empty(nbytes, device=means.device, dtype=torch.uint8)
+            v_viewmats = torch.empty_like(viewmats)
+            check(lib.misplat_project_bwd_pose(C.byref(P), ptr(means), ptr(quats), ptr(scales), ptr(viewmats), ptr(Ks),
+                                               ptr(radii), *[ptr(t) for t in g], ptr(work), ptr(v_viewmats),
+                                               stream_ptr()), "misplat_project_bwd_pose")
+        return v_means, v_quats, v_scales, None, v_viewmats, None, None
 
 
 def project(means: Tensor, quats: Tensor, scales: Tensor, opacities: Optional[Tensor], viewmats: Tensor,
@@ -345,6 +354,8 @@ class _ProjectPack(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means, quats, scales, opacities, colors, colors_rest, viewmats, Ks, P: Params, sh_degree,
                 depth_channel: bool, prebin: Optional[dict] = None):
+        if ctx.needs_input_grad[6]:
+            raise NotImplementedError(_o.POSE_GRAD_MESSAGE.format(node="_ProjectPack"))
         lib = _lib.load()
         require_gpu(means, quats, scales, opacities, colors, viewmats, Ks)
         N, Cn = P.n_gauss, P.n_cams
@@ -559,6 +570,8 @@ class _ProjectPackX(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means, quats, scales, opacities, colors, viewmats, Ks, P: Params, depth_channel: bool, nxq: int):
+        if ctx.needs_input_grad[5]:
+            raise NotImplementedError(_o.POSE_GRAD_MESSAGE.format(node="_ProjectPackX"))
         lib = _lib.load()
         require_gpu(means, quats, scales, opacities, colors, viewmats, Ks)
         N, Cn = P.n_gauss, P.n_cams

@@ -222,6 +222,12 @@ class RadegsModelConfig:
     # applied to the training render (rade_gs_model.py:231-234), with its TV loss (:284-289); grid_shape = (GW, GH, L)
     use_bilateral_grid: bool = False
     grid_shape: Tuple[int, int, int] = (16, 16, 8)
+    # Splatfacto's camera optimizer [UNVERIFIED-UPSTREAM] (the ``camera_opt`` group of configs/rade_gs_method.py:72-77): a
+    # learned pose refinement per training camera, "off" | "SO3xR3" | "SE3" (camera_opt.py), applied to the training
+    # camera's view matrix; the rasterizer's viewmats gradient trains it
+    camera_optimizer_mode: str = "off"
+    camera_opt_trans_l2_penalty: float = 1e-2
+    camera_opt_rot_l2_penalty: float = 1e-3
 
 
 class RadegsModel(nn.Module):
@@ -244,6 +250,14 @@ class RadegsModel(nn.Module):
             if len(config.grid_shape) != 3:
                 raise ValueError(f"RadegsModel: grid_shape must be (GW, GH, L), got {tuple(config.grid_shape)}")
             self.bil_grids = BilateralGrid(int(num_train_data), *(int(v) for v in config.grid_shape))
+        if config.camera_optimizer_mode != "off":
+            # Splatfacto's ``camera_optimizer`` [UNVERIFIED-UPSTREAM]: one pose adjustment per training image
+            from .camera_opt import CameraOptimizer
+            if int(num_train_data) < 1:
+                raise ValueError(f"RadegsModel: camera_optimizer_mode {config.camera_optimizer_mode!r} needs num_train_data >= 1 "
+                                 f"(one pose adjustment per training camera), got {num_train_data}")
+            self.camera_optimizer = CameraOptimizer(int(num_train_data), config.camera_optimizer_mode,
+                                                    config.camera_opt_trans_l2_penalty, config.camera_opt_rot_l2_penalty)
         self.gauss_params = nn.ParameterDict({
             "means": nn.Parameter(means), "scales": nn.Parameter(scales), "quats": nn.Parameter(quats),
             "opacities": nn.Parameter(opacities.reshape(-1, 1)), "features_dc": nn.Parameter(features_dc),
@@ -384,6 +398,14 @@ class RadegsModel(nn.Module):
             W, H = int(camera.width.item()), int(camera.height.item())
             self.last_size = (H, W)
             camera_params = self._get_camera_parameters(camera)
+            cam_meta = getattr(camera, "metadata", None)
+            if (self.config.camera_optimizer_mode != "off" and self.training and cam_meta is not None
+                    and "cam_idx" in cam_meta):
+                # Splatfacto's ``camera_optimizer.apply_to_camera`` (the call the reference's get_outputs override dropped),
+                # on the OpenCV view matrix: the training render sees the refined pose, evaluation the stored one
+                vm = self.camera_optimizer.apply_to_viewmat(camera_params["viewmats"], int(cam_meta["cam_idx"]))
+                camera_params = dict(camera_params, viewmats=vm,
+                                     camera_center=-(vm[0, :3, :3].transpose(0, 1) @ vm[0, :3, 3]))
         finally:
             if saved is not None:
                 for k, v in saved.items():
@@ -437,7 +459,6 @@ class RadegsModel(nn.Module):
             ep = ops.outputs_epilogue(render, alpha, expected_depths, median_depths, expected_normals, bg_list, want_depth_im)
             rgb, expected_depths, median_depths, normals = ep[0], ep[1], ep[2], ep[3]
             depth_im = ep[4].squeeze(0) if want_depth_im else None
-        cam_meta = getattr(camera, "metadata", None)
         if self.config.use_bilateral_grid and self.training and cam_meta is not None and "cam_idx" in cam_meta:
             # rade_gs_model.py:231-234: the camera's colour transform, on the composited and clamped training render only
             rgb = ops.bilagrid_slice(rgb.contiguous(), self.bil_grids.grids, int(cam_meta["cam_idx"]))
@@ -1081,7 +1102,7 @@ class RadegsModel(nn.Module):
                 loss_dict["scale_reg"] = self._scale_reg(rgb.device)
             if with_dn:
                 loss_dict["depth_normal_loss"] = dn_loss
-            return self._add_tv_loss(loss_dict)
+            return self._add_camera_opt_loss(self._add_tv_loss(loss_dict))
         if gt is not None:
             if self.config.ssim_lambda > 0:
                 raise MisplatError(f"get_loss_dict: main_loss (L1 + SSIM) takes float32 images of equal shape on the GPU; got "
@@ -1092,7 +1113,14 @@ class RadegsModel(nn.Module):
         if with_dn:
             depth_normal_loss = ((1 - self.config.depth_ratio) * e1.mean() + self.config.depth_ratio * e2.mean())
             loss_dict["depth_normal_loss"] = self.config.depth_normal_lambda * depth_normal_loss
-        return self._add_tv_loss(loss_dict)
+        return self._add_camera_opt_loss(self._add_tv_loss(loss_dict))
+
+    def _add_camera_opt_loss(self, loss_dict: Dict[str, Tensor]) -> Dict[str, Tensor]:
+        """Splatfacto's ``camera_optimizer.get_loss_dict`` [UNVERIFIED-UPSTREAM]: the L2 regulariser of the pose adjustments,
+        while training with a camera optimizer; otherwise the dict as it is."""
+        if self.config.camera_optimizer_mode != "off" and self.training:
+            self.camera_optimizer.get_loss_dict(loss_dict)
+        return loss_dict
 
     def _add_tv_loss(self, loss_dict: Dict[str, Tensor]) -> Dict[str, Tensor]:
         """Splatfacto's "total variation loss (cameras)" (rade_gs_model.py:284-289) [UNVERIFIED-UPSTREAM]: 10 x the TV of every
@@ -1111,6 +1139,8 @@ class RadegsModel(nn.Module):
         groups = self.get_gaussian_param_groups()
         if self.config.use_bilateral_grid:
             groups["bilateral_grid"] = list(self.bil_grids.parameters())
+        if self.config.camera_optimizer_mode != "off":
+            self.camera_optimizer.get_param_groups(groups)              # "camera_opt" (configs/rade_gs_method.py:72-77)
         return groups
 
 

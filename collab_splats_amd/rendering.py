@@ -161,6 +161,12 @@ def rasterization(
     aa = rasterize_mode == "antialiased"
     viewmats = viewmats.contiguous().float()
     Ks = Ks.contiguous().float()
+    # a camera pose gradient (viewmats.requires_grad) exists on the generic staged path only: ops.project's backward forms
+    # it (misplat_project_bwd_pose) and the SH directions carry their share through the camera centres below.  The packed
+    # nodes refuse such a call, so it is routed here whatever its channel count.
+    pose_grad = viewmats.requires_grad and torch.is_grad_enabled()
+    if viewmats.requires_grad and not pose_grad:
+        viewmats = viewmats.detach()                       # (no gradient is being recorded: nothing for the packed nodes to refuse)
 
     if features is not None:
         if sh_degree is None or render_mode in ("D", "ED"):
@@ -171,13 +177,13 @@ def rasterization(
     if features is not None:
         n_user += features.shape[1]
     n_sh = (1 + colors[1].shape[1]) if split_sh else (colors.shape[1] if sh_degree is not None else 0)
-    fused = n_user + int(depth_channel) <= 4 and n_sh <= 16
+    fused = n_user + int(depth_channel) <= 4 and n_sh <= 16 and not pose_grad
     # N-D colours in one pass (a8): 5..20 channels, pass-through colours, atomic gradient mode
     n_total = n_user + int(depth_channel)
     fused_x = (ENABLE_ND_ONE_PASS and (not fused) and sh_degree is None and 5 <= n_total <= 20
-               and not ops.DETERMINISTIC_BACKWARD)
-    fused_feat = features is not None and ENABLE_ND_ONE_PASS and 5 <= n_total <= 20 and n_sh <= 16 and Cn == 1
-    if features is not None and not (fused_feat and ops.fused_node_ok() and N > 0):
+               and not ops.DETERMINISTIC_BACKWARD and not pose_grad)
+    fused_feat = features is not None and ENABLE_ND_ONE_PASS and 5 <= n_total <= 20 and n_sh <= 16 and Cn == 1 and not pose_grad
+    if features is not None and not pose_grad and not (fused_feat and ops.fused_node_ok() and N > 0):
         # outside the one-entry path (deterministic mode, > 20 channels, several cameras): as the reference composes it
         from .wrapper import spherical_harmonics
         coeffs = torch.cat((colors[0][:, None, :], colors[1]), dim=1) if split_sh else colors
@@ -257,6 +263,8 @@ def rasterization(
             dirs = means[None, :, :] - cam_centers[:, None, :]
             cols = ops.spherical_harmonics_raw(sh_degree, dirs, colors, radii)
             cols = torch.clamp_min(cols + 0.5, 0.0)                  # rade_features_model.py:438
+            if features is not None:                                 # (pose_grad only: :441, the features behind the colours)
+                cols = torch.cat((cols, features.float()[None].expand(Cn, N, features.shape[1])), dim=-1)
         else:
             cols = colors if colors.dim() == 3 else colors[None].expand(Cn, N, colors.shape[-1])
         if render_mode in ("RGB+D", "RGB+ED"):

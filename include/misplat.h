@@ -128,6 +128,20 @@ int misplat_project_bwd(const misplat_params* p, const float* means, const float
                         const float* v_ray_ts, const float* v_ray_planes, const float* v_normals,
                         float* v_means, float* v_quats, float* v_scales, misplat_stream_t stream);
 
+/* The view-matrix gradient of the same projection: v_viewmats[C,4,4] (fp32, fully overwritten, bottom rows zero) from the
+ * same inputs as misplat_project_bwd.  With Rw = V[c,:3,:3], t = V[c,:3,3]: v_V[c,:3,:3] = sum_g (v_mu (x) mean +
+ * v_Rc Rg(q)^T), v_V[c,:3,3] = sum_g v_mu over the rows with radii > 0.  fp64 sums in a fixed order (two launches, no
+ * atomics, no host read): two calls give the same bits.  Ks gets no gradient.  workspace: device memory of
+ * misplat_project_bwd_pose_workspace(n_gauss, n_cams) bytes (depends on the sizes only; NULL is MISPLAT_EINVAL).
+ * n_gauss == 0 writes zeros. */
+int64_t misplat_project_bwd_pose_workspace(int32_t n_gauss, int32_t n_cams);
+int misplat_project_bwd_pose(const misplat_params* p, const float* means, const float* quats,
+                             const float* scales, const float* viewmats, const float* Ks,
+                             const int32_t* radii, const float* v_means2d, const float* v_depths,
+                             const float* v_conics, const float* v_compensations,
+                             const float* v_ray_ts, const float* v_ray_planes, const float* v_normals,
+                             void* workspace, float* v_viewmats, misplat_stream_t stream);
+
 /* ---- a2.2 SH: spherical_harmonics(degrees_to_use, dirs, coeffs) (rade_features_model.py:430-434).
  * dirs[C*N,3] (normalised inside), coeffs[N,K,3] shared by the C cameras, radii[C*N,2] or NULL
  * (rows with radii==0 are skipped and get colour 0), colors[C*N,3] = raw SH (no +0.5). */
