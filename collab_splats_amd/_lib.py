@@ -137,6 +137,10 @@ SYMBOLS = {
     "misplat_meshclean_plane_count": (C.c_int, 8), "misplat_meshclean_plane_moments": (C.c_int, 9),
     "misplat_decimate_workspace": (C.c_int64, 2), "misplat_decimate_round": (C.c_int, 12),
     "misplat_decimate_apply": (C.c_int, 15), "misplat_decimate_resolve": (C.c_int, 4),
+    "misplat_meshfill_workspace": (C.c_int64, 2), "misplat_meshfill_round": (C.c_int, 10), "misplat_meshfill_apply": (C.c_int, 14),
+    "misplat_meshfill_fair_workspace": (C.c_int64, 4), "misplat_meshfill_fair_count": (C.c_int, 8),
+    "misplat_meshfill_fair_build": (C.c_int, 11), "misplat_meshfill_fair_step": (C.c_int, 16),
+    "misplat_meshfill_fair_lds": (C.c_int, 13), "misplat_meshfill_fair_finish": (C.c_int, 5),
     "misplat_depthcloud_workspace": (C.c_int64, 4), "misplat_depthcloud_edges": (C.c_int, 10),
     "misplat_depthcloud_candidates": (C.c_int, 7), "misplat_depthcloud_sample": (C.c_int, 15),
     "misplat_depthcloud_backproject": (C.c_int, 15), "misplat_depthcloud_gaussian_filter": (C.c_int, 10),

@@ -64,6 +64,8 @@ SOURCES = {
     "density.hip": ["-ffp-contract=off"],
     # decimate.hip: the same: quadrics, collapse targets and cost bits (the selection's priority) equal the fp64 restatement (tests/)
     "decimate.hip": ["-ffp-contract=off"],
+    # meshfill.hip: the same: edge lengths (the split priority), midpoints and the fp64 neighbour means equal the restatement (tests/)
+    "meshfill.hip": ["-ffp-contract=off"],
 }
 
 

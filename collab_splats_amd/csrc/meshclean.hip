@@ -18,6 +18,7 @@
 #include "radixsort.h"
 #include "unionfind.h"
 #include "hashmix.h"
+#include "meshedge.h"
 
 namespace {
 
@@ -29,29 +30,11 @@ struct EdgeTable {
     unsigned long long mask;
 };
 
-__device__ __forceinline__ unsigned long long edge_key(int32_t a, int32_t b) {
-    const uint32_t lo = (uint32_t)(a < b ? a : b), hi = (uint32_t)(a < b ? b : a);
-    return ((unsigned long long)lo << 32) | hi;
-}
-
-__device__ __forceinline__ unsigned long long edge_home(unsigned long long key, unsigned long long mask) {
-    key ^= key >> 31;
-    key *= 0x7fb5d329728ea185ull;
-    key ^= key >> 27;
-    return key & mask;
-}
-
 // the slot of an edge that was inserted
 __device__ __forceinline__ int64_t edge_find(const EdgeTable& E, unsigned long long key) {
     unsigned long long s = edge_home(key, E.mask);
     while (E.keys[s] != key) s = (s + 1) & E.mask;
     return (int64_t)s;
-}
-
-// corner c of face f: the directed edge tri[3 f + c] -> tri[3 f + (c + 1) % 3]
-__device__ __forceinline__ void corner_edge(const int32_t* __restrict__ tri, int64_t f, int c, int32_t& a, int32_t& b) {
-    a = tri[3 * f + c];
-    b = tri[3 * f + (c == 2 ? 0 : c + 1)];
 }
 
 __global__ __launch_bounds__(256) void edge_insert_kernel(const int32_t* __restrict__ tri, int64_t T, EdgeTable E) {
@@ -81,12 +64,6 @@ __global__ __launch_bounds__(256) void edge_count_kernel(EdgeTable E, int64_t ca
 
 // ------------------------------------------------------------------------------------------------- fixed-order sums
 // wgprims.h's: K doubles per thread through block_sums<K>, the workgroup partials through sum_final_kernel<K, 256>.
-__device__ __forceinline__ float edge_length(const float* __restrict__ V, int32_t a, int32_t b) {
-    const float dx = V[3 * (int64_t)b] - V[3 * (int64_t)a], dy = V[3 * (int64_t)b + 1] - V[3 * (int64_t)a + 1],
-                dz = V[3 * (int64_t)b + 2] - V[3 * (int64_t)a + 2];
-    return sqrtf((dx * dx + dy * dy) + dz * dz);
-}
-
 // Every undirected edge once, in an order the table has no part in: at the lowest corner of its smallest incident face.
 __global__ __launch_bounds__(256) void edge_length_kernel(const float* __restrict__ V, const int32_t* __restrict__ tri, int64_t T,
                                                           EdgeTable E, double* __restrict__ part) {

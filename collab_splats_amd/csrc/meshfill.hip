@@ -1,0 +1,861 @@
+// meshfill.hip -- hole patches at the mesh's own resolution: longest-edge bisection of a face region in
+// rounds of edges that share no face, and membrane fairing (uniform-weight Jacobi with everything that is not free held
+// fixed) of patches of free vertices, each to its own tolerance.
+//
+// Semantics: tests/meshfill_restatement.py is the oracle, bit for bit.  Compiled with -ffp-contract=off: every fp32 and fp64
+// expression is evaluated in the written order.  Integer atomics only (the edge table's counts and faces, the maxima of the
+// displacement's bits); every fp64 sum runs over a sorted CSR row in ascending order: two runs are bitwise equal.
+//
+// Subdivision, one round (misplat_meshfill_round): the edge table of the current mesh -- meshclean.hip's, with the largest
+// incident face beside the smallest, which names both faces of a two-face edge; per corner the length bits of a splittable
+// edge; per face the corner of its first splittable edge in priority; per face again whether that edge is first in its other
+// face too (it is then selected); two scans number the selected edges and the faces they split.  The host reads the two
+// totals, makes room, and misplat_meshfill_apply writes the midpoints and the faces.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "misplat.h"
+#include "internal.h"
+#include "wgprims.h"
+#include "radixsort.h"
+#include "unionfind.h"
+#include "hashmix.h"
+#include "meshedge.h"
+
+namespace {
+
+typedef unsigned long long u64;
+
+// ----------------------------------------------------------------------------------------------------- edge table
+struct EdgeTable {
+    u64* keys;
+    int32_t *cnt, *fmin, *fmax;
+    u64 mask;
+};
+
+__device__ __forceinline__ int64_t edge_find(const EdgeTable& E, u64 key) {
+    u64 s = edge_home(key, E.mask);
+    while (E.keys[s] != key) s = (s + 1) & E.mask;
+    return (int64_t)s;
+}
+
+__global__ __launch_bounds__(256) void edge_insert_kernel(const int32_t* __restrict__ tri, int64_t T, EdgeTable E) {
+    const int64_t h = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (h >= 3 * T) return;
+    const int64_t f = h / 3;
+    int32_t a, b;
+    corner_edge(tri, f, (int)(h - 3 * f), a, b);
+    if (a == b) return;
+    const u64 key = edge_key(a, b);
+    const u64 s = claim_slot(E.keys, E.mask, edge_home(key, E.mask), key);
+    atomicAdd(&E.cnt[s], 1);
+    atomicMin(&E.fmin[s], (int32_t)f);
+    atomicMax(&E.fmax[s], (int32_t)f);
+}
+
+__device__ __forceinline__ bool repeated(const int32_t* __restrict__ tri, int64_t f) {
+    const int32_t a = tri[3 * f], b = tri[3 * f + 1], c = tri[3 * f + 2];
+    return a == b || b == c || a == c;
+}
+
+// ------------------------------------------------------------------------------------------------------ selection
+// sbits[h] = the fp32 bits of the length of corner h's edge if it is splittable (one incident face or two distinct ones, all
+// in the region, none with a repeated corner, length > max_len), else 0 (no length above max_len > 0 has these bits)
+__global__ __launch_bounds__(256) void splittable_kernel(const float* __restrict__ V, const int32_t* __restrict__ tri, int64_t T,
+                                                         const uint8_t* __restrict__ region, EdgeTable E, float max_len,
+                                                         uint32_t* __restrict__ sbits) {
+    const int64_t h = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (h >= 3 * T) return;
+    const int64_t f = h / 3;
+    int32_t a, b;
+    corner_edge(tri, f, (int)(h - 3 * f), a, b);
+    uint32_t bits = 0;
+    if (a != b) {
+        const int64_t s = edge_find(E, edge_key(a, b));
+        const int32_t n = E.cnt[s], f0 = E.fmin[s], f1 = E.fmax[s];
+        if ((n == 1 || (n == 2 && f0 != f1)) && region[f0] && region[f1] && !repeated(tri, f0) && !repeated(tri, f1)) {
+            const float len = edge_length(V, a, b);
+            if (len > max_len) bits = __float_as_uint(len);
+        }
+    }
+    sbits[h] = bits;
+}
+
+// the priority of a splittable edge: larger length bits first, then the smaller mix32(lo, hi, 0), then the smaller key
+struct Prio {
+    uint32_t bits, mix;
+    u64 key;
+};
+__device__ __forceinline__ Prio prio_of(uint32_t bits, int32_t a, int32_t b) {
+    const u64 key = edge_key(a, b);
+    return Prio{bits, mix32((uint32_t)(key >> 32), (uint32_t)key, 0u), key};
+}
+__device__ __forceinline__ bool before(const Prio& x, const Prio& y) {
+    if (x.bits != y.bits) return x.bits > y.bits;
+    if (x.mix != y.mix) return x.mix < y.mix;
+    return x.key < y.key;
+}
+
+// best[f] = the corner of face f's first splittable edge in priority, -1 if it has none
+__global__ __launch_bounds__(256) void face_best_kernel(const int32_t* __restrict__ tri, int64_t T, const uint32_t* __restrict__ sbits,
+                                                        int32_t* __restrict__ best) {
+    const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (f >= T) return;
+    int32_t bc = -1;
+    Prio bp = {};
+    for (int c = 0; c < 3; c++) {
+        const uint32_t bits = sbits[3 * f + c];
+        if (!bits) continue;
+        int32_t a, b;
+        corner_edge(tri, f, c, a, b);
+        const Prio p = prio_of(bits, a, b);
+        if (bc < 0 || before(p, bp)) { bc = c; bp = p; }
+    }
+    best[f] = bc;
+}
+
+// Face f's first edge is selected iff it is the first edge of its other face too.  owner[f] = the slot (3 face + corner, at
+// the edge's smallest face) that numbers the selected edge, -1 if f is not split; fsplit[f] = 1 / 0; flag[3 f + c] = 1 at the
+// owner slots.
+__global__ __launch_bounds__(256) void select_kernel(const int32_t* __restrict__ tri, int64_t T, EdgeTable E,
+                                                     const int32_t* __restrict__ best, int32_t* __restrict__ owner,
+                                                     int32_t* __restrict__ fsplit, int32_t* __restrict__ flag) {
+    const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (f >= T) return;
+    const int32_t c = best[f];
+    int32_t own = -1;
+    if (c >= 0) {
+        int32_t a, b;
+        corner_edge(tri, f, c, a, b);
+        const u64 key = edge_key(a, b);
+        const int64_t s = edge_find(E, key);
+        const int32_t f0 = E.fmin[s], f1 = E.fmax[s];
+        const int32_t g = f0 == (int32_t)f ? f1 : f0;
+        bool sel = true;
+        int32_t c0 = c;                                     // the edge's corner in its smallest face
+        if (g != (int32_t)f) {
+            const int32_t cg = best[g];
+            sel = false;
+            if (cg >= 0) {
+                int32_t ga, gb;
+                corner_edge(tri, g, cg, ga, gb);
+                sel = edge_key(ga, gb) == key;
+            }
+            if (g == f0) c0 = cg;
+        }
+        if (sel) own = 3 * f0 + c0;
+    }
+    owner[f] = own;
+    fsplit[f] = own >= 0 ? 1 : 0;
+    for (int k = 0; k < 3; k++) flag[3 * f + k] = (own == (int32_t)(3 * f + k)) ? 1 : 0;
+}
+
+__global__ void totals_kernel(const int32_t* __restrict__ spos, const int32_t* __restrict__ frank, int64_t T, int32_t* __restrict__ counts) {
+    counts[0] = spos[3 * T];
+    counts[1] = frank[T];
+}
+
+// ---------------------------------------------------------------------------------------------------------- landing
+// the owner slots in slot order
+__global__ __launch_bounds__(256) void gather_kernel(const int32_t* __restrict__ flag, const int32_t* __restrict__ spos, int64_t n,
+                                                     int64_t S, int32_t* __restrict__ list) {
+    const int64_t h = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (h < n && flag[h] && spos[h] < S) list[spos[h]] = (int32_t)h;
+}
+
+// one 32-bit digit of the priority of the listed edges: 0 hi, 1 lo, 2 mix, 3 the complement of the length bits
+__global__ __launch_bounds__(256) void digit_kernel(const int32_t* __restrict__ tri, const uint32_t* __restrict__ sbits,
+                                                    const int32_t* __restrict__ list, int64_t S, int which, int32_t* __restrict__ key) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= S) return;
+    const int32_t h = list[i];
+    const int64_t f = h / 3;
+    int32_t a, b;
+    corner_edge(tri, f, (int)(h - 3 * f), a, b);
+    const Prio p = prio_of(sbits[h], a, b);
+    key[i] = (int32_t)(which == 0 ? (uint32_t)p.key : which == 1 ? (uint32_t)(p.key >> 32) : which == 2 ? p.mix : ~p.bits);
+}
+
+// the listed edges are in priority order: those from `limit` on are dropped
+__global__ __launch_bounds__(256) void drop_kernel(const int32_t* __restrict__ list, int64_t S, int64_t limit, int32_t* __restrict__ flag) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < S && i >= limit) flag[list[i]] = 0;
+}
+
+__global__ __launch_bounds__(256) void restrict_kernel(int64_t T, const int32_t* __restrict__ flag, int32_t* __restrict__ owner,
+                                                       int32_t* __restrict__ fsplit) {
+    const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (f >= T || owner[f] < 0 || flag[owner[f]]) return;
+    owner[f] = -1;
+    fsplit[f] = 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------ apply
+// owner slot h, number s: vertex M + s = 0.5f (x_lo + x_hi), every attribute channel the same
+__global__ __launch_bounds__(256) void midpoint_kernel(float* __restrict__ V, int64_t M, const int32_t* __restrict__ tri, int64_t T,
+                                                       const int32_t* __restrict__ flag, const int32_t* __restrict__ spos,
+                                                       float* __restrict__ att, int D) {
+    const int64_t h = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (h >= 3 * T || !flag[h]) return;
+    const int64_t f = h / 3;
+    int32_t a, b;
+    corner_edge(tri, f, (int)(h - 3 * f), a, b);
+    const int64_t lo = a < b ? a : b, hi = a < b ? b : a, m = M + spos[h];
+    for (int k = 0; k < 3; k++) V[3 * m + k] = 0.5f * (V[3 * lo + k] + V[3 * hi + k]);
+    for (int k = 0; k < D; k++) att[m * D + k] = 0.5f * (att[lo * D + k] + att[hi * D + k]);
+}
+
+// face f = (a, b, c) rotated so that a -> b is its selected edge: (a, m, c) in slot f, (m, b, c) in slot T + rank(f)
+__global__ __launch_bounds__(256) void split_kernel(int32_t* __restrict__ tri, int64_t M, int64_t T, const int32_t* __restrict__ best,
+                                                    const int32_t* __restrict__ owner, const int32_t* __restrict__ spos,
+                                                    const int32_t* __restrict__ frank, uint8_t* __restrict__ region,
+                                                    int32_t* __restrict__ origin) {
+    const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (f >= T || owner[f] < 0) return;
+    const int c = best[f];
+    const int32_t a = tri[3 * f + c], b = tri[3 * f + (c + 1) % 3], d = tri[3 * f + (c + 2) % 3];
+    const int32_t m = (int32_t)(M + spos[owner[f]]);
+    const int64_t g = T + frank[f];
+    tri[3 * f] = a; tri[3 * f + 1] = m; tri[3 * f + 2] = d;
+    tri[3 * g] = m; tri[3 * g + 1] = b; tri[3 * g + 2] = d;
+    region[g] = region[f];
+    origin[g] = origin[f];
+}
+
+// ------------------------------------------------------------------------------------------------------- workspace
+inline int64_t edge_capacity(int64_t T) {
+    int64_t cap = 64;
+    while (cap < 6 * T) cap <<= 1;
+    return cap;
+}
+
+inline int64_t max2(int64_t a, int64_t b) { return a > b ? a : b; }
+
+struct Work {
+    int64_t cap;
+    u64* keys;
+    int32_t *cnt, *fmin, *fmax;
+    uint32_t* sbits;
+    int32_t *best, *owner, *fsplit, *flag, *spos, *frank;
+    int32_t *sk, *sv, *skb, *svb;                 // the landing sort of the selected edges (at most one per face)
+    int32_t* scr;
+    SortBufs sort;
+};
+
+inline Work carve(Carver& c, int64_t T) {
+    Work W = {};
+    W.cap = edge_capacity(T);
+    W.keys = c.take<u64>(W.cap);
+    W.cnt = c.take<int32_t>(W.cap);
+    W.fmin = c.take<int32_t>(W.cap);
+    W.fmax = c.take<int32_t>(W.cap);
+    W.sbits = c.take<uint32_t>(3 * T);
+    W.best = c.take<int32_t>(T);
+    W.owner = c.take<int32_t>(T);
+    W.fsplit = c.take<int32_t>(T);
+    W.flag = c.take<int32_t>(3 * T);
+    W.spos = c.take<int32_t>(3 * T + 1);
+    W.frank = c.take<int32_t>(T + 1);
+    W.sk = c.take<int32_t>(T); W.sv = c.take<int32_t>(T); W.skb = c.take<int32_t>(T); W.svb = c.take<int32_t>(T);
+    W.scr = take_scan(c, max2(3 * T + 1, 256 * ((T + kTile - 1) / kTile) + 1));
+    W.sort = take_sort(c, T);
+    return W;
+}
+
+inline bool sizes_ok(int64_t M, int64_t T) { return M >= 1 && M < (1ll << 31) && T >= 1 && 6 * T < (1ll << 31) - kTile; }
+
+inline void number(const Work& W, int64_t T, int32_t* counts, hipStream_t s) {
+    scan(W.flag, 3 * T, W.spos, W.scr, s);
+    scan(W.fsplit, T, W.frank, W.scr, s);
+    hipLaunchKernelGGL(totals_kernel, dim3(1), dim3(1), 0, s, (const int32_t*)W.spos, (const int32_t*)W.frank, T, counts);
+}
+
+// ========================================================================================================== fairing
+// The free vertices in ascending order (fl[k]); a CSR of their rows only: the directed edges whose source is free, as (key =
+// target, value = the source's free index), sorted by target and then stably by source; patches = the components of the free
+// vertices under edges with both ends free (union-find over the free indices: a patch's root is its smallest vertex).
+__global__ __launch_bounds__(256) void free_flag_kernel(const uint8_t* __restrict__ free, int64_t M, int32_t* __restrict__ f32) {
+    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (v < M) f32[v] = free[v] ? 1 : 0;
+}
+
+// directed edge 2 h + d of corner h: d = 0 as the face runs, d = 1 against it
+__device__ __forceinline__ void directed(const int32_t* __restrict__ tri, int64_t e, int32_t& src, int32_t& tgt) {
+    const int64_t h = e >> 1, f = h / 3;
+    int32_t a, b;
+    corner_edge(tri, f, (int)(h - 3 * f), a, b);
+    src = (e & 1) ? b : a;
+    tgt = (e & 1) ? a : b;
+}
+
+__global__ __launch_bounds__(256) void free_edge_flag_kernel(const int32_t* __restrict__ tri, int64_t E6, const uint8_t* __restrict__ free,
+                                                             int32_t* __restrict__ eflag) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= E6) return;
+    int32_t src, tgt;
+    directed(tri, e, src, tgt);
+    eflag[e] = (src != tgt && free[src]) ? 1 : 0;
+}
+
+__global__ void fair_totals_kernel(const int32_t* __restrict__ fidx, int64_t M, const int32_t* __restrict__ epos, int64_t E6,
+                                   int32_t* __restrict__ counts) {
+    counts[0] = fidx[M];
+    counts[1] = epos[E6];
+}
+
+__global__ __launch_bounds__(256) void free_list_kernel(const uint8_t* __restrict__ free, const int32_t* __restrict__ fidx, int64_t M,
+                                                        int64_t n_free, int32_t* __restrict__ fl) {
+    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (v < M && free[v] && fidx[v] < n_free) fl[fidx[v]] = (int32_t)v;
+}
+
+__global__ __launch_bounds__(256) void free_edge_emit_kernel(const int32_t* __restrict__ tri, int64_t E6, const int32_t* __restrict__ eflag,
+                                                             const int32_t* __restrict__ epos, const int32_t* __restrict__ fidx,
+                                                             int64_t Ef, int32_t* __restrict__ tgt_out, int32_t* __restrict__ src_out) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= E6 || !eflag[e] || epos[e] >= Ef) return;
+    int32_t src, tgt;
+    directed(tri, e, src, tgt);
+    tgt_out[epos[e]] = tgt;
+    src_out[epos[e]] = fidx[src];
+}
+
+// rows[2 k], rows[2 k + 1] = free vertex k's part of the sorted edges (zeroed by the caller)
+__global__ __launch_bounds__(256) void rows_kernel(const int32_t* __restrict__ key, int64_t E, int32_t* __restrict__ rows) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= E) return;
+    const int32_t s = key[e];
+    if (e == 0 || key[e - 1] != s) rows[2 * (int64_t)s] = (int32_t)e;
+    if (e == E - 1 || key[e + 1] != s) rows[2 * (int64_t)s + 1] = (int32_t)(e + 1);
+}
+
+__global__ __launch_bounds__(256) void patch_init_kernel(int64_t n, int32_t* __restrict__ parent, int32_t* __restrict__ iters,
+                                                         uint32_t* __restrict__ disp) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= n) return;
+    parent[k] = (int32_t)k;
+    iters[k] = 0;
+    disp[k] = 0xffffffffu;                                  // "iteration 0" moved every patch: nothing has stopped before 1
+    disp[n + k] = 0u;
+    disp[2 * n + k] = 0u;
+}
+
+__global__ __launch_bounds__(256) void patch_union_kernel(const int32_t* __restrict__ src, const int32_t* __restrict__ tgt, int64_t Ef,
+                                                          const uint8_t* __restrict__ free, const int32_t* __restrict__ fidx,
+                                                          int32_t* __restrict__ parent) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= Ef) return;
+    const int32_t j = tgt[e];
+    if (free[j]) (void)unite(parent, src[e], fidx[j]);
+}
+
+__global__ __launch_bounds__(256) void patch_root_kernel(const int32_t* __restrict__ parent, int64_t n, int32_t* __restrict__ root,
+                                                         int32_t* __restrict__ isroot) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= n) return;
+    int32_t r = (int32_t)k;
+    for (int32_t p = parent[r]; p != r; p = parent[r]) r = p;
+    root[k] = r;
+    isroot[k] = r == (int32_t)k ? 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void patch_label_kernel(const int32_t* __restrict__ root, const int32_t* __restrict__ rank, int64_t n,
+                                                          int32_t* __restrict__ pid, int32_t* __restrict__ counts) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k == 0) counts[2] = rank[n];
+    if (k < n) pid[k] = rank[root[k]];
+}
+
+// What an iteration reads (built once per call, kept in the workspace).
+struct Fair {
+    const int32_t *fl, *rows, *nbr, *pid, *isroot;
+};
+
+// x_i' = fp32(sum_j (double) x_j / |N(i)|) over the distinct neighbours in ascending order (a repeat follows its twin); no
+// neighbour: unchanged.  The row is read kRowChunk entries at a time, the entries first and then their values: loads that do
+// not wait for each other (every launch finds the values cold: another XCD's L2 wrote them), then the sum in order.  (Chunks
+// of 8 and of 32 measured the same on the hole-fill timing script: the rows are not what a launch waits for.)
+constexpr int kRowChunk = 32;
+constexpr int kLdsRowChunk = 16;                            // (the LDS kernel holds three values per entry in registers)
+constexpr int32_t kNoEntry = INT32_MIN;                     // no vertex, no place in a patch and no complement of a vertex
+
+__device__ __forceinline__ float membrane(const float* __restrict__ in, int D, int c, const Fair& F, int64_t k, float x) {
+    double S = 0.0;
+    int32_t cnt = 0, prev = kNoEntry;
+    const int32_t r0 = F.rows[2 * k], r1 = F.rows[2 * k + 1];
+    for (int32_t e0 = r0; e0 < r1; e0 += kRowChunk) {
+        int32_t j[kRowChunk];
+        float v[kRowChunk];
+#pragma unroll
+        for (int u = 0; u < kRowChunk; u++) j[u] = e0 + u < r1 ? F.nbr[e0 + u] : kNoEntry;
+#pragma unroll
+        for (int u = 0; u < kRowChunk; u++) v[u] = j[u] != kNoEntry ? in[(int64_t)j[u] * D + c] : 0.f;
+#pragma unroll
+        for (int u = 0; u < kRowChunk; u++)
+            if (j[u] != kNoEntry && j[u] != prev) {
+                prev = j[u];
+                S += (double)v[u];
+                cnt++;
+            }
+    }
+    return cnt ? (float)(S / (double)cnt) : x;
+}
+
+// Iteration n, one lane per (free vertex k, channel c) of values [M, D].  Measured mode (fixed = 0): patch p has stopped iff
+// iters[p] is set or the displacement of iteration n - 1 (d_prev, complete: the previous launch) is below the tolerance; its
+// root then records n - 1 once.  A stopped patch is copied.  A running one moves, and the bits of max |x' - x| go into
+// d_cur[p] by an integer maximum; the root clears d_next[p] for iteration n + 1 (d_next was last read in iteration n - 1).
+// Counted mode (fixed = 1): patch p runs iff n <= iters[p].
+constexpr int kStepThreads = 256;
+
+__global__ __launch_bounds__(kStepThreads) void fair_step_kernel(const float* __restrict__ in, float* __restrict__ out, int D,
+                                                                 int64_t n_free, Fair F, int32_t* __restrict__ iters,
+                                                                 const uint32_t* __restrict__ d_prev, uint32_t* __restrict__ d_cur,
+                                                                 uint32_t* __restrict__ d_next, uint32_t tol_bits, int32_t n, int fixed) {
+    __shared__ int32_t wave_p[kStepThreads / 64];
+    __shared__ uint32_t wave_m[kStepThreads / 64];
+    const int64_t idx = (int64_t)blockIdx.x * kStepThreads + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    bool moving = false;                                    // (no lane leaves before the workgroup's maxima below)
+    int32_t p = -1;
+    uint32_t bits = 0u;
+    if (idx < n_free * D) {
+        const int64_t k = idx / D;
+        const int c = (int)(idx - k * D);
+        const int64_t at = (int64_t)F.fl[k] * D + c;
+        p = F.pid[k];
+        // A plain load beside the root's store below: in the one launch that stores, `now` holds for every lane of the patch,
+        // so either value read gives the same answer; every later launch sees the store.
+        const int32_t it = iters[p];
+        if (fixed) {
+            moving = n <= it;
+        } else {
+            const bool now = d_prev[p] < tol_bits;
+            moving = it == 0 && !now;
+            if (c == 0 && F.isroot[k]) {
+                if (it == 0 && now) iters[p] = n - 1;
+                d_next[p] = 0u;
+            }
+        }
+        const float x = in[at];
+        const float y = moving ? membrane(in, D, c, F, k, x) : x;
+        out[at] = y;
+        bits = __float_as_uint(fabsf(y - x));
+    }
+    if (fixed) return;                                      // (uniform)
+    // The maxima reach memory as few integer atomics as the patches allow.  A wave whose moving lanes are of one patch hands
+    // (patch, maximum) to the workgroup, where lane 0 merges neighbouring waves of one patch into one atomic; a wave of several
+    // patches (subdivision numbers a round's vertices across all holes, so late rounds interleave the patches in the list)
+    // issues one per lane, and none where the patch's word is already as large.
+    const unsigned long long mv = __ballot(moving);
+    int32_t wp = -1;
+    uint32_t m = 0u;
+    if (mv) {
+        const int leader = __ffsll((long long)mv) - 1;
+        const int32_t p0 = __shfl(p, leader);
+        if (__ballot(moving && p != p0) == 0ull) {
+            wp = p0;
+            m = moving ? bits : 0u;
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                const uint32_t o = (uint32_t)__shfl_xor((int)m, off);
+                m = o > m ? o : m;
+            }
+        } else if (moving && bits > __hip_atomic_load(d_cur + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
+            atomicMax(d_cur + p, bits);                     // (none where the patch's word is already as large)
+        }
+    }
+    if (lane == 0) { wave_p[threadIdx.x >> 6] = wp; wave_m[threadIdx.x >> 6] = m; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int32_t cp = -1;
+        uint32_t cm = 0u;
+        for (int w = 0; w < kStepThreads / 64; w++) {
+            if (wave_p[w] < 0) continue;
+            if (wave_p[w] != cp) {
+                if (cp >= 0) atomicMax(d_cur + cp, cm);
+                cp = wave_p[w];
+                cm = 0u;
+            }
+            cm = wave_m[w] > cm ? wave_m[w] : cm;
+        }
+        if (cp >= 0) atomicMax(d_cur + cp, cm);
+    }
+}
+
+// counts[3] = the patches that are still running after the iteration whose displacements are d_last
+__global__ __launch_bounds__(256) void running_kernel(const int32_t* __restrict__ iters, const uint32_t* __restrict__ d_last,
+                                                      uint32_t tol_bits, int32_t* __restrict__ counts) {
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p < counts[2] && iters[p] == 0 && !(d_last[p] < tol_bits)) atomicAdd(&counts[3], 1);
+}
+
+// a patch that was never seen stopped took every iteration that ran
+__global__ __launch_bounds__(256) void finish_kernel(int32_t* __restrict__ iters, int32_t n_done, const int32_t* __restrict__ counts) {
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p < counts[2] && iters[p] == 0) iters[p] = n_done;
+}
+
+
+// ------------------------------------------------------------------------------------------------------- LDS path
+// A patch of at most MISPLAT_MESHFILL_LDS_VERTICES free vertices runs ALL its iterations in one workgroup: both iterates of
+// its vertices in LDS (24 B a vertex), a barrier between iterations instead of a launch.  The patch's vertices are listed by
+// patch (plist, prow); every CSR entry is translated once (lnbr): >= 0 the neighbour's place in its patch's list (a free
+// neighbour is in the same patch by definition), < 0 the complement of a fixed vertex, read from memory (it never changes).
+// Same rows, same order, same arithmetic as fair_step_kernel: the same bits and the same iteration counts.
+constexpr int kLdsVertices = MISPLAT_MESHFILL_LDS_VERTICES;
+constexpr int kLdsThreads = 1024;
+
+__global__ __launch_bounds__(256) void patch_keys_kernel(const int32_t* __restrict__ pid, int64_t n, int32_t* __restrict__ key,
+                                                         int32_t* __restrict__ val) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k < n) { key[k] = pid[k]; val[k] = (int32_t)k; }
+}
+
+__global__ __launch_bounds__(256) void patch_place_kernel(const int32_t* __restrict__ plist, const int32_t* __restrict__ pkey,
+                                                          const int32_t* __restrict__ prow, int64_t n, int32_t* __restrict__ loc) {
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (q < n) loc[plist[q]] = (int32_t)(q - prow[2 * (int64_t)pkey[q]]);
+}
+
+__global__ __launch_bounds__(256) void local_edges_kernel(const int32_t* __restrict__ nbr, int64_t Ef, const int32_t* __restrict__ f32,
+                                                          const int32_t* __restrict__ fidx, const int32_t* __restrict__ loc,
+                                                          int32_t* __restrict__ lnbr) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= Ef) return;
+    const int32_t j = nbr[e];
+    lnbr[e] = f32[j] ? loc[fidx[j]] : ~j;
+}
+
+__global__ __launch_bounds__(kLdsThreads) void fair_lds_kernel(float* __restrict__ pos, Fair F, const int32_t* __restrict__ plist,
+                                                               const int32_t* __restrict__ prow, const int32_t* __restrict__ lnbr,
+                                                               uint32_t tol_bits, int32_t max_it, int32_t* __restrict__ iters,
+                                                               int32_t* __restrict__ counts) {
+    __shared__ float X[2][3 * kLdsVertices];
+    __shared__ uint32_t wmax[kLdsThreads / 64];
+    const int32_t p = blockIdx.x;
+    const int32_t k0 = prow[2 * (int64_t)p], nv = prow[2 * (int64_t)p + 1] - k0;
+    if (nv > kLdsVertices) {                                     // (uniform) left to the launches per iteration
+        if (threadIdx.x == 0) atomicAdd(&counts[3], 1);
+        return;
+    }
+    for (int32_t idx = threadIdx.x; idx < 3 * nv; idx += kLdsThreads) {
+        const int32_t l = idx / 3;
+        X[0][idx] = pos[3 * (int64_t)F.fl[plist[k0 + l]] + (idx - 3 * l)];
+    }
+    __syncthreads();
+    int32_t it = 0;
+    while (it < max_it) {
+        const float* in = X[it & 1];
+        float* out = X[(it & 1) ^ 1];
+        uint32_t mine = 0u;
+        for (int32_t l = threadIdx.x; l < nv; l += kLdsThreads) {            // one lane per vertex: its row is read once
+            const int64_t k = plist[k0 + l];
+            double S[3] = {0.0, 0.0, 0.0};
+            int32_t cnt = 0, prev = kNoEntry;
+            const int32_t r0 = F.rows[2 * k], r1 = F.rows[2 * k + 1];
+            for (int32_t e0 = r0; e0 < r1; e0 += kLdsRowChunk) {              // as membrane(): entries, then values, then the sum
+                int32_t q[kLdsRowChunk];
+                float v[kLdsRowChunk][3];
+#pragma unroll
+                for (int u = 0; u < kLdsRowChunk; u++) q[u] = e0 + u < r1 ? lnbr[e0 + u] : kNoEntry;
+#pragma unroll
+                for (int u = 0; u < kLdsRowChunk; u++) {
+                    const float* from = q[u] >= 0 ? in + 3 * q[u] : q[u] != kNoEntry ? pos + 3 * (int64_t)(~q[u]) : in;
+#pragma unroll
+                    for (int c = 0; c < 3; c++) v[u][c] = from[c];
+                }
+#pragma unroll
+                for (int u = 0; u < kLdsRowChunk; u++)
+                    if (q[u] != kNoEntry && q[u] != prev) {
+                        prev = q[u];
+#pragma unroll
+                        for (int c = 0; c < 3; c++) S[c] += (double)v[u][c];
+                        cnt++;
+                    }
+            }
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                const float x = in[3 * l + c];
+                const float y = cnt ? (float)(S[c] / (double)cnt) : x;
+                out[3 * l + c] = y;
+                const uint32_t bits = __float_as_uint(fabsf(y - x));
+                mine = bits > mine ? bits : mine;
+            }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const uint32_t o = (uint32_t)__shfl_xor((int)mine, off);
+            mine = o > mine ? o : mine;
+        }
+        if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = mine;
+        __syncthreads();                                         // the new iterate and the waves' maxima are written
+        uint32_t all = 0u;
+#pragma unroll
+        for (int w = 0; w < kLdsThreads / 64; w++) all = wmax[w] > all ? wmax[w] : all;
+        __syncthreads();                                         // wmax is read before the next iteration writes it
+        it++;
+        if (all < tol_bits) break;                               // (uniform)
+    }
+    const float* fin = X[it & 1];
+    for (int32_t idx = threadIdx.x; idx < 3 * nv; idx += kLdsThreads) {
+        const int32_t l = idx / 3;
+        pos[3 * (int64_t)F.fl[plist[k0 + l]] + (idx - 3 * l)] = fin[idx];
+    }
+    if (threadIdx.x == 0) iters[p] = it;
+}
+
+struct FairWork {
+    int32_t *f32, *fidx, *eflag, *epos;           // the part the count call uses: M and T alone size it
+    int32_t *fl, *ka, *va, *kb, *vb, *rows, *parent, *root, *isroot, *rank, *pid;
+    uint32_t* disp;                               // three rotating rows [n_free] of displacement bits, one entry per patch
+    int32_t *pk, *pv, *pkb, *pvb, *prow, *loc, *lnbr;     // the LDS path: the free vertices by patch, the translated entries
+    int32_t* scr;
+    SortBufs sort;
+};
+
+inline FairWork carve_fair(Carver& c, int64_t M, int64_t T, int64_t n, int64_t Ef) {
+    FairWork W = {};
+    W.f32 = c.take<int32_t>(M);
+    W.fidx = c.take<int32_t>(M + 1);
+    W.eflag = c.take<int32_t>(6 * T);
+    W.epos = c.take<int32_t>(6 * T + 1);
+    const int64_t most = max2(n, Ef);                           // (both sorts: the edges, the free vertices by patch)
+    W.scr = take_scan(c, max2(max2(M, 6 * T), max2(n, 256 * ((most + kTile - 1) / kTile)) + 1));
+    W.fl = c.take<int32_t>(n);
+    W.ka = c.take<int32_t>(Ef); W.va = c.take<int32_t>(Ef); W.kb = c.take<int32_t>(Ef); W.vb = c.take<int32_t>(Ef);
+    W.rows = c.take<int32_t>(2 * n);
+    W.parent = c.take<int32_t>(n);
+    W.root = c.take<int32_t>(n);
+    W.isroot = c.take<int32_t>(n);
+    W.rank = c.take<int32_t>(n + 1);
+    W.pid = c.take<int32_t>(n);
+    W.disp = c.take<uint32_t>(3 * n);
+    W.pk = c.take<int32_t>(n); W.pv = c.take<int32_t>(n); W.pkb = c.take<int32_t>(n); W.pvb = c.take<int32_t>(n);
+    W.prow = c.take<int32_t>(2 * n);
+    W.loc = c.take<int32_t>(n);
+    W.lnbr = c.take<int32_t>(Ef);
+    W.sort = take_sort(c, most);
+    return W;
+}
+
+inline bool fair_ok(int64_t M, int64_t T, int64_t n, int64_t Ef) {
+    return M >= 1 && M < (1ll << 31) && T >= 0 && 6 * T < (1ll << 31) - kTile && n >= 0 && n <= M && Ef >= 0 && Ef <= 6 * T;
+}
+
+// the free indices and the edge positions (two scans)
+inline void fair_scans(const FairWork& W, const int32_t* tri, int64_t T, const uint8_t* free, int64_t M, hipStream_t s) {
+    hipLaunchKernelGGL(free_flag_kernel, dim3(blocks(M, 256)), dim3(256), 0, s, free, M, W.f32);
+    scan(W.f32, M, W.fidx, W.scr, s);
+    if (T > 0) hipLaunchKernelGGL(free_edge_flag_kernel, dim3(blocks(6 * T, 256)), dim3(256), 0, s, tri, 6 * T, free, W.eflag);
+    scan(W.eflag, 6 * T, W.epos, W.scr, s);
+}
+
+// where the two sorts of the build leave the sources and the targets
+inline void sorted_names(const FairWork& W, int64_t M, int64_t n, const int32_t*& src, const int32_t*& tgt) {
+    int32_t *ka = W.ka, *va = W.va, *kb = W.kb, *vb = W.vb, *t;
+    if (radix_passes(M - 1) & 1) { t = ka; ka = kb; kb = t; t = va; va = vb; vb = t; }
+    if (radix_passes(n - 1) & 1) { t = ka; ka = kb; kb = t; t = va; va = vb; vb = t; }
+    src = va;
+    tgt = ka;
+}
+
+}  // namespace
+
+extern "C" int64_t misplat_meshfill_workspace(int64_t n_vertices, int64_t n_triangles) {
+    if (!sizes_ok(n_vertices, n_triangles)) return -1;
+    Carver c{nullptr};
+    carve(c, n_triangles);
+    return c.o;
+}
+
+extern "C" int misplat_meshfill_round(const float* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles,
+                                      const uint8_t* region, float max_edge_len, void* workspace, int64_t workspace_bytes,
+                                      int32_t* counts, misplat_stream_t stream) {
+    const int64_t M = n_vertices, T = n_triangles;
+    if (!sizes_ok(M, T) || !(max_edge_len > 0.f) || !vertices || !triangles || !region || !workspace || !counts) return MISPLAT_EINVAL;
+    Carver c{(char*)workspace};
+    const Work W = carve(c, T);
+    if (workspace_bytes < c.o) return MISPLAT_EWORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    EdgeTable E{W.keys, W.cnt, W.fmin, W.fmax, (u64)(W.cap - 1)};
+    misplat_internal::fill_bytes(E.keys, 8 * W.cap, 0xffffffffu, s);
+    misplat_internal::fill_bytes(E.cnt, 4 * W.cap, 0u, s);
+    misplat_internal::fill_bytes(E.fmin, 4 * W.cap, 0x7fffffffu, s);
+    misplat_internal::fill_bytes(E.fmax, 4 * W.cap, 0u, s);
+    const unsigned nh = blocks(3 * T, 256), nf = blocks(T, 256);
+    hipLaunchKernelGGL(edge_insert_kernel, dim3(nh), dim3(256), 0, s, triangles, T, E);
+    hipLaunchKernelGGL(splittable_kernel, dim3(nh), dim3(256), 0, s, vertices, triangles, T, region, E, max_edge_len, W.sbits);
+    hipLaunchKernelGGL(face_best_kernel, dim3(nf), dim3(256), 0, s, triangles, T, (const uint32_t*)W.sbits, W.best);
+    hipLaunchKernelGGL(select_kernel, dim3(nf), dim3(256), 0, s, triangles, T, E, (const int32_t*)W.best, W.owner, W.fsplit, W.flag);
+    number(W, T, counts, s);
+    return launched();
+}
+
+extern "C" int misplat_meshfill_apply(float* vertices, int64_t n_vertices, int32_t* triangles, int64_t n_triangles, uint8_t* region,
+                                      int32_t* origin, float* attributes, int32_t n_channels, int64_t n_selected, int64_t limit,
+                                      void* workspace, int64_t workspace_bytes, int32_t* counts, misplat_stream_t stream) {
+    const int64_t M = n_vertices, T = n_triangles, S = n_selected;
+    const int D = n_channels;
+    if (!sizes_ok(M, T) || S < 1 || S > T || M + S >= (1ll << 31) || limit == 0 || limit > S || D < 0 || D > 4096 ||
+        (M + S) * (int64_t)(D > 3 ? D : 3) >= (1ll << 39) || !vertices || !triangles || !region || !origin || (D > 0 && !attributes) ||
+        !workspace || !counts)
+        return MISPLAT_EINVAL;
+    Carver c{(char*)workspace};
+    const Work W = carve(c, T);
+    if (workspace_bytes < c.o) return MISPLAT_EWORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned nh = blocks(3 * T, 256), nf = blocks(T, 256);
+    if (limit > 0 && limit < S) {
+        // Only the `limit` first in priority: the owner slots in slot order, sorted stably by the four 32-bit digits of the
+        // priority from the least significant on (hi, lo, the mixed key, the complement of the length bits).
+        int32_t *sk = W.sk, *sv = W.sv, *skb = W.skb, *svb = W.svb;
+        misplat_internal::fill_bytes(sv, 4 * (size_t)S, 0u, s);         // (a wrong n_selected reads slot 0)
+        hipLaunchKernelGGL(gather_kernel, dim3(nh), dim3(256), 0, s, (const int32_t*)W.flag, (const int32_t*)W.spos, 3 * T, S, sv);
+        SortBufs sb = W.sort;
+        sb.nblk = (S + kTile - 1) / kTile;
+        const int index_passes = radix_passes(M - 1);
+        for (int which = 0; which < 4; which++) {
+            hipLaunchKernelGGL(digit_kernel, dim3(blocks(S, 256)), dim3(256), 0, s, (const int32_t*)triangles, (const uint32_t*)W.sbits,
+                               (const int32_t*)sv, S, which, sk);
+            radix_sort(sk, sv, skb, svb, S, which < 2 ? index_passes : 4, sb, W.scr, s);
+        }
+        hipLaunchKernelGGL(drop_kernel, dim3(blocks(S, 256)), dim3(256), 0, s, (const int32_t*)sv, S, limit, W.flag);
+        hipLaunchKernelGGL(restrict_kernel, dim3(nf), dim3(256), 0, s, T, (const int32_t*)W.flag, W.owner, W.fsplit);
+        number(W, T, counts, s);
+    }
+    hipLaunchKernelGGL(midpoint_kernel, dim3(nh), dim3(256), 0, s, vertices, M, (const int32_t*)triangles, T, (const int32_t*)W.flag,
+                       (const int32_t*)W.spos, attributes, D);
+    hipLaunchKernelGGL(split_kernel, dim3(nf), dim3(256), 0, s, triangles, M, T, (const int32_t*)W.best, (const int32_t*)W.owner,
+                       (const int32_t*)W.spos, (const int32_t*)W.frank, region, origin);
+    return launched();
+}
+
+extern "C" int64_t misplat_meshfill_fair_workspace(int64_t n_vertices, int64_t n_triangles, int64_t n_free, int64_t n_edges) {
+    if (!fair_ok(n_vertices, n_triangles, n_free, n_edges)) return -1;
+    Carver c{nullptr};
+    carve_fair(c, n_vertices, n_triangles, n_free, n_edges);
+    return c.o;
+}
+
+extern "C" int misplat_meshfill_fair_count(const int32_t* triangles, int64_t n_triangles, const uint8_t* free, int64_t n_vertices,
+                                           void* workspace, int64_t workspace_bytes, int32_t* counts, misplat_stream_t stream) {
+    const int64_t M = n_vertices, T = n_triangles;
+    if (!fair_ok(M, T, 0, 0) || !free || (T > 0 && !triangles) || !workspace || !counts) return MISPLAT_EINVAL;
+    Carver c{(char*)workspace};
+    const FairWork W = carve_fair(c, M, T, 0, 0);
+    if (workspace_bytes < c.o) return MISPLAT_EWORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    fair_scans(W, triangles, T, free, M, s);
+    hipLaunchKernelGGL(fair_totals_kernel, dim3(1), dim3(1), 0, s, (const int32_t*)W.fidx, M, (const int32_t*)W.epos, 6 * T, counts);
+    return launched();
+}
+
+extern "C" int misplat_meshfill_fair_build(const int32_t* triangles, int64_t n_triangles, const uint8_t* free, int64_t n_vertices,
+                                           int64_t n_free, int64_t n_edges, void* workspace, int64_t workspace_bytes, int32_t* iterations,
+                                           int32_t* counts, misplat_stream_t stream) {
+    const int64_t M = n_vertices, T = n_triangles, n = n_free, Ef = n_edges;
+    if (!fair_ok(M, T, n, Ef) || n < 1 || !free || (T > 0 && !triangles) || !workspace || !iterations || !counts) return MISPLAT_EINVAL;
+    Carver c{(char*)workspace};
+    const FairWork W = carve_fair(c, M, T, n, Ef);
+    if (workspace_bytes < c.o) return MISPLAT_EWORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    fair_scans(W, triangles, T, free, M, s);
+    const unsigned nk = blocks(n, 256);
+    misplat_internal::fill_bytes(W.fl, 4 * (size_t)n, 0u, s);           // (a wrong n_free reads vertex 0, never beyond the list)
+    hipLaunchKernelGGL(free_list_kernel, dim3(blocks(M, 256)), dim3(256), 0, s, free, (const int32_t*)W.fidx, M, n, W.fl);
+    hipLaunchKernelGGL(patch_init_kernel, dim3(nk), dim3(256), 0, s, n, W.parent, iterations, W.disp);
+    misplat_internal::fill_bytes(W.rows, 8 * (size_t)n, 0u, s);
+    if (Ef > 0) {
+        int32_t *ka = W.ka, *va = W.va, *kb = W.kb, *vb = W.vb;
+        misplat_internal::fill_bytes(ka, 4 * (size_t)Ef, 0u, s);        // (a wrong n_edges leaves edges 0 -> 0 of free vertex 0)
+        misplat_internal::fill_bytes(va, 4 * (size_t)Ef, 0u, s);
+        hipLaunchKernelGGL(free_edge_emit_kernel, dim3(blocks(6 * T, 256)), dim3(256), 0, s, triangles, 6 * T, (const int32_t*)W.eflag,
+                           (const int32_t*)W.epos, (const int32_t*)W.fidx, Ef, ka, va);
+        radix_sort(ka, va, kb, vb, Ef, radix_passes(M - 1), W.sort, W.scr, s);          // by target
+        radix_sort(va, ka, vb, kb, Ef, radix_passes(n - 1), W.sort, W.scr, s);          // stably by source: va sources, ka targets
+        hipLaunchKernelGGL(rows_kernel, dim3(blocks(Ef, 256)), dim3(256), 0, s, (const int32_t*)va, Ef, W.rows);
+        hipLaunchKernelGGL(patch_union_kernel, dim3(blocks(Ef, 256)), dim3(256), 0, s, (const int32_t*)va, (const int32_t*)ka, Ef, free,
+                           (const int32_t*)W.fidx, W.parent);
+    }
+    hipLaunchKernelGGL(patch_root_kernel, dim3(nk), dim3(256), 0, s, (const int32_t*)W.parent, n, W.root, W.isroot);
+    scan(W.isroot, n, W.rank, W.scr, s);
+    hipLaunchKernelGGL(patch_label_kernel, dim3(nk), dim3(256), 0, s, (const int32_t*)W.root, (const int32_t*)W.rank, n, W.pid, counts);
+    return launched();
+}
+
+extern "C" int misplat_meshfill_fair_step(float* values_a, float* values_b, int64_t n_vertices, int64_t n_triangles, int32_t n_channels,
+                                          int64_t n_free, int64_t n_edges, int32_t first, int32_t count, float tolerance, int32_t fixed,
+                                          void* workspace, int64_t workspace_bytes, int32_t* iterations, int32_t* counts,
+                                          misplat_stream_t stream) {
+    const int64_t M = n_vertices, T = n_triangles, n = n_free, Ef = n_edges;
+    const int D = n_channels;
+    if (!fair_ok(M, T, n, Ef) || n < 1 || D < 1 || D > 4096 || M * (int64_t)D >= (1ll << 39) || first < 1 || count < 1 ||
+        (int64_t)first + count > (1ll << 31) - 1 || !(tolerance > 0.f) || !values_a || !values_b || !workspace || !iterations || !counts)
+        return MISPLAT_EINVAL;
+    Carver c{(char*)workspace};
+    const FairWork W = carve_fair(c, M, T, n, Ef);
+    if (workspace_bytes < c.o) return MISPLAT_EWORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    Fair F{W.fl, W.rows, nullptr, W.pid, W.isroot};
+    const int32_t* src;
+    sorted_names(W, M, n, src, F.nbr);
+    uint32_t tol_bits;
+    __builtin_memcpy(&tol_bits, &tolerance, 4);
+    const unsigned nb = blocks(n * D, kStepThreads);
+    for (int32_t it = first; it < first + count; it++) {
+        const float* in = (it & 1) ? values_a : values_b;       // iteration 1 reads a
+        float* out = (it & 1) ? values_b : values_a;
+        hipLaunchKernelGGL(fair_step_kernel, dim3(nb), dim3(kStepThreads), 0, s, in, out, D, n, F, iterations,
+                           (const uint32_t*)(W.disp + (int64_t)((it + 2) % 3) * n), W.disp + (int64_t)(it % 3) * n,
+                           W.disp + (int64_t)((it + 1) % 3) * n, tol_bits, it, (int)(fixed != 0));
+    }
+    if (!fixed) {
+        const int32_t last = first + count - 1;
+        misplat_internal::fill_bytes(counts + 3, 4, 0u, s);
+        hipLaunchKernelGGL(running_kernel, dim3(blocks(n, 256)), dim3(256), 0, s, (const int32_t*)iterations,
+                           (const uint32_t*)(W.disp + (int64_t)(last % 3) * n), tol_bits, counts);
+    }
+    return launched();
+}
+
+extern "C" int misplat_meshfill_fair_lds(float* vertices, int64_t n_vertices, int64_t n_triangles, int64_t n_free, int64_t n_edges,
+                                         int32_t n_patches, float tolerance, int32_t max_iterations, void* workspace,
+                                         int64_t workspace_bytes, int32_t* iterations, int32_t* counts, misplat_stream_t stream) {
+    const int64_t M = n_vertices, T = n_triangles, n = n_free, Ef = n_edges;
+    if (!fair_ok(M, T, n, Ef) || n < 1 || n_patches < 1 || n_patches > n || !(tolerance > 0.f) || max_iterations < 1 || !vertices ||
+        !workspace || !iterations || !counts)
+        return MISPLAT_EINVAL;
+    Carver c{(char*)workspace};
+    const FairWork W = carve_fair(c, M, T, n, Ef);
+    if (workspace_bytes < c.o) return MISPLAT_EWORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    Fair F{W.fl, W.rows, nullptr, W.pid, W.isroot};
+    const int32_t* src;
+    sorted_names(W, M, n, src, F.nbr);
+    uint32_t tol_bits;
+    __builtin_memcpy(&tol_bits, &tolerance, 4);
+    const unsigned nk = blocks(n, 256);
+    int32_t *pk = W.pk, *pv = W.pv, *pkb = W.pkb, *pvb = W.pvb;
+    hipLaunchKernelGGL(patch_keys_kernel, dim3(nk), dim3(256), 0, s, (const int32_t*)W.pid, n, pk, pv);
+    SortBufs sb = W.sort;
+    sb.nblk = (n + kTile - 1) / kTile;
+    radix_sort(pk, pv, pkb, pvb, n, radix_passes(n_patches - 1), sb, W.scr, s);     // stable: a patch's vertices stay ascending
+    misplat_internal::fill_bytes(W.prow, 8 * (size_t)n, 0u, s);
+    hipLaunchKernelGGL(rows_kernel, dim3(nk), dim3(256), 0, s, (const int32_t*)pk, n, W.prow);
+    hipLaunchKernelGGL(patch_place_kernel, dim3(nk), dim3(256), 0, s, (const int32_t*)pv, (const int32_t*)pk, (const int32_t*)W.prow, n,
+                       W.loc);
+    if (Ef > 0)
+        hipLaunchKernelGGL(local_edges_kernel, dim3(blocks(Ef, 256)), dim3(256), 0, s, F.nbr, Ef, (const int32_t*)W.f32,
+                           (const int32_t*)W.fidx, (const int32_t*)W.loc, W.lnbr);
+    misplat_internal::fill_bytes(counts + 3, 4, 0u, s);
+    hipLaunchKernelGGL(fair_lds_kernel, dim3((unsigned)n_patches), dim3(kLdsThreads), 0, s, vertices, F, (const int32_t*)pv,
+                       (const int32_t*)W.prow, (const int32_t*)W.lnbr, tol_bits, max_iterations, iterations, counts);
+    return launched();
+}
+
+extern "C" int misplat_meshfill_fair_finish(int64_t n_free, int32_t n_done, int32_t* iterations, const int32_t* counts,
+                                            misplat_stream_t stream) {
+    if (n_free < 1 || n_free >= (1ll << 31) || n_done < 0 || !iterations || !counts) return MISPLAT_EINVAL;
+    hipLaunchKernelGGL(finish_kernel, dim3(blocks(n_free, 256)), dim3(256), 0, (hipStream_t)stream, iterations, n_done, counts);
+    return launched();
+}

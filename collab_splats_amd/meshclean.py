@@ -8,9 +8,9 @@ RANSAC hypotheses, their inlier counts and the refit's moments are HIP kernels; 
 3x3 eigenproblem on the host.  ``smooth_laplacian`` is the Laplacian smoothing that ends the reference's ``LevelSetExtractor``
 (mesh.py:1217-1223, Open3D's ``filter_smooth_laplacian``).  There is no CPU fallback.
 
-What is NOT restated: MeshLib's ``fillHoleNicely`` (and the subdivision and smoothing of the standard fill).  ``fill_holes``
-is the reference's *fallback*, ``fillHoleTrivially``: one new vertex per hole and a fan of triangles to it.  Nothing about it
-can be pinned to MeshLib's output.
+``fill_holes`` is the reference's *fallback*, MeshLib's ``fillHoleTrivially``: one new vertex per hole and a fan of triangles to
+it.  What stands where the reference's default, ``fillHoleNicely``, stands (the fan subdivided to the mesh's edge length, its
+new vertices positioned smoothly) is ``meshfill.fill_holes_nicely``, which shares the fans built here.
 """
 from __future__ import annotations
 
@@ -199,28 +199,40 @@ def fill_holes(vertices: Tensor, triangles: Tensor, max_hole_size: float = 3.0, 
     the triangle (b, a, c).  Loops go in rank order, their edges in list order.  Returns (vertices, triangles, attributes,
     n_filled).
 
-    This is MeshLib's ``fillHoleTrivially``, the reference's *fallback* (mesh.py:312), NOT its ``fillHoleNicely``: no
-    triangulation metric, no subdivision, no smoothing.  Nothing here can be compared with MeshLib's output."""
+    This is MeshLib's ``fillHoleTrivially``, the reference's *fallback* (mesh.py:312): no triangulation metric, no subdivision,
+    no smoothing.  ``meshfill.fill_holes_nicely`` subdivides and fairs these same fans, as the reference's default
+    ``fillHoleNicely`` does its patches."""
     name = "fill_holes"
     v, t = _mesh(name, vertices, triangles)
     attributes = _attributes(name, attributes, v.shape[0], True)
+    limit = _limit(name, max_hole_size)
+    require_gpu(vertices, triangles, *attributes)
+    attributes = tuple(_prep(a) for a in attributes)
+    filled = _fans(v, t, attributes, limit) if t.shape[0] else None
+    if filled is None:
+        return v, t.to(triangles.dtype), attributes, 0
+    return filled[0], filled[1].to(triangles.dtype), filled[2], filled[3]
+
+
+def _limit(name: str, max_hole_size) -> float:
     try:
         limit = float(max_hole_size)
     except (TypeError, ValueError):
         limit = math.nan
     if math.isnan(limit):
         raise ValueError(f"{name}: max_hole_size must be a number, got {max_hole_size!r}")
-    require_gpu(vertices, triangles, *attributes)
-    attributes = tuple(_prep(a) for a in attributes)
+    return limit
+
+
+def _fans(v: Tensor, t: Tensor, attributes: Tuple[Tensor, ...], limit: float):
+    """The fans of ``fill_holes`` over a prepared mesh with at least one face: (vertices, triangles int64, attributes,
+    n_filled), or None where no loop is below the limit.  Shared with ``meshfill.fill_holes_nicely``."""
     m = v.shape[0]
-    unchanged = (v, t.to(triangles.dtype), attributes, 0)
-    if t.shape[0] == 0:
-        return unchanged
     loop, edges, _, perimeter, order = _holes(v, t)
     fill = perimeter < limit
     n_fill = int(fill.sum())
     if n_fill == 0:
-        return unchanged
+        return None
     new_id = torch.cumsum(fill, 0) - 1                              # rank of a filled loop among the filled ones
     order = order.long()
     chosen = order[fill[loop.long()[order]]]                        # the fans' edges: loops in rank order, edges in list order
@@ -236,7 +248,7 @@ def fill_holes(vertices: Tensor, triangles: Tensor, max_hole_size: float = 3.0, 
         check(load().misplat_pointcloud_voxel_mean(ptr(x), C.c_int64(m), x.shape[1], ptr(members), ptr(offsets), C.c_int64(n_fill),
                                                    ptr(mean), stream_ptr()), "misplat_pointcloud_voxel_mean")
         outs.append(torch.cat([x, mean]))
-    return outs[0], torch.cat([t.long(), fans]).to(triangles.dtype), tuple(outs[1:]), n_fill
+    return outs[0], torch.cat([t.long(), fans]), tuple(outs[1:]), n_fill
 
 
 # -------------------------------------------------------------------------------------------------------- smoothing

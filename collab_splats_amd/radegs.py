@@ -599,23 +599,36 @@ class RadegsModel(nn.Module):
 
     @torch.no_grad()
     def finish_mesh(self, vertices: Tensor, triangles: Tensor, colors: Tensor, clean_repair: bool = True, use_largest: bool = False,
-                    max_hole_size: float = 3.0, align: bool = True, k: int = 5, sdf_trunc: float = 0.03) -> Dict[str, Tensor]:
+                    max_hole_size: float = 3.0, align: bool = True, k: int = 5, sdf_trunc: float = 0.03, fill: str = "fan"
+                    ) -> Dict[str, Tensor]:
         """What the reference's ``Open3DTSDFFusion.main`` does to the extracted mesh (mesh.py:1634-1718), on the device:
         ``clean_repair``: ``filter_mesh_components`` then ``fill_holes`` (the colours are carried exactly; a fan's new vertex
-        takes the mean of its loop's); ``mesh_attributes`` on the result; ``align``: ``align_floor`` of the mesh, the same
+        takes the mean of its loop's), or with ``fill="nicely"`` ``fill_holes_nicely`` (the reference's default,
+        ``use_advanced_fill``: the fans subdivided to the mesh's edge length and faired, the colours with them; ``fill_info`` is
+        then its ``info``); ``mesh_attributes`` on the result; ``align``: ``align_floor`` of the mesh, the same
         rotation applied to the mapped normals (Open3D's ``rotate`` turns them too) and the rigid motion to the means
         (mesh.py:1709).  Returns ``vertices``, ``triangles``, ``colors``, the attributes, ``vertex_index`` ([M'] int64: the
-        row of the input each vertex was, -1 for a fan's new vertex), ``means`` (moved, [N,3]), ``n_removed``, ``n_filled`` and
+        row of the input each vertex was, -1 for a vertex the fill created), ``means`` (moved, [N,3]), ``n_removed``, ``n_filled`` and
         ``mesh_transform`` ([4,4] fp64 on the host, [[R, t], [0, 0, 0, 1]] as mesh.py:1712-1718; the identity without
         ``align``).  The model itself is not changed."""
         from .meshclean import align_floor, apply_rigid, fill_holes, filter_mesh_components
+        if fill not in ("fan", "nicely"):
+            raise ValueError(f"finish_mesh: fill must be 'fan' or 'nicely', got {fill!r}")
         index = torch.arange(vertices.shape[0], dtype=torch.int64, device=vertices.device)
         n_removed = n_filled = 0
+        info = None
         if clean_repair:
             vertices, triangles, index, (colors,), n_removed = filter_mesh_components(vertices, triangles, use_largest, (colors,))
-            vertices, triangles, (colors,), n_filled = fill_holes(vertices, triangles, max_hole_size, (colors,))
+            if fill == "nicely":
+                from .meshfill import fill_holes_nicely
+                vertices, triangles, (colors,), n_filled, info = fill_holes_nicely(vertices, triangles, max_hole_size,
+                                                                                   attributes=(colors,))
+            else:
+                vertices, triangles, (colors,), n_filled = fill_holes(vertices, triangles, max_hole_size, (colors,))
             index = torch.cat([index, index.new_full((vertices.shape[0] - index.shape[0],), -1)])
         out = {"triangles": triangles, "colors": colors, "vertex_index": index, "n_removed": n_removed, "n_filled": n_filled}
+        if info is not None:
+            out["fill_info"] = info
         out.update(self.mesh_attributes(vertices, k=k, sdf_trunc=sdf_trunc))
         means = self.means.detach()
         transform = torch.eye(4, dtype=torch.float64)

@@ -1119,6 +1119,61 @@ int misplat_density_raycast(const misplat_tsdf_grid* grid, const int32_t* slot_m
                             const float* t1, int64_t n_rays, float level0, float level1, float level2, float level3,
                             int32_t n_levels, float* t_out, uint8_t* hit_out, misplat_stream_t stream);
 
+/* ---- hole patches at the mesh's resolution: subdivision and fairing (csrc/meshfill.hip) ----
+ * Restated from the published methods (longest-edge bisection, membrane fairing with the rim fixed); the oracle is
+ * tests/meshfill_restatement.py.  vertices [M,3] fp32, triangles [T,3] int32 with every index in 0 .. M - 1.  Integer atomics
+ * only, every fp64 sum in a fixed order: two runs are bitwise equal.  No call synchronises.
+ *
+ * Subdivision.  An undirected edge is splittable iff it has one incident face or two distinct ones, all with region != 0 and
+ * three distinct corners, and its fp32 length sqrtf((dx dx + dy dy) + dz dz) > max_edge_len.  Priority: larger length bits, then
+ * smaller mix32(lo, hi, 0), then smaller key lo << 32 | hi.  A round selects the splittable edges that are first among the
+ * splittable edges of each of their faces.  1 <= T, 6 T < 2^31 - 4096. */
+/* workspace bytes for round and apply at n_triangles faces (both carve it for the T they are given); -1 for sizes refused. */
+int64_t misplat_meshfill_workspace(int64_t n_vertices, int64_t n_triangles);
+/* One round up to the selection (kept in the workspace for misplat_meshfill_apply).  region [T] uint8.  counts [2] int32 on the
+ * device: the selected edges, the faces they split. */
+int misplat_meshfill_round(const float* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles,
+                           const uint8_t* region, float max_edge_len, void* workspace, int64_t workspace_bytes, int32_t* counts,
+                           misplat_stream_t stream);
+/* Applies the round: limit < 0 every selected edge (n_selected of them), else the `limit` first in priority (counts is written
+ * again for them).  Edge number s (a scan over the (face, corner) slots, each edge at the lowest corner of its smallest face)
+ * creates vertex M + s = 0.5f (x_lo + x_hi), every attribute channel ([., n_channels]) the same; a split face (a, b, c), a -> b
+ * the edge, becomes (a, m, c) in its slot and (m, b, c) in slot T + its rank among the split faces, which inherits region and
+ * origin.  vertices / attributes need M + (the edges applied) rows, triangles / region / origin T + (the faces split). */
+int misplat_meshfill_apply(float* vertices, int64_t n_vertices, int32_t* triangles, int64_t n_triangles, uint8_t* region,
+                           int32_t* origin, float* attributes, int32_t n_channels, int64_t n_selected, int64_t limit,
+                           void* workspace, int64_t workspace_bytes, int32_t* counts, misplat_stream_t stream);
+/* Fairing.  free [M] uint8; a patch = free vertices connected by edges with both ends free, numbered by smallest vertex.  Per
+ * iteration a free vertex moves to fp32(sum_j (double) x_j / |N(i)|) over its distinct neighbours in ascending index; a patch
+ * stops after the first iteration whose largest |x' - x| (fp32, over its vertices and channels) is < tolerance.  Order of
+ * calls: count (the host reads counts[0] = n_free and counts[1] = n_edges, the directed edges that leave a free vertex); build
+ * (counts[2] = the patches; iterations [n_free] int32, one entry per patch, starts at 0); lds and / or step; finish.  counts [4]
+ * int32 on the device.  A patch of more than MISPLAT_MESHFILL_LDS_VERTICES free vertices is left to step. */
+#define MISPLAT_MESHFILL_LDS_VERTICES 4096
+/* workspace bytes (count: n_free = n_edges = 0); -1 for sizes refused (6 T < 2^31 - 4096). */
+int64_t misplat_meshfill_fair_workspace(int64_t n_vertices, int64_t n_triangles, int64_t n_free, int64_t n_edges);
+int misplat_meshfill_fair_count(const int32_t* triangles, int64_t n_triangles, const uint8_t* free, int64_t n_vertices,
+                                void* workspace, int64_t workspace_bytes, int32_t* counts, misplat_stream_t stream);
+int misplat_meshfill_fair_build(const int32_t* triangles, int64_t n_triangles, const uint8_t* free, int64_t n_vertices,
+                                int64_t n_free, int64_t n_edges, void* workspace, int64_t workspace_bytes, int32_t* iterations,
+                                int32_t* counts, misplat_stream_t stream);
+/* Iterations first .. first + count - 1 (1-based) of values [M, n_channels], one launch each: an odd iteration reads values_a
+ * and writes values_b, an even one the other way (both hold the fixed rows; a stopped patch is copied).  fixed = 0: measured
+ * (iterations[p] is set when patch p is seen to have stopped; counts[3] = the patches still running after the last one);
+ * fixed != 0: patch p runs iff the iteration is <= iterations[p] (attributes). */
+int misplat_meshfill_fair_step(float* values_a, float* values_b, int64_t n_vertices, int64_t n_triangles, int32_t n_channels,
+                               int64_t n_free, int64_t n_edges, int32_t first, int32_t count, float tolerance, int32_t fixed,
+                               void* workspace, int64_t workspace_bytes, int32_t* iterations, int32_t* counts,
+                               misplat_stream_t stream);
+/* Every patch that fits, to its end in ONE workgroup (both iterates of its xyz in LDS), in place in vertices; iterations[p] is
+ * set for them; counts[3] = the patches that do not fit.  Same bits and counts as step. */
+int misplat_meshfill_fair_lds(float* vertices, int64_t n_vertices, int64_t n_triangles, int64_t n_free, int64_t n_edges,
+                              int32_t n_patches, float tolerance, int32_t max_iterations, void* workspace, int64_t workspace_bytes,
+                              int32_t* iterations, int32_t* counts, misplat_stream_t stream);
+/* iterations[p] = n_done for every patch that was never seen stopped. */
+int misplat_meshfill_fair_finish(int64_t n_free, int32_t n_done, int32_t* iterations, const int32_t* counts,
+                                 misplat_stream_t stream);
+
 /* Library identification ("misplat <version> gfx950"). */
 const char* misplat_version(void);
 
