@@ -66,6 +66,9 @@ SOURCES = {
     "decimate.hip": ["-ffp-contract=off"],
     # meshfill.hip: the same: edge lengths (the split priority), midpoints and the fp64 neighbour means equal the restatement (tests/)
     "meshfill.hip": ["-ffp-contract=off"],
+    # meshtri.hip: the same: triangle areas and the fp64 sums of the triangulation's table, the cotangents and normals of the flip
+    # test equal the restatement (tests/) bit for bit
+    "meshtri.hip": ["-ffp-contract=off"],
 }
 
 

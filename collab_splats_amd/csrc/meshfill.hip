@@ -7,7 +7,8 @@
 // displacement's bits); every fp64 sum runs over a sorted CSR row in ascending order: two runs are bitwise equal.
 //
 // Subdivision, one round (misplat_meshfill_round): the edge table of the current mesh -- meshclean.hip's, with the largest
-// incident face beside the smallest, which names both faces of a two-face edge; per corner the length bits of a splittable
+// incident face beside the smallest, which names both faces of a two-face edge (facetable.h, shared with meshtri.hip, as are
+// the priority and the selection); per corner the length bits of a splittable
 // edge; per face the corner of its first splittable edge in priority; per face again whether that edge is first in its other
 // face too (it is then selected); two scans number the selected edges and the faces they split.  The host reads the two
 // totals, makes room, and misplat_meshfill_apply writes the midpoints and the faces.
@@ -20,42 +21,9 @@
 #include "unionfind.h"
 #include "hashmix.h"
 #include "meshedge.h"
+#include "facetable.h"
 
 namespace {
-
-typedef unsigned long long u64;
-
-// ----------------------------------------------------------------------------------------------------- edge table
-struct EdgeTable {
-    u64* keys;
-    int32_t *cnt, *fmin, *fmax;
-    u64 mask;
-};
-
-__device__ __forceinline__ int64_t edge_find(const EdgeTable& E, u64 key) {
-    u64 s = edge_home(key, E.mask);
-    while (E.keys[s] != key) s = (s + 1) & E.mask;
-    return (int64_t)s;
-}
-
-__global__ __launch_bounds__(256) void edge_insert_kernel(const int32_t* __restrict__ tri, int64_t T, EdgeTable E) {
-    const int64_t h = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (h >= 3 * T) return;
-    const int64_t f = h / 3;
-    int32_t a, b;
-    corner_edge(tri, f, (int)(h - 3 * f), a, b);
-    if (a == b) return;
-    const u64 key = edge_key(a, b);
-    const u64 s = claim_slot(E.keys, E.mask, edge_home(key, E.mask), key);
-    atomicAdd(&E.cnt[s], 1);
-    atomicMin(&E.fmin[s], (int32_t)f);
-    atomicMax(&E.fmax[s], (int32_t)f);
-}
-
-__device__ __forceinline__ bool repeated(const int32_t* __restrict__ tri, int64_t f) {
-    const int32_t a = tri[3 * f], b = tri[3 * f + 1], c = tri[3 * f + 2];
-    return a == b || b == c || a == c;
-}
 
 // ------------------------------------------------------------------------------------------------------ selection
 // sbits[h] = the fp32 bits of the length of corner h's edge if it is splittable (one incident face or two distinct ones, all
@@ -80,75 +48,6 @@ __global__ __launch_bounds__(256) void splittable_kernel(const float* __restrict
     sbits[h] = bits;
 }
 
-// the priority of a splittable edge: larger length bits first, then the smaller mix32(lo, hi, 0), then the smaller key
-struct Prio {
-    uint32_t bits, mix;
-    u64 key;
-};
-__device__ __forceinline__ Prio prio_of(uint32_t bits, int32_t a, int32_t b) {
-    const u64 key = edge_key(a, b);
-    return Prio{bits, mix32((uint32_t)(key >> 32), (uint32_t)key, 0u), key};
-}
-__device__ __forceinline__ bool before(const Prio& x, const Prio& y) {
-    if (x.bits != y.bits) return x.bits > y.bits;
-    if (x.mix != y.mix) return x.mix < y.mix;
-    return x.key < y.key;
-}
-
-// best[f] = the corner of face f's first splittable edge in priority, -1 if it has none
-__global__ __launch_bounds__(256) void face_best_kernel(const int32_t* __restrict__ tri, int64_t T, const uint32_t* __restrict__ sbits,
-                                                        int32_t* __restrict__ best) {
-    const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (f >= T) return;
-    int32_t bc = -1;
-    Prio bp = {};
-    for (int c = 0; c < 3; c++) {
-        const uint32_t bits = sbits[3 * f + c];
-        if (!bits) continue;
-        int32_t a, b;
-        corner_edge(tri, f, c, a, b);
-        const Prio p = prio_of(bits, a, b);
-        if (bc < 0 || before(p, bp)) { bc = c; bp = p; }
-    }
-    best[f] = bc;
-}
-
-// Face f's first edge is selected iff it is the first edge of its other face too.  owner[f] = the slot (3 face + corner, at
-// the edge's smallest face) that numbers the selected edge, -1 if f is not split; fsplit[f] = 1 / 0; flag[3 f + c] = 1 at the
-// owner slots.
-__global__ __launch_bounds__(256) void select_kernel(const int32_t* __restrict__ tri, int64_t T, EdgeTable E,
-                                                     const int32_t* __restrict__ best, int32_t* __restrict__ owner,
-                                                     int32_t* __restrict__ fsplit, int32_t* __restrict__ flag) {
-    const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (f >= T) return;
-    const int32_t c = best[f];
-    int32_t own = -1;
-    if (c >= 0) {
-        int32_t a, b;
-        corner_edge(tri, f, c, a, b);
-        const u64 key = edge_key(a, b);
-        const int64_t s = edge_find(E, key);
-        const int32_t f0 = E.fmin[s], f1 = E.fmax[s];
-        const int32_t g = f0 == (int32_t)f ? f1 : f0;
-        bool sel = true;
-        int32_t c0 = c;                                     // the edge's corner in its smallest face
-        if (g != (int32_t)f) {
-            const int32_t cg = best[g];
-            sel = false;
-            if (cg >= 0) {
-                int32_t ga, gb;
-                corner_edge(tri, g, cg, ga, gb);
-                sel = edge_key(ga, gb) == key;
-            }
-            if (g == f0) c0 = cg;
-        }
-        if (sel) own = 3 * f0 + c0;
-    }
-    owner[f] = own;
-    fsplit[f] = own >= 0 ? 1 : 0;
-    for (int k = 0; k < 3; k++) flag[3 * f + k] = (own == (int32_t)(3 * f + k)) ? 1 : 0;
-}
-
 __global__ void totals_kernel(const int32_t* __restrict__ spos, const int32_t* __restrict__ frank, int64_t T, int32_t* __restrict__ counts) {
     counts[0] = spos[3 * T];
     counts[1] = frank[T];
@@ -171,7 +70,7 @@ __global__ __launch_bounds__(256) void digit_kernel(const int32_t* __restrict__ 
     const int64_t f = h / 3;
     int32_t a, b;
     corner_edge(tri, f, (int)(h - 3 * f), a, b);
-    const Prio p = prio_of(sbits[h], a, b);
+    const PrioOf<uint32_t> p = prio_of(sbits[h], a, b);
     key[i] = (int32_t)(which == 0 ? (uint32_t)p.key : which == 1 ? (uint32_t)(p.key >> 32) : which == 2 ? p.mix : ~p.bits);
 }
 
@@ -222,12 +121,6 @@ __global__ __launch_bounds__(256) void split_kernel(int32_t* __restrict__ tri, i
 }
 
 // ------------------------------------------------------------------------------------------------------- workspace
-inline int64_t edge_capacity(int64_t T) {
-    int64_t cap = 64;
-    while (cap < 6 * T) cap <<= 1;
-    return cap;
-}
-
 inline int64_t max2(int64_t a, int64_t b) { return a > b ? a : b; }
 
 struct Work {
@@ -677,15 +570,10 @@ extern "C" int misplat_meshfill_round(const float* vertices, int64_t n_vertices,
     const Work W = carve(c, T);
     if (workspace_bytes < c.o) return MISPLAT_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    EdgeTable E{W.keys, W.cnt, W.fmin, W.fmax, (u64)(W.cap - 1)};
-    misplat_internal::fill_bytes(E.keys, 8 * W.cap, 0xffffffffu, s);
-    misplat_internal::fill_bytes(E.cnt, 4 * W.cap, 0u, s);
-    misplat_internal::fill_bytes(E.fmin, 4 * W.cap, 0x7fffffffu, s);
-    misplat_internal::fill_bytes(E.fmax, 4 * W.cap, 0u, s);
     const unsigned nh = blocks(3 * T, 256), nf = blocks(T, 256);
-    hipLaunchKernelGGL(edge_insert_kernel, dim3(nh), dim3(256), 0, s, triangles, T, E);
+    const EdgeTable E = build_edge_table(triangles, T, W.keys, W.cnt, W.fmin, W.fmax, W.cap, s);
     hipLaunchKernelGGL(splittable_kernel, dim3(nh), dim3(256), 0, s, vertices, triangles, T, region, E, max_edge_len, W.sbits);
-    hipLaunchKernelGGL(face_best_kernel, dim3(nf), dim3(256), 0, s, triangles, T, (const uint32_t*)W.sbits, W.best);
+    hipLaunchKernelGGL(face_best_kernel<uint32_t>, dim3(nf), dim3(256), 0, s, triangles, T, (const uint32_t*)W.sbits, W.best);
     hipLaunchKernelGGL(select_kernel, dim3(nf), dim3(256), 0, s, triangles, T, E, (const int32_t*)W.best, W.owner, W.fsplit, W.flag);
     number(W, T, counts, s);
     return launched();

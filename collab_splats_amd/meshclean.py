@@ -10,7 +10,9 @@ RANSAC hypotheses, their inlier counts and the refit's moments are HIP kernels; 
 
 ``fill_holes`` is the reference's *fallback*, MeshLib's ``fillHoleTrivially``: one new vertex per hole and a fan of triangles to
 it.  What stands where the reference's default, ``fillHoleNicely``, stands (the fan subdivided to the mesh's edge length, its
-new vertices positioned smoothly) is ``meshfill.fill_holes_nicely``, which shares the fans built here.
+new vertices positioned smoothly) is ``meshfill.fill_holes_nicely`` (DESIGN.md section 29), which shares the fans built here;
+``meshfill.triangulate_holes`` (section 30) closes the same loops without a centre vertex and keeps the fan for the loops it
+cannot triangulate.
 """
 from __future__ import annotations
 
@@ -227,12 +229,20 @@ def _limit(name: str, max_hole_size) -> float:
 def _fans(v: Tensor, t: Tensor, attributes: Tuple[Tensor, ...], limit: float):
     """The fans of ``fill_holes`` over a prepared mesh with at least one face: (vertices, triangles int64, attributes,
     n_filled), or None where no loop is below the limit.  Shared with ``meshfill.fill_holes_nicely``."""
-    m = v.shape[0]
     loop, edges, _, perimeter, order = _holes(v, t)
     fill = perimeter < limit
     n_fill = int(fill.sum())
     if n_fill == 0:
         return None
+    fans, _, outs = _fan_patches(v, attributes, loop, edges, order, fill, n_fill)
+    return outs[0], torch.cat([t.long(), fans]), tuple(outs[1:]), n_fill
+
+
+def _fan_patches(v: Tensor, attributes: Tuple[Tensor, ...], loop: Tensor, edges: Tensor, order: Tensor, fill: Tensor, n_fill: int):
+    """The fans of the ``n_fill`` loops of the mask ``fill`` ([L] bool): (faces [F,3] int64, the fan each face belongs to [F]
+    int64, (vertices, *attributes) with the fans' centres appended).  Fans go in loop rank order, their edges in list order;
+    fan r's centre is vertex M + r.  Shared with ``meshfill.triangulate_holes`` (the loops it does not triangulate)."""
+    m = v.shape[0]
     new_id = torch.cumsum(fill, 0) - 1                              # rank of a filled loop among the filled ones
     order = order.long()
     chosen = order[fill[loop.long()[order]]]                        # the fans' edges: loops in rank order, edges in list order
@@ -248,7 +258,7 @@ def _fans(v: Tensor, t: Tensor, attributes: Tuple[Tensor, ...], limit: float):
         check(load().misplat_pointcloud_voxel_mean(ptr(x), C.c_int64(m), x.shape[1], ptr(members), ptr(offsets), C.c_int64(n_fill),
                                                    ptr(mean), stream_ptr()), "misplat_pointcloud_voxel_mean")
         outs.append(torch.cat([x, mean]))
-    return outs[0], torch.cat([t.long(), fans]), tuple(outs[1:]), n_fill
+    return fans, new_id[l], outs
 
 
 # -------------------------------------------------------------------------------------------------------- smoothing

@@ -1174,6 +1174,50 @@ int misplat_meshfill_fair_lds(float* vertices, int64_t n_vertices, int64_t n_tri
 int misplat_meshfill_fair_finish(int64_t n_free, int32_t n_done, int32_t* iterations, const int32_t* counts,
                                  misplat_stream_t stream);
 
+/* ---- minimum-area hole triangulation and Delaunay-like edge flips (csrc/meshtri.hip) ----
+ * The oracle is tests/meshtri_restatement.py, bit for bit.  Integer atomics only: two runs are bitwise equal.  No call
+ * synchronises.
+ *
+ * Triangulation.  The boundary edges of misplat_meshclean_holes, listed by loop: edges [B,2] int32, order [B] int32 (the edges by
+ * loop, in list order inside a loop), offsets [L + 1] int32, fill [L] uint8 (the loops to close).  A loop of n edges is
+ * triangulated iff it is filled, 3 <= n <= MISPLAT_MESHTRI_MAX_LOOP and it is a simple cycle (its n tails are distinct, its n
+ * heads are distinct and they are the same vertices).  Its polygon: p_0 the smallest vertex, p_{i+1} the head of the edge whose
+ * tail is p_i, q_0 = p_0, q_i = p_{n-i}.  W[i][i+1] = 0, W[i][j] = min over i < k < j of ((W[i][k] + W[k][j]) + (double) A(i,k,j))
+ * in fp64, strict < in ascending k, A = 0.5f sqrtf((cx cx + cy cy) + cz cz) of the fp32 cross product of q_k - q_i and q_j - q_i.
+ * A loop of at most MISPLAT_MESHTRI_LDS_LOOP edges keeps its table (n (n - 1) / 2 entries of 8 + 2 bytes: 154000 bytes at 176,
+ * with the polygon 156816 of the 163840 a workgroup may declare) in LDS; a longer one, up to MISPLAT_MESHTRI_MAX_LOOP (a stated
+ * limit: 523776 entries, 5.2 MB), in the workspace.  Both run the same code and give the same bits. */
+#define MISPLAT_MESHTRI_LDS_LOOP 176
+#define MISPLAT_MESHTRI_MAX_LOOP 1024
+/* Loops of at most this many edges run in a workgroup of 256 with 21 KB of LDS (misplat_meshtri_dp's path 1); no result depends on it. */
+#define MISPLAT_MESHTRI_SMALL_LOOP 64
+/* code [L] int32: 0 triangulated, 1 not a simple cycle, 2 fewer than 3 edges, 3 more than MAX_LOOP, -1 not filled; polygon [B]
+ * int32: q_0 .. q_{n-1} of every triangulated loop at offsets[l]. */
+int misplat_meshtri_order(const int32_t* edges, const int32_t* order, const int32_t* offsets, const uint8_t* fill, int64_t n_edges,
+                          int64_t n_loops, int32_t* code, int32_t* polygon, misplat_stream_t stream);
+/* workspace bytes for tables of n_entries entries in all (the loops above MISPLAT_MESHTRI_LDS_LOOP); -1 for sizes refused. */
+int64_t misplat_meshtri_workspace(int64_t n_entries);
+/* The tables and the faces of the loops with code 0.  paths: 1 the loops up to SMALL_LOOP edges, 2 those up to LDS_LOOP, 4 the longer
+ * ones (slab_offset [L] int64: where a loop's table starts, in entries; the others take neither it nor the workspace).  Loop l
+ * writes its n - 2 faces (q_i, q_k, q_j), by ascending apex k = 1 .. n - 2, from row face_base[l] of faces [n_faces,3] int32,
+ * and W[0][n-1] into area[area_slot[l]] ([n_area] fp64); a loop whose rows or slot lie outside is skipped. */
+int misplat_meshtri_dp(const float* vertices, int64_t n_vertices, const int32_t* polygon, const int32_t* offsets, const int32_t* code,
+                       int64_t n_loops, int32_t paths, const int64_t* slab_offset, int64_t n_entries, void* workspace,
+                       int64_t workspace_bytes, const int32_t* face_base, int64_t n_faces, const int32_t* area_slot, int64_t n_area,
+                       int32_t* faces, double* area, misplat_stream_t stream);
+/* Flips.  An undirected edge is flippable iff it has exactly two distinct incident faces, both with region != 0 and three
+ * distinct corners, f_max runs it against f_min (f_min = (a, b, c) rotated, f_max holds b -> a and d), c != d, the edge (c, d) is
+ * not in the mesh, the fp64 sum cot(c) + cot(d) (each dot / |cross| of the two edge vectors at the corner, from the fp32
+ * coordinates) is < -min_violation, and each new face's normal has a positive dot product with the sum of the old faces'
+ * unnormalised normals.  Priority: the larger fp64 bits of -(cot c + cot d), then the smaller mix32(lo, hi, 0), then the smaller
+ * key.  One round: the flippable edges that are first among the flippable edges of each of their faces are selected; of those
+ * that want the same new edge the smallest key flips; f_min <- (a, d, c), f_max <- (d, b, c) in place.  counts [1] int32 on the
+ * device: the flips applied.  1 <= T, 6 T < 2^31 - 4096. */
+int64_t misplat_meshtri_flip_workspace(int64_t n_vertices, int64_t n_triangles);
+int misplat_meshtri_flip_round(const float* vertices, int64_t n_vertices, int32_t* triangles, int64_t n_triangles,
+                               const uint8_t* region, double min_violation, void* workspace, int64_t workspace_bytes, int32_t* counts,
+                               misplat_stream_t stream);
+
 /* Library identification ("misplat <version> gfx950"). */
 const char* misplat_version(void);
 
