@@ -20,7 +20,7 @@ from .pointcloud import (calculate_accuracy, calculate_completeness, clean_pcd, 
 from .meshclean import (align_floor, fill_holes, filter_mesh_components, mesh_components, mesh_edge_stats,  # noqa: F401
                         mesh_holes, plane_inlier_counts, ransac_planes, sample_surface, segment_plane, smooth_laplacian)
 from .decimate import simplify_quadric_decimation  # noqa: F401
-from .meshfill import fair_vertices, fill_holes_nicely, flip_edges, subdivide_mesh, triangulate_holes  # noqa: F401
+from .meshfill import fair_vertices, fair_vertices_curvature, fill_holes_nicely, flip_edges, subdivide_mesh, triangulate_holes  # noqa: F401
 from .depthcloud import backproject, depth_edges, depth_normal_cloud, gaussian_mask_filter, sample_pixels  # noqa: F401
 from .featureloss import TwoLayerMLP, feature_decode, feature_loss  # noqa: F401
 from .bilagrid import BilateralGrid, bilagrid_slice, bilagrid_tv_loss  # noqa: F401

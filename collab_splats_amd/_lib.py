@@ -141,7 +141,11 @@ SYMBOLS = {
     "misplat_meshfill_fair_workspace": (C.c_int64, 4), "misplat_meshfill_fair_count": (C.c_int, 8),
     "misplat_meshfill_fair_build": (C.c_int, 11), "misplat_meshfill_fair_step": (C.c_int, 16),
     "misplat_meshfill_fair_lds": (C.c_int, 13), "misplat_meshfill_fair_finish": (C.c_int, 5),
+    "misplat_meshfill_curv_patches": (C.c_int, 8), "misplat_meshfill_curv_workspace": (C.c_int64, 2),
+    "misplat_meshfill_curv_solve": (C.c_int, 23),
     "misplat_meshtri_order": (C.c_int, 9), "misplat_meshtri_workspace": (C.c_int64, 1), "misplat_meshtri_dp": (C.c_int, 18),
+    "misplat_meshtri_rim_workspace": (C.c_int64, 1), "misplat_meshtri_order_rim": (C.c_int, 14),
+    "misplat_meshtri_angle_workspace": (C.c_int64, 1), "misplat_meshtri_angle_dp": (C.c_int, 20),
     "misplat_meshtri_flip_workspace": (C.c_int64, 2), "misplat_meshtri_flip_round": (C.c_int, 10),
     "misplat_depthcloud_workspace": (C.c_int64, 4), "misplat_depthcloud_edges": (C.c_int, 10),
     "misplat_depthcloud_candidates": (C.c_int, 7), "misplat_depthcloud_sample": (C.c_int, 15),

@@ -1,6 +1,7 @@
 // meshfill.hip -- hole patches at the mesh's own resolution: longest-edge bisection of a face region in
 // rounds of edges that share no face, and membrane fairing (uniform-weight Jacobi with everything that is not free held
-// fixed) of patches of free vertices, each to its own tolerance.
+// fixed) of patches of free vertices, each to its own tolerance; at the end of the file, curvature (thin-plate) fairing by
+// conjugate gradients, one persistent workgroup per patch (section 31).
 //
 // Semantics: tests/meshfill_restatement.py is the oracle, bit for bit.  Compiled with -ffp-contract=off: every fp32 and fp64
 // expression is evaluated in the written order.  Integer atomics only (the edge table's counts and faces, the maxima of the
@@ -745,5 +746,251 @@ extern "C" int misplat_meshfill_fair_finish(int64_t n_free, int32_t n_done, int3
                                             misplat_stream_t stream) {
     if (n_free < 1 || n_free >= (1ll << 31) || n_done < 0 || !iterations || !counts) return MISPLAT_EINVAL;
     hipLaunchKernelGGL(finish_kernel, dim3(blocks(n_free, 256)), dim3(256), 0, (hipStream_t)stream, iterations, n_done, counts);
+    return launched();
+}
+
+// ================================================================================================ curvature fairing
+// Thin-plate fairing of the free vertices: the energy sum over S of |U_i|^2, U the umbrella operator, S the
+// free vertices F and the fixed vertices R with a free neighbour, minimised over the free coordinates by conjugate gradients
+// on A = L^T L.  The oracle is tests/meshsmooth_restatement.py, bit for bit.
+//
+// The S-list holds the free vertices by patch and then by vertex (places 0 .. nF - 1), then the rows of R the same way (places nF
+// .. nS - 1); a CSR row per place lists its vertex's distinct neighbours in ascending order, as vertices (nbr) and as places
+// (place: -1 for a fixed vertex outside S).  One persistent workgroup per patch runs the whole solve: x, r, p, q over the
+// patch's free places and t, t / n over its places of S are its part of the workspace, touched by this workgroup only and read
+// after the barrier that follows their writes; every dot product is summed in a fixed order (thread t adds the patch's elements
+// t, t + B, ... in ascending order, then block_sum); alpha, beta and the stop are computed once by thread 0 and broadcast from
+// LDS, so the loop's bound and exit are uniform and every barrier sits outside divergent code.
+namespace {
+
+constexpr int kCgThreads = 1024;
+
+__global__ __launch_bounds__(256) void curv_union_kernel(const int32_t* __restrict__ src, const int32_t* __restrict__ tgt, int64_t n_edges,
+                                                         const uint8_t* __restrict__ free, int64_t M, int32_t* __restrict__ parent) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n_edges) return;
+    const int32_t a = src[e], b = tgt[e];
+    if (a < 0 || a >= M || b < 0 || b >= M || !free[b]) return;
+    (void)unite(parent, a, b);                                  // a row of S and a free neighbour of it: one patch
+}
+
+__global__ __launch_bounds__(256) void curv_root_kernel(const int32_t* __restrict__ parent, int64_t M, int32_t* __restrict__ root) {
+    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (v >= M) return;
+    int32_t r = (int32_t)v;
+    for (int32_t p = parent[r]; p != r; p = parent[r]) r = p;
+    root[v] = r;
+}
+
+struct Curv {
+    const int32_t *foff, *roff, *vertex, *row, *deg, *nbr, *place, *code;
+    int64_t nF, nS;
+    double *x, *r, *p, *q, *t, *tn;
+};
+
+struct CurvCtl {
+    double alpha[3], beta[3], rr[3], rr0, ratio;
+    int32_t stop;
+};
+
+// place number idx of patch p's part of the S-list: its free places first, then its rows of R
+__device__ __forceinline__ int64_t curv_place(const Curv& C, int32_t f0, int32_t nf, int32_t r0, int32_t idx) {
+    return idx < nf ? (int64_t)f0 + idx : C.nF + r0 + (idx - nf);
+}
+
+__global__ __launch_bounds__(kCgThreads) void curv_solve_kernel(const float* __restrict__ pos, float* __restrict__ out, Curv C,
+                                                                double rtol2, int32_t max_it, int32_t* __restrict__ iterations,
+                                                                uint8_t* __restrict__ converged, double* __restrict__ residual) {
+    __shared__ double sh[kCgThreads / 64];
+    __shared__ CurvCtl ctl;
+    const int32_t pt = blockIdx.x, tid = threadIdx.x;
+    const int32_t f0 = C.foff[pt], nf = C.foff[pt + 1] - f0, r0 = C.roff[pt], nr = C.roff[pt + 1] - r0;
+    bool ok = C.code[pt] == 0 && f0 >= 0 && nf >= 1 && (int64_t)f0 + nf <= C.nF && r0 >= 0 && nr >= 0 && C.nF + r0 + nr <= C.nS;
+    if (!ok) {                                                  // (uniform) codes 1, 2, 3: unchanged
+        if (tid == 0) { iterations[pt] = 0; converged[pt] = 0; residual[pt] = 0.0; }
+        return;
+    }
+    const int32_t ns = nf + nr;
+    const int32_t limit = max_it < 0 ? nf : max_it;
+    // t = U(x0) over the patch's places of S, from the fp32 positions
+    for (int32_t idx = tid; idx < ns; idx += kCgThreads) {
+        const int64_t s = curv_place(C, f0, nf, r0, idx);
+        const int64_t v = C.vertex[s];
+        const int32_t e0 = C.row[s], n = C.deg[s];
+        double sum[3] = {0.0, 0.0, 0.0};
+        for (int32_t e = e0; e < e0 + n; e++) {
+            const int64_t j = C.nbr[e];
+            for (int c = 0; c < 3; c++) sum[c] += (double)pos[3 * j + c];
+        }
+        for (int c = 0; c < 3; c++) {
+            const double t = sum[c] / (double)n - (double)pos[3 * v + c];
+            C.t[3 * s + c] = t;
+            C.tn[3 * s + c] = t / (double)n;
+        }
+    }
+    __syncthreads();
+    // r0 = -L^T t, p = r, x = x0
+    double acc[3] = {0.0, 0.0, 0.0};
+    for (int32_t idx = tid; idx < nf; idx += kCgThreads) {
+        const int64_t s = (int64_t)f0 + idx;
+        const int64_t v = C.vertex[s];
+        const int32_t e0 = C.row[s], n = C.deg[s];
+        double sum[3] = {0.0, 0.0, 0.0};
+        for (int32_t e = e0; e < e0 + n; e++) {
+            const int64_t j = C.place[e];
+            for (int c = 0; c < 3; c++) sum[c] += C.tn[3 * j + c];
+        }
+        for (int c = 0; c < 3; c++) {
+            const double r = -(sum[c] - C.t[3 * s + c]);
+            C.x[3 * s + c] = (double)pos[3 * v + c];
+            C.r[3 * s + c] = r;
+            C.p[3 * s + c] = r;
+            acc[c] += r * r;
+        }
+    }
+    double rr[3];
+    for (int c = 0; c < 3; c++) rr[c] = block_sum<kCgThreads / 64>(acc[c], sh);
+    if (tid == 0) {
+        for (int c = 0; c < 3; c++) ctl.rr[c] = rr[c];
+        ctl.rr0 = (rr[0] + rr[1]) + rr[2];
+        ctl.ratio = 0.0;
+        ctl.stop = ctl.rr0 == 0.0 ? 1 : 0;                      // a right-hand side of 0: no iteration
+    }
+    __syncthreads();
+    int32_t it = 0;
+    while (it < limit && !ctl.stop) {                           // (uniform: ctl is written by thread 0 between barriers)
+        // t = L p over the places of S (p is zero off F)
+        for (int32_t idx = tid; idx < ns; idx += kCgThreads) {
+            const int64_t s = curv_place(C, f0, nf, r0, idx);
+            const int32_t e0 = C.row[s], n = C.deg[s];
+            double sum[3] = {0.0, 0.0, 0.0};
+            for (int32_t e = e0; e < e0 + n; e++) {
+                const int64_t j = C.place[e];
+                if (j >= 0 && j < C.nF)
+                    for (int c = 0; c < 3; c++) sum[c] += C.p[3 * j + c];
+            }
+            for (int c = 0; c < 3; c++) {
+                double t = sum[c] / (double)n;
+                if (idx < nf) t = t - C.p[3 * s + c];
+                C.t[3 * s + c] = t;
+                C.tn[3 * s + c] = t / (double)n;
+            }
+        }
+        __syncthreads();
+        // q = L^T t over the free places, and p . q
+        for (int c = 0; c < 3; c++) acc[c] = 0.0;
+        for (int32_t idx = tid; idx < nf; idx += kCgThreads) {
+            const int64_t s = (int64_t)f0 + idx;
+            const int32_t e0 = C.row[s], n = C.deg[s];
+            double sum[3] = {0.0, 0.0, 0.0};
+            for (int32_t e = e0; e < e0 + n; e++) {
+                const int64_t j = C.place[e];
+                for (int c = 0; c < 3; c++) sum[c] += C.tn[3 * j + c];
+            }
+            for (int c = 0; c < 3; c++) {
+                const double q = sum[c] - C.t[3 * s + c];
+                C.q[3 * s + c] = q;
+                acc[c] += C.p[3 * s + c] * q;
+            }
+        }
+        double pq[3];
+        for (int c = 0; c < 3; c++) pq[c] = block_sum<kCgThreads / 64>(acc[c], sh);
+        if (tid == 0)
+            for (int c = 0; c < 3; c++) ctl.alpha[c] = pq[c] == 0.0 ? 0.0 : ctl.rr[c] / pq[c];
+        __syncthreads();
+        for (int c = 0; c < 3; c++) acc[c] = 0.0;
+        for (int32_t idx = tid; idx < nf; idx += kCgThreads) {
+            const int64_t s = (int64_t)f0 + idx;
+            for (int c = 0; c < 3; c++) {
+                const double a = ctl.alpha[c];
+                C.x[3 * s + c] = C.x[3 * s + c] + a * C.p[3 * s + c];
+                const double r = C.r[3 * s + c] - a * C.q[3 * s + c];
+                C.r[3 * s + c] = r;
+                acc[c] += r * r;
+            }
+        }
+        for (int c = 0; c < 3; c++) rr[c] = block_sum<kCgThreads / 64>(acc[c], sh);
+        if (tid == 0) {
+            for (int c = 0; c < 3; c++) {
+                ctl.beta[c] = pq[c] == 0.0 ? 0.0 : rr[c] / ctl.rr[c];
+                ctl.rr[c] = rr[c];
+            }
+            const double now = (rr[0] + rr[1]) + rr[2];
+            ctl.ratio = now / ctl.rr0;
+            ctl.stop = now <= rtol2 * ctl.rr0 ? 1 : 0;
+        }
+        __syncthreads();
+        for (int32_t idx = tid; idx < nf; idx += kCgThreads) {
+            const int64_t s = (int64_t)f0 + idx;
+            for (int c = 0; c < 3; c++) C.p[3 * s + c] = C.r[3 * s + c] + ctl.beta[c] * C.p[3 * s + c];
+        }
+        it++;
+        __syncthreads();                                        // p is written before the next pass gathers it; ctl is read
+    }
+    if (it > 0)
+        for (int32_t idx = tid; idx < nf; idx += kCgThreads) {
+            const int64_t s = (int64_t)f0 + idx;
+            const int64_t v = C.vertex[s];
+            for (int c = 0; c < 3; c++) out[3 * v + c] = (float)C.x[3 * s + c];
+        }
+    if (tid == 0) {
+        iterations[pt] = it;
+        converged[pt] = (uint8_t)ctl.stop;
+        residual[pt] = sqrt(ctl.ratio);
+    }
+}
+
+inline bool curv_ok(int64_t M, int64_t nF, int64_t nS, int64_t nE, int64_t P) {
+    return M >= 1 && M < (1ll << 31) && nF >= 1 && nF <= nS && nS <= M && nE >= 0 && nE < (1ll << 31) && P >= 1 && P <= nF;
+}
+
+inline Curv carve_curv(Carver& c, int64_t nF, int64_t nS) {
+    Curv C = {};
+    C.x = c.take<double>(3 * nF);
+    C.r = c.take<double>(3 * nF);
+    C.p = c.take<double>(3 * nF);
+    C.q = c.take<double>(3 * nF);
+    C.t = c.take<double>(3 * nS);
+    C.tn = c.take<double>(3 * nS);
+    return C;
+}
+
+}  // namespace
+
+extern "C" int misplat_meshfill_curv_patches(const int32_t* src, const int32_t* tgt, int64_t n_edges, const uint8_t* free,
+                                             int64_t n_vertices, int32_t* parent, int32_t* root, misplat_stream_t stream) {
+    const int64_t M = n_vertices;
+    if (M < 1 || M >= (1ll << 31) || n_edges < 0 || n_edges >= (1ll << 31) || (n_edges > 0 && (!src || !tgt)) || !free || !parent || !root)
+        return MISPLAT_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    if (n_edges > 0)
+        hipLaunchKernelGGL(curv_union_kernel, dim3(blocks(n_edges, 256)), dim3(256), 0, s, src, tgt, n_edges, free, M, parent);
+    hipLaunchKernelGGL(curv_root_kernel, dim3(blocks(M, 256)), dim3(256), 0, s, (const int32_t*)parent, M, root);
+    return launched();
+}
+
+extern "C" int64_t misplat_meshfill_curv_workspace(int64_t n_free, int64_t n_rows) {
+    if (n_free < 1 || n_rows < n_free || n_rows >= (1ll << 31)) return -1;
+    Carver c{nullptr};
+    carve_curv(c, n_free, n_rows);
+    return c.o;
+}
+
+extern "C" int misplat_meshfill_curv_solve(const float* vertices, float* out, int64_t n_vertices, const int32_t* free_offset,
+                                           const int32_t* rim_offset, const int32_t* vertex, const int32_t* row, const int32_t* degree,
+                                           const int32_t* neighbour, const int32_t* place, int64_t n_free, int64_t n_rows,
+                                           int64_t n_entries, const int32_t* code, int32_t n_patches, double rtol,
+                                           int32_t max_iterations, void* workspace, int64_t workspace_bytes, int32_t* iterations,
+                                           uint8_t* converged, double* residual, misplat_stream_t stream) {
+    if (!curv_ok(n_vertices, n_free, n_rows, n_entries, n_patches) || !(rtol >= 0.0) || !vertices || !out || !free_offset || !rim_offset ||
+        !vertex || !row || !degree || (n_entries > 0 && (!neighbour || !place)) || !code || !workspace || !iterations || !converged || !residual)
+        return MISPLAT_EINVAL;
+    Carver c{(char*)workspace};
+    Curv C = carve_curv(c, n_free, n_rows);
+    if (workspace_bytes < c.o) return MISPLAT_EWORKSPACE;
+    C.foff = free_offset; C.roff = rim_offset; C.vertex = vertex; C.row = row; C.deg = degree; C.nbr = neighbour; C.place = place;
+    C.code = code; C.nF = n_free; C.nS = n_rows;
+    hipLaunchKernelGGL(curv_solve_kernel, dim3((unsigned)n_patches), dim3(kCgThreads), 0, (hipStream_t)stream, vertices, out, C,
+                       rtol * rtol, max_iterations, iterations, converged, residual);
     return launched();
 }

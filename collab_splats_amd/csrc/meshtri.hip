@@ -10,6 +10,8 @@
 // p_{n - i}; a loop that is no simple cycle, too short or too long gets its code and is left to the fan.  dp_kernel, one
 // workgroup per loop: the table W[i][j], i < j, of the recurrence by diagonals with a barrier between them, in LDS for the
 // loops that fit (two sizes of workgroup) and in the caller's slab for the others -- the same code over another pointer.
+// The entry's weight is a template policy: the area sum (section 30), or Liepa's angle-and-area pair (section 31;
+// tests/meshsmooth_restatement.py is its oracle), which also needs the rim faces' third corners from order_kernel<true>.
 //
 // Flips, one round (misplat_meshtri_flip_round): facetable.h's edge table; per corner the fp64 bits of the violation of a
 // flippable edge; per face its first flippable edge, selected iff first in its other face too; the selected edges claim their
@@ -33,15 +35,24 @@ constexpr int kHash = 2 * kMaxLoop;                         // the order kernel'
 static_assert((kHash & (kHash - 1)) == 0, "the hash is masked");
 static_assert(kMaxLoop < 65536, "a split is kept in 16 bits");
 static_assert(10 * (kLdsLoop * (kLdsLoop - 1) / 2) + 16 * kLdsLoop <= 160 * 1024, "the table of an LDS loop fits a workgroup's LDS");
+constexpr int kAngleLdsLoop = MISPLAT_MESHTRI_ANGLE_LDS_LOOP;   // the angle-and-area weight: 12 B an entry, 28 B a polygon vertex
+constexpr int kAngleSteps = MISPLAT_MESHTRI_ANGLE_STEPS;
+static_assert(12 * (kAngleLdsLoop * (kAngleLdsLoop - 1) / 2) + 28 * kAngleLdsLoop <= 160 * 1024, "the angle table of an LDS loop fits");
+static_assert(12 * ((kAngleLdsLoop + 1) * kAngleLdsLoop / 2) + 28 * (kAngleLdsLoop + 1) > 160 * 1024, "and it is the longest that does");
+static_assert(kSmallLoop <= kAngleLdsLoop && kAngleSteps + 1 < 65536, "a badness is kept in 16 bits");
 
 enum { kTriangulated = 0, kNotSimple = 1, kTooShort = 2, kTooLong = 3, kNotFilled = -1 };
 
 // ------------------------------------------------------------------------------------------------------ cycle order
 __device__ __forceinline__ uint32_t vertex_home(int32_t v) { return mix32((uint32_t)v, 0u, 0u) & (kHash - 1); }
 
+// RIM: also rim[e0 + i] = o_i, the third corner of the one mesh face that holds the polygon's edge i = (q_i, q_{i+1}) (edge n - 1
+// closes the polygon: (q_{n-1}, q_0)), found through the edge table E of the mesh; -1 where the table does not name such a face.
+template <bool RIM>
 __global__ __launch_bounds__(256) void order_kernel(const int32_t* __restrict__ edges, const int32_t* __restrict__ order,
                                                     const int32_t* __restrict__ offsets, const uint8_t* __restrict__ fill,
-                                                    int64_t n_edges, int32_t* __restrict__ code, int32_t* __restrict__ polygon) {
+                                                    int64_t n_edges, int32_t* __restrict__ code, int32_t* __restrict__ polygon,
+                                                    const int32_t* __restrict__ tri, int64_t T, EdgeTable E, int32_t* __restrict__ rim) {
     __shared__ int32_t hk[kHash], hv[kHash];
     __shared__ int32_t tl[kMaxLoop], hd[kMaxLoop], nx[kMaxLoop], seen[kMaxLoop];
     __shared__ int32_t bad, pmin;
@@ -94,15 +105,49 @@ __global__ __launch_bounds__(256) void order_kernel(const int32_t* __restrict__ 
         while (hk[s] != pmin) s = (s + 1) & (kHash - 1);
         int32_t cur = hv[s];
         polygon[e0] = pmin;
+        if constexpr (RIM) seen[cur] = n - 1;                   // (seen is free again: the edge p_0 -> p_1 closes the polygon)
         for (int i = 1; i < n; i++) {
             cur = nx[cur];
             polygon[e0 + (n - i)] = tl[cur];
+            if constexpr (RIM) seen[cur] = n - 1 - i;           // the edge p_i -> p_{i+1} is (q_{n-i-1}, q_{n-i}) against its run
         }
         if (nx[cur] != hv[s]) bad = 1;                          // (it has not closed after n steps: not one cycle)
     }
     __syncthreads();
     if (threadIdx.x == 0) code[l] = bad ? kNotSimple : kTriangulated;
+    if constexpr (RIM) {
+        if (bad) return;                                        // (uniform)
+        for (int i = threadIdx.x; i < n; i += 256) {
+            const int32_t a = tl[i], b = hd[i];
+            int32_t o = -1;
+            if (a != b) {
+                const u64 key = edge_key(a, b);
+                u64 s = edge_home(key, E.mask);
+                while (E.keys[s] != key && E.keys[s] != kEmpty) s = (s + 1) & E.mask;   // (the table is never full)
+                if (E.keys[s] == key) {
+                    const int64_t f = E.fmin[s];
+                    if (f >= 0 && f < T)
+                        for (int c = 0; c < 3; c++)
+                            if (tri[3 * f + c] == a && tri[3 * f + (c + 1) % 3] == b) o = tri[3 * f + (c + 2) % 3];
+                }
+            }
+            rim[e0 + seen[i]] = o;
+        }
+    }
 }
+
+// the fp64 vector helpers of the crease weight and of the flips
+struct D3 {
+    double x, y, z;
+};
+__device__ __forceinline__ D3 point(const float* __restrict__ V, int32_t v) {
+    return D3{(double)V[3 * (int64_t)v], (double)V[3 * (int64_t)v + 1], (double)V[3 * (int64_t)v + 2]};
+}
+__device__ __forceinline__ D3 sub(const D3& p, const D3& q) { return D3{p.x - q.x, p.y - q.y, p.z - q.z}; }
+__device__ __forceinline__ D3 cross(const D3& u, const D3& v) {
+    return D3{u.y * v.z - u.z * v.y, u.z * v.x - u.x * v.z, u.x * v.y - u.y * v.x};
+}
+__device__ __forceinline__ double dot(const D3& u, const D3& v) { return (u.x * v.x + u.y * v.y) + u.z * v.z; }
 
 // --------------------------------------------------------------------------------------------------------------- DP
 // Entry (i, j), i < j < n, of the triangular table, stored one diagonal after another (diagonal d = j - i holds its n - d
@@ -121,23 +166,53 @@ __device__ __forceinline__ float tri_area(const float* Q, int i, int k, int j) {
     return 0.5f * sqrtf((cx * cx + cy * cy) + cz * cz);
 }
 
+// The weight of a table entry as a policy.  AreaWeight: the fp64 area sum alone (section 30).  AngleWeight (section 31): the pair
+// (b, a), b the integer badness of the sharpest crease of the entry's faces among themselves and against the rim faces, a the
+// same area sum, compared lexicographically; an entry is 8 + 2 + 2 bytes, so its LDS instance holds a shorter loop.
+struct AreaWeight {
+    static constexpr bool kAngle = false;
+    static constexpr int kCap = kLdsLoop;
+};
+struct AngleWeight {
+    static constexpr bool kAngle = true;
+    static constexpr int kCap = kAngleLdsLoop;
+};
+
+__device__ __forceinline__ D3 lds_point(const float* Q, int i) { return D3{(double)Q[3 * i], (double)Q[3 * i + 1], (double)Q[3 * i + 2]}; }
+// the unnormalised fp64 normal of the oriented face (a, b, c)
+__device__ __forceinline__ D3 face_normal(const D3& a, const D3& b, const D3& c) { return cross(sub(b, a), sub(c, a)); }
+// the badness of the crease between two oriented faces with these normals: 0 flat .. kAngleSteps folded over; a face without a
+// normal (a squared length of 0, or a rim corner that is not there: NaN) poisons nothing
+__device__ __forceinline__ int crease(const D3& n1, const D3& n2) {
+    const double d1 = dot(n1, n1), d2 = dot(n2, n2);
+    if (d1 == 0.0 || d2 == 0.0) return 0;
+    const double c = dot(n1, n2) / sqrt(d1 * d2);
+    const double x = floor((1.0 - c) * 0.5 * (double)kAngleSteps);
+    if (!(x > 0.0)) return 0;
+    return x > (double)kAngleSteps ? kAngleSteps : (int)x;
+}
+
 // One workgroup per loop with lo <= n <= hi.  CAP > 0: the table in LDS (n <= CAP); CAP = 0: in the slab at slab_off[l].
 // Diagonal d has n - d entries of d - 1 candidates each: G lanes share an entry (G = 1 while the entries fill the workgroup,
 // then the power of two that keeps it filled, at most a wave), each takes every G-th candidate in ascending k with a strict <,
 // and a butterfly takes the smaller weight, on equal weights the smaller k: the first minimum in ascending k whatever G is.
-template <int CAP, int THREADS>
-__global__ __launch_bounds__(THREADS) void dp_kernel(const float* __restrict__ V, const int32_t* __restrict__ polygon,
-                                                     const int32_t* __restrict__ offsets, const int32_t* __restrict__ code, int lo,
-                                                     int hi, double* slabW, uint16_t* slabS, const int64_t* __restrict__ slab_off,
-                                                     int64_t n_entries, const int32_t* __restrict__ face_base, int64_t n_faces,
+template <class WEIGHT, int CAP, int THREADS>
+__global__ __launch_bounds__(THREADS) void dp_kernel(const float* __restrict__ V, int64_t M, const int32_t* __restrict__ polygon,
+                                                     const int32_t* __restrict__ rim, const int32_t* __restrict__ offsets,
+                                                     const int32_t* __restrict__ code, int lo, int hi, double* slabW, uint16_t* slabS,
+                                                     uint16_t* slabB, const int64_t* __restrict__ slab_off, int64_t n_entries,
+                                                     const int32_t* __restrict__ face_base, int64_t n_faces,
                                                      const int32_t* __restrict__ area_slot, int64_t n_area, int32_t* __restrict__ faces,
-                                                     double* __restrict__ area) {
+                                                     double* __restrict__ area, int32_t* __restrict__ badness) {
+    constexpr bool ANGLE = WEIGHT::kAngle;
     constexpr int NQ = CAP ? CAP : kMaxLoop;
     constexpr int NT = CAP ? CAP * (CAP - 1) / 2 : 1;
     __shared__ double Wl[NT];
     __shared__ float Q[3 * NQ];
+    __shared__ float Rm[ANGLE ? 3 * NQ : 1];                    // the rim corners o_i
     __shared__ int32_t P[NQ];
     __shared__ uint16_t Sl[NT];
+    __shared__ uint16_t Bl[ANGLE ? NT : 1];
     const int64_t l = blockIdx.x;
     if (code[l] != kTriangulated) return;                       // (every return here is uniform)
     const int32_t e0 = offsets[l];
@@ -146,23 +221,35 @@ __global__ __launch_bounds__(THREADS) void dp_kernel(const float* __restrict__ V
     const int64_t fb = face_base[l], as = area_slot[l];
     if (fb < 0 || fb + n - 2 > n_faces || as < 0 || as >= n_area) return;
     double* W;
-    uint16_t* S;
+    uint16_t *S, *B;
     if constexpr (CAP != 0) {
         W = Wl;
         S = Sl;
+        B = Bl;
     } else {
         const int64_t off = slab_off[l];
         if (off < 0 || off + (int64_t)n * (n - 1) / 2 > n_entries) return;
         W = slabW + off;
         S = slabS + off;
+        B = ANGLE ? slabB + off : nullptr;
     }
     const int tid = threadIdx.x;
     for (int i = tid; i < n; i += THREADS) {
         const int32_t v = polygon[e0 + i];
         P[i] = v;
         for (int c = 0; c < 3; c++) Q[3 * i + c] = V[3 * (int64_t)v + c];
+        if constexpr (ANGLE) {
+            const int32_t o = rim[e0 + i];
+            for (int c = 0; c < 3; c++) Rm[3 * i + c] = o >= 0 && o < M ? V[3 * (int64_t)o + c] : __builtin_nanf("");
+        }
     }
-    for (int i = tid; i < n - 1; i += THREADS) W[tri_index(n, i, i + 1)] = 0.0;
+    for (int i = tid; i < n - 1; i += THREADS) {
+        W[tri_index(n, i, i + 1)] = 0.0;
+        if constexpr (ANGLE) {
+            B[tri_index(n, i, i + 1)] = 0;
+            S[tri_index(n, i, i + 1)] = 0;                      // (read beside a rim face's normal, never used)
+        }
+    }
     __syncthreads();
     for (int d = 2; d < n; d++) {                               // (the bounds are the loop's n: every barrier is uniform)
         const int E = n - d;
@@ -173,19 +260,43 @@ __global__ __launch_bounds__(THREADS) void dp_kernel(const float* __restrict__ V
             const int i = base + tid / G, j = i + d;
             double best = __builtin_huge_val();
             int bk = i + 1;
+            int bb = kAngleSteps + 1;                           // (no candidate yet: above every badness)
             if (i < E)
                 for (int k = i + 1 + g; k < j; k += G) {
-                    const double v = (W[tri_index(n, i, k)] + W[tri_index(n, k, j)]) + (double)tri_area(Q, i, k, j);
-                    if (v < best) { best = v; bk = k; }
+                    const int ik = tri_index(n, i, k), kj = tri_index(n, k, j);
+                    const double v = (W[ik] + W[kj]) + (double)tri_area(Q, i, k, j);
+                    if constexpr (ANGLE) {
+                        const D3 pi = lds_point(Q, i), pk = lds_point(Q, k), pj = lds_point(Q, j);
+                        const D3 nt = face_normal(pi, pk, pj);
+                        const D3 nl = k - i == 1 ? face_normal(pk, pi, lds_point(Rm, i)) : face_normal(pi, lds_point(Q, S[ik]), pk);
+                        const D3 nr = j - k == 1 ? face_normal(pj, pk, lds_point(Rm, k)) : face_normal(pk, lds_point(Q, S[kj]), pj);
+                        int b = B[ik] > B[kj] ? B[ik] : B[kj];
+                        const int bl = crease(nt, nl), br = crease(nt, nr);
+                        b = bl > b ? bl : b;
+                        b = br > b ? br : b;
+                        if (d == n - 1) {                       // the top entry: the rim face of the closing edge
+                            const int bc = crease(nt, face_normal(pi, pj, lds_point(Rm, n - 1)));
+                            b = bc > b ? bc : b;
+                        }
+                        if (b < bb || (b == bb && v < best)) { bb = b; best = v; bk = k; }
+                    } else {
+                        if (v < best) { best = v; bk = k; }
+                    }
                 }
             for (int off = G >> 1; off > 0; off >>= 1) {
                 const double ov = __shfl_xor(best, off);
                 const int ok = __shfl_xor(bk, off);
-                if (ov < best || (ov == best && ok < bk)) { best = ov; bk = ok; }
+                if constexpr (ANGLE) {
+                    const int ob = __shfl_xor(bb, off);
+                    if (ob < bb || (ob == bb && (ov < best || (ov == best && ok < bk)))) { bb = ob; best = ov; bk = ok; }
+                } else {
+                    if (ov < best || (ov == best && ok < bk)) { best = ov; bk = ok; }
+                }
             }
             if (i < E && g == 0) {
                 W[tri_index(n, i, j)] = best;
                 S[tri_index(n, i, j)] = (uint16_t)bk;
+                if constexpr (ANGLE) B[tri_index(n, i, j)] = (uint16_t)bb;
             }
         }
         __syncthreads();
@@ -201,10 +312,42 @@ __global__ __launch_bounds__(THREADS) void dp_kernel(const float* __restrict__ V
         int32_t* out = faces + 3 * (fb + k - 1);
         out[0] = P[i]; out[1] = P[k]; out[2] = P[j];
     }
-    if (tid == 0) area[as] = W[tri_index(n, 0, n - 1)];
+    if (tid == 0) {
+        area[as] = W[tri_index(n, 0, n - 1)];
+        if constexpr (ANGLE) badness[as] = B[tri_index(n, 0, n - 1)];
+    }
 }
 
 inline int64_t slab_bytes(int64_t n_entries) { return al(8 * n_entries) + al(2 * n_entries); }
+inline int64_t angle_slab_bytes(int64_t n_entries) { return slab_bytes(n_entries) + al(2 * n_entries); }
+
+// the three instances of one weight: the small workgroup, the LDS table, the table in the slab
+template <class WEIGHT>
+inline void launch_dp(int paths, int64_t L, hipStream_t s, const float* vertices, int64_t M, const int32_t* polygon, const int32_t* rim,
+                      const int32_t* offsets, const int32_t* code, void* workspace, const int64_t* slab_offset, int64_t n_entries,
+                      const int32_t* face_base, int64_t n_faces, const int32_t* area_slot, int64_t n_area, int32_t* faces, double* area,
+                      int32_t* badness) {
+    constexpr int CAP = WEIGHT::kCap;
+    double* slabW = nullptr;
+    uint16_t *slabS = nullptr, *slabB = nullptr;
+    if (paths & 4) {
+        slabW = (double*)workspace;
+        slabS = (uint16_t*)((char*)workspace + al(8 * n_entries));
+        slabB = (uint16_t*)((char*)workspace + slab_bytes(n_entries));      // (the angle weight's slab alone reaches this far)
+    }
+    if (paths & 1)
+        hipLaunchKernelGGL((dp_kernel<WEIGHT, kSmallLoop, 256>), dim3((unsigned)L), dim3(256), 0, s, vertices, M, polygon, rim, offsets,
+                           code, 3, kSmallLoop, nullptr, nullptr, nullptr, nullptr, 0, face_base, n_faces, area_slot, n_area, faces, area,
+                           badness);
+    if (paths & 2)
+        hipLaunchKernelGGL((dp_kernel<WEIGHT, CAP, 1024>), dim3((unsigned)L), dim3(1024), 0, s, vertices, M, polygon, rim, offsets, code,
+                           kSmallLoop + 1, CAP, nullptr, nullptr, nullptr, nullptr, 0, face_base, n_faces, area_slot, n_area, faces, area,
+                           badness);
+    if (paths & 4)
+        hipLaunchKernelGGL((dp_kernel<WEIGHT, 0, 1024>), dim3((unsigned)L), dim3(1024), 0, s, vertices, M, polygon, rim, offsets, code,
+                           CAP + 1, kMaxLoop, slabW, slabS, slabB, slab_offset, n_entries, face_base, n_faces, area_slot, n_area, faces,
+                           area, badness);
+}
 
 // ------------------------------------------------------------------------------------------------------------ flips
 struct Quad {
@@ -234,17 +377,6 @@ __device__ __forceinline__ bool quad_of(const int32_t* __restrict__ tri, int32_t
     return false;
 }
 
-struct D3 {
-    double x, y, z;
-};
-__device__ __forceinline__ D3 point(const float* __restrict__ V, int32_t v) {
-    return D3{(double)V[3 * (int64_t)v], (double)V[3 * (int64_t)v + 1], (double)V[3 * (int64_t)v + 2]};
-}
-__device__ __forceinline__ D3 sub(const D3& p, const D3& q) { return D3{p.x - q.x, p.y - q.y, p.z - q.z}; }
-__device__ __forceinline__ D3 cross(const D3& u, const D3& v) {
-    return D3{u.y * v.z - u.z * v.y, u.z * v.x - u.x * v.z, u.x * v.y - u.y * v.x};
-}
-__device__ __forceinline__ double dot(const D3& u, const D3& v) { return (u.x * v.x + u.y * v.y) + u.z * v.z; }
 // the cotangent of the angle at p between p -> s and p -> t
 __device__ __forceinline__ double cotangent(const D3& p, const D3& s, const D3& t) {
     const D3 u = sub(s, p), v = sub(t, p), n = cross(u, v);
@@ -354,6 +486,22 @@ inline FlipWork carve_flip(Carver& c, int64_t T) {
     return W;
 }
 
+struct RimWork {
+    int64_t cap;
+    u64* keys;
+    int32_t *cnt, *fmin, *fmax;
+};
+
+inline RimWork carve_rim(Carver& c, int64_t T) {
+    RimWork W = {};
+    W.cap = edge_capacity(T);
+    W.keys = c.take<u64>(W.cap);
+    W.cnt = c.take<int32_t>(W.cap);
+    W.fmin = c.take<int32_t>(W.cap);
+    W.fmax = c.take<int32_t>(W.cap);
+    return W;
+}
+
 inline bool flip_ok(int64_t M, int64_t T) { return M >= 1 && M < (1ll << 31) && T >= 1 && 6 * T < (1ll << 31) - kTile; }
 
 }  // namespace
@@ -363,8 +511,33 @@ extern "C" int misplat_meshtri_order(const int32_t* edges, const int32_t* order,
     if (n_edges < 1 || n_edges >= (1ll << 31) || n_loops < 1 || n_loops > n_edges || !edges || !order || !offsets || !fill || !code ||
         !polygon)
         return MISPLAT_EINVAL;
-    hipLaunchKernelGGL(order_kernel, dim3((unsigned)n_loops), dim3(256), 0, (hipStream_t)stream, edges, order, offsets, fill, n_edges,
-                       code, polygon);
+    hipLaunchKernelGGL(order_kernel<false>, dim3((unsigned)n_loops), dim3(256), 0, (hipStream_t)stream, edges, order, offsets, fill,
+                       n_edges, code, polygon, (const int32_t*)nullptr, (int64_t)0, EdgeTable{}, (int32_t*)nullptr);
+    return launched();
+}
+
+extern "C" int64_t misplat_meshtri_rim_workspace(int64_t n_triangles) {
+    if (n_triangles < 1 || 6 * n_triangles >= (1ll << 31) - kTile) return -1;
+    Carver c{nullptr};
+    carve_rim(c, n_triangles);
+    return c.o;
+}
+
+extern "C" int misplat_meshtri_order_rim(const int32_t* edges, const int32_t* order, const int32_t* offsets, const uint8_t* fill,
+                                         int64_t n_edges, int64_t n_loops, const int32_t* triangles, int64_t n_triangles,
+                                         void* workspace, int64_t workspace_bytes, int32_t* code, int32_t* polygon, int32_t* rim,
+                                         misplat_stream_t stream) {
+    const int64_t T = n_triangles;
+    if (n_edges < 1 || n_edges >= (1ll << 31) || n_loops < 1 || n_loops > n_edges || T < 1 || 6 * T >= (1ll << 31) - kTile || !edges ||
+        !order || !offsets || !fill || !triangles || !workspace || !code || !polygon || !rim)
+        return MISPLAT_EINVAL;
+    Carver c{(char*)workspace};
+    const RimWork W = carve_rim(c, T);
+    if (workspace_bytes < c.o) return MISPLAT_EWORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    const EdgeTable E = build_edge_table(triangles, T, W.keys, W.cnt, W.fmin, W.fmax, W.cap, s);
+    hipLaunchKernelGGL(order_kernel<true>, dim3((unsigned)n_loops), dim3(256), 0, s, edges, order, offsets, fill, n_edges, code, polygon,
+                       triangles, T, E, rim);
     return launched();
 }
 
@@ -383,18 +556,29 @@ extern "C" int misplat_meshtri_dp(const float* vertices, int64_t n_vertices, con
         !faces || !area || ((paths & 4) && (!slab_offset || !workspace)))
         return MISPLAT_EINVAL;
     if ((paths & 4) && workspace_bytes < slab_bytes(n_entries)) return MISPLAT_EWORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    double* slabW = (double*)workspace;
-    uint16_t* slabS = (uint16_t*)((char*)workspace + al(8 * n_entries));
-    if (paths & 1)
-        hipLaunchKernelGGL((dp_kernel<kSmallLoop, 256>), dim3((unsigned)L), dim3(256), 0, s, vertices, polygon, offsets, code, 3,
-                           kSmallLoop, nullptr, nullptr, nullptr, 0, face_base, n_faces, area_slot, n_area, faces, area);
-    if (paths & 2)
-        hipLaunchKernelGGL((dp_kernel<kLdsLoop, 1024>), dim3((unsigned)L), dim3(1024), 0, s, vertices, polygon, offsets, code,
-                           kSmallLoop + 1, kLdsLoop, nullptr, nullptr, nullptr, 0, face_base, n_faces, area_slot, n_area, faces, area);
-    if (paths & 4)
-        hipLaunchKernelGGL((dp_kernel<0, 1024>), dim3((unsigned)L), dim3(1024), 0, s, vertices, polygon, offsets, code, kLdsLoop + 1,
-                           kMaxLoop, slabW, slabS, slab_offset, n_entries, face_base, n_faces, area_slot, n_area, faces, area);
+    launch_dp<AreaWeight>(paths, L, (hipStream_t)stream, vertices, n_vertices, polygon, nullptr, offsets, code, workspace, slab_offset,
+                          n_entries, face_base, n_faces, area_slot, n_area, faces, area, nullptr);
+    return launched();
+}
+
+extern "C" int64_t misplat_meshtri_angle_workspace(int64_t n_entries) {
+    if (n_entries < 0 || n_entries >= (1ll << 40)) return -1;
+    return angle_slab_bytes(n_entries);
+}
+
+extern "C" int misplat_meshtri_angle_dp(const float* vertices, int64_t n_vertices, const int32_t* polygon, const int32_t* rim,
+                                        const int32_t* offsets, const int32_t* code, int64_t n_loops, int32_t paths,
+                                        const int64_t* slab_offset, int64_t n_entries, void* workspace, int64_t workspace_bytes,
+                                        const int32_t* face_base, int64_t n_faces, const int32_t* area_slot, int64_t n_area,
+                                        int32_t* faces, double* area, int32_t* badness, misplat_stream_t stream) {
+    const int64_t L = n_loops;
+    if (n_vertices < 1 || n_vertices >= (1ll << 31) || L < 1 || L >= (1ll << 31) || paths < 1 || paths > 7 || n_entries < 0 ||
+        n_entries >= (1ll << 40) || n_faces < 1 || n_area < 1 || !vertices || !polygon || !rim || !offsets || !code || !face_base ||
+        !area_slot || !faces || !area || !badness || ((paths & 4) && (!slab_offset || !workspace)))
+        return MISPLAT_EINVAL;
+    if ((paths & 4) && workspace_bytes < angle_slab_bytes(n_entries)) return MISPLAT_EWORKSPACE;
+    launch_dp<AngleWeight>(paths, L, (hipStream_t)stream, vertices, n_vertices, polygon, rim, offsets, code, workspace, slab_offset,
+                           n_entries, face_base, n_faces, area_slot, n_area, faces, area, badness);
     return launched();
 }
 

@@ -7,9 +7,11 @@ subdivided to the mesh's edge length while its edges are flipped, and its new ve
 steps run on device tensors: the fan of ``fill_holes`` or the minimum-area triangulation of the loop (``triangulate_holes``,
 csrc/meshtri.hip), longest-edge bisection of the patch's faces in rounds (``subdivide_mesh``), Delaunay-like
 flips of its edges (``flip_edges``, section 30), membrane fairing of the created vertices with the rim held fixed
-(``fair_vertices``).  Restated from the published methods [UNVERIFIED-UPSTREAM]: MeshLib is not available to compare with and
-its output cannot be pinned; its universal metric (with a dihedral term) and its curvature fairing are NOT built.  The oracles
-are tests/meshfill_restatement.py and tests/meshtri_restatement.py, bit for bit.  There is no CPU fallback.
+(``fair_vertices``).  Behind options: Liepa's angle-and-area weight for the triangulation
+(``metric="angle_area"``) and a thin-plate solve after the membrane (``fair_vertices_curvature``, ``fairing="curvature"``).
+Restated from the published methods [UNVERIFIED-UPSTREAM]: MeshLib is not available to compare with and its output cannot be
+pinned; its own universal-metric formula is NOT built.  The oracles are tests/meshfill_restatement.py,
+tests/meshtri_restatement.py and tests/meshsmooth_restatement.py, bit for bit.  There is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -39,6 +41,16 @@ LDS_MAX_VERTICES = 4096
 LDS_LOOP = 176
 MAX_LOOP = 1024
 SMALL_LOOP = 64
+# The angle-and-area weight of ``triangulate_holes(metric="angle_area")`` keeps 12 bytes an entry and 28 a polygon vertex: its
+# table fits a workgroup's LDS up to ANGLE_LDS_LOOP edges (MISPLAT_MESHTRI_ANGLE_LDS_LOOP; DESIGN.md section 31.2 holds the
+# arithmetic).  ANGLE_STEPS (MISPLAT_MESHTRI_ANGLE_STEPS) is the number of buckets a crease's badness is quantised to.
+ANGLE_LDS_LOOP = 163
+ANGLE_STEPS = 1024
+METRICS = ("area", "angle_area")
+# fair_vertices_curvature leaves a patch of more free vertices unchanged (MISPLAT_MESHFILL_CG_VERTICES: a stated limit of the
+# one-workgroup-per-patch solve, not a measurement).
+CG_VERTICES = 65536
+FAIRINGS = ("membrane", "curvature")
 
 
 def _count(name: str, what: str, x) -> int:
@@ -227,11 +239,117 @@ def fair_vertices(vertices: Tensor, triangles: Tensor, free: Tensor, tolerance: 
     return pos, tuple(out), iterations
 
 
+# ------------------------------------------------------------------------------------------------ curvature fairing
+def fair_vertices_curvature(vertices: Tensor, triangles: Tensor, free: Tensor, rtol: float = 1e-6,
+                            max_iterations: Optional[int] = None) -> Tuple[Tensor, dict]:
+    """Thin-plate fairing of the ``free`` vertices (bool [M]; every other vertex is fixed): ``(vertices', info)``.  Positions
+    only.
+
+    N(i) is ``fair_vertices``'s distinct edge-neighbours of vertex i in ascending order, n_i their number; F the free set, R the
+    fixed vertices with a free neighbour, S their union.  The umbrella ``U_i(x) = (sum_{j in N(i)} x_j) / (double) n_i - x_i`` is
+    taken in fp64 (fixed coordinates are the doubles of their fp32), and the energy ``sum_{i in S} |U_i|^2`` is minimised over
+    the free coordinates: ``A x_F = b`` with ``A = L^T L``, L the rows of S and the columns of F of the umbrella operator,
+    symmetric positive definite whenever the patch has a fixed neighbour.  A patch is a connected set of free vertices, two
+    being connected when they are adjacent or share a neighbour in R (two holes that share a rim vertex are one patch: every
+    row of R belongs to exactly one); patches are numbered by their smallest free vertex.
+
+    Per patch, plain conjugate gradients without a preconditioner, all state fp64, from the input positions; the result is
+    rounded to fp32 once.  The three coordinates are three independent CGs (a column whose ``p.q`` is 0 takes alpha = beta = 0)
+    with one stop: after iteration k, iff ``sum_c r_c.r_c <= rtol^2 sum_c r0_c.r0_c`` (0 iterations if the right-hand side is 0),
+    or at ``max_iterations`` (None: the patch's free count, CG's own bound in exact arithmetic).  Applying A to p is two gathers
+    over the same rows, ``t_i = (sum_{j in N(i) and F} p_j) / n_i - [i in F] p_i`` over S and ``q_i = (sum_{j in N(i)} t_j / n_j) -
+    t_i`` over F; dot products are summed in a fixed order.  One workgroup runs a patch's whole solve: no host read and no launch
+    inside the iteration.  ``info``: ``iterations`` [P] int32, ``converged`` [P] bool, ``residual`` [P] fp64 (the square root of
+    the final ratio) and ``code`` [P] int32: 0 solved; 1 no neighbour at all, 2 no fixed neighbour (a closed free component), 3
+    more than ``CG_VERTICES`` free vertices (a stated limit) -- all three unchanged.  The CSR of the rows of S and the lists by
+    patch are index plumbing on the device (sorts, scans); the components and the solve are csrc/meshfill.hip's.  Two runs are
+    bitwise equal."""
+    name = "fair_vertices_curvature"
+    v, t = _mesh(name, vertices, triangles)
+    m = v.shape[0]
+    if not isinstance(free, Tensor) or free.dtype != torch.bool or tuple(free.shape) != (m,):
+        raise ValueError(f"{name}: free must be a bool tensor [{m}]")
+    try:
+        rtol = float(rtol)
+    except (TypeError, ValueError):
+        rtol = math.nan
+    if not (0.0 <= rtol < math.inf):
+        raise ValueError(f"{name}: rtol must be a finite number >= 0")
+    if max_iterations is not None:
+        max_iterations = _count(name, "max_iterations", max_iterations)
+        if max_iterations >= 1 << 31:
+            raise ValueError(f"{name}: max_iterations must be below 2^31, got {max_iterations}")
+    if 6 * t.shape[0] >= (1 << 31) - 4096:
+        raise ValueError(f"{name}: {t.shape[0]} triangles are beyond the library's limits (6 T < 2^31 - 4096)")
+    require_gpu(vertices, triangles, free)
+    dev = v.device
+    i32 = dict(dtype=torch.int32, device=dev)
+    fr = free.detach().contiguous()
+    flist = torch.nonzero(fr).view(-1)                              # ascending
+    n_free = flist.shape[0]
+    if n_free == 0:
+        return v.clone(), {"iterations": torch.zeros(0, **i32), "converged": torch.zeros(0, dtype=torch.bool, device=dev),
+                           "residual": torch.zeros(0, dtype=torch.float64, device=dev), "code": torch.zeros(0, **i32)}
+    lib = load()
+    # the directed edges that leave a row of S, distinct, by source and then by target
+    tl = t.long()
+    src, tgt = tl[:, [0, 1, 2, 1, 2, 0]].reshape(-1), tl[:, [1, 2, 0, 0, 1, 2]].reshape(-1)
+    keep = src != tgt
+    src, tgt = src[keep], tgt[keep]
+    in_r = torch.zeros(m, dtype=torch.bool, device=dev)
+    in_r[src[fr[tgt]]] = True
+    in_r &= ~fr
+    keep = (fr | in_r)[src]
+    key = torch.unique(src[keep] * m + tgt[keep])                   # sorted
+    es, et = (key // m).to(torch.int32), (key % m).to(torch.int32)
+    n_entries = es.shape[0]
+    parent = torch.arange(m, **i32)
+    root = torch.empty(m, **i32)
+    check(lib.misplat_meshfill_curv_patches(ptr(es), ptr(et), C.c_int64(n_entries), ptr(fr.view(torch.uint8)), C.c_int64(m), ptr(parent),
+                                            ptr(root), stream_ptr()), "misplat_meshfill_curv_patches")
+    # patches by their smallest free vertex; the free vertices and the rows of R by patch and then by vertex
+    roots, of_free = torch.unique(root[flist].long(), return_inverse=True)
+    n_patches = roots.shape[0]
+    first = torch.full((n_patches,), m, dtype=torch.int64, device=dev).scatter_reduce(0, of_free, flist, "amin")
+    rank = torch.empty(n_patches, dtype=torch.int64, device=dev)
+    rank[torch.argsort(first)] = torch.arange(n_patches, device=dev)
+    patch_of_root = torch.full((m,), -1, dtype=torch.int64, device=dev)
+    patch_of_root[roots] = rank
+    rlist = torch.nonzero(in_r).view(-1)
+    pf, pr = rank[of_free], patch_of_root[root[rlist].long()]
+    flist, rlist = flist[torch.sort(pf, stable=True).indices], rlist[torch.sort(pr, stable=True).indices]
+    n_f, n_r = torch.bincount(pf, minlength=n_patches), torch.bincount(pr, minlength=n_patches)
+    foff, roff = torch.zeros(n_patches + 1, **i32), torch.zeros(n_patches + 1, **i32)
+    foff[1:], roff[1:] = torch.cumsum(n_f, 0), torch.cumsum(n_r, 0)
+    slist = torch.cat([flist, rlist])
+    n_rows = slist.shape[0]
+    place_of = torch.full((m,), -1, **i32)
+    place_of[slist] = torch.arange(n_rows, **i32)
+    degree_of = torch.bincount(es.long(), minlength=m)
+    start_of = torch.cumsum(degree_of, 0) - degree_of
+    has_degree = torch.zeros(n_patches, dtype=torch.bool, device=dev)
+    has_degree[pf[degree_of[torch.nonzero(fr).view(-1)] > 0]] = True
+    code = torch.where(~has_degree, 1, torch.where(n_r == 0, 2, torch.where(n_f > CG_VERTICES, 3, 0))).to(torch.int32)
+    ws = torch.empty(int(lib.misplat_meshfill_curv_workspace(C.c_int64(n_free), C.c_int64(n_rows))), dtype=torch.uint8, device=dev)
+    out = v.clone()
+    iterations = torch.empty(n_patches, **i32)
+    converged = torch.empty(n_patches, dtype=torch.uint8, device=dev)
+    residual = torch.empty(n_patches, dtype=torch.float64, device=dev)
+    vertex, row, degree = slist.to(torch.int32), start_of[slist].to(torch.int32), degree_of[slist].to(torch.int32)
+    place = place_of[et.long()].contiguous()
+    check(lib.misplat_meshfill_curv_solve(ptr(v), ptr(out), C.c_int64(m), ptr(foff), ptr(roff), ptr(vertex), ptr(row), ptr(degree),
+                                          ptr(et), ptr(place), C.c_int64(n_free), C.c_int64(n_rows), C.c_int64(n_entries), ptr(code),
+                                          n_patches, C.c_double(rtol), -1 if max_iterations is None else max_iterations, ptr(ws),
+                                          C.c_int64(ws.numel()), ptr(iterations), ptr(converged), ptr(residual), stream_ptr()),
+          "misplat_meshfill_curv_solve")
+    return out, {"iterations": iterations, "converged": converged.bool(), "residual": residual, "code": code}
+
+
 # --------------------------------------------------------------------------------------------------------- the fill
 def fill_holes_nicely(vertices: Tensor, triangles: Tensor, max_hole_size: float = 3.0, max_edge_len: Optional[float] = None,
                       max_edge_splits: int = 10000, tolerance: Optional[float] = None, max_iterations: int = 10000,
-                      attributes: Sequence[Tensor] = (), triangulation: str = "fan", flip: bool = False, max_passes: int = 4
-                      ) -> Tuple[Tensor, Tensor, Tuple[Tensor, ...], int, dict]:
+                      attributes: Sequence[Tensor] = (), triangulation: str = "fan", flip: bool = False, max_passes: int = 4,
+                      metric: str = "area", fairing: str = "membrane") -> Tuple[Tensor, Tensor, Tuple[Tensor, ...], int, dict]:
     """``fill_holes`` whose patches are subdivided to the mesh's edge length and faired: ``(vertices', triangles', attributes',
     n_filled, info)``; ``info`` holds ``n_splits``, ``rounds``, ``iterations`` ([P] int32, one entry per patch of created
     vertices), ``n_new_vertices``, ``n_flips``, ``flip_rounds``, ``passes``, ``n_triangulated`` and ``n_fans``.
@@ -246,11 +364,18 @@ def fill_holes_nicely(vertices: Tensor, triangles: Tensor, max_hole_size: float 
     mesh.py:386-390); ``tolerance=None`` is ``1e-3 max_edge_len`` (a chosen default).  The reference's ``maxEdgeSplits`` is per
     hole; here the call's total is ``max_edge_splits * n_filled``, the same worst case: a single hole may take more than its
     share.  The input's vertices and faces are a bit-identical prefix of the output; loops at or above ``max_hole_size`` are
-    untouched.  The defaults (``"fan"``, no flips) give what they always gave, bit for bit.
+    untouched.  The defaults (``"fan"``, no flips, ``"area"``, ``"membrane"``) give what they always gave, bit for bit.
+
+    ``metric="angle_area"`` is passed to ``triangulate_holes`` (it needs ``triangulation="min_area"``).  ``fairing="curvature"``
+    runs ``fair_vertices`` as above, which yields the attributes and the start of the solve, and then
+    ``fair_vertices_curvature`` on the same free set: the patch continues the rim's tangent planes instead
+    of spanning it like a membrane; a patch whose ``curvature_code`` is not 0 keeps the membrane's result.  ``info`` then gains
+    ``curvature_iterations``, ``curvature_converged`` and ``curvature_code``.
 
     This stands where MeshLib's ``fillHoleNicely`` stands in the reference, restated from the published methods (minimum-area
-    triangulation, longest-edge bisection, Delaunay flips, membrane fairing with the rim fixed): MeshLib's universal metric and
-    its curvature fairing are not built, and nothing here can be compared with MeshLib's output."""
+    triangulation and Liepa's angle-and-area weight, longest-edge bisection, Delaunay flips, membrane and thin-plate fairing
+    with the rim fixed): MeshLib's own universal-metric formula is not built, and nothing here can be compared with MeshLib's
+    output."""
     name = "fill_holes_nicely"
     v, t = _mesh(name, vertices, triangles)
     attributes = _attributes(name, attributes, v.shape[0], True)
@@ -263,6 +388,12 @@ def fill_holes_nicely(vertices: Tensor, triangles: Tensor, max_hole_size: float 
     max_iterations = _count(name, "max_iterations", max_iterations)
     if triangulation not in ("fan", "min_area"):
         raise ValueError(f"{name}: triangulation must be 'fan' or 'min_area', got {triangulation!r}")
+    if metric not in METRICS:
+        raise ValueError(f"{name}: metric must be 'area' or 'angle_area', got {metric!r}")
+    if metric != "area" and triangulation != "min_area":
+        raise ValueError(f"{name}: metric={metric!r} needs triangulation='min_area'")
+    if fairing not in FAIRINGS:
+        raise ValueError(f"{name}: fairing must be 'membrane' or 'curvature', got {fairing!r}")
     max_passes = _count(name, "max_passes", max_passes)
     if flip and max_passes < 1:
         raise ValueError(f"{name}: max_passes must be at least 1 with flip=True, got {max_passes}")
@@ -271,8 +402,12 @@ def fill_holes_nicely(vertices: Tensor, triangles: Tensor, max_hole_size: float 
     m, n = v.shape[0], t.shape[0]
     info = {"n_splits": 0, "rounds": 0, "iterations": torch.zeros(0, dtype=torch.int32, device=v.device), "n_new_vertices": 0,
             "n_flips": 0, "flip_rounds": 0, "passes": 0, "n_triangulated": 0, "n_fans": 0}
+    if fairing == "curvature":
+        info.update(curvature_iterations=torch.zeros(0, dtype=torch.int32, device=v.device),
+                    curvature_converged=torch.zeros(0, dtype=torch.bool, device=v.device),
+                    curvature_code=torch.zeros(0, dtype=torch.int32, device=v.device))
     if triangulation == "min_area":
-        filled = _triangulated(v, t, attributes, limit) if n else None
+        filled = _triangulated(v, t, attributes, limit, metric) if n else None
     else:
         filled = _fans(v, t, attributes, limit) if n else None
     if filled is None:
@@ -301,12 +436,15 @@ def fill_holes_nicely(vertices: Tensor, triangles: Tensor, max_hole_size: float 
     v4, a4, iterations = fair_vertices(v3, t3, free, tolerance, max_iterations, a3)
     info.update(n_splits=n_splits, rounds=rounds, iterations=iterations, n_new_vertices=v4.shape[0] - m, n_flips=n_flips,
                 flip_rounds=flip_rounds, passes=passes, n_triangulated=n_triangulated, n_fans=n_filled - n_triangulated)
+    if fairing == "curvature":
+        v4, cinfo = fair_vertices_curvature(v4, t3, free)
+        info.update(curvature_iterations=cinfo["iterations"], curvature_converged=cinfo["converged"], curvature_code=cinfo["code"])
     return v4, t3.to(triangles.dtype), a4, n_filled, info
 
 
 # ---------------------------------------------------------------------------------------------------- triangulation
-def triangulate_holes(vertices: Tensor, triangles: Tensor, max_hole_size: float = 3.0, attributes: Sequence[Tensor] = ()
-                      ) -> Tuple[Tensor, Tensor, Tuple[Tensor, ...], int, dict]:
+def triangulate_holes(vertices: Tensor, triangles: Tensor, max_hole_size: float = 3.0, attributes: Sequence[Tensor] = (),
+                      metric: str = "area") -> Tuple[Tensor, Tensor, Tuple[Tensor, ...], int, dict]:
     """Close every loop of ``mesh_holes`` whose perimeter is below ``max_hole_size`` with the triangulation of its polygon of
     least total area: ``(vertices', triangles', attributes', n_filled, info)``.
 
@@ -322,22 +460,39 @@ def triangulate_holes(vertices: Tensor, triangles: Tensor, max_hole_size: float 
     output, and where every loop falls back the result is ``fill_holes``'s.  ``info``: ``n_triangulated``, ``n_fans``, ``area``
     ([n_triangulated] fp64, the minima W[0][n-1]) and ``fallback`` (int32 per filled loop: 0 triangulated, 1 not simple, 2 too
     short, 3 too long).  Two host reads: the counts of ``mesh_holes`` and the counts of the classification.  Two runs are
-    bitwise equal."""
+    bitwise equal.
+
+    ``metric="angle_area"`` (Liepa's angle-and-area weight restated) keeps the loops, the polygon, the
+    fallback codes and the face order and weighs a table entry by the pair (b, a): a the area sum above, b the integer badness
+    of the sharpest crease among the entry's faces and against the rim.  The badness of two oriented faces with fp64 cross
+    products n1, n2 (edge vectors in fp64 from the fp32 coordinates, dots as ``(x x' + y y') + z z'``) is ``clamp((int)
+    floor((1 - c) * 0.5 * ANGLE_STEPS), 0, ANGLE_STEPS)``, ``c = dot(n1, n2) / sqrt(dot(n1, n1) dot(n2, n2))``, and 0 where
+    either squared length is 0.  Candidate k of entry (i, j), face T = (q_i, q_k, q_j): its neighbour across (i, k) is the rim
+    face ``(q_{i+1}, q_i, o_i)`` if k - i = 1 (o_i the third corner of the mesh face that holds that boundary edge), else ``(q_i,
+    q_{S[i][k]}, q_k)`` with S the stored split, and likewise across (k, j); ``b = max(W[i][k].b, W[k][j].b, bad(T, left),
+    bad(T, right))``, for the top entry (0, n - 1) also ``bad(T, (q_0, q_{n-1}, o_{n-1}))``.  Entries compare lexicographically
+    on (b, a) with a strict < in ascending k: on a nearly flat hole every crease falls into bucket 0 (bucket 1 starts at about
+    3.6 degrees) and the area decides.  An entry's neighbour is what its sub-problem chose: the recurrence, not a global optimum.
+    ``info`` gains ``badness`` (int32 per triangulated loop, the top entry's b)."""
     name = "triangulate_holes"
     v, t = _mesh(name, vertices, triangles)
     attributes = _attributes(name, attributes, v.shape[0], True)
     limit = _limit(name, max_hole_size)
+    if metric not in METRICS:
+        raise ValueError(f"{name}: metric must be 'area' or 'angle_area', got {metric!r}")
     require_gpu(vertices, triangles, *attributes)
     attributes = tuple(_prep(a) for a in attributes)
-    filled = _triangulated(v, t, attributes, limit) if t.shape[0] else None
+    filled = _triangulated(v, t, attributes, limit, metric) if t.shape[0] else None
     if filled is None:
         none = {"n_triangulated": 0, "n_fans": 0, "area": torch.zeros(0, dtype=torch.float64, device=v.device),
                 "fallback": torch.zeros(0, dtype=torch.int32, device=v.device)}
+        if metric == "angle_area":
+            none["badness"] = torch.zeros(0, dtype=torch.int32, device=v.device)
         return v, t.to(triangles.dtype), attributes, 0, none
     return filled[0], filled[1].to(triangles.dtype), filled[2], filled[3], filled[4]
 
 
-def _triangulated(v: Tensor, t: Tensor, attributes: Tuple[Tensor, ...], limit: float):
+def _triangulated(v: Tensor, t: Tensor, attributes: Tuple[Tensor, ...], limit: float, metric: str = "area"):
     """``triangulate_holes`` over a prepared mesh with at least one face: (vertices, triangles int64, attributes, n_filled,
     info), or None where no loop is below the limit."""
     dev = v.device
@@ -351,27 +506,47 @@ def _triangulated(v: Tensor, t: Tensor, attributes: Tuple[Tensor, ...], limit: f
     offsets[1:] = torch.cumsum(n_edges, 0)
     code = torch.empty(n_loops, dtype=torch.int32, device=dev)
     polygon = torch.empty(n_boundary, dtype=torch.int32, device=dev)
-    check(lib.misplat_meshtri_order(ptr(edges), ptr(order), ptr(offsets), ptr(fill.view(torch.uint8)), C.c_int64(n_boundary),
-                                    C.c_int64(n_loops), ptr(code), ptr(polygon), stream_ptr()), "misplat_meshtri_order")
+    angle = metric == "angle_area"
+    if angle:
+        if 6 * t.shape[0] >= (1 << 31) - 4096:
+            raise ValueError(f"triangulate_holes: {t.shape[0]} triangles are beyond the library's limits (6 T < 2^31 - 4096)")
+        rim = torch.empty(n_boundary, dtype=torch.int32, device=dev)
+        ws = torch.empty(int(lib.misplat_meshtri_rim_workspace(C.c_int64(t.shape[0]))), dtype=torch.uint8, device=dev)
+        check(lib.misplat_meshtri_order_rim(ptr(edges), ptr(order), ptr(offsets), ptr(fill.view(torch.uint8)), C.c_int64(n_boundary),
+                                            C.c_int64(n_loops), ptr(t), C.c_int64(t.shape[0]), ptr(ws), C.c_int64(ws.numel()),
+                                            ptr(code), ptr(polygon), ptr(rim), stream_ptr()), "misplat_meshtri_order_rim")
+    else:
+        check(lib.misplat_meshtri_order(ptr(edges), ptr(order), ptr(offsets), ptr(fill.view(torch.uint8)), C.c_int64(n_boundary),
+                                        C.c_int64(n_loops), ptr(code), ptr(polygon), stream_ptr()), "misplat_meshtri_order")
+    lds_loop = ANGLE_LDS_LOOP if angle else LDS_LOOP
     n = n_edges.long()
     tri, fan = code == 0, code > 0
     faces_of = torch.where(tri, n - 2, torch.where(fan, n, torch.zeros_like(n)))
     face_base = (torch.cumsum(faces_of, 0) - faces_of).to(torch.int32)
     area_slot = (torch.cumsum(tri, 0) - 1).to(torch.int32)
-    entries = torch.where(tri & (n > LDS_LOOP), n * (n - 1) // 2, torch.zeros_like(n))
+    entries = torch.where(tri & (n > lds_loop), n * (n - 1) // 2, torch.zeros_like(n))
     slab_offset = torch.cumsum(entries, 0) - entries
-    small, medium = tri & (n <= SMALL_LOOP), tri & (n > SMALL_LOOP) & (n <= LDS_LOOP)
+    small, medium = tri & (n <= SMALL_LOOP), tri & (n > SMALL_LOOP) & (n <= lds_loop)
     n_tri, n_fans, n_faces, n_entries, n_small, n_medium = torch.stack(
         [tri.sum(), fan.sum(), faces_of.sum(), entries.sum(), small.sum(), medium.sum()]).tolist()    # the call's second host read
     if n_tri + n_fans == 0:
         return None
     faces = torch.empty((n_faces, 3), dtype=torch.int32, device=dev)
     area = torch.empty(n_tri, dtype=torch.float64, device=dev)
+    badness = torch.empty(n_tri, dtype=torch.int32, device=dev) if angle else None
     if n_tri:
         paths = (1 if n_small else 0) | (2 if n_medium else 0) | (4 if n_entries else 0)
         ws = None
         if n_entries:
-            ws = torch.empty(int(lib.misplat_meshtri_workspace(C.c_int64(n_entries))), dtype=torch.uint8, device=dev)
+            size = lib.misplat_meshtri_angle_workspace if angle else lib.misplat_meshtri_workspace
+            ws = torch.empty(int(size(C.c_int64(n_entries))), dtype=torch.uint8, device=dev)
+    if n_tri and angle:
+        check(lib.misplat_meshtri_angle_dp(ptr(v), C.c_int64(v.shape[0]), ptr(polygon), ptr(rim), ptr(offsets), ptr(code),
+                                           C.c_int64(n_loops), paths, ptr(slab_offset), C.c_int64(n_entries), ptr(ws),
+                                           C.c_int64(ws.numel() if n_entries else 0), ptr(face_base), C.c_int64(n_faces),
+                                           ptr(area_slot), C.c_int64(n_tri), ptr(faces), ptr(area), ptr(badness), stream_ptr()),
+              "misplat_meshtri_angle_dp")
+    elif n_tri:
         check(lib.misplat_meshtri_dp(ptr(v), C.c_int64(v.shape[0]), ptr(polygon), ptr(offsets), ptr(code), C.c_int64(n_loops), paths,
                                      ptr(slab_offset), C.c_int64(n_entries), ptr(ws), C.c_int64(ws.numel() if n_entries else 0),
                                      ptr(face_base), C.c_int64(n_faces), ptr(area_slot), C.c_int64(n_tri), ptr(faces), ptr(area),
@@ -383,6 +558,8 @@ def _triangulated(v: Tensor, t: Tensor, attributes: Tuple[Tensor, ...], limit: f
         at = face_base[fan].long()[fan_of] + (torch.arange(fans.shape[0], device=dev) - first[fan_of])
         faces[at] = fans.to(torch.int32)
     info = {"n_triangulated": n_tri, "n_fans": n_fans, "area": area, "fallback": code[code >= 0].clone()}
+    if angle:
+        info["badness"] = badness
     return outs[0], torch.cat([t.long(), faces.long()]), tuple(outs[1:]), n_tri + n_fans, info
 
 
@@ -438,4 +615,4 @@ def flip_edges(vertices: Tensor, triangles: Tensor, region: Optional[Tensor] = N
     return tri.to(triangles.dtype), n_flips, rounds
 
 
-__all__ = ["subdivide_mesh", "fair_vertices", "fill_holes_nicely", "triangulate_holes", "flip_edges"]
+__all__ = ["subdivide_mesh", "fair_vertices", "fair_vertices_curvature", "fill_holes_nicely", "triangulate_holes", "flip_edges"]

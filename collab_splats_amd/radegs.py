@@ -606,15 +606,17 @@ class RadegsModel(nn.Module):
         takes the mean of its loop's), or with ``fill="nicely"`` ``fill_holes_nicely`` (the reference's default,
         ``use_advanced_fill``: the fans subdivided to the mesh's edge length and faired, the colours with them; ``fill_info`` is
         then its ``info``), or with ``fill="min_area"`` the same from the loops' minimum-area triangulations, with edge flips
-        between the subdivisions (``triangulation="min_area", flip=True``); ``mesh_attributes`` on the result; ``align``: ``align_floor`` of the mesh, the same
+        between the subdivisions (``triangulation="min_area", flip=True``), or with ``fill="smooth"`` the same under the
+        angle-and-area weight and with curvature fairing on top (``metric="angle_area", fairing="curvature"``: the patch continues
+        the rim's tangent planes); ``mesh_attributes`` on the result; ``align``: ``align_floor`` of the mesh, the same
         rotation applied to the mapped normals (Open3D's ``rotate`` turns them too) and the rigid motion to the means
         (mesh.py:1709).  Returns ``vertices``, ``triangles``, ``colors``, the attributes, ``vertex_index`` ([M'] int64: the
         row of the input each vertex was, -1 for a vertex the fill created), ``means`` (moved, [N,3]), ``n_removed``, ``n_filled`` and
         ``mesh_transform`` ([4,4] fp64 on the host, [[R, t], [0, 0, 0, 1]] as mesh.py:1712-1718; the identity without
         ``align``).  The model itself is not changed."""
         from .meshclean import align_floor, apply_rigid, fill_holes, filter_mesh_components
-        if fill not in ("fan", "nicely", "min_area"):
-            raise ValueError(f"finish_mesh: fill must be 'fan' or 'nicely' or 'min_area', got {fill!r}")
+        if fill not in ("fan", "nicely", "min_area", "smooth"):
+            raise ValueError(f"finish_mesh: fill must be 'fan' or 'nicely' or 'min_area' or 'smooth', got {fill!r}")
         index = torch.arange(vertices.shape[0], dtype=torch.int64, device=vertices.device)
         n_removed = n_filled = 0
         info = None
@@ -622,7 +624,9 @@ class RadegsModel(nn.Module):
             vertices, triangles, index, (colors,), n_removed = filter_mesh_components(vertices, triangles, use_largest, (colors,))
             if fill != "fan":
                 from .meshfill import fill_holes_nicely
-                how = dict(triangulation="min_area", flip=True) if fill == "min_area" else {}
+                how = dict(triangulation="min_area", flip=True) if fill in ("min_area", "smooth") else {}
+                if fill == "smooth":
+                    how.update(metric="angle_area", fairing="curvature")
                 vertices, triangles, (colors,), n_filled, info = fill_holes_nicely(vertices, triangles, max_hole_size,
                                                                                    attributes=(colors,), **how)
             else:

@@ -1174,6 +1174,36 @@ int misplat_meshfill_fair_lds(float* vertices, int64_t n_vertices, int64_t n_tri
 int misplat_meshfill_fair_finish(int64_t n_free, int32_t n_done, int32_t* iterations, const int32_t* counts,
                                  misplat_stream_t stream);
 
+/* Curvature (thin-plate) fairing (the oracle is tests/meshsmooth_restatement.py, bit for bit).  N(i) the
+ * distinct edge-neighbours of vertex i in ascending order, n_i their number; F the free vertices, R the fixed vertices with a
+ * free neighbour, S = F + R.  U_i(x) = (sum_{j in N(i)} x_j) / (double) n_i - x_i in fp64; the energy sum_{i in S} |U_i|^2 is
+ * minimised over the free coordinates by plain conjugate gradients on A = L^T L, one independent CG per coordinate, all fp64,
+ * from the fp32 positions, rounded to fp32 once.  A patch is a connected set of free vertices, two being connected when they
+ * are adjacent or share a neighbour in R. */
+#define MISPLAT_MESHFILL_CG_VERTICES 65536
+/* The components that make the patches: (src [E], tgt [E]) the directed edges that leave a vertex of S; every edge whose target
+ * is free unites its ends in parent [M] int32 (parent[v] = v on entry); root [M] int32 = every vertex's smallest member. */
+int misplat_meshfill_curv_patches(const int32_t* src, const int32_t* tgt, int64_t n_edges, const uint8_t* free, int64_t n_vertices,
+                                  int32_t* parent, int32_t* root, misplat_stream_t stream);
+/* workspace bytes of curv_solve: x, r, p, q over the n_free free places, t and t / n over the n_rows places of S; -1 refused. */
+int64_t misplat_meshfill_curv_workspace(int64_t n_free, int64_t n_rows);
+/* One persistent workgroup of 1024 threads per patch, for the whole solve.  The S-list: places 0 .. n_free - 1 the free
+ * vertices by patch and then by vertex (patch p: free_offset[p] .. free_offset[p + 1]), places n_free .. n_rows - 1 the rows of
+ * R the same way (patch p: n_free + rim_offset[p] ..).  vertex [n_rows]: the place's vertex; row / degree [n_rows]: where its
+ * distinct neighbours start in neighbour / place [n_entries] (as vertices, and as places with -1 for a vertex outside S), and
+ * how many they are.  code [P]: 0 solve, else leave unchanged (1 no neighbour, 2 no fixed neighbour, 3 more than
+ * MISPLAT_MESHFILL_CG_VERTICES free vertices).  Every dot product: thread t adds the patch's elements t, t + 1024, ... in
+ * ascending order, then wgprims.h's block_sum.  A column whose p.q is 0 takes alpha = beta = 0.  After iteration k the patch
+ * stops iff sum_c r_c.r_c <= rtol^2 sum_c r0_c.r0_c (0 iterations if the right-hand side is 0), or at max_iterations (< 0: the
+ * patch's free count).  out [M,3] holds the input's positions on entry; the free vertices of a patch that iterated are
+ * written.  iterations [P] int32, converged [P] uint8, residual [P] fp64 = sqrt of the final ratio. */
+int misplat_meshfill_curv_solve(const float* vertices, float* out, int64_t n_vertices, const int32_t* free_offset,
+                                const int32_t* rim_offset, const int32_t* vertex, const int32_t* row, const int32_t* degree,
+                                const int32_t* neighbour, const int32_t* place, int64_t n_free, int64_t n_rows, int64_t n_entries,
+                                const int32_t* code, int32_t n_patches, double rtol, int32_t max_iterations, void* workspace,
+                                int64_t workspace_bytes, int32_t* iterations, uint8_t* converged, double* residual,
+                                misplat_stream_t stream);
+
 /* ---- minimum-area hole triangulation and Delaunay-like edge flips (csrc/meshtri.hip) ----
  * The oracle is tests/meshtri_restatement.py, bit for bit.  Integer atomics only: two runs are bitwise equal.  No call
  * synchronises.
@@ -1205,6 +1235,31 @@ int misplat_meshtri_dp(const float* vertices, int64_t n_vertices, const int32_t*
                        int64_t n_loops, int32_t paths, const int64_t* slab_offset, int64_t n_entries, void* workspace,
                        int64_t workspace_bytes, const int32_t* face_base, int64_t n_faces, const int32_t* area_slot, int64_t n_area,
                        int32_t* faces, double* area, misplat_stream_t stream);
+/* The angle-and-area weight (the oracle is tests/meshsmooth_restatement.py, bit for bit): an entry is the
+ * pair (b, a), a the area sum above, b = max(W[i][k].b, W[k][j].b, bad(T, left), bad(T, right)) for the candidate T = (q_i, q_k,
+ * q_j), left = the rim face (q_{i+1}, q_i, o_i) if k - i = 1, else (q_i, q_{S[i][k]}, q_k) with S the stored split; right likewise
+ * across (k, j); the top entry (0, n - 1) also takes bad(T, (q_0, q_{n-1}, o_{n-1})).  bad of two oriented faces: n1, n2 their fp64
+ * cross products (edge vectors in fp64 from the fp32 coordinates, dot = (x x' + y y') + z z'), c = dot(n1, n2) / sqrt(dot(n1, n1)
+ * dot(n2, n2)), bad = clamp((int) floor((1 - c) 0.5 STEPS), 0, STEPS), 0 if either squared length is 0 or the value is not a
+ * number.  Entries compare lexicographically on (b, a), strict < in ascending k.  An entry is 8 + 2 + 2 bytes and a polygon vertex
+ * 28 (its coordinates, its index, its rim corner's coordinates): 12 n (n - 1) / 2 + 28 n <= 163840 holds up to n = 163. */
+#define MISPLAT_MESHTRI_ANGLE_STEPS 1024
+#define MISPLAT_MESHTRI_ANGLE_LDS_LOOP 163
+/* order, and rim [B] int32: rim[offsets[l] + i] = o_i, the third corner of the one face of triangles [T,3] that holds the polygon's
+ * edge (q_i, q_{i+1}) (i = n - 1: the closing edge (q_{n-1}, q_0)), -1 where there is none.  The workspace holds the mesh's edge
+ * table (rim_workspace(T) bytes; -1 for sizes refused: 1 <= T, 6 T < 2^31 - 4096). */
+int64_t misplat_meshtri_rim_workspace(int64_t n_triangles);
+int misplat_meshtri_order_rim(const int32_t* edges, const int32_t* order, const int32_t* offsets, const uint8_t* fill, int64_t n_edges,
+                              int64_t n_loops, const int32_t* triangles, int64_t n_triangles, void* workspace, int64_t workspace_bytes,
+                              int32_t* code, int32_t* polygon, int32_t* rim, misplat_stream_t stream);
+/* misplat_meshtri_workspace and misplat_meshtri_dp under the angle-and-area weight: the paths split at SMALL_LOOP and
+ * ANGLE_LDS_LOOP; badness [n_area] int32 takes the top entry's b beside area. */
+int64_t misplat_meshtri_angle_workspace(int64_t n_entries);
+int misplat_meshtri_angle_dp(const float* vertices, int64_t n_vertices, const int32_t* polygon, const int32_t* rim,
+                             const int32_t* offsets, const int32_t* code, int64_t n_loops, int32_t paths, const int64_t* slab_offset,
+                             int64_t n_entries, void* workspace, int64_t workspace_bytes, const int32_t* face_base, int64_t n_faces,
+                             const int32_t* area_slot, int64_t n_area, int32_t* faces, double* area, int32_t* badness,
+                             misplat_stream_t stream);
 /* Flips.  An undirected edge is flippable iff it has exactly two distinct incident faces, both with region != 0 and three
  * distinct corners, f_max runs it against f_min (f_min = (a, b, c) rotated, f_max holds b -> a and d), c != d, the edge (c, d) is
  * not in the mesh, the fp64 sum cot(c) + cot(d) (each dot / |cross| of the two edge vectors at the corner, from the fp32
