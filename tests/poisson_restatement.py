@@ -1,9 +1,11 @@
 """numpy restatement of the dense-grid screened Poisson reconstruction: the oracle of csrc/poisson.hip.
 
 The grid, the splat, the system and the sampler are evaluated in the kernels' order with float32 operands, so the int64 grids, b
-and D are bit-identical to the GPU's.  The conjugate gradients are the same recurrence in fp32 (``cg``) or fp64; their sums run
-in numpy's order, so chi is compared through residuals, never bit for bit.  Extraction reuses the TSDF restatement's marching
-cubes on chi - iso.  Neither Kazhdan's octree solver nor Open3D is pinned.
+and D are bit-identical to the GPU's.  The conjugate gradients come twice: ``cg`` is the recurrence in fp32 or fp64 with its sums
+in numpy's order (chi is compared with it through residuals), ``cg_exact`` is the kernels' recurrence with every sum in the
+device's written order (x, r, z, p and the solver state are compared with it bit for bit, iteration by iteration); ``mean_exact``
+is the iso value's mean in the same order.  Extraction reuses the TSDF restatement's marching cubes on chi - iso.  Neither
+Kazhdan's octree solver nor Open3D is pinned.
 """
 from __future__ import annotations
 
@@ -148,6 +150,146 @@ def cg(b, D, tol=1e-5, max_iters=None, dtype=np.float32):
         rz = rz_new
     resid = float(np.sqrt(rr / bb)) if bb > 0 else 0.0
     return x, it, resid, bool(done)
+
+
+# ------------------------------------------------------------------------------------------------- the device's own sums
+# csrc/wgprims.h and csrc/poisson.hip write every fp64 sum's order down; these are those orders in numpy (the model is
+# pointcloud_restatement._tree256).  Everything below is fp64 and vectorised over the leading axes.
+CELLS_PER_BLOCK = 1024               # 256 lanes of 4 consecutive values
+FINAL = 1024                         # threads of the one workgroup of the second level
+S_RZ, S_PAP, S_RR, S_BB, S_ALPHA, S_BETA, S_DONE, S_ITERS = range(8)
+
+
+def _wave_tree(w):
+    """wave_sum: [..., 64] -> [...], the shuffle-down tree 32, 16, ... 1 as lane 0 sees it."""
+    w = np.array(w, np.float64)
+    for off in (32, 16, 8, 4, 2, 1):
+        w[..., :off] = w[..., :off] + w[..., off:2 * off]
+    return w[..., 0]
+
+
+def _block_tree(v, waves):
+    """block_sum<waves>: [..., 64 waves] -> [...], each wave's tree, then the waves in ascending order."""
+    w = _wave_tree(np.asarray(v, np.float64).reshape(*np.shape(v)[:-1], waves, 64))
+    s = w[..., 0]
+    for k in range(1, waves):
+        s = s + w[..., k]
+    return s
+
+
+def _lane4(a, from_zero=False):
+    """[..., 4] -> [...]: ((a0 + a1) + a2) + a3, or (((0.0 + a0) + a1) + a2) + a3 for the mean's lanes."""
+    s = (0.0 + a[..., 0]) if from_zero else a[..., 0]
+    for k in range(1, 4):
+        s = s + a[..., k]
+    return s
+
+
+def block_partials(values, from_zero=False):
+    """The first level: [1024 nb] fp64 -> [nb], one partial per workgroup of 256 lanes with 4 consecutive values each."""
+    v = np.asarray(values, np.float64).reshape(-1, CELLS_PER_BLOCK // 4, 4)
+    return _block_tree(_lane4(v, from_zero), 4)
+
+
+def second_level(partials):
+    """final_sum: thread t adds partials t, t + 1024, ... in ascending order from 0.0, then block_sum over 16 waves.  (A thread's sum
+    is never -0.0, so the zero padding of the last trip is no addition the device does not make in effect.)"""
+    part = np.asarray(partials, np.float64).reshape(-1)
+    trips = max((len(part) + FINAL - 1) // FINAL, 1)
+    part = np.concatenate([part, np.zeros(trips * FINAL - len(part))]).reshape(trips, FINAL)
+    s = np.zeros(FINAL)
+    for k in range(trips):
+        s = s + part[k]
+    return float(_block_tree(s, FINAL // 64))
+
+
+def dot_exact(a, b):
+    """sum a b over a grid as the CG kernels form it: exact fp64 products of two floats, the lane's four cells, the workgroup's
+    tree, the second level."""
+    prod = np.asarray(a, np.float32).reshape(-1).astype(np.float64) * np.asarray(b, np.float32).reshape(-1).astype(np.float64)
+    return second_level(block_partials(prod))
+
+
+def mean_exact(values):
+    """misplat_poisson_mean: the fp64 mean of n fp32 values; blocks of 1024 (the last one padded with 0.0, as the kernel adds 0.0
+    past n), each lane 4 values in ascending order from 0.0, the second level, then the division by n."""
+    v = np.asarray(values, np.float32).reshape(-1).astype(np.float64)
+    n = len(v)
+    nb = (n + CELLS_PER_BLOCK - 1) // CELLS_PER_BLOCK
+    v = np.concatenate([v, np.zeros(nb * CELLS_PER_BLOCK - n)])
+    return second_level(block_partials(v, from_zero=True)) / float(n)
+
+
+def sum_path_length(n, lane_adds=3):
+    """The largest number of fp64 additions any one of n summands passes through in the two-level sum: the lane's, 6 + 3 of the
+    workgroup's tree, the thread's trips of the second level, 6 + 15 of its tree."""
+    nb = (n + CELLS_PER_BLOCK - 1) // CELLS_PER_BLOCK
+    return lane_adds + 6 + 3 + (nb + FINAL - 1) // FINAL + 6 + 15
+
+
+def apply_A32(D, p):
+    """cg_stencil_kernel's Ap in fp32: D p - (((((x- + x+) + y-) + y+) + z-) + z+), 0 outside the grid."""
+    s = _shift(p, 0, -1) + _shift(p, 0, 1)
+    for a in (1, 2):
+        s = s + _shift(p, a, -1)
+        s = s + _shift(p, a, 1)
+    return D * p - s
+
+
+def cg_exact(b, D, tol=1e-5, max_iters=None, n_steps=None, start=None):
+    """The kernels' recurrence in their own order: (x, r, z, p, state [8] fp64, iterations, done) after n_steps iterations of
+    misplat_poisson_cg_iterate (a no-op once done != 0), or at the stop when n_steps is None.  state is the workspace head (S_RZ,
+    S_PAP, S_RR, S_BB, S_ALPHA, S_BETA, S_DONE, S_ITERS); done = 1 converged (rr <= tol^2 bb, or b = 0), 2 the cap, 3 p.Ap = 0 or
+    r.z = 0.  alpha and beta are rounded through float as the kernels round them.  `start` = an earlier result, to go on from."""
+    b, D = np.asarray(b, np.float32), np.asarray(D, np.float32)
+    G = b.shape[0]
+    max_iters = 8 * G if max_iters is None else int(max_iters)
+    tol2 = float(tol) * float(tol)
+    if start is None:
+        x = np.zeros_like(b)
+        r = b.copy()
+        z = r / D
+        p = z.copy()
+        st = np.zeros(8)
+        st[S_RZ] = dot_exact(r, z)
+        st[S_RR] = st[S_BB] = dot_exact(b, b)
+        st[S_DONE] = 1.0 if st[S_BB] == 0.0 else (2.0 if max_iters <= 0 else 0.0)
+    else:
+        x, r, z, p = (np.array(v, np.float32) for v in start[:4])
+        st = np.array(start[4], np.float64)
+    step = 0
+    while st[S_DONE] == 0.0 and (n_steps is None or step < n_steps):
+        step += 1
+        Ap = apply_A32(D, p)
+        pAp = dot_exact(p, Ap)
+        st[S_PAP] = pAp
+        if pAp == 0.0 or st[S_RZ] == 0.0:
+            st[S_ALPHA] = 0.0
+            st[S_DONE] = 3.0
+            break
+        alpha = F(st[S_RZ] / pAp)
+        st[S_ALPHA] = float(alpha)
+        x = x + alpha * p
+        r = r - alpha * Ap
+        z = r / D
+        rz, rr = dot_exact(r, z), dot_exact(r, r)
+        beta = F(rz / st[S_RZ])
+        st[S_BETA] = float(beta)
+        st[S_RZ], st[S_RR] = rz, rr
+        st[S_ITERS] += 1.0
+        if rr <= tol2 * st[S_BB]:
+            st[S_DONE] = 1.0
+        elif st[S_ITERS] >= float(max_iters):
+            st[S_DONE] = 2.0
+        else:
+            p = z + beta * p
+    return x, r, z, p, st, int(st[S_ITERS]), int(st[S_DONE])
+
+
+def exact_info(st):
+    """poisson._solve's info from a state."""
+    return {"iterations": int(st[S_ITERS]), "residual": float(np.sqrt(st[S_RR] / st[S_BB])) if st[S_BB] > 0 else 0.0,
+            "converged": bool(st[S_DONE] == 1.0)}
 
 
 def true_residual(b, D, x):

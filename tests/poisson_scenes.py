@@ -1,5 +1,7 @@
 """Oriented point clouds for the Poisson tests (host and GPU): a seeded sphere, its open cap, a sparse sampling and the splat's
-edge cases.  Everything is float32 numpy; every scene is small enough for the numpy restatement to solve in well under a second."""
+edge cases.  Everything is float32 numpy; every scene of SCENES is small enough for the numpy restatement to solve in a second or
+so.  LARGE holds the spheres of the depth-7 and depth-8 solver tests (a few iterations of them on the host), and the dense random
+system, the mean's values and the sampler's queries are the inputs of the bit-for-bit kernel tests."""
 from __future__ import annotations
 
 import numpy as np
@@ -46,6 +48,66 @@ def scene(name):
     build, depth = SCENES[name]
     p, n, c = build()
     return p, n, c, depth
+
+
+# Scenes of the bit-for-bit solver tests that the numpy solve cannot finish in test time (a few iterations of them it can): the
+# grid depths at which the second-level sums make more than one trip.  name -> (builder, depth); kept out of SCENES, whose every
+# entry is solved to the end on the host.
+LARGE = {
+    "sphere7": (lambda: sphere(200000, seed=3), 7),        # 2 048 partials: two trips per thread
+    "sphere8": (lambda: sphere(500000, seed=4), 8),        # 16 384 partials: 16 trips, the unrolled body twice
+}
+SMALL = {"sphere4": (lambda: sphere(5000, seed=5), 4)}     # the smallest grid: 4 partials
+
+
+def any_scene(name):
+    build, depth = {**SCENES, **LARGE, **SMALL}[name]
+    p, n, c = build()
+    return p, n, c, depth
+
+
+def dense_random_system(depth, seed=11):
+    """(b, D) fp32 [G,G,G] with no zero anywhere: b normal deviates in every cell, border cells included, D = the in-grid neighbour
+    count + U(0, 2).  Every face, edge and corner of the stencil then changes the result."""
+    G = 1 << depth
+    rng = np.random.default_rng(seed + depth)
+    b = rng.standard_normal((G, G, G)).astype(np.float32)
+    nn = np.zeros((G, G, G), np.float32)
+    for ax in range(3):
+        idx = np.arange(G).reshape([G if a == ax else 1 for a in range(3)])
+        nn = nn + (idx > 0) + (idx < G - 1)
+    D = (nn.astype(np.float32) + rng.uniform(0.0, 2.0, (G, G, G)).astype(np.float32)).astype(np.float32)
+    return b, D
+
+
+def mean_values(n, wide=False, seed=13):
+    """n fp32 values for the fp64 mean.  Default: normal deviates around a large common offset (1000).  These share one exponent,
+    so they are multiples of 2^-14 and ANY order sums them exactly in fp64 (below 2^39 of them): they test the count, the ragged
+    last block and the division, not the order.  wide: normal deviates scaled over 60 binades; their exact sum does not fit 53
+    bits, so the order shows in the low bits of the mean."""
+    rng = np.random.default_rng(seed + n % 1009)
+    x = rng.standard_normal(n).astype(np.float32)
+    if wide:
+        return (x * np.exp2(rng.uniform(-30.0, 30.0, n)).astype(np.float32)).astype(np.float32)
+    return (np.float32(1000.0) + x).astype(np.float32)
+
+
+def sampler_queries(o, h, G, seed=17):
+    """[n, 3] fp32 queries for the trilinear sampler on the grid (o, h, G): uniform in the cube; exactly on cell centres; on the
+    cube's faces and corners; up to 3 h outside on every side; one at o + (G - 0.5) h on each axis (the last cell's centre)."""
+    rng = np.random.default_rng(seed + G)
+    o = np.asarray(o, np.float32)
+    h = np.float32(h)
+    s = np.float32(G) * h
+    inside = o + rng.random((2000, 3)).astype(np.float32) * s
+    centres = o + (rng.integers(0, G, (500, 3)).astype(np.float32) + np.float32(0.5)) * h
+    corners = np.array([[x, y, z] for x in (0, 1) for y in (0, 1) for z in (0, 1)], np.float32)
+    faces = rng.random((600, 3)).astype(np.float32)
+    faces[np.arange(600), np.arange(600) % 3] = (np.arange(600) // 3 % 2).astype(np.float32)      # one coordinate on a face
+    outside = o + (rng.random((1500, 3)).astype(np.float32) * (np.float32(G) + np.float32(6)) - np.float32(3)) * h
+    last = np.full((3, 3), 0.37, np.float32) * s + o
+    last[np.arange(3), np.arange(3)] = o[np.arange(3)] + (np.float32(G) - np.float32(0.5)) * h
+    return np.concatenate([inside, centres, o + corners * s, o + faces * s, outside, last]).astype(np.float32)
 
 
 def splat_edge_cases(depth=5, scale=1.1):

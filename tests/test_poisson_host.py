@@ -5,6 +5,7 @@ Bounds: the figures of the fp64 prototype the feature was specified with (DESIGN
 reproduces a figure, the figure is the bound, rounded up in its second digit (the fp32 solve moves a crossing by ~1e-4 h); where it
 does not (another seed), the bound is 3 x the restatement's own value, recorded next to it."""
 import functools
+import math
 
 import numpy as np
 import pytest
@@ -105,6 +106,137 @@ def test_iteration_cap_does_not_raise():
     assert it0 == 0 and not conv0 and resid0 == 1.0 and not x0.any()
     z = np.zeros_like(out["b"])
     assert R.cg(z, out["D"], 1e-5)[1:] == (0, 0.0, True)                          # b = 0: chi = 0, no 0 / 0
+
+
+# ------------------------------------------------------------------------------------------------- the device's order
+U64 = 2.0 ** -53                              # the unit roundoff of fp64
+
+
+def _gamma(d):
+    return d * U64 / (1.0 - d * U64)
+
+
+def _bits64(a, b):
+    a, b = np.ascontiguousarray(a, np.float64), np.ascontiguousarray(b, np.float64)
+    return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
+
+
+def _same_run(a, b):
+    return all(np.array_equal(u.view(np.uint32), v.view(np.uint32)) for u, v in zip(a[:4], b[:4])) and _bits64(a[4], b[4]) \
+        and a[5:] == b[5:]
+
+
+@pytest.mark.parametrize("n", [1024, 4096, 32 * 1024, 1025 * 1024, 2304 * 1024])
+def test_exact_sums_are_within_the_path_bound_of_fsum(n):
+    """Bound: every addition returns (a + b)(1 + e) with |e| <= u = 2^-53.  A summand that passes through d additions on its way to
+    the root carries the product of d such factors, so |computed - exact| <= ((1 + u)^d - 1) sum |v_i| <= gamma_d sum |v_i| with
+    gamma_d = d u / (1 - d u) (Higham, Accuracy and Stability, section 4.2: any order of summation).  d is the longest path of the
+    two-level sum (``sum_path_length``): the lane's 3 additions (4 in the mean, which starts from 0.0), 6 + 3 of the workgroup's
+    tree, the thread's trips through the partials, 6 + 15 of the second tree: 34 for one trip, 36 for three.  math.fsum is the
+    exact sum rounded once; the mean adds that rounding, the division's and the reference's own division: gamma_(d + 3)."""
+    rng = np.random.default_rng(n)
+    v = rng.standard_normal(n) * np.exp(rng.uniform(-6.0, 6.0, n))
+    got = R.second_level(R.block_partials(v))
+    d = R.sum_path_length(n)
+    assert d == 3 + 9 + (n // 1024 + 1023) // 1024 + 21
+    assert abs(got - math.fsum(v)) <= _gamma(d) * math.fsum(np.abs(v))
+    a, b = rng.standard_normal(n).astype(np.float32), rng.standard_normal(n).astype(np.float32)
+    prod = a.astype(np.float64) * b.astype(np.float64)                             # exact: 24 + 24 bits
+    assert abs(R.dot_exact(a, b) - math.fsum(prod)) <= _gamma(d) * math.fsum(np.abs(prod))
+    for m in (n, n - 1023, n + 1):                                                 # the mean's ragged last block
+        if m < 1:
+            continue
+        for wide in (False, True):
+            x = S.mean_values(m, wide)
+            want = math.fsum(x.astype(np.float64)) / m
+            dm = R.sum_path_length(m, lane_adds=4) + 3
+            assert abs(R.mean_exact(x) - want) <= _gamma(dm) * math.fsum(np.abs(x.astype(np.float64))) / m
+
+
+def test_exact_sums_are_not_numpys_order():
+    """On a cancelling input the order shows: the device's tree and numpy's pairwise sum round differently."""
+    rng = np.random.default_rng(3)
+    v = rng.standard_normal(32 * 1024) * 1e6
+    v[1::2] = -v[::2] + rng.standard_normal(16 * 1024)                             # pairs that cancel to O(1)
+    got, ref = R.second_level(R.block_partials(v)), float(np.sum(v))
+    exact = math.fsum(v)
+    bound = _gamma(R.sum_path_length(len(v))) * math.fsum(np.abs(v))
+    assert abs(got - exact) <= bound and abs(ref - exact) <= bound
+    assert got != ref
+    x = S.mean_values((1 << 20) + 1, wide=True)
+    assert R.mean_exact(x) != float(np.sum(x.astype(np.float64)) / len(x))
+    x = S.mean_values((1 << 20) + 1)                                               # one exponent: every order is exact
+    assert R.mean_exact(x) == float(np.sum(x.astype(np.float64)) / len(x)) == math.fsum(x.astype(np.float64)) / len(x)
+    a = rng.standard_normal((32, 32, 32)).astype(np.float32)
+    assert R.dot_exact(a, a) != float(np.vdot(a.astype(np.float64), a.astype(np.float64)))
+
+
+def test_tree_primitives_on_hand_values():
+    """Powers of two that only one order sums without loss: the wave tree pairs lane i with lane i + 32 first."""
+    w = np.zeros(64)
+    w[0], w[32], w[1] = 1.0, -1.0, 2.0 ** -60                                      # (w0 + w32) + ... keeps the small term
+    assert R._wave_tree(w) == 2.0 ** -60
+    assert float(np.cumsum(w[[0, 1, 32]])[-1]) == 0.0                              # the ascending order would lose it
+    v = np.zeros(256)
+    v[0], v[64], v[128], v[192] = 1.0, 2.0 ** -53, 2.0 ** -53, -1.0                # waves in ascending order: both halves are lost
+    assert R._block_tree(v, 4) == 0.0
+    lane = np.array([1.0, 2.0 ** -53, 2.0 ** -53, 2.0 ** -52])                     # ((a0 + a1) + a2) + a3
+    assert R._lane4(lane) == 1.0 + 2.0 ** -52 and math.fsum(lane) == 1.0 + 2.0 ** -51
+    part = np.zeros(2048)
+    part[5], part[1029], part[6] = 1.0, -1.0, 2.0 ** -60                           # thread 5 adds partials 5 and 1029 before the tree
+    assert R.second_level(part) == 2.0 ** -60
+    assert R.mean_exact(np.array([3.0], np.float32)) == 3.0 and R.mean_exact(np.array([1, 2, 4], np.float32)) == 7.0 / 3.0
+
+
+@pytest.mark.parametrize("name", ["sphere5", "sparse5"])
+def test_exact_order_cg_converges_like_the_numpy_order_cg(name):
+    """The two differ only in the order of their sums: the same bars as the GPU's chi is held to against ``cg`` (3 x its true
+    residual, 4 x its distance from the fp64 solution)."""
+    out = recon(name)
+    b, D, G = out["b"], out["D"], out["G"]
+    x, r, z, p, st, it, done = R.cg_exact(b, D, 1e-5)
+    info = R.exact_info(st)
+    assert done == 1 and info["converged"] and 0 < it <= 8 * G and info["residual"] <= 1e-5 and info["iterations"] == it
+    x64 = R.cg(b, D, 1e-12, 50 * G, np.float64)[0]
+    true32, err32 = R.true_residual(b, D, out["chi"]), np.abs(out["chi"] - x64).max() / np.abs(x64).max()
+    true_x, err_x = R.true_residual(b, D, x), np.abs(x - x64).max() / np.abs(x64).max()
+    print(name, "iterations", it, "(", out["iterations"], ") true residual", true_x, "(", true32, ") chi error", err_x, "(", err32, ")")
+    assert true_x <= 3 * true32 and err_x <= 4 * err32
+
+
+@pytest.mark.parametrize("name, k, total", [("dense4", 1, 3), ("dense4", 5, 17), ("sphere5", 16, 17), ("sphere5", 7, None)])
+def test_exact_order_cg_continues_where_it_stopped(name, k, total):
+    if name == "dense4":
+        b, D = S.dense_random_system(4)
+    else:
+        b, D = recon(name)["b"], recon(name)["D"]
+    whole = R.cg_exact(b, D, 1e-5, None, total)
+    part = R.cg_exact(b, D, 1e-5, None, k)
+    assert part[5] == k and part[6] == 0
+    rest = R.cg_exact(b, D, 1e-5, None, None if total is None else total - k, start=part)
+    assert _same_run(rest, whole) and whole[5] == (total if total is not None else whole[5])
+    again = R.cg_exact(b, D, 1e-5, None, 16, start=whole) if total is None else None   # after the stop: a no-op
+    assert again is None or (_same_run(again, whole) and whole[6] == 1)
+
+
+def test_exact_order_cg_stop_rules():
+    b, D = S.dense_random_system(4)
+    assert (D > R.neighbours(16)).all() and (D < R.neighbours(16) + 2).all() and (b != 0).all()
+    run = R.cg_exact(b, D, 1e-5, 10)
+    assert run[5:] == (10, 2) and run[4][R.S_ITERS] == 10.0 and not R.exact_info(run[4])["converged"]
+    nine = R.cg_exact(b, D, 1e-5, 10, 9)
+    assert nine[6] == 0 and np.array_equal(nine[3], run[3])                        # the cap's iteration leaves p alone, as the
+    assert not np.array_equal(R.cg_exact(b, D, 1e-5, None, 10)[3], run[3])         # direction kernel's guard does; an uncapped one moves it
+    assert _same_run(R.cg_exact(b, D, 1e-5, 10, 1, start=nine), run)
+    none = R.cg_exact(b, D, 1e-5, 0)
+    assert none[5:] == (0, 2) and not none[0].any() and np.array_equal(none[1], b) and none[4][R.S_RR] == none[4][R.S_BB]
+    zero = R.cg_exact(np.zeros_like(b), D, 1e-5)
+    assert zero[5:] == (0, 1) and not zero[0].any() and R.exact_info(zero[4]) == {"iterations": 0, "residual": 0.0, "converged": True}
+    loose = R.cg_exact(b, D, 1e-1)
+    assert loose[6] == 1 and loose[4][R.S_RR] <= 1e-2 * loose[4][R.S_BB] and 0 < loose[5] < R.cg_exact(b, D, 1e-5)[5]
+    first = R.cg_exact(b, D, 1e-5, None, 1)[4]                                      # alpha and beta are floats held in doubles
+    assert first[R.S_ALPHA] == float(np.float32(first[R.S_ALPHA])) and first[R.S_BETA] == float(np.float32(first[R.S_BETA]))
+    assert first[R.S_ALPHA] != 0 and first[R.S_BETA] != 0 and first[R.S_PAP] > 0
 
 
 # -------------------------------------------------------------------------------------------------------------- geometry
