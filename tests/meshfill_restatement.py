@@ -189,6 +189,21 @@ def fair(V, tri, free, tolerance, max_iterations=10000, attributes=()):
     return X, tuple(out), iterations
 
 
+def fair_displacements(V, tri, free, n_iterations):
+    """[n_iterations, P] uint32: the displacement bits of every patch in iterations 1 .. n_iterations when no patch ever stops.
+    Patches share no edge, so up to its stop a patch's column is what fair() compares with the tolerance: a test picks a
+    tolerance from it that stops a patch at a chosen count."""
+    X = np.asarray(V, F).copy()
+    fl, nb, deg, patch = free_rows(tri, free)
+    out = np.zeros((n_iterations, int(patch.max()) + 1 if len(fl) else 0), np.uint32)
+    for row in out:
+        Y = _membrane(X, fl, nb, deg)
+        with np.errstate(all="ignore"):
+            np.maximum.at(row, patch, np.abs(Y - X[fl]).view(np.uint32).max(1))
+        X[fl] = Y
+    return out
+
+
 # --------------------------------------------------------------------------------------------------------- the fill
 def fans(V, tri, max_hole_size=3.0, attributes=()):
     """meshclean_restatement.fill_holes with attributes: (vertices, triangles, attributes, n_filled)."""
