@@ -20,7 +20,8 @@
 namespace {
 
 // ---------------------------------------------------------------------------------------------------------- union
-// (the union-find itself, and why stale reads are harmless in it: csrc/unionfind.h)
+// (the union-find itself, why stale reads are harmless in it, and its read-out -- the initial forest, the flatten kernel that
+// gives an unselected vertex root -1: csrc/unionfind.h)
 
 // kSub lanes per entry of the cell-ordered list (the selected vertices), each taking every kSub-th candidate of every cell:
 // neighbouring lanes hold vertices of one cell and walk the same candidate lists.  (One lane per vertex left a 106 k-vertex
@@ -69,39 +70,6 @@ __global__ __launch_bounds__(256) void union_kernel(Index ix, int64_t cap, float
                     if (j < i && d2 < r2) root = unite(parent, root, j);      // each edge once, from its larger end
                 }
             }
-}
-
-// ------------------------------------------------------------------------------------------------- flatten, sizes
-__global__ __launch_bounds__(256) void init_kernel(int64_t M, int32_t* __restrict__ parent, int32_t* __restrict__ size) {
-    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (v >= M) return;
-    parent[v] = (int32_t)v;
-    size[v] = 0;
-}
-
-// After the kernel boundary parent[] is read-only: plain loads.  root[v] = the root of v's tree (-1: not selected), and
-// size[root] counts its members: integer adds, one per distinct root among a wave's lanes.
-__global__ __launch_bounds__(256) void flatten_kernel(const int32_t* __restrict__ parent, const uint8_t* __restrict__ mask,
-                                                      int64_t M, int32_t* __restrict__ root, int32_t* __restrict__ size) {
-    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int lane = threadIdx.x & 63;
-    bool pending = v < M && mask[v];
-    int32_t r = -1;
-    if (pending) {
-        r = (int32_t)v;
-        for (int32_t p = parent[r]; p != r; p = parent[r]) r = p;
-    }
-    if (v < M) root[v] = r;
-    while (true) {
-        const unsigned long long todo = __ballot(pending);
-        if (!todo) break;
-        const int leader = __ffsll((long long)todo) - 1;
-        const int32_t r0 = __shfl(r, leader);
-        const bool same = pending && r == r0;
-        const unsigned long long group = __ballot(same);
-        if (lane == leader) atomicAdd(&size[r0], __popcll(group));
-        if (same) pending = false;
-    }
 }
 
 // ----------------------------------------------------------------------------------------------------------- rank
@@ -174,10 +142,10 @@ extern "C" int misplat_cluster_radius(const float* vertices, int64_t n_vertices,
     }
     const unsigned nb = blocks(M, 256);
     const Index ix = build_index(vertices, M, mask, inv_h, W.ix, W.vslot, W.scr, s);
-    hipLaunchKernelGGL(init_kernel, dim3(nb), dim3(256), 0, s, M, W.parent, W.size);
+    hipLaunchKernelGGL(uf_init_kernel<int32_t>, dim3(nb), dim3(256), 0, s, M, W.parent, W.size);
     hipLaunchKernelGGL(union_kernel, dim3(blocks(M * kSub, 256)), dim3(256), 0, s, ix, W.ix.cap, radius, radius * radius, inv_h,
                        W.parent);
-    hipLaunchKernelGGL(flatten_kernel, dim3(nb), dim3(256), 0, s, (const int32_t*)W.parent, mask, M, W.root, W.size);
+    hipLaunchKernelGGL(flatten_kernel<true>, dim3(nb), dim3(256), 0, s, (const int32_t*)W.parent, mask, M, W.root, W.size);
     hipLaunchKernelGGL(keep_kernel, dim3(nb), dim3(256), 0, s, (const int32_t*)W.root, (const int32_t*)W.size, M, min_cluster_size,
                        W.keep);
     scan(W.keep, M, W.rank, W.scr, s);

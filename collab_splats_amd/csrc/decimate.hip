@@ -14,6 +14,7 @@
 #include "internal.h"
 #include "wgprims.h"
 #include "radixsort.h"
+#include "meshadj.h"
 
 namespace {
 
@@ -63,13 +64,14 @@ __device__ __forceinline__ double quadric_cost(const double* q, float fx, float 
     return c > 0.0 ? c : 0.0;
 }
 
-// a bijection of the 64-bit edge keys (the finaliser of splitmix64): the tie-break among equal costs
+// a bijection of the 64-bit edge keys (the finaliser of splitmix64): the tie-break among equal costs.  (Not hashmix.h's mix32,
+// a 32-bit hash; and pair_key is not meshedge.h's edge_key, which orders its ends: (a, b) is taken as the entry holds it.)
 __device__ __forceinline__ u64 mix_key(u64 k) {
     k ^= k >> 30; k *= 0xBF58476D1CE4E5B9ull;
     k ^= k >> 27; k *= 0x94D049BB133111EBull;
     return k ^ (k >> 31);
 }
-__device__ __forceinline__ u64 edge_key(int32_t a, int32_t b) { return ((u64)(uint32_t)a << 32) | (uint32_t)b; }
+__device__ __forceinline__ u64 pair_key(int32_t a, int32_t b) { return ((u64)(uint32_t)a << 32) | (uint32_t)b; }
 
 __device__ __forceinline__ bool has(const int32_t* __restrict__ t, int32_t v) { return t[0] == v || t[1] == v || t[2] == v; }
 
@@ -87,6 +89,7 @@ __global__ __launch_bounds__(256) void live_list_kernel(const int32_t* __restric
     if (f < T && alive[f] && pos[f] < n) lf[pos[f]] = (int32_t)f;
 }
 
+// the corners of the live faces as (key = vertex, value = corner index), and their directed edges (meshadj.h)
 __global__ __launch_bounds__(256) void emit_kernel(const int32_t* __restrict__ tri, const int32_t* __restrict__ lf, int64_t n,
                                                    int32_t* __restrict__ ck, int32_t* __restrict__ cv, int32_t* __restrict__ tgt,
                                                    int32_t* __restrict__ src) {
@@ -95,19 +98,8 @@ __global__ __launch_bounds__(256) void emit_kernel(const int32_t* __restrict__ t
     const int64_t g = h / 3;
     const int c = (int)(h - 3 * g);
     const int64_t f = lf[g];
-    const int32_t a = tri[3 * f + c], b = tri[3 * f + (c == 2 ? 0 : c + 1)];
-    ck[h] = a; cv[h] = (int32_t)(3 * f + c);
-    tgt[2 * h] = b; src[2 * h] = a;
-    tgt[2 * h + 1] = a; src[2 * h + 1] = b;
-}
-
-// rows[2 i], rows[2 i + 1] = vertex i's part of the sorted keys (zeroed by the caller)
-__global__ __launch_bounds__(256) void rows_kernel(const int32_t* __restrict__ key, int64_t E, int32_t* __restrict__ rows) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= E) return;
-    const int32_t s = key[e];
-    if (e == 0 || key[e - 1] != s) rows[2 * (int64_t)s] = (int32_t)e;
-    if (e == E - 1 || key[e + 1] != s) rows[2 * (int64_t)s + 1] = (int32_t)(e + 1);
+    ck[h] = tri[3 * f + c]; cv[h] = (int32_t)(3 * f + c);
+    emit_corner_edges(tri, f, c, h, tgt, src);
 }
 
 // Per vertex: is it on the boundary (a neighbour met once), its minima reset, and in the first round its quadric: the face
@@ -249,7 +241,7 @@ __global__ __launch_bounds__(256) void vote_key_kernel(Tables tb, int64_t E, con
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= E || ebits[e] == kNone) return;
     const int32_t a = tb.nsrc[e], b = tb.ntgt[e];
-    const u64 tie = mix_key(edge_key(a, b));
+    const u64 tie = mix_key(pair_key(a, b));
     if (ebits[e] == l1c[a]) atomicMin(&l1k[a], tie);
     if (ebits[e] == l1c[b]) atomicMin(&l1k[b], tie);
 }
@@ -278,7 +270,7 @@ __global__ __launch_bounds__(256) void select_kernel(Tables tb, int64_t E, const
     int32_t s = 0;
     if (ebits[e] != kNone) {
         const int32_t a = tb.nsrc[e], b = tb.ntgt[e];
-        const u64 bits = ebits[e], tie = mix_key(edge_key(a, b));
+        const u64 bits = ebits[e], tie = mix_key(pair_key(a, b));
         if (bits == l2c[a] && tie == l2k[a] && bits == l2c[b] && tie == l2k[b]) s = efaces[e];
     }
     sel[e] = s;
@@ -292,13 +284,6 @@ __global__ __launch_bounds__(256) void select_kernel(Tables tb, int64_t E, const
 __global__ __launch_bounds__(256) void flag_kernel(const int32_t* __restrict__ sel, int64_t E, int32_t* __restrict__ flag) {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (e < E) flag[e] = sel[e] ? 1 : 0;
-}
-
-// the selected entries in entry order, which is ascending edge key
-__global__ __launch_bounds__(256) void gather_kernel(const int32_t* __restrict__ sel, const int32_t* __restrict__ pos, int64_t E, int64_t S,
-                                                     int32_t* __restrict__ list) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e < E && sel[e] && pos[e] < S) list[pos[e]] = (int32_t)e;
 }
 
 __global__ __launch_bounds__(256) void digit_kernel(const u64* __restrict__ ebits, const int32_t* __restrict__ list, int64_t S, int shift,
@@ -385,21 +370,6 @@ inline Work carve(Carver& c, int64_t M, int64_t T, int64_t n) {
     return W;
 }
 
-// the buffers of a sort of fewer items than W.sort was taken for
-inline SortBufs sort_for(const Work& W, int64_t items) {
-    SortBufs b = W.sort;
-    b.nblk = (items + kTile - 1) / kTile;
-    return b;
-}
-
-// where radix_sort leaves the sorted pair after `passes` passes (it swaps the pairs once per pass)
-inline void sorted_names(int32_t*& ka, int32_t*& va, int32_t*& kb, int32_t*& vb, int passes) {
-    if (passes & 1) {
-        int32_t* t = ka; ka = kb; kb = t;
-        t = va; va = vb; vb = t;
-    }
-}
-
 inline bool sizes_ok(int64_t M, int64_t T, int64_t n) {
     return M >= 1 && M < (1ll << 31) && T >= 1 && 6 * T < (1ll << 31) - kTile && n >= 1 && n <= T;
 }
@@ -411,17 +381,15 @@ inline Tables tables(const Work& W, int64_t M, int64_t n, const int32_t* tri, bo
     int32_t *ck = W.ck, *cv = W.cv, *ckb = W.ckb, *cvb = W.cvb, *nk = W.nk, *nv = W.nv, *nkb = W.nkb, *nvb = W.nvb;
     if (build) {
         hipLaunchKernelGGL(emit_kernel, dim3(blocks(3 * n, 256)), dim3(256), 0, s, tri, (const int32_t*)W.lf, n, ck, cv, nk, nv);
-        radix_sort(ck, cv, ckb, cvb, 3 * n, passes, sort_for(W, 3 * n), W.scr, s);       // corners by vertex
-        radix_sort(nk, nv, nkb, nvb, E, passes, W.sort, W.scr, s);                       // directed edges by target ...
-        radix_sort(nv, nk, nvb, nkb, E, passes, W.sort, W.scr, s);                       // ... then stably by source
+        radix_sort(ck, cv, ckb, cvb, 3 * n, passes, sort_for(W.sort, 3 * n), W.scr, s);  // corners by vertex
+        sort_directed(nk, nv, nkb, nvb, E, passes, passes, W.sort, W.scr, s);            // nv the sources, nk the targets
         misplat_internal::fill_bytes(W.crow, 8 * (size_t)M, 0u, s);
         misplat_internal::fill_bytes(W.nrow, 8 * (size_t)M, 0u, s);
         hipLaunchKernelGGL(rows_kernel, dim3(blocks(3 * n, 256)), dim3(256), 0, s, (const int32_t*)ck, 3 * n, W.crow);
         hipLaunchKernelGGL(rows_kernel, dim3(blocks(E, 256)), dim3(256), 0, s, (const int32_t*)nv, E, W.nrow);
     } else {
         sorted_names(ck, cv, ckb, cvb, passes);
-        sorted_names(nk, nv, nkb, nvb, passes);
-        sorted_names(nv, nk, nvb, nkb, passes);
+        sorted_directed_names(nk, nv, nkb, nvb, passes, passes);
     }
     return Tables{W.crow, cv, W.nrow, nv, nk};
 }
@@ -485,8 +453,9 @@ extern "C" int misplat_decimate_apply(float* vertices, int64_t n_vertices, int32
     scan(W.efaces, E, W.spos, W.scr, s);
     int32_t *sk = W.sk, *sv = W.sv, *skb = W.skb, *svb = W.svb;
     misplat_internal::fill_bytes(sv, 4 * (size_t)S, 0u, s);             // (a wrong n_selected reads entry 0)
-    hipLaunchKernelGGL(gather_kernel, dim3(blocks(E, 256)), dim3(256), 0, s, (const int32_t*)W.sel, (const int32_t*)W.spos, E, S, sv);
-    const SortBufs sb = sort_for(W, S);
+    hipLaunchKernelGGL(compact_kernel<int32_t>, dim3(blocks(E, 256)), dim3(256), 0, s, (const int32_t*)W.sel, (const int32_t*)W.spos, E, S,
+                       sv);                                             // (in entry order, which is ascending edge key)
+    const SortBufs sb = sort_for(W.sort, S);
     for (int digit = 0; digit < 3; digit++) {
         hipLaunchKernelGGL(digit_kernel, dim3(blocks(S, 256)), dim3(256), 0, s, (const u64*)W.ebits, (const int32_t*)sv, S, 21 * digit, sk);
         radix_sort(sk, sv, skb, svb, S, 3, sb, W.scr, s);

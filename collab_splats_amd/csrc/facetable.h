@@ -1,7 +1,8 @@
-// facetable.h -- the edge table that names both faces of a two-face edge, shared by meshfill.hip and
-// meshtri.hip (section 30): per undirected edge its count of incidences, its smallest and its largest incident face; the
-// priority (bits, mixed key, key) by which both files pick one edge per face.  meshclean.hip's table keeps one face only and
-// stays its own.  In an unnamed namespace, as wgprims.h: each translation unit compiles its own copy.
+// facetable.h -- the edge table of a triangle mesh, shared by meshclean.hip, meshfill.hip (section 29)
+// and meshtri.hip (section 30): per undirected edge its count of incidences, its smallest and, where the caller takes it, its
+// largest incident face, which names both faces of a two-face edge (meshclean.hip takes none: 4 B a slot and one atomic the
+// less); the priority (bits, mixed key, key) by which meshfill.hip and meshtri.hip pick one edge per face.  In an unnamed
+// namespace, as wgprims.h: each translation unit compiles its own copy.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -16,10 +17,11 @@ typedef unsigned long long u64;
 
 struct EdgeTable {
     u64* keys;
-    int32_t *cnt, *fmin, *fmax;
-    u64 mask;
+    int32_t *cnt, *fmin, *fmax;                             // fmax: null in a table that keeps the smallest face only
+    u64 mask;                                               // capacity - 1
 };
 
+// the slot of an edge that was inserted
 __device__ __forceinline__ int64_t edge_find(const EdgeTable& E, u64 key) {
     u64 s = edge_home(key, E.mask);
     while (E.keys[s] != key) s = (s + 1) & E.mask;
@@ -48,7 +50,7 @@ __global__ __launch_bounds__(256) void edge_insert_kernel(const int32_t* __restr
     const u64 s = claim_slot(E.keys, E.mask, edge_home(key, E.mask), key);
     atomicAdd(&E.cnt[s], 1);
     atomicMin(&E.fmin[s], (int32_t)f);
-    atomicMax(&E.fmax[s], (int32_t)f);
+    if (E.fmax) atomicMax(&E.fmax[s], (int32_t)f);
 }
 
 __device__ __forceinline__ bool repeated(const int32_t* __restrict__ tri, int64_t f) {
@@ -62,16 +64,26 @@ inline int64_t edge_capacity(int64_t T) {
     return cap;
 }
 
-// the table of the T faces of `tri` over storage of `cap` slots (cleared by kernels, not memsets: internal.h)
-inline EdgeTable build_edge_table(const int32_t* tri, int64_t T, u64* keys, int32_t* cnt, int32_t* fmin, int32_t* fmax, int64_t cap,
-                                  hipStream_t s) {
-    EdgeTable E{keys, cnt, fmin, fmax, (u64)(cap - 1)};
+// the storage of the table of T faces, `both`: with the largest incident face
+inline EdgeTable take_edge_table(Carver& c, int64_t T, bool both = true) {
+    const int64_t cap = edge_capacity(T);
+    EdgeTable E = {};
+    E.keys = c.take<u64>(cap);
+    E.cnt = c.take<int32_t>(cap);
+    E.fmin = c.take<int32_t>(cap);
+    if (both) E.fmax = c.take<int32_t>(cap);
+    E.mask = (u64)(cap - 1);
+    return E;
+}
+
+// fills the table with the T faces of `tri` (cleared by kernels, not memsets: internal.h); an empty mesh launches no insertion
+inline void build_edge_table(const int32_t* tri, int64_t T, const EdgeTable& E, hipStream_t s) {
+    const size_t cap = (size_t)E.mask + 1;
     misplat_internal::fill_bytes(E.keys, 8 * cap, 0xffffffffu, s);
     misplat_internal::fill_bytes(E.cnt, 4 * cap, 0u, s);
     misplat_internal::fill_bytes(E.fmin, 4 * cap, 0x7fffffffu, s);
-    misplat_internal::fill_bytes(E.fmax, 4 * cap, 0u, s);
-    hipLaunchKernelGGL(edge_insert_kernel, dim3(blocks(3 * T, 256)), dim3(256), 0, s, tri, T, E);
-    return E;
+    if (E.fmax) misplat_internal::fill_bytes(E.fmax, 4 * cap, 0u, s);
+    if (T > 0) hipLaunchKernelGGL(edge_insert_kernel, dim3(blocks(3 * T, 256)), dim3(256), 0, s, tri, T, E);
 }
 
 // The priority of an edge among the candidates of a round: larger bits first (the fp32 length's in meshfill.hip, the fp64

@@ -6,8 +6,8 @@
 // evaluated in the written order.  Integer atomics only; every fp64 sum runs in a fixed order; two runs are bitwise equal.
 //
 // Edge table: every undirected edge (lo, hi), lo < hi, of every triangle in an open-addressing hash, key lo << 32 | hi,
-// capacity the power of two >= max(64, 6 T).  A slot holds the number of (face, corner) incidences of its edge and the
-// smallest incident face.  Which slot an edge takes depends on the insertion race; nothing that is read back does.  A corner
+// capacity the power of two >= max(64, 6 T): facetable.h's.  A slot holds the number of (face, corner) incidences of its edge
+// and the smallest incident face.  Which slot an edge takes depends on the insertion race; nothing that is read back does.  A corner
 // repeated inside a triangle gives an edge (a, a): it is ignored everywhere.  Readers find an edge's slot by probing
 // again: the table keeps no per-corner slot list (3 T int32 the less).
 #include <hip/hip_runtime.h>
@@ -19,36 +19,13 @@
 #include "unionfind.h"
 #include "hashmix.h"
 #include "meshedge.h"
+#include "facetable.h"
+#include "meshadj.h"
 
 namespace {
 
 // ----------------------------------------------------------------------------------------------------- edge table
-struct EdgeTable {
-    unsigned long long* keys;
-    int32_t* cnt;
-    int32_t* face;
-    unsigned long long mask;
-};
-
-// the slot of an edge that was inserted
-__device__ __forceinline__ int64_t edge_find(const EdgeTable& E, unsigned long long key) {
-    unsigned long long s = edge_home(key, E.mask);
-    while (E.keys[s] != key) s = (s + 1) & E.mask;
-    return (int64_t)s;
-}
-
-__global__ __launch_bounds__(256) void edge_insert_kernel(const int32_t* __restrict__ tri, int64_t T, EdgeTable E) {
-    const int64_t h = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (h >= 3 * T) return;
-    const int64_t f = h / 3;
-    int32_t a, b;
-    corner_edge(tri, f, (int)(h - 3 * f), a, b);
-    if (a == b) return;
-    const unsigned long long key = edge_key(a, b);
-    const unsigned long long s = claim_slot(E.keys, E.mask, edge_home(key, E.mask), key);
-    atomicAdd(&E.cnt[s], 1);
-    atomicMin(&E.face[s], (int32_t)f);
-}
+// (facetable.h's, taken without the largest face)
 
 // counts: 0 edges, 1 boundary edges (one incidence), 2 non-manifold edges (more than two)
 __global__ __launch_bounds__(256) void edge_count_kernel(EdgeTable E, int64_t cap, int32_t* __restrict__ counts) {
@@ -76,7 +53,7 @@ __global__ __launch_bounds__(256) void edge_length_kernel(const float* __restric
         corner_edge(tri, f, c, a, b);
         if (a != b) {
             const unsigned long long key = edge_key(a, b);
-            bool first = E.face[edge_find(E, key)] == (int32_t)f;
+            bool first = E.fmin[edge_find(E, key)] == (int32_t)f;
             for (int c0 = 0; c0 < c; c0++) {
                 int32_t a0, b0;
                 corner_edge(tri, f, c0, a0, b0);
@@ -93,13 +70,6 @@ __global__ void edge_mean_kernel(const double* __restrict__ sum, const int32_t* 
 }
 
 // ------------------------------------------------------------------------------------------------------ components
-__global__ __launch_bounds__(256) void iota_kernel(int64_t n, int32_t* __restrict__ parent, int32_t* __restrict__ zero) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    parent[i] = (int32_t)i;
-    zero[i] = 0;
-}
-
 // every face is united with the smallest face of each of its edges: the faces around one edge, a non-manifold one
 // included, end in one tree
 __global__ __launch_bounds__(256) void face_union_kernel(const int32_t* __restrict__ tri, int64_t T, EdgeTable E,
@@ -110,33 +80,8 @@ __global__ __launch_bounds__(256) void face_union_kernel(const int32_t* __restri
     int32_t a, b;
     corner_edge(tri, f, (int)(h - 3 * f), a, b);
     if (a == b) return;
-    const int32_t g = E.face[edge_find(E, edge_key(a, b))];
+    const int32_t g = E.fmin[edge_find(E, edge_key(a, b))];
     if (g != (int32_t)f) (void)unite(parent, (int32_t)f, g);
-}
-
-// After the kernel boundary parent[] is read-only: plain loads.  root[i] = the root of i's tree, size[root] counts its
-// members: integer adds, one per distinct root among a wave's lanes (as cluster.hip's flatten_kernel).
-__global__ __launch_bounds__(256) void flatten_kernel(const int32_t* __restrict__ parent, int64_t n, int32_t* __restrict__ root,
-                                                      int32_t* __restrict__ size) {
-    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int lane = threadIdx.x & 63;
-    bool pending = v < n;
-    int32_t r = -1;
-    if (pending) {
-        r = (int32_t)v;
-        for (int32_t p = parent[r]; p != r; p = parent[r]) r = p;
-        root[v] = r;
-    }
-    while (true) {
-        const unsigned long long todo = __ballot(pending);
-        if (!todo) break;
-        const int leader = __ffsll((long long)todo) - 1;
-        const int32_t r0 = __shfl(r, leader);
-        const bool same = pending && r == r0;
-        const unsigned long long group = __ballot(same);
-        if (lane == leader) atomicAdd(&size[r0], __popcll(group));
-        if (same) pending = false;
-    }
 }
 
 __global__ __launch_bounds__(256) void is_root_kernel(const int32_t* __restrict__ root, int64_t n, int32_t* __restrict__ keep) {
@@ -191,8 +136,7 @@ __global__ __launch_bounds__(256) void loop_root_kernel(const int32_t* __restric
                                                         int32_t* __restrict__ on) {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= *n_boundary) return;
-    int32_t r = edges[2 * e];
-    for (int32_t p = vparent[r]; p != r; p = vparent[r]) r = p;
+    const int32_t r = walk_root(vparent, edges[2 * e]);
     eroot[e] = r;
     on[r] = 1;
 }
@@ -355,26 +299,13 @@ __global__ __launch_bounds__(256) void moment_cov_kernel(const float* __restrict
 }
 
 // ------------------------------------------------------------------------------------------------------- smoothing
-// Laplacian smoothing.  The directed edges of all corners, both ways, as (key = target, value =
-// source): sorted by target, then stably by source, they form a CSR over the sources with every row ascending in its target.
+// Laplacian smoothing over the CSR of the sorted directed edges of all corners (meshadj.h).
 __global__ __launch_bounds__(256) void smooth_edges_kernel(const int32_t* __restrict__ tri, int64_t T, int32_t* __restrict__ tgt,
                                                            int32_t* __restrict__ src) {
     const int64_t h = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (h >= 3 * T) return;
     const int64_t f = h / 3;
-    int32_t a, b;
-    corner_edge(tri, f, (int)(h - 3 * f), a, b);
-    tgt[2 * h] = b; src[2 * h] = a;
-    tgt[2 * h + 1] = a; src[2 * h + 1] = b;
-}
-
-// rows[2 i], rows[2 i + 1] = vertex i's part of the sorted edges (zeroed by the caller: a vertex without an edge keeps 0, 0)
-__global__ __launch_bounds__(256) void smooth_rows_kernel(const int32_t* __restrict__ src, int64_t E, int32_t* __restrict__ rows) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= E) return;
-    const int32_t s = src[e];
-    if (e == 0 || src[e - 1] != s) rows[2 * (int64_t)s] = (int32_t)e;
-    if (e == E - 1 || src[e + 1] != s) rows[2 * (int64_t)s + 1] = (int32_t)(e + 1);
+    emit_corner_edges(tri, f, (int)(h - 3 * f), h, tgt, src);
 }
 
 // One lane per (vertex i, channel c) of values [M, D]: out = x + lam (sum_j w_ij x_j / sum_j w_ij - x) over the distinct
@@ -407,17 +338,10 @@ __global__ __launch_bounds__(256) void smooth_gather_kernel(const float* __restr
 // ------------------------------------------------------------------------------------------------------- workspace
 enum { kKindStats = 0, kKindComponents = 1, kKindHoles = 2, kKindMoments = 3, kKindSmooth = 4 };
 
-inline int64_t edge_capacity(int64_t T) {
-    int64_t cap = 64;
-    while (cap < 6 * T) cap <<= 1;
-    return cap;
-}
-
 // what a kind does not use stays null
 struct Work {
-    int64_t cap;
-    unsigned long long* keys;         // the edge table: keys, cnt, face [cap]
-    int32_t *cnt, *face, *scr;
+    EdgeTable edges;                  // (the smallest face only)
+    int32_t* scr;
     double *part, *sum;
     int32_t *parent, *size, *root, *keep, *rank, *flag, *pos, *eroot;
     int32_t *ka, *va, *kb, *vb, *rows;    // smoothing: the two pairs of the sort over the 6 T directed edges, the CSR rows [2 M]
@@ -442,10 +366,7 @@ inline Work carve(Carver& c, int64_t M, int64_t T, int kind) {
         W.sort = take_sort(c, E);
         return W;
     }
-    W.cap = edge_capacity(T);
-    W.keys = c.take<unsigned long long>(W.cap);
-    W.cnt = c.take<int32_t>(W.cap);
-    W.face = c.take<int32_t>(W.cap);
+    W.edges = take_edge_table(c, T, false);
     W.scr = take_scan(c, 3 * T > M ? 3 * T : M);
     if (kind == kKindStats) {
         W.part = c.take<double>((3 * T + 255) / 256 + 1);
@@ -476,15 +397,6 @@ inline bool cloud_ok(int64_t N) { return N >= 0 && N < (1ll << 30); }
 // smoothing sorts the 6 T directed edges
 inline bool smooth_ok(int64_t T) { return 6 * T < (1ll << 31) - kTile; }
 
-inline EdgeTable build_edges(const int32_t* tri, int64_t T, const Work& W, hipStream_t s) {
-    EdgeTable E{W.keys, W.cnt, W.face, (unsigned long long)(W.cap - 1)};
-    misplat_internal::fill_bytes(E.keys, 8 * W.cap, 0xffffffffu, s);          // (kernels, not memsets: internal.h)
-    misplat_internal::fill_bytes(E.cnt, 4 * W.cap, 0u, s);
-    misplat_internal::fill_bytes(E.face, 4 * W.cap, 0x7fffffffu, s);
-    if (T > 0) hipLaunchKernelGGL(edge_insert_kernel, dim3(blocks(3 * T, 256)), dim3(256), 0, s, tri, T, E);
-    return E;
-}
-
 }  // namespace
 
 extern "C" int64_t misplat_meshclean_workspace(int64_t n_vertices, int64_t n_triangles, int32_t kind) {
@@ -508,9 +420,11 @@ extern "C" int misplat_meshclean_edge_stats(const float* vertices, int64_t n_ver
     const Work W = carve(c, M, T, kKindStats);
     if (workspace_bytes < c.o) return MISPLAT_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    const EdgeTable E = build_edges(triangles, T, W, s);
+    const EdgeTable& E = W.edges;
+    build_edge_table(triangles, T, E, s);
     misplat_internal::fill_bytes(counts, 12, 0u, s);
-    hipLaunchKernelGGL(edge_count_kernel, dim3(blocks(W.cap, 256)), dim3(256), 0, s, E, W.cap, counts);
+    const int64_t cap = (int64_t)E.mask + 1;
+    hipLaunchKernelGGL(edge_count_kernel, dim3(blocks(cap, 256)), dim3(256), 0, s, E, cap, counts);
     const int64_t nb = (3 * T + 255) / 256;
     if (nb > 0) hipLaunchKernelGGL(edge_length_kernel, dim3((unsigned)nb), dim3(256), 0, s, vertices, triangles, T, E, W.part);
     hipLaunchKernelGGL((sum_final_kernel<1, 256>), dim3(1), dim3(256), 0, s, (const double*)W.part, nb, W.sum);
@@ -531,11 +445,13 @@ extern "C" int misplat_meshclean_components(const int32_t* triangles, int64_t n_
         misplat_internal::fill_bytes(n_components, 4, 0u, s);
         return launched();
     }
-    const EdgeTable E = build_edges(triangles, T, W, s);
+    const EdgeTable& E = W.edges;
+    build_edge_table(triangles, T, E, s);
     const unsigned nb = blocks(T, 256);
-    hipLaunchKernelGGL(iota_kernel, dim3(nb), dim3(256), 0, s, T, W.parent, W.size);
+    hipLaunchKernelGGL(uf_init_kernel<int32_t>, dim3(nb), dim3(256), 0, s, T, W.parent, W.size);
     hipLaunchKernelGGL(face_union_kernel, dim3(blocks(3 * T, 256)), dim3(256), 0, s, triangles, T, E, W.parent);
-    hipLaunchKernelGGL(flatten_kernel, dim3(nb), dim3(256), 0, s, (const int32_t*)W.parent, T, W.root, W.size);
+    hipLaunchKernelGGL(flatten_kernel<false>, dim3(nb), dim3(256), 0, s, (const int32_t*)W.parent, (const uint8_t*)nullptr, T, W.root,
+                       W.size);
     hipLaunchKernelGGL(is_root_kernel, dim3(nb), dim3(256), 0, s, (const int32_t*)W.root, T, W.keep);
     scan(W.keep, T, W.rank, W.scr, s);
     hipLaunchKernelGGL(face_label_kernel, dim3(nb), dim3(256), 0, s, (const int32_t*)W.root, (const int32_t*)W.size,
@@ -558,11 +474,12 @@ extern "C" int misplat_meshclean_holes(const float* vertices, int64_t n_vertices
         misplat_internal::fill_bytes(counts, 8, 0u, s);
         return launched();
     }
-    const EdgeTable E = build_edges(triangles, T, W, s);
+    const EdgeTable& E = W.edges;
+    build_edge_table(triangles, T, E, s);
     int32_t *scr = W.scr, *flag = W.flag, *pos = W.pos, *eroot = W.eroot;
     int32_t *vparent = W.parent, *on = W.keep, *vrank = W.rank;     // (over the vertices here)
     const unsigned nh = blocks(3 * T, 256);
-    hipLaunchKernelGGL(iota_kernel, dim3(blocks(M, 256)), dim3(256), 0, s, M, vparent, on);
+    hipLaunchKernelGGL(uf_init_kernel<int32_t>, dim3(blocks(M, 256)), dim3(256), 0, s, M, vparent, on);
     hipLaunchKernelGGL(boundary_flag_kernel, dim3(nh), dim3(256), 0, s, triangles, T, E, flag);
     scan(flag, 3 * T, pos, scr, s);
     hipLaunchKernelGGL(boundary_emit_kernel, dim3(nh), dim3(256), 0, s, vertices, triangles, T, (const int32_t*)flag,
@@ -602,10 +519,9 @@ extern "C" int misplat_meshclean_smooth(const float* vertices, int64_t n_vertice
     int32_t *ka = W.ka, *va = W.va, *kb = W.kb, *vb = W.vb;
     hipLaunchKernelGGL(smooth_edges_kernel, dim3(blocks(3 * T, 256)), dim3(256), 0, s, triangles, T, ka, va);
     const int passes = radix_passes(M - 1);
-    radix_sort(ka, va, kb, vb, E, passes, W.sort, W.scr, s);           // by target; (ka, va) name the sorted pair
-    radix_sort(va, ka, vb, kb, E, passes, W.sort, W.scr, s);           // stably by source: va the sources, ka the targets
+    sort_directed(ka, va, kb, vb, E, passes, passes, W.sort, W.scr, s);        // va the sources, ka the targets
     misplat_internal::fill_bytes(W.rows, 8 * (size_t)M, 0u, s);
-    hipLaunchKernelGGL(smooth_rows_kernel, dim3(blocks(E, 256)), dim3(256), 0, s, (const int32_t*)va, E, W.rows);
+    hipLaunchKernelGGL(rows_kernel, dim3(blocks(E, 256)), dim3(256), 0, s, (const int32_t*)va, E, W.rows);
     const float *pos = vertices, *att = attributes;
     for (int it = 0; it < iterations; it++) {
         const bool last_parity = (iterations - 1 - it) % 2 == 0;        // the last iteration writes the outputs

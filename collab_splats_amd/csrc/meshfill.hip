@@ -23,6 +23,7 @@
 #include "hashmix.h"
 #include "meshedge.h"
 #include "facetable.h"
+#include "meshadj.h"
 
 namespace {
 
@@ -55,13 +56,6 @@ __global__ void totals_kernel(const int32_t* __restrict__ spos, const int32_t* _
 }
 
 // ---------------------------------------------------------------------------------------------------------- landing
-// the owner slots in slot order
-__global__ __launch_bounds__(256) void gather_kernel(const int32_t* __restrict__ flag, const int32_t* __restrict__ spos, int64_t n,
-                                                     int64_t S, int32_t* __restrict__ list) {
-    const int64_t h = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (h < n && flag[h] && spos[h] < S) list[spos[h]] = (int32_t)h;
-}
-
 // one 32-bit digit of the priority of the listed edges: 0 hi, 1 lo, 2 mix, 3 the complement of the length bits
 __global__ __launch_bounds__(256) void digit_kernel(const int32_t* __restrict__ tri, const uint32_t* __restrict__ sbits,
                                                     const int32_t* __restrict__ list, int64_t S, int which, int32_t* __restrict__ key) {
@@ -125,9 +119,7 @@ __global__ __launch_bounds__(256) void split_kernel(int32_t* __restrict__ tri, i
 inline int64_t max2(int64_t a, int64_t b) { return a > b ? a : b; }
 
 struct Work {
-    int64_t cap;
-    u64* keys;
-    int32_t *cnt, *fmin, *fmax;
+    EdgeTable edges;
     uint32_t* sbits;
     int32_t *best, *owner, *fsplit, *flag, *spos, *frank;
     int32_t *sk, *sv, *skb, *svb;                 // the landing sort of the selected edges (at most one per face)
@@ -137,11 +129,7 @@ struct Work {
 
 inline Work carve(Carver& c, int64_t T) {
     Work W = {};
-    W.cap = edge_capacity(T);
-    W.keys = c.take<u64>(W.cap);
-    W.cnt = c.take<int32_t>(W.cap);
-    W.fmin = c.take<int32_t>(W.cap);
-    W.fmax = c.take<int32_t>(W.cap);
+    W.edges = take_edge_table(c, T);
     W.sbits = c.take<uint32_t>(3 * T);
     W.best = c.take<int32_t>(T);
     W.owner = c.take<int32_t>(T);
@@ -172,15 +160,6 @@ __global__ __launch_bounds__(256) void free_flag_kernel(const uint8_t* __restric
     if (v < M) f32[v] = free[v] ? 1 : 0;
 }
 
-// directed edge 2 h + d of corner h: d = 0 as the face runs, d = 1 against it
-__device__ __forceinline__ void directed(const int32_t* __restrict__ tri, int64_t e, int32_t& src, int32_t& tgt) {
-    const int64_t h = e >> 1, f = h / 3;
-    int32_t a, b;
-    corner_edge(tri, f, (int)(h - 3 * f), a, b);
-    src = (e & 1) ? b : a;
-    tgt = (e & 1) ? a : b;
-}
-
 __global__ __launch_bounds__(256) void free_edge_flag_kernel(const int32_t* __restrict__ tri, int64_t E6, const uint8_t* __restrict__ free,
                                                              int32_t* __restrict__ eflag) {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -196,12 +175,6 @@ __global__ void fair_totals_kernel(const int32_t* __restrict__ fidx, int64_t M, 
     counts[1] = epos[E6];
 }
 
-__global__ __launch_bounds__(256) void free_list_kernel(const uint8_t* __restrict__ free, const int32_t* __restrict__ fidx, int64_t M,
-                                                        int64_t n_free, int32_t* __restrict__ fl) {
-    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (v < M && free[v] && fidx[v] < n_free) fl[fidx[v]] = (int32_t)v;
-}
-
 __global__ __launch_bounds__(256) void free_edge_emit_kernel(const int32_t* __restrict__ tri, int64_t E6, const int32_t* __restrict__ eflag,
                                                              const int32_t* __restrict__ epos, const int32_t* __restrict__ fidx,
                                                              int64_t Ef, int32_t* __restrict__ tgt_out, int32_t* __restrict__ src_out) {
@@ -211,15 +184,6 @@ __global__ __launch_bounds__(256) void free_edge_emit_kernel(const int32_t* __re
     directed(tri, e, src, tgt);
     tgt_out[epos[e]] = tgt;
     src_out[epos[e]] = fidx[src];
-}
-
-// rows[2 k], rows[2 k + 1] = free vertex k's part of the sorted edges (zeroed by the caller)
-__global__ __launch_bounds__(256) void rows_kernel(const int32_t* __restrict__ key, int64_t E, int32_t* __restrict__ rows) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= E) return;
-    const int32_t s = key[e];
-    if (e == 0 || key[e - 1] != s) rows[2 * (int64_t)s] = (int32_t)e;
-    if (e == E - 1 || key[e + 1] != s) rows[2 * (int64_t)s + 1] = (int32_t)(e + 1);
 }
 
 __global__ __launch_bounds__(256) void patch_init_kernel(int64_t n, int32_t* __restrict__ parent, int32_t* __restrict__ iters,
@@ -246,8 +210,7 @@ __global__ __launch_bounds__(256) void patch_root_kernel(const int32_t* __restri
                                                          int32_t* __restrict__ isroot) {
     const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (k >= n) return;
-    int32_t r = (int32_t)k;
-    for (int32_t p = parent[r]; p != r; p = parent[r]) r = p;
+    const int32_t r = walk_root(parent, (int32_t)k);
     root[k] = r;
     isroot[k] = r == (int32_t)k ? 1 : 0;
 }
@@ -348,12 +311,7 @@ __global__ __launch_bounds__(kStepThreads) void fair_step_kernel(const float* __
         const int32_t p0 = __shfl(p, leader);
         if (__ballot(moving && p != p0) == 0ull) {
             wp = p0;
-            m = moving ? bits : 0u;
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                const uint32_t o = (uint32_t)__shfl_xor((int)m, off);
-                m = o > m ? o : m;
-            }
+            m = wave_max(moving ? bits : 0u);
         } else if (moving && bits > __hip_atomic_load(d_cur + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
             atomicMax(d_cur + p, bits);                     // (none where the patch's word is already as large)
         }
@@ -476,11 +434,7 @@ __global__ __launch_bounds__(kLdsThreads) void fair_lds_kernel(float* __restrict
                 mine = bits > mine ? bits : mine;
             }
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const uint32_t o = (uint32_t)__shfl_xor((int)mine, off);
-            mine = o > mine ? o : mine;
-        }
+        mine = wave_max(mine);
         if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = mine;
         __syncthreads();                                         // the new iterate and the waves' maxima are written
         uint32_t all = 0u;
@@ -544,13 +498,11 @@ inline void fair_scans(const FairWork& W, const int32_t* tri, int64_t T, const u
     scan(W.eflag, 6 * T, W.epos, W.scr, s);
 }
 
-// where the two sorts of the build leave the sources and the targets
-inline void sorted_names(const FairWork& W, int64_t M, int64_t n, const int32_t*& src, const int32_t*& tgt) {
-    int32_t *ka = W.ka, *va = W.va, *kb = W.kb, *vb = W.vb, *t;
-    if (radix_passes(M - 1) & 1) { t = ka; ka = kb; kb = t; t = va; va = vb; vb = t; }
-    if (radix_passes(n - 1) & 1) { t = ka; ka = kb; kb = t; t = va; va = vb; vb = t; }
-    src = va;
-    tgt = ka;
+// the sorted targets (the rows' entries), where the two sorts of the build left them
+inline const int32_t* sorted_targets(const FairWork& W, int64_t M, int64_t n) {
+    int32_t *ka = W.ka, *va = W.va, *kb = W.kb, *vb = W.vb;
+    sorted_directed_names(ka, va, kb, vb, radix_passes(M - 1), radix_passes(n - 1));
+    return ka;
 }
 
 }  // namespace
@@ -572,7 +524,8 @@ extern "C" int misplat_meshfill_round(const float* vertices, int64_t n_vertices,
     if (workspace_bytes < c.o) return MISPLAT_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     const unsigned nh = blocks(3 * T, 256), nf = blocks(T, 256);
-    const EdgeTable E = build_edge_table(triangles, T, W.keys, W.cnt, W.fmin, W.fmax, W.cap, s);
+    const EdgeTable& E = W.edges;
+    build_edge_table(triangles, T, E, s);
     hipLaunchKernelGGL(splittable_kernel, dim3(nh), dim3(256), 0, s, vertices, triangles, T, region, E, max_edge_len, W.sbits);
     hipLaunchKernelGGL(face_best_kernel<uint32_t>, dim3(nf), dim3(256), 0, s, triangles, T, (const uint32_t*)W.sbits, W.best);
     hipLaunchKernelGGL(select_kernel, dim3(nf), dim3(256), 0, s, triangles, T, E, (const int32_t*)W.best, W.owner, W.fsplit, W.flag);
@@ -599,9 +552,9 @@ extern "C" int misplat_meshfill_apply(float* vertices, int64_t n_vertices, int32
         // priority from the least significant on (hi, lo, the mixed key, the complement of the length bits).
         int32_t *sk = W.sk, *sv = W.sv, *skb = W.skb, *svb = W.svb;
         misplat_internal::fill_bytes(sv, 4 * (size_t)S, 0u, s);         // (a wrong n_selected reads slot 0)
-        hipLaunchKernelGGL(gather_kernel, dim3(nh), dim3(256), 0, s, (const int32_t*)W.flag, (const int32_t*)W.spos, 3 * T, S, sv);
-        SortBufs sb = W.sort;
-        sb.nblk = (S + kTile - 1) / kTile;
+        hipLaunchKernelGGL(compact_kernel<int32_t>, dim3(nh), dim3(256), 0, s, (const int32_t*)W.flag, (const int32_t*)W.spos, 3 * T, S,
+                           sv);                                         // (the owner slots in slot order)
+        const SortBufs sb = sort_for(W.sort, S);
         const int index_passes = radix_passes(M - 1);
         for (int which = 0; which < 4; which++) {
             hipLaunchKernelGGL(digit_kernel, dim3(blocks(S, 256)), dim3(256), 0, s, (const int32_t*)triangles, (const uint32_t*)W.sbits,
@@ -651,7 +604,8 @@ extern "C" int misplat_meshfill_fair_build(const int32_t* triangles, int64_t n_t
     fair_scans(W, triangles, T, free, M, s);
     const unsigned nk = blocks(n, 256);
     misplat_internal::fill_bytes(W.fl, 4 * (size_t)n, 0u, s);           // (a wrong n_free reads vertex 0, never beyond the list)
-    hipLaunchKernelGGL(free_list_kernel, dim3(blocks(M, 256)), dim3(256), 0, s, free, (const int32_t*)W.fidx, M, n, W.fl);
+    hipLaunchKernelGGL(compact_kernel<int32_t>, dim3(blocks(M, 256)), dim3(256), 0, s, (const int32_t*)W.f32, (const int32_t*)W.fidx, M, n,
+                       W.fl);
     hipLaunchKernelGGL(patch_init_kernel, dim3(nk), dim3(256), 0, s, n, W.parent, iterations, W.disp);
     misplat_internal::fill_bytes(W.rows, 8 * (size_t)n, 0u, s);
     if (Ef > 0) {
@@ -660,8 +614,7 @@ extern "C" int misplat_meshfill_fair_build(const int32_t* triangles, int64_t n_t
         misplat_internal::fill_bytes(va, 4 * (size_t)Ef, 0u, s);
         hipLaunchKernelGGL(free_edge_emit_kernel, dim3(blocks(6 * T, 256)), dim3(256), 0, s, triangles, 6 * T, (const int32_t*)W.eflag,
                            (const int32_t*)W.epos, (const int32_t*)W.fidx, Ef, ka, va);
-        radix_sort(ka, va, kb, vb, Ef, radix_passes(M - 1), W.sort, W.scr, s);          // by target
-        radix_sort(va, ka, vb, kb, Ef, radix_passes(n - 1), W.sort, W.scr, s);          // stably by source: va sources, ka targets
+        sort_directed(ka, va, kb, vb, Ef, radix_passes(M - 1), radix_passes(n - 1), W.sort, W.scr, s);     // va sources, ka targets
         hipLaunchKernelGGL(rows_kernel, dim3(blocks(Ef, 256)), dim3(256), 0, s, (const int32_t*)va, Ef, W.rows);
         hipLaunchKernelGGL(patch_union_kernel, dim3(blocks(Ef, 256)), dim3(256), 0, s, (const int32_t*)va, (const int32_t*)ka, Ef, free,
                            (const int32_t*)W.fidx, W.parent);
@@ -685,9 +638,7 @@ extern "C" int misplat_meshfill_fair_step(float* values_a, float* values_b, int6
     const FairWork W = carve_fair(c, M, T, n, Ef);
     if (workspace_bytes < c.o) return MISPLAT_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    Fair F{W.fl, W.rows, nullptr, W.pid, W.isroot};
-    const int32_t* src;
-    sorted_names(W, M, n, src, F.nbr);
+    const Fair F{W.fl, W.rows, sorted_targets(W, M, n), W.pid, W.isroot};
     uint32_t tol_bits;
     __builtin_memcpy(&tol_bits, &tolerance, 4);
     const unsigned nb = blocks(n * D, kStepThreads);
@@ -718,17 +669,13 @@ extern "C" int misplat_meshfill_fair_lds(float* vertices, int64_t n_vertices, in
     const FairWork W = carve_fair(c, M, T, n, Ef);
     if (workspace_bytes < c.o) return MISPLAT_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    Fair F{W.fl, W.rows, nullptr, W.pid, W.isroot};
-    const int32_t* src;
-    sorted_names(W, M, n, src, F.nbr);
+    const Fair F{W.fl, W.rows, sorted_targets(W, M, n), W.pid, W.isroot};
     uint32_t tol_bits;
     __builtin_memcpy(&tol_bits, &tolerance, 4);
     const unsigned nk = blocks(n, 256);
     int32_t *pk = W.pk, *pv = W.pv, *pkb = W.pkb, *pvb = W.pvb;
     hipLaunchKernelGGL(patch_keys_kernel, dim3(nk), dim3(256), 0, s, (const int32_t*)W.pid, n, pk, pv);
-    SortBufs sb = W.sort;
-    sb.nblk = (n + kTile - 1) / kTile;
-    radix_sort(pk, pv, pkb, pvb, n, radix_passes(n_patches - 1), sb, W.scr, s);     // stable: a patch's vertices stay ascending
+    radix_sort(pk, pv, pkb, pvb, n, radix_passes(n_patches - 1), sort_for(W.sort, n), W.scr, s);    // (a patch's vertices stay ascending)
     misplat_internal::fill_bytes(W.prow, 8 * (size_t)n, 0u, s);
     hipLaunchKernelGGL(rows_kernel, dim3(nk), dim3(256), 0, s, (const int32_t*)pk, n, W.prow);
     hipLaunchKernelGGL(patch_place_kernel, dim3(nk), dim3(256), 0, s, (const int32_t*)pv, (const int32_t*)pk, (const int32_t*)W.prow, n,
@@ -777,9 +724,7 @@ __global__ __launch_bounds__(256) void curv_union_kernel(const int32_t* __restri
 __global__ __launch_bounds__(256) void curv_root_kernel(const int32_t* __restrict__ parent, int64_t M, int32_t* __restrict__ root) {
     const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (v >= M) return;
-    int32_t r = (int32_t)v;
-    for (int32_t p = parent[r]; p != r; p = parent[r]) r = p;
-    root[v] = r;
+    root[v] = walk_root(parent, (int32_t)v);
 }
 
 struct Curv {

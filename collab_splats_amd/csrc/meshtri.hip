@@ -462,20 +462,17 @@ __global__ __launch_bounds__(256) void flip_kernel(int32_t* __restrict__ tri, in
 }
 
 struct FlipWork {
-    int64_t cap, ccap;
-    u64 *keys, *vbits, *ckeys, *cval;
-    int32_t *cnt, *fmin, *fmax, *best, *owner, *fsel, *flag;
+    EdgeTable edges;
+    int64_t ccap;
+    u64 *vbits, *ckeys, *cval;
+    int32_t *best, *owner, *fsel, *flag;
 };
 
 inline FlipWork carve_flip(Carver& c, int64_t T) {
     FlipWork W = {};
-    W.cap = edge_capacity(T);
     W.ccap = 64;
     while (W.ccap < 2 * T) W.ccap <<= 1;                        // (selected edges share no face: at most T / 2 claims)
-    W.keys = c.take<u64>(W.cap);
-    W.cnt = c.take<int32_t>(W.cap);
-    W.fmin = c.take<int32_t>(W.cap);
-    W.fmax = c.take<int32_t>(W.cap);
+    W.edges = take_edge_table(c, T);
     W.vbits = c.take<u64>(3 * T);
     W.best = c.take<int32_t>(T);
     W.owner = c.take<int32_t>(T);
@@ -483,22 +480,6 @@ inline FlipWork carve_flip(Carver& c, int64_t T) {
     W.flag = c.take<int32_t>(3 * T);
     W.ckeys = c.take<u64>(W.ccap);
     W.cval = c.take<u64>(W.ccap);
-    return W;
-}
-
-struct RimWork {
-    int64_t cap;
-    u64* keys;
-    int32_t *cnt, *fmin, *fmax;
-};
-
-inline RimWork carve_rim(Carver& c, int64_t T) {
-    RimWork W = {};
-    W.cap = edge_capacity(T);
-    W.keys = c.take<u64>(W.cap);
-    W.cnt = c.take<int32_t>(W.cap);
-    W.fmin = c.take<int32_t>(W.cap);
-    W.fmax = c.take<int32_t>(W.cap);
     return W;
 }
 
@@ -519,7 +500,7 @@ extern "C" int misplat_meshtri_order(const int32_t* edges, const int32_t* order,
 extern "C" int64_t misplat_meshtri_rim_workspace(int64_t n_triangles) {
     if (n_triangles < 1 || 6 * n_triangles >= (1ll << 31) - kTile) return -1;
     Carver c{nullptr};
-    carve_rim(c, n_triangles);
+    take_edge_table(c, n_triangles);
     return c.o;
 }
 
@@ -532,10 +513,10 @@ extern "C" int misplat_meshtri_order_rim(const int32_t* edges, const int32_t* or
         !order || !offsets || !fill || !triangles || !workspace || !code || !polygon || !rim)
         return MISPLAT_EINVAL;
     Carver c{(char*)workspace};
-    const RimWork W = carve_rim(c, T);
+    const EdgeTable E = take_edge_table(c, T);
     if (workspace_bytes < c.o) return MISPLAT_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    const EdgeTable E = build_edge_table(triangles, T, W.keys, W.cnt, W.fmin, W.fmax, W.cap, s);
+    build_edge_table(triangles, T, E, s);
     hipLaunchKernelGGL(order_kernel<true>, dim3((unsigned)n_loops), dim3(256), 0, s, edges, order, offsets, fill, n_edges, code, polygon,
                        triangles, T, E, rim);
     return launched();
@@ -599,7 +580,8 @@ extern "C" int misplat_meshtri_flip_round(const float* vertices, int64_t n_verti
     if (workspace_bytes < c.o) return MISPLAT_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     const unsigned nh = blocks(3 * T, 256), nf = blocks(T, 256);
-    const EdgeTable E = build_edge_table(triangles, T, W.keys, W.cnt, W.fmin, W.fmax, W.cap, s);
+    const EdgeTable& E = W.edges;
+    build_edge_table(triangles, T, E, s);
     hipLaunchKernelGGL(flippable_kernel, dim3(nh), dim3(256), 0, s, vertices, (const int32_t*)triangles, T, region, E, min_violation,
                        W.vbits);
     hipLaunchKernelGGL(face_best_kernel<u64>, dim3(nf), dim3(256), 0, s, (const int32_t*)triangles, T, (const u64*)W.vbits, W.best);

@@ -1,6 +1,8 @@
 // radixsort.h -- the stable radix sort of (int32 key, int32 value) pairs and its host driver.  Used by meshmap.hip
 // (contributions by vertex), pointcloud.hip (points by voxel, section 17), grouping.hip (Gaussians by
-// depth, then by cell, section 22) and density.hip (pairs by unit, section 25).  In an unnamed namespace, as cellhash.h: each
+// depth, then by cell, section 22), density.hip (pairs by unit, section 25) and, through meshadj.h, the mesh files (adjacency
+// rows, sections 26.5, 27 and 29).  What a caller must know about the sort lives here too: which of its two pairs holds the
+// result (sorted_names) and the buffers of a shorter sort (sort_for).  In an unnamed namespace, as cellhash.h: each
 // translation unit that includes this header compiles its own copy of the kernels into its own code object.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -110,6 +112,21 @@ inline void radix_sort(int32_t*& ka, int32_t*& va, int32_t*& kb, int32_t*& vb, i
         int32_t* t = ka; ka = kb; kb = t;
         t = va; va = vb; vb = t;
     }
+}
+
+// The same renaming without the sort: where radix_sort left the sorted pair after `passes` passes, for a later call that
+// reads what an earlier one sorted.
+inline void sorted_names(int32_t*& ka, int32_t*& va, int32_t*& kb, int32_t*& vb, int passes) {
+    if (passes & 1) {
+        int32_t* t = ka; ka = kb; kb = t;
+        t = va; va = vb; vb = t;
+    }
+}
+
+// the buffers of a sort of fewer items than `b` was taken for
+inline SortBufs sort_for(SortBufs b, int64_t items) {
+    b.nblk = (items + kTile - 1) / kTile;
+    return b;
 }
 
 }  // namespace

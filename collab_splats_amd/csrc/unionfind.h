@@ -1,6 +1,8 @@
-// unionfind.h -- the lock-free union-find shared by cluster.hip (radius-graph clustering) and
-// meshclean.hip (mesh components and boundary loops, section 18): links always point to a smaller index, so every
-// component's root is its smallest member, whatever the scheduling.
+// unionfind.h -- the lock-free union-find shared by cluster.hip (radius-graph clustering),
+// meshclean.hip (mesh components and boundary loops, section 18) and meshfill.hip (the patches of the free vertices, sections
+// 29 and 31): links always point to a smaller index, so every component's root is its smallest member, whatever the
+// scheduling.  After the uniting part, its read-out: the initial forest, the root walk by plain loads, and the kernel that
+// flattens the trees and counts their members.
 //
 // Everything sits in an unnamed namespace, as in cellhash.h: each translation unit compiles its own copy.
 #pragma once
@@ -56,6 +58,46 @@ __device__ __forceinline__ int32_t unite(int32_t* parent, int32_t a, int32_t b) 
         const int32_t seen = atomicCAS(parent + a, a, b);         // the larger root under the smaller
         if (seen == a) return b;
         a = seen;
+    }
+}
+
+// ----------------------------------------------------------------------------------------------------- read-out
+// (kernels as templates: a file that includes this header and launches none of them gets none in its code object)
+// every vertex its own tree, and the array that goes with it (sizes, flags) cleared
+template <typename Z>
+__global__ __launch_bounds__(256) void uf_init_kernel(int64_t n, int32_t* __restrict__ parent, Z* __restrict__ zero) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    parent[i] = (int32_t)i;
+    zero[i] = 0;
+}
+
+// The root of v's tree in a kernel AFTER the uniting one: past the kernel boundary parent[] is read-only, so plain loads.
+__device__ __forceinline__ int32_t walk_root(const int32_t* __restrict__ parent, int32_t v) {
+    int32_t r = v;
+    for (int32_t p = parent[r]; p != r; p = parent[r]) r = p;
+    return r;
+}
+
+// root[v] = the root of v's tree (MASKED: -1 where mask[v] is 0), and size[root] counts its members: integer adds, one per
+// distinct root among a wave's lanes.
+template <bool MASKED>
+__global__ __launch_bounds__(256) void flatten_kernel(const int32_t* __restrict__ parent, const uint8_t* __restrict__ mask, int64_t n,
+                                                      int32_t* __restrict__ root, int32_t* __restrict__ size) {
+    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    bool pending = v < n && (!MASKED || mask[v]);
+    const int32_t r = pending ? walk_root(parent, (int32_t)v) : -1;
+    if (v < n) root[v] = r;
+    while (true) {
+        const unsigned long long todo = __ballot(pending);
+        if (!todo) break;
+        const int leader = __ffsll((long long)todo) - 1;
+        const int32_t r0 = __shfl(r, leader);
+        const bool same = pending && r == r0;
+        const unsigned long long group = __ballot(same);
+        if (lane == leader) atomicAdd(&size[r0], __popcll(group));
+        if (same) pending = false;
     }
 }
 

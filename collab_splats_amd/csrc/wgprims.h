@@ -1,7 +1,7 @@
 // wgprims.h -- the workgroup primitives the kernel files share: fp64 sums in a fixed order, integer
-// scans, the wave-level helpers of the timed path, the claim loop of the open-addressing hashes, and the host helpers that
-// go with them.  The order of the fp64 sums is a contract: the restatements under tests/ (`_tree256` and its siblings)
-// mirror it, and the results are compared bit for bit.
+// scans and the compaction that follows one, the wave-level helpers of the timed path, the claim loop of the open-addressing
+// hashes, and the host helpers that go with them.  The order of the fp64 sums is a contract: the restatements under tests/
+// (`_tree256` and its siblings) mirror it, and the results are compared bit for bit.
 //
 // Everything sits in an unnamed namespace on purpose: each translation unit that includes this header compiles its own
 // copy into its own code object (the library is built without relocatable device code).
@@ -71,6 +71,16 @@ __device__ __forceinline__ float wave_sum_xor(float v) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
     return v;
+}
+
+// the integer maximum of 64 lanes, xor butterfly: every lane gets it
+__device__ __forceinline__ uint32_t wave_max(uint32_t m) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint32_t o = (uint32_t)__shfl_xor((int)m, off);
+        m = o > m ? o : m;
+    }
+    return m;
 }
 
 // ------------------------------------------------------------------------------------------------------- wave scans
@@ -168,6 +178,15 @@ inline void scan(const T* in, int64_t n, T* out, T* scratch, hipStream_t s) {
                        scratch + 2 * nb);
     hipLaunchKernelGGL(scan_down_kernel<T>, dim3((unsigned)(nb > 0 ? nb : 1)), dim3(kScanBlock), 0, s, in, n,
                        (const T*)(scratch + nb), nb, out);
+}
+
+// Compaction after a scan: list[pos[i]] = i for the flagged i of 0 .. n - 1, pos the exclusive scan of the flags -- the flagged
+// items in ascending order.  cap = the list's length: a caller's wrong count writes nothing beyond it.
+template <typename T>
+__global__ __launch_bounds__(256) void compact_kernel(const T* __restrict__ flag, const T* __restrict__ pos, int64_t n, int64_t cap,
+                                                      T* __restrict__ list) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n && flag[i] && pos[i] < cap) list[pos[i]] = (T)i;
 }
 
 // ------------------------------------------------------------------------------------------------------ hash claim
