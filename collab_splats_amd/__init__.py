@@ -29,6 +29,7 @@ from .textquery import TextQuery, fold_text_queries, gaussian_similarity, simila
 from .poisson import (poisson_grid, poisson_reconstruct, poisson_solve, poisson_splat, poisson_system,  # noqa: F401
                       poisson_trim)
 from .density import DensityField, gaussian_density, gaussian_density_grad, level_surface_points  # noqa: F401
+from .pointtsdf import PointTSDFVolume  # noqa: F401
 from .grouping import FrontGaussians, MemoryBank, convert_matched_mask, front_gaussians, project_gaussians  # noqa: F401
 
 __version__ = "0.1.0"

@@ -165,6 +165,8 @@ SYMBOLS = {
     "misplat_density_count": (C.c_int, 13), "misplat_density_emit": (C.c_int, 14), "misplat_density_lists": (C.c_int, 12),
     "misplat_density_accumulate": (C.c_int, 10), "misplat_density_query": (C.c_int, 15),
     "misplat_density_raycast": (C.c_int, 19),
+    "misplat_ptsdf_workspace": (C.c_int64, 2), "misplat_ptsdf_count": (C.c_int, 11), "misplat_ptsdf_emit": (C.c_int, 12),
+    "misplat_ptsdf_lists": (C.c_int, 12), "misplat_ptsdf_accumulate": (C.c_int, 18), "misplat_ptsdf_finalize": (C.c_int, 8),
     "misplat_version": (C.c_char_p, 0),
 }
 

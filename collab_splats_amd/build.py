@@ -69,6 +69,8 @@ SOURCES = {
     # meshtri.hip: the same: triangle areas and the fp64 sums of the triangulation's table, the cotangents and normals of the flip
     # test equal the restatement (tests/) bit for bit
     "meshtri.hip": ["-ffp-contract=off"],
+    # pointtsdf.hip: the same: the rays' voxel walks and fixed-point sdf terms, hence the integer planes, equal the restatement (tests/)
+    "pointtsdf.hip": ["-ffp-contract=off"],
 }
 
 

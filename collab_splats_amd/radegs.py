@@ -889,6 +889,48 @@ class RadegsModel(nn.Module):
             vertices, triangles, (vcol,), _, _ = simplify_quadric_decimation(vertices, triangles, target_triangles, attributes=(vcol,))
         return vertices, triangles, vcol
 
+    # ------------------------------------------------------------------ point-cloud TSDF with carving
+    @torch.no_grad()
+    def tsdf_points_mesh(self, cameras: Sequence, voxel_size: float = 0.01, sdf_trunc: float = 0.03, depth_name: str = "depth",
+                         rgb_name: str = "rgb", min_weight: int = 5, space_carving: bool = True, masks=None,
+                         target_triangles: Optional[int] = None, batch_size: int = 4, crop_box=None
+                         ) -> Tuple[Tensor, Tensor, Tensor]:
+        """The reference's ``TSDFFusion.main`` (mesh.py:1363-1469) on the device: ``render_views`` ``batch_size`` views at a
+        time, every pixel of ``maps[depth_name]`` back-projected and integrated from its camera's centre into a
+        ``pointtsdf.PointTSDFVolume(voxel_size, sdf_trunc, space_carving)`` (``integrate_depth``, colours ``maps[rgb_name]``),
+        ``extract_mesh(min_weight)`` and, with ``target_triangles``, ``decimate.simplify_quadric_decimation`` (the colours
+        averaged along).  ``masks`` ([V,H,W(,1)] bool, or None): a pixel where False is no ray.  With ``crop_box`` only the
+        Gaussians inside it are rendered and the volume's bounds are the box's AABB padded by ``sdf_trunc``.  Returns
+        ``(vertices [M,3], triangles [T,3] int32, colors [M,3])``: what ``extract_mesh`` returns."""
+        from .pointtsdf import PointTSDFVolume
+        from .tsdf import obb_bounds
+        name = "tsdf_points_mesh"
+        if target_triangles is not None and (not isinstance(target_triangles, int) or isinstance(target_triangles, bool)
+                                             or target_triangles < 0):
+            raise ValueError(f"{name}: target_triangles must be None or a non-negative integer, got {target_triangles!r}")
+        cameras = list(cameras)
+        if masks is not None:
+            masks = torch.as_tensor(masks).to(self.device)
+            if masks.shape[0] != len(cameras):
+                raise ValueError(f"{name}: one mask per camera")
+        vol = PointTSDFVolume(voxel_size, sdf_trunc, space_carving, bounds=obb_bounds(crop_box, sdf_trunc), device=self.device)
+        bs = max(1, int(batch_size))
+        for b in range(0, len(cameras), bs):
+            chunk = cameras[b:b + bs]
+            maps = self.render_views(chunk, batch_size=bs, crop_box=crop_box)
+            for key in (depth_name, rgb_name):
+                if key not in maps:
+                    raise KeyError(f"{name}: {key!r} is not among the rendered maps {sorted(maps)}")
+            c2w, intr = self._camera_poses(chunk, self.device)
+            vol.integrate_depth(maps[depth_name], c2w, intr, rgbs=maps[rgb_name], masks=None if masks is None else masks[b:b + bs])
+            del maps
+        vertices, triangles, colors = vol.extract_mesh(min_weight)
+        if target_triangles is not None and triangles.shape[0] > 0:
+            from .decimate import simplify_quadric_decimation
+            vertices, triangles, (colors,), _, _ = simplify_quadric_decimation(vertices, triangles, target_triangles,
+                                                                              attributes=(colors,))
+        return vertices, triangles, colors
+
     # ------------------------------------------------------------------ level-set surface points (DESIGN.md section 26)
     _NORMAL_MODES = ("analytical", "closest_gaussian", "average")
 

@@ -1119,6 +1119,50 @@ int misplat_density_raycast(const misplat_tsdf_grid* grid, const int32_t* slot_m
                             const float* t1, int64_t n_rays, float level0, float level1, float level2, float level3,
                             int32_t n_levels, float* t_out, uint8_t* hit_out, misplat_stream_t stream);
 
+/* ---- TSDF fusion of point clouds with origins, with space carving (csrc/pointtsdf.hip) ----
+ * What the reference's TSDFFusion asks of vdbfusion's VDBVolume::Integrate, restated (the oracle is
+ * tests/pointtsdf_restatement.py; vdbfusion itself is unpinned).  Lattice, unit map, words and slots are misplat_tsdf's; of the
+ * grid voxel_size, sdf_trunc, lo and dims are read.  points [N,3] fp32; origins [3] (origin_stride 0) or [N,3] (origin_stride
+ * 3).  Per ray o -> p, in fp32 in the order pointtsdf.hip's head states: a voxel walk from floor(o / h) (space_carving) or from
+ * the voxel at L - sdf_trunc to L + sdf_trunc; per visited voxel with sdf > -sdf_trunc: sum_q += rint(min(sdf_trunc, sdf) /
+ * sdf_trunc * 16384), count += 1; where |sdf| < sdf_trunc: rgb_sum += uint8(rgb 255), rgb_count += 1.  Planes per slot: sum_q
+ * [4096] int64, count [4096] int32, rgb_sum [3][4096] int32, rgb_count [4096] int32 (112 KiB a unit), voxel i = lx + 16 ly +
+ * 256 lz, zeroed by the caller when a slot is new.  Integer sums: the planes depend on no order of rays or calls.  A ray with a
+ * non-finite coordinate, zero length or a coordinate at or beyond 2^22 voxels is skipped; a ray is walked only inside the map.
+ * Order of calls per chunk of rays: count (the host reads n_pairs); emit into zeroed words; misplat_tsdf_alloc (the host reads
+ * its counters and grows the planes); lists; accumulate.  Then finalize and misplat_tsdf_mc_* at will. */
+/* workspace bytes that serve count (n_pairs = 0), accumulate (n_rays = its n_touched, n_pairs = 0) or lists (n_rays = 0);
+ * -1 for sizes the library refuses (both < 2^31). */
+int64_t misplat_ptsdf_workspace(int64_t n_rays, int64_t n_pairs);
+/* count: pair_off [N + 1] = the exclusive scan of the units each ray passes inside the map; n_pairs: DEVICE int64, their
+ * number. */
+int misplat_ptsdf_count(const misplat_tsdf_grid* grid, const float* points, const float* origins, int32_t origin_stride,
+                        int64_t n_rays, int32_t space_carving, void* workspace, int64_t workspace_bytes, int32_t* pair_off,
+                        int64_t* n_pairs, misplat_stream_t stream);
+/* emit: keys / ids [n_pairs] = (unit map index, ray) from pair_off[ray] on, in walk order; words[unit] = 1 for every unit
+ * listed. */
+int misplat_ptsdf_emit(const misplat_tsdf_grid* grid, const float* points, const float* origins, int32_t origin_stride,
+                       int64_t n_rays, int32_t space_carving, const int32_t* pair_off, int64_t n_pairs, int32_t* keys, int32_t* ids,
+                       uint64_t* words, misplat_stream_t stream);
+/* lists: the pairs sorted by unit, stable (keys and ids are used as scratch); ranges [n_units, 2]: the part [begin, end) of
+ * ids_sorted of the unit in pool slot s, written for the units listed only. */
+int misplat_ptsdf_lists(const misplat_tsdf_grid* grid, const int32_t* slot_map, int32_t* keys, int32_t* ids, int64_t n_pairs,
+                        int32_t n_units, void* workspace, int64_t workspace_bytes, int32_t* keys_sorted, int32_t* ids_sorted,
+                        int32_t* ranges, misplat_stream_t stream);
+/* accumulate: the n_pairs listed rays into the planes of the n_touched units of touched (misplat_tsdf_alloc's {map index,
+ * slot} pairs), one workgroup per 8192 rays of a unit's list.  colors [N,3] fp32 in [0,1], or NULL (black).  workspace:
+ * misplat_ptsdf_workspace(n_touched, 0) bytes. */
+int misplat_ptsdf_accumulate(const misplat_tsdf_grid* grid, const int32_t* touched, int32_t n_touched, const float* points,
+                             const float* origins, int32_t origin_stride, const float* colors, int32_t space_carving,
+                             const int32_t* ids_sorted, const int32_t* ranges, int64_t n_pairs, void* workspace,
+                             int64_t workspace_bytes, int64_t* sum_q, int32_t* count, int32_t* rgb_sum, int32_t* rgb_count,
+                             misplat_stream_t stream);
+/* finalize: pool [n_units, 5, 4096] fp32 of misplat_tsdf_mc_*: tsdf = (float)((double)sum_q / (double)count) / 16384 (in units
+ * of sdf_trunc; 0 where count = 0), w = count >= min_weight ? count : 0, colours = rgb_sum / rgb_count in 0..255 (0 where
+ * rgb_count = 0). */
+int misplat_ptsdf_finalize(int32_t n_units, const int64_t* sum_q, const int32_t* count, const int32_t* rgb_sum,
+                           const int32_t* rgb_count, int32_t min_weight, float* pool, misplat_stream_t stream);
+
 /* ---- hole patches at the mesh's resolution: subdivision and fairing (csrc/meshfill.hip) ----
  * Restated from the published methods (longest-edge bisection, membrane fairing with the rim fixed); the oracle is
  * tests/meshfill_restatement.py.  vertices [M,3] fp32, triangles [T,3] int32 with every index in 0 .. M - 1.  Integer atomics
