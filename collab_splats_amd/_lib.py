@@ -122,6 +122,7 @@ SYMBOLS = {
     "misplat_rows_pack": (C.c_int, 8), "misplat_rows_unpack": (C.c_int, 8),
     "misplat_debug_memset_replay": (C.c_int, 5),
     "misplat_tsdf_mark": (C.c_int, 10), "misplat_tsdf_alloc": (C.c_int, 6), "misplat_tsdf_integrate": (C.c_int, 14),
+    "misplat_unit_lists": (C.c_int, 12),
     "misplat_tsdf_order": (C.c_int, 5), "misplat_tsdf_mc_count": (C.c_int, 11), "misplat_tsdf_mc_emit": (C.c_int, 13),
     "misplat_meshmap_workspace": (C.c_int64, 4), "misplat_meshmap_knn": (C.c_int, 12),
     "misplat_meshmap_aggregate": (C.c_int, 13),
@@ -162,11 +163,11 @@ SYMBOLS = {
     "misplat_bilagrid_scratch_floats": (C.c_int64, 5), "misplat_bilagrid_slice_fwd": (C.c_int, 9),
     "misplat_bilagrid_slice_bwd": (C.c_int, 14), "misplat_bilagrid_tv_fwd": (C.c_int, 8), "misplat_bilagrid_tv_bwd": (C.c_int, 8),
     "misplat_density_workspace": (C.c_int64, 2), "misplat_density_records": (C.c_int, 9),
-    "misplat_density_count": (C.c_int, 13), "misplat_density_emit": (C.c_int, 14), "misplat_density_lists": (C.c_int, 12),
+    "misplat_density_count": (C.c_int, 13), "misplat_density_emit": (C.c_int, 14),
     "misplat_density_accumulate": (C.c_int, 10), "misplat_density_query": (C.c_int, 15),
     "misplat_density_raycast": (C.c_int, 19),
     "misplat_ptsdf_workspace": (C.c_int64, 2), "misplat_ptsdf_count": (C.c_int, 11), "misplat_ptsdf_emit": (C.c_int, 12),
-    "misplat_ptsdf_lists": (C.c_int, 12), "misplat_ptsdf_accumulate": (C.c_int, 18), "misplat_ptsdf_finalize": (C.c_int, 8),
+    "misplat_ptsdf_accumulate": (C.c_int, 18), "misplat_ptsdf_finalize": (C.c_int, 8),
     "misplat_version": (C.c_char_p, 0),
 }
 

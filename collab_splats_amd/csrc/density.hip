@@ -14,14 +14,12 @@
 //   E_i = r sqrt(sum_a (R[i][a] s_a)^2);  range per axis: units floor(((mu_i - E_i) - h) / L) .. floor(((mu_i + E_i) + h) / L),
 //   clipped to the map;  slab test: keep unit u iff for each a  |e_a . (c - mu)| <= r s_a + H sum_i |R[i][a]|,
 //   c = (u + 0.5) L,  H = 0.5 L + h  (the unit's box widened by one voxel: marching cubes needs all 8 corners of a cell).
-// Pipeline: records -> count + scan -> emit (unit map index, g) in Gaussian order, marking the unit's word -> misplat_tsdf_alloc
-// -> stable radix sort by unit (lists ascending in g) + per-slot ranges -> accumulate.
+// Pipeline: records -> the list layer of unitlists.h (count, emit in Gaussian order, misplat_tsdf_alloc, misplat_unit_lists: the
+// sort being stable, every list is ascending in g) -> accumulate.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "misplat.h"
-#include "wgprims.h"
-#include "radixsort.h"
-#include "unitgrid.h"
+#include "unitlists.h"
 
 namespace {
 
@@ -136,57 +134,26 @@ __device__ __forceinline__ bool slab_keep(const Grid& g, const Geom& G, const Sl
     return keep;
 }
 
-// EMIT = false: counts[g] = pairs of Gaussian g (and the 64-bit total); EMIT = true: the pairs from pair_off[g] on, units in
-// z, y, x order (ascending map index), and the unit's word set
+// One lane per Gaussian: its pairs (PairSink, unitlists.h), units in z, y, x order (ascending map index)
 template <bool EMIT>
 __global__ __launch_bounds__(256) void density_pairs_kernel(Grid g, const float* __restrict__ means, const float* __restrict__ quats,
                                                             const float* __restrict__ scales, const float* __restrict__ opacities,
-                                                            int64_t N, float r, float min_opacity, int32_t* __restrict__ counts,
-                                                            unsigned long long* __restrict__ total,
-                                                            const int32_t* __restrict__ pair_off, int64_t n_pairs,
-                                                            int32_t* __restrict__ keys, int32_t* __restrict__ ids,
-                                                            unsigned long long* __restrict__ words) {
+                                                            int64_t N, float r, float min_opacity, PairBufs bufs) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= N) return;
     Geom G;
     int lo[3], hi[3];
-    int64_t n = 0;
+    PairSink<EMIT> sink(bufs);
     if (gauss_geom(means, quats, scales, opacities, i, r, min_opacity, G) && unit_range(g, G, lo, hi)) {
         const Slabs S = slab_bounds(g, G, r);
-        int64_t pos = EMIT ? (int64_t)pair_off[i] : 0;
+        sink.open(i);
         for (int uz = lo[2]; uz <= hi[2]; uz++)
             for (int uy = lo[1]; uy <= hi[1]; uy++)
-                for (int ux = lo[0]; ux <= hi[0]; ux++) {
-                    if (!slab_keep(g, G, S, ux, uy, uz)) continue;
-                    if (EMIT) {
-                        const int64_t m = map_index(g, ux, uy, uz);     // (inside the map: the range is clipped to it)
-                        if (pos + n < n_pairs) {           // (always: the offsets are the scan of the same test's counts)
-                            keys[pos + n] = (int32_t)m;
-                            ids[pos + n] = (int32_t)i;
-                        }
-                        words[m] = 1ull;                   // (every writer stores the same value)
-                    }
-                    n++;
-                }
+                for (int ux = lo[0]; ux <= hi[0]; ux++)
+                    if (slab_keep(g, G, S, ux, uy, uz))
+                        sink.add(EMIT ? map_index(g, ux, uy, uz) : 0, i);   // (inside the map: the range is clipped to it)
     }
-    if (!EMIT) {
-        counts[i] = (int32_t)(n < 0x7fffffffll ? n : 0x7fffffffll);
-        if (n) atomicAdd(total, (unsigned long long)n);
-    }
-}
-
-// ranges[2 slot], ranges[2 slot + 1] = the unit's part of the sorted pairs
-__global__ __launch_bounds__(256) void density_ranges_kernel(const int32_t* __restrict__ keys, int64_t E,
-                                                             const int32_t* __restrict__ slot_map, int32_t* __restrict__ ranges) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= E) return;
-    const int32_t k = keys[e];
-    const bool first = e == 0 || keys[e - 1] != k, last = e == E - 1 || keys[e + 1] != k;
-    if (!first && !last) return;
-    const int32_t s = slot_map[k];
-    if (s < 0) return;                                     // (never: emit marked the unit and alloc gave it a slot)
-    if (first) ranges[2 * s] = (int32_t)e;
-    if (last) ranges[2 * s + 1] = (int32_t)(e + 1);
+    sink.finish(i);
 }
 
 // ---------------------------------------------------------------------------------------------------------- accumulate
@@ -439,38 +406,9 @@ __global__ __launch_bounds__(256) void density_raycast_kernel(Grid g, const int3
     }
 }
 
-// ----------------------------------------------------------------------------------------------------------- workspace
-// N Gaussians (misplat_density_count) and E pairs (misplat_density_lists): either may be 0 for the call that does not use it
-struct Work {
-    int32_t *counts, *scr;
-    unsigned long long* total;
-    int32_t *kb, *vb;                 // (not used: the sort runs between the caller's two pairs)
-    SortBufs sort;
-};
-inline Work carve(Carver& c, int64_t N, int64_t E) {
-    Work W;
-    const int64_t n_hist = 256 * ((E + kTile - 1) / kTile);
-    W.counts = c.take<int32_t>(N + 1);
-    W.scr = take_scan(c, (N > n_hist ? N : n_hist) + 1);
-    W.total = c.take<unsigned long long>(1);
-    W.kb = c.take<int32_t>(E);
-    W.vb = c.take<int32_t>(E);
-    W.sort = take_sort(c, E);
-    return W;
-}
-inline bool sizes_ok(int64_t N, int64_t E) { return N >= 0 && N < (1ll << 31) && E >= 0 && E < (1ll << 31) - kTile; }
-
-__global__ void density_clear_total_kernel(unsigned long long* total) { *total = 0ull; }
-__global__ void density_copy_total_kernel(const unsigned long long* total, int64_t* out) { *out = (int64_t)*total; }
-
 }  // namespace
 
-extern "C" int64_t misplat_density_workspace(int64_t n_gauss, int64_t n_pairs) {
-    if (!sizes_ok(n_gauss, n_pairs)) return -1;
-    Carver c{nullptr};
-    carve(c, n_gauss, n_pairs);
-    return c.o;
-}
+extern "C" int64_t misplat_density_workspace(int64_t n_gauss, int64_t n_pairs) { return work_bytes(n_gauss, n_pairs); }
 
 extern "C" int misplat_density_records(const float* means, const float* quats, const float* scales, const float* opacities,
                                        int64_t n_gauss, float cutoff, float min_opacity, float* records,
@@ -495,12 +433,10 @@ extern "C" int misplat_density_count(const misplat_tsdf_grid* grid, const float*
     const Work W = carve(c, n_gauss, 0);
     if (workspace_bytes < c.o) return MISPLAT_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(density_clear_total_kernel, dim3(1), dim3(1), 0, s, W.total);
-    hipLaunchKernelGGL(density_pairs_kernel<false>, dim3(blocks(n_gauss, 256)), dim3(256), 0, s, g, means, quats, scales, opacities,
-                       n_gauss, cutoff, min_opacity, W.counts, W.total, (const int32_t*)nullptr, (int64_t)0, (int32_t*)nullptr,
-                       (int32_t*)nullptr, (unsigned long long*)nullptr);
-    scan(W.counts, n_gauss, pair_off, W.scr, s);
-    hipLaunchKernelGGL(density_copy_total_kernel, dim3(1), dim3(1), 0, s, (const unsigned long long*)W.total, n_pairs);
+    count_pairs(W, n_gauss, pair_off, n_pairs, s, [&](PairBufs bufs) {
+        hipLaunchKernelGGL(density_pairs_kernel<false>, dim3(blocks(n_gauss, 256)), dim3(256), 0, s, g, means, quats, scales,
+                           opacities, n_gauss, cutoff, min_opacity, bufs);
+    });
     return launched();
 }
 
@@ -514,32 +450,25 @@ extern "C" int misplat_density_emit(const misplat_tsdf_grid* grid, const float* 
         !(min_opacity == min_opacity) || !means || !quats || !scales || !opacities || !pair_off || !keys || !ids || !words)
         return MISPLAT_EINVAL;
     hipLaunchKernelGGL(density_pairs_kernel<true>, dim3(blocks(n_gauss, 256)), dim3(256), 0, (hipStream_t)stream, g, means, quats,
-                       scales, opacities, n_gauss, cutoff, min_opacity, (int32_t*)nullptr, (unsigned long long*)nullptr, pair_off,
-                       n_pairs, keys, ids, (unsigned long long*)words);
+                       scales, opacities, n_gauss, cutoff, min_opacity,
+                       PairBufs{nullptr, nullptr, pair_off, n_pairs, keys, ids, (unsigned long long*)words});
     return launched();
 }
 
-extern "C" int misplat_density_lists(const misplat_tsdf_grid* grid, const int32_t* slot_map, int32_t* keys, int32_t* ids,
-                                     int64_t n_pairs, int32_t n_units, void* workspace, int64_t workspace_bytes,
-                                     int32_t* keys_sorted, int32_t* ids_sorted, int32_t* ranges, misplat_stream_t stream) {
-    Grid g;
+// The list layer's sort and ranges (unitlists.h), exported once, for this file's pairs and pointtsdf.hip's (DESIGN.md section
+// 14.5 says why here).  Of the grid only voxel_size, lo and dims are read.
+extern "C" int misplat_unit_lists(const misplat_tsdf_grid* grid, const int32_t* slot_map, int32_t* keys, int32_t* ids,
+                                  int64_t n_pairs, int32_t n_units, void* workspace, int64_t workspace_bytes, int32_t* keys_sorted,
+                                  int32_t* ids_sorted, int32_t* ranges, misplat_stream_t stream) {
+    UnitGrid g;
     int64_t n_map;
-    const int64_t E = n_pairs;
-    if (!make_grid(grid, g, n_map) || !sizes_ok(0, E) || E < 1 || n_units < 1 || n_units > n_map || !slot_map || !keys || !ids ||
-        !workspace || !keys_sorted || !ids_sorted || !ranges)
+    if (!make_unit_grid(grid, g, n_map) || !(grid->voxel_size < 1e30f) || !sizes_ok(0, n_pairs) || n_pairs < 1 || n_units < 1 ||
+        n_units > n_map || !slot_map || !keys || !ids || !workspace || !keys_sorted || !ids_sorted || !ranges)
         return MISPLAT_EINVAL;
     Carver c{(char*)workspace};
-    const Work W = carve(c, 0, E);
+    const Work W = carve(c, 0, n_pairs);
     if (workspace_bytes < c.o) return MISPLAT_EWORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    // passes over the bits of the largest map index; one more over zero digits (the identity, the sort being stable) where
-    // that makes their number odd: the result then lies in keys_sorted / ids_sorted.  (A fifth pass repeats the top byte:
-    // the identity again.)
-    int passes = radix_passes(n_map - 1);
-    if (passes % 2 == 0) passes++;
-    int32_t *ka = keys, *va = ids, *kb = keys_sorted, *vb = ids_sorted;
-    radix_sort(ka, va, kb, vb, E, passes, W.sort, W.scr, s);
-    hipLaunchKernelGGL(density_ranges_kernel, dim3(blocks(E, 256)), dim3(256), 0, s, (const int32_t*)keys_sorted, E, slot_map, ranges);
+    unit_lists(n_map, slot_map, keys, ids, n_pairs, keys_sorted, ids_sorted, ranges, W, (hipStream_t)stream);
     return launched();
 }
 

@@ -13,14 +13,12 @@
 // Voxel with centre c = ((float)g + 0.5f) h: sdf = +-sqrtf(|p - c|^2), + iff ((c - o) . (p - c)) >= 0 (sums as above);
 // where sdf > -trunc: sum_q += (int)rintf((fminf(trunc, sdf) / trunc) * 16384.f), count += 1; where |sdf| < trunc the
 // colour sums take uint8(rgb 255) and the band count 1.  Integer sums: the result depends on no order.
-// Pipeline per chunk of rays: count + scan -> emit (unit map index, ray) pairs, marking the unit's word -> misplat_tsdf_alloc
-// -> stable radix sort by unit + per-slot ranges -> accumulate, one workgroup per piece of a touched unit's list.
+// Pipeline per chunk of rays: the list layer of unitlists.h (count, emit, misplat_tsdf_alloc, misplat_unit_lists) ->
+// accumulate, one workgroup per piece of a touched unit's list.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "misplat.h"
-#include "wgprims.h"
-#include "radixsort.h"
-#include "unitgrid.h"
+#include "unitlists.h"
 
 namespace {
 
@@ -179,61 +177,31 @@ __device__ __forceinline__ int to_u8(float x) {          // uint8(rgb * 255) wit
 
 // ------------------------------------------------------------------------------------------------------------- pairs
 // One lane per ray: the voxel walk inside the unit map, reduced to the units it passes (each once: the walk is monotone per
-// axis).  EMIT = false: counts[i] = units of ray i (and the 64-bit total); EMIT = true: the pairs from pair_off[i] on, in walk
-// order, and the unit's word set.
+// axis), handed to the PairSink (unitlists.h) in walk order.
 template <bool EMIT>
 __global__ __launch_bounds__(256) void ptsdf_pairs_kernel(Grid g, const float* __restrict__ points, const float* __restrict__ origins,
-                                                          int ostride, int64_t N, int32_t* __restrict__ counts,
-                                                          unsigned long long* __restrict__ total,
-                                                          const int32_t* __restrict__ pair_off, int64_t n_pairs,
-                                                          int32_t* __restrict__ keys, int32_t* __restrict__ ids,
-                                                          unsigned long long* __restrict__ words) {
+                                                          int ostride, int64_t N, PairBufs bufs) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= N) return;
     Ray R;
-    int64_t n = 0;
+    PairSink<EMIT> sink(bufs);
     if (make_ray(g, points, origins, ostride, i, R)) {
         const int blo[3] = {g.lo[0] * 16, g.lo[1] * 16, g.lo[2] * 16};
         const int bhi[3] = {(g.lo[0] + g.dims[0]) * 16 - 1, (g.lo[1] + g.dims[1]) * 16 - 1, (g.lo[2] + g.dims[2]) * 16 - 1};
         int ex, ey, ez;
         if (enter_box(R, blo, bhi, ex, ey, ez)) {
-            const int64_t pos = EMIT ? (int64_t)pair_off[i] : 0;
+            sink.open(i);
             int lx = 0, ly = 0, lz = 0;
             bool have = false;
             walk_box(R, ex, ey, ez, blo, bhi, [&](int gx, int gy, int gz) {
                 const int ux = gx >> 4, uy = gy >> 4, uz = gz >> 4;
                 if (have && ux == lx && uy == ly && uz == lz) return;
                 have = true; lx = ux; ly = uy; lz = uz;
-                if (EMIT) {
-                    const int64_t m = map_index(g, ux, uy, uz);         // (inside the map: the walk is confined to it)
-                    if (m >= 0 && pos + n < n_pairs) {                  // (always: the offsets are the scan of this walk's counts)
-                        keys[pos + n] = (int32_t)m;
-                        ids[pos + n] = (int32_t)i;
-                        words[m] = 1ull;                                // (every writer stores the same value)
-                    }
-                }
-                n++;
+                sink.add(EMIT ? map_index(g, ux, uy, uz) : 0, i);       // (inside the map: the walk is confined to it)
             });
         }
     }
-    if (!EMIT) {
-        counts[i] = (int32_t)(n < 0x7fffffffll ? n : 0x7fffffffll);
-        if (n) atomicAdd(total, (unsigned long long)n);
-    }
-}
-
-// ranges[2 slot], ranges[2 slot + 1] = the unit's part of the sorted pairs
-__global__ __launch_bounds__(256) void ptsdf_ranges_kernel(const int32_t* __restrict__ keys, int64_t E,
-                                                           const int32_t* __restrict__ slot_map, int32_t* __restrict__ ranges) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= E) return;
-    const int32_t k = keys[e];
-    const bool first = e == 0 || keys[e - 1] != k, last = e == E - 1 || keys[e + 1] != k;
-    if (!first && !last) return;
-    const int32_t s = slot_map[k];
-    if (s < 0) return;                                     // (never: emit marked the unit and alloc gave it a slot)
-    if (first) ranges[2 * s] = (int32_t)e;
-    if (last) ranges[2 * s + 1] = (int32_t)(e + 1);
+    sink.finish(i);
 }
 
 // -------------------------------------------------------------------------------------------------------- accumulate
@@ -344,38 +312,12 @@ __global__ __launch_bounds__(256) void ptsdf_finalize_kernel(int64_t n, const lo
         pool[pool_index(slot, 2 + k, i)] = bc > 0 ? (float)((double)rgb_sum[(3 * slot + k) * kUnitVoxels + i] / (double)bc) : 0.f;
 }
 
-// ----------------------------------------------------------------------------------------------------------- workspace
-// N rays (misplat_ptsdf_count; for misplat_ptsdf_accumulate N touched units) and E pairs (misplat_ptsdf_lists): either may be
-// 0 for the call that does not use it
-struct Work {
-    int32_t *counts, *offs, *scr;
-    unsigned long long* total;
-    SortBufs sort;
-};
-inline Work carve(Carver& c, int64_t N, int64_t E) {
-    Work W;
-    const int64_t n_hist = 256 * ((E + kTile - 1) / kTile);
-    W.counts = c.take<int32_t>(N + 1);
-    W.offs = c.take<int32_t>(N + 1);
-    W.scr = take_scan(c, (N > n_hist ? N : n_hist) + 1);
-    W.total = c.take<unsigned long long>(1);
-    W.sort = take_sort(c, E);
-    return W;
-}
-inline bool sizes_ok(int64_t N, int64_t E) { return N >= 0 && N < (1ll << 31) && E >= 0 && E < (1ll << 31) - kTile; }
 inline bool stride_ok(int32_t s) { return s == 0 || s == 3; }
-
-__global__ void ptsdf_clear_total_kernel(unsigned long long* total) { *total = 0ull; }
-__global__ void ptsdf_copy_total_kernel(const unsigned long long* total, int64_t* out) { *out = (int64_t)*total; }
 
 }  // namespace
 
-extern "C" int64_t misplat_ptsdf_workspace(int64_t n_rays, int64_t n_pairs) {
-    if (!sizes_ok(n_rays, n_pairs)) return -1;
-    Carver c{nullptr};
-    carve(c, n_rays, n_pairs);
-    return c.o;
-}
+// (unitlists.h's workspace: N rays for count, N touched units for accumulate's piece scan)
+extern "C" int64_t misplat_ptsdf_workspace(int64_t n_rays, int64_t n_pairs) { return work_bytes(n_rays, n_pairs); }
 
 extern "C" int misplat_ptsdf_count(const misplat_tsdf_grid* grid, const float* points, const float* origins, int32_t origin_stride,
                                    int64_t n_rays, int32_t space_carving, void* workspace, int64_t workspace_bytes,
@@ -389,12 +331,10 @@ extern "C" int misplat_ptsdf_count(const misplat_tsdf_grid* grid, const float* p
     const Work W = carve(c, n_rays, 0);
     if (workspace_bytes < c.o) return MISPLAT_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(ptsdf_clear_total_kernel, dim3(1), dim3(1), 0, s, W.total);
-    hipLaunchKernelGGL(ptsdf_pairs_kernel<false>, dim3(blocks(n_rays, 256)), dim3(256), 0, s, g, points, origins, (int)origin_stride,
-                       n_rays, W.counts, W.total, (const int32_t*)nullptr, (int64_t)0, (int32_t*)nullptr, (int32_t*)nullptr,
-                       (unsigned long long*)nullptr);
-    scan(W.counts, n_rays, pair_off, W.scr, s);
-    hipLaunchKernelGGL(ptsdf_copy_total_kernel, dim3(1), dim3(1), 0, s, (const unsigned long long*)W.total, n_pairs);
+    count_pairs(W, n_rays, pair_off, n_pairs, s, [&](PairBufs bufs) {
+        hipLaunchKernelGGL(ptsdf_pairs_kernel<false>, dim3(blocks(n_rays, 256)), dim3(256), 0, s, g, points, origins,
+                           (int)origin_stride, n_rays, bufs);
+    });
     return launched();
 }
 
@@ -407,31 +347,7 @@ extern "C" int misplat_ptsdf_emit(const misplat_tsdf_grid* grid, const float* po
         !stride_ok(origin_stride) || !points || !origins || !pair_off || !keys || !ids || !words)
         return MISPLAT_EINVAL;
     hipLaunchKernelGGL(ptsdf_pairs_kernel<true>, dim3(blocks(n_rays, 256)), dim3(256), 0, (hipStream_t)stream, g, points, origins,
-                       (int)origin_stride, n_rays, (int32_t*)nullptr, (unsigned long long*)nullptr, pair_off, n_pairs, keys, ids,
-                       (unsigned long long*)words);
-    return launched();
-}
-
-extern "C" int misplat_ptsdf_lists(const misplat_tsdf_grid* grid, const int32_t* slot_map, int32_t* keys, int32_t* ids,
-                                   int64_t n_pairs, int32_t n_units, void* workspace, int64_t workspace_bytes,
-                                   int32_t* keys_sorted, int32_t* ids_sorted, int32_t* ranges, misplat_stream_t stream) {
-    Grid g;
-    int64_t n_map;
-    const int64_t E = n_pairs;
-    if (!make_grid(grid, 0, g, n_map) || !sizes_ok(0, E) || E < 1 || n_units < 1 || n_units > n_map || !slot_map || !keys || !ids ||
-        !workspace || !keys_sorted || !ids_sorted || !ranges)
-        return MISPLAT_EINVAL;
-    Carver c{(char*)workspace};
-    const Work W = carve(c, 0, E);
-    if (workspace_bytes < c.o) return MISPLAT_EWORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    // an odd number of passes (one more over zero digits, the identity, where needed): the result lies in the caller's
-    // second pair, as in density.hip
-    int passes = radix_passes(n_map - 1);
-    if (passes % 2 == 0) passes++;
-    int32_t *ka = keys, *va = ids, *kb = keys_sorted, *vb = ids_sorted;
-    radix_sort(ka, va, kb, vb, E, passes, W.sort, W.scr, s);
-    hipLaunchKernelGGL(ptsdf_ranges_kernel, dim3(blocks(E, 256)), dim3(256), 0, s, (const int32_t*)keys_sorted, E, slot_map, ranges);
+                       (int)origin_stride, n_rays, PairBufs{nullptr, nullptr, pair_off, n_pairs, keys, ids, (unsigned long long*)words});
     return launched();
 }
 

@@ -1,7 +1,8 @@
 // radixsort.h -- the stable radix sort of (int32 key, int32 value) pairs and its host driver.  Used by meshmap.hip
 // (contributions by vertex), pointcloud.hip (points by voxel, section 17), grouping.hip (Gaussians by
-// depth, then by cell, section 22), density.hip (pairs by unit, section 25) and, through meshadj.h, the mesh files (adjacency
-// rows, sections 26.5, 27 and 29).  What a caller must know about the sort lives here too: which of its two pairs holds the
+// depth, then by cell, section 22), through unitlists.h the unit lists of density.hip and pointtsdf.hip (pairs by unit, sorted in
+// density.hip's misplat_unit_lists; sections 14.5, 25 and 32) and, through meshadj.h, the mesh files (adjacency rows, sections
+// 26.5, 27 and 29).  What a caller must know about the sort lives here too: which of its two pairs holds the
 // result (sorted_names) and the buffers of a shorter sort (sort_for).  In an unnamed namespace, as cellhash.h: each
 // translation unit that includes this header compiles its own copy of the kernels into its own code object.
 #pragma once

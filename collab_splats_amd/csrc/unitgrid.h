@@ -1,4 +1,4 @@
-// unitgrid.h -- the sparse unit volume that tsdf.hip, density.hip and poisson.hip share.
+// unitgrid.h -- the sparse unit volume that tsdf.hip, density.hip, pointtsdf.hip and poisson.hip share.
 //
 // Units of 16^3 voxels; voxel g (global integer coordinate) has its centre at (g + 0.5) * voxel_size.  A DENSE unit map over the
 // grid's bounds (lo, dims, x fastest) holds per unit the pool slot (int32, -1 = unallocated).  The pool holds per slot kPlanes

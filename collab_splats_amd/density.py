@@ -18,7 +18,6 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import time
 from typing import Dict, Optional, Tuple
 
 import numpy as np
@@ -27,7 +26,8 @@ from torch import Tensor
 
 from ._lib import MisplatError, check, load, ptr, require_gpu, stream_ptr
 from .meshmap import _prep
-from .unitvolume import MAX_UNITS, UNIT, UNIT_VOXELS, Grid, _unit_range, make_grid, map_span, marching_cubes, unit_coords
+from .unitvolume import (MAX_UNITS, UNIT, UNIT_VOXELS, Grid, Stages, _unit_range, alloc_units, empty_mesh, make_grid, map_order,
+                         map_span, marching_cubes, unit_coords, unit_lists)
 
 REC = 16                             # floats per record (include/misplat.h MISPLAT_DENSITY_REC)
 MAX_CHANNELS = 16                    # channels of query's values (MISPLAT_DENSITY_MAX_CHANNELS)
@@ -118,23 +118,6 @@ def _levels(name: str, levels) -> Tuple[float, ...]:
     return lv
 
 
-class _Stages:
-    """Seconds per build stage into a dict, each stage synchronised; nothing at all without a dict."""
-
-    def __init__(self, out: Optional[dict]):
-        self.out = out
-        if out is not None:
-            torch.cuda.synchronize()
-            self.t = time.perf_counter()
-
-    def __call__(self, stage: str) -> None:
-        if self.out is not None:
-            torch.cuda.synchronize()
-            now = time.perf_counter()
-            self.out[stage] = now - self.t
-            self.t = now
-
-
 class DensityField:
     """The mixture's density on the lattice of voxel size ``voxel_size``.
 
@@ -172,7 +155,7 @@ class DensityField:
             return
         lib = load()
         dev = self.device
-        mark = _Stages(_timings)                                # (scripts/density_bench.py: seconds per stage, synchronised)
+        mark = Stages(_timings)                                # (scripts/density_bench.py: seconds per stage, synchronised)
         mu, q, s, o = _prep(means), _prep(quats), _prep(scales), _prep(opacities)
         cr, cmo = C.c_float(r), C.c_float(mo)
         check(lib.misplat_density_records(ptr(mu), ptr(q), ptr(s), ptr(o), C.c_int64(self.n_gauss), cr, cmo, ptr(self._records),
@@ -215,21 +198,12 @@ class DensityField:
                                        ptr(ids), ptr(words), stream_ptr()), "misplat_density_emit")
         counters = torch.zeros(2, dtype=torch.int32, device=dev)
         touched = torch.empty(2 * min(n_map, n_pairs), dtype=torch.int32, device=dev)
-        tgrid = self._grid()
-        check(lib.misplat_tsdf_alloc(C.byref(tgrid), ptr(words), ptr(self._slot_map), ptr(counters), ptr(touched), stream_ptr()),
-              "misplat_tsdf_alloc")
-        n_units = int(counters[0].item())                                            # host read: the pool's size
+        n_units, _ = alloc_units(grid, words, self._slot_map, counters, touched)    # host read: the pool's size
         del words
         mark("emit_alloc")
-        ws = torch.empty(int(lib.misplat_density_workspace(C.c_int64(0), E)), dtype=torch.uint8, device=dev)
-        keys_sorted = torch.empty(n_pairs, dtype=torch.int32, device=dev)
-        self._ids = torch.empty(n_pairs, dtype=torch.int32, device=dev)
-        self._ranges = torch.zeros((n_units, 2), dtype=torch.int32, device=dev)
-        check(lib.misplat_density_lists(C.byref(grid), ptr(self._slot_map), ptr(keys), ptr(ids), E, n_units, ptr(ws),
-                                        C.c_int64(ws.numel()), ptr(keys_sorted), ptr(self._ids), ptr(self._ranges), stream_ptr()),
-              "misplat_density_lists")
+        self._ids, self._ranges = unit_lists(grid, self._slot_map, keys, ids, n_pairs, n_units)
         mark("lists")
-        del keys, ids, keys_sorted, ws
+        del keys, ids, ws
         self._touched = touched
         self._pool = torch.empty((n_units, 5, UNIT_VOXELS), dtype=torch.float32, device=dev)
         check(lib.misplat_density_accumulate(C.byref(grid), ptr(touched), n_units, ptr(self._records), ptr(self._ids),
@@ -244,7 +218,7 @@ class DensityField:
         return make_grid(self.voxel_size, self.voxel_size, 1.0, self.lo, self.dims)
 
     def _map_order(self) -> Tensor:
-        return torch.nonzero(self._slot_map >= 0).squeeze(1)
+        return map_order(self._slot_map)
 
     # -------------------------------------------------------------------------------------------------------------- public
     def units(self):
@@ -344,16 +318,19 @@ class DensityField:
         require_gpu(values)
         dev = self.device
         D = None if values is None else int(values.shape[1])
-        empty = (torch.zeros((0, 3), dtype=torch.float32, device=dev), torch.zeros((0, 3), dtype=torch.int32, device=dev),
-                 None if D is None else torch.zeros((0, D), dtype=torch.float32, device=dev))
+
+        def empty():                                               # (the empty mesh, values in place of its colours)
+            v, t, _ = empty_mesh(dev)
+            return v, t, None if D is None else torch.zeros((0, D), dtype=torch.float32, device=dev)
+
         if self.n_units == 0:
-            return empty
+            return empty()
         work = self._pool.clone()                                  # (the extraction takes 5 planes: DESIGN.md section 25)
         torch.sub(iso, self._pool[:, 0], out=work[:, 0])
         mesh = marching_cubes(self._grid(), self._slot_map, self.n_units, work)
         del work
         if mesh is None:
-            return empty
+            return empty()
         vertices, triangles = mesh[:2]                             # (the pool carries no colour)
         del mesh
         return vertices, triangles, None if values is None else self.query(vertices, values)["values"]

@@ -20,7 +20,8 @@ from torch import Tensor
 from ._lib import MisplatError, check, load, ptr, require_gpu, stream_ptr
 from .depthcloud import _backproject, _cameras, _depth, _flag, _map3
 from .meshmap import _prep
-from .unitvolume import MAX_UNITS, UNIT, UNIT_VOXELS, Grid, _unit_range, make_grid, map_span, marching_cubes, unit_coords
+from .unitvolume import (MAX_UNITS, UNIT_VOXELS, Grid, GrowingVolume, Stages, _unit_range, empty_mesh, make_grid, marching_cubes,
+                         unit_coords, unit_lists)
 
 CHUNK_RAYS = 1 << 20                 # rays per kernel chunk: their (unit, ray) pairs stay far below the sort's 2^31
 MAX_PAIRS = (1 << 31) - 4096
@@ -28,7 +29,7 @@ MAX_COORD = float(1 << 22)           # voxels from the origin beyond which a ray
 UNIT_BYTES = UNIT_VOXELS * (8 + 4 + 12 + 4)   # sum_q int64, count int32, rgb_sum 3 x int32, rgb_count int32
 
 
-class PointTSDFVolume:
+class PointTSDFVolume(GrowingVolume):
     """A TSDF volume fed with points and their origins.
 
     ``voxel_size`` / ``sdf_trunc`` / ``space_carving`` as vdbfusion's ``VDBVolume``.  ``bounds`` (optional, ``[[xmin, ymin,
@@ -36,61 +37,27 @@ class PointTSDFVolume:
     The dense unit map covers the points (padded by ``sdf_trunc`` and a voxel) and, with carving, the origins; it grows from
     call to call; more than ``max_units`` map entries raise ``MisplatError``.  A unit holds 112 KiB of integer planes."""
 
+    _name, _what, _advice = "PointTSDFVolume", "the points and origins", "pass bounds= or a larger voxel_size"
+
     def __init__(self, voxel_size: float, sdf_trunc: float, space_carving: bool = True, bounds=None, device=None,
                  max_units: int = MAX_UNITS):
         if not (voxel_size > 0 and sdf_trunc > 0 and np.isfinite(voxel_size) and np.isfinite(sdf_trunc)):
             raise ValueError(f"PointTSDFVolume: voxel_size and sdf_trunc must be finite and positive, got {voxel_size!r} and "
                              f"{sdf_trunc!r}")
-        self.device = torch.device(device) if device is not None else torch.device("cuda")
-        if self.device.type != "cuda":
-            raise MisplatError("PointTSDFVolume runs on the MI355X only: there is no CPU fallback")
-        self.voxel_size, self.sdf_trunc, self.space_carving = float(voxel_size), float(sdf_trunc), bool(space_carving)
-        self.ulen = float(np.float32(self.voxel_size) * np.float32(UNIT))
-        self.max_units = min(int(max_units), MAX_UNITS)
-        self.clip = None
+        super().__init__(voxel_size, device, max_units)
+        self.sdf_trunc, self.space_carving = float(sdf_trunc), bool(space_carving)
         if bounds is not None:
             b = np.asarray(bounds.detach().cpu() if isinstance(bounds, Tensor) else bounds, np.float64)
             if b.shape != (2, 3) or not np.all(np.isfinite(b)) or not np.all(b[1] >= b[0]):
                 raise ValueError("PointTSDFVolume: bounds must be finite [[min xyz], [max xyz]] with max >= min")
             self.clip = _unit_range(b[0], b[1], self.ulen)
-        self.lo = self.dims = None                 # unit map (none before the first integrate)
-        self.n_units = 0                           # allocated units (= slots in use)
         self.n_rays = 0                            # rays handed to integrate
         self.n_pairs = 0                           # (unit, ray) pairs so far
         self._sum_q = self._count = self._rgb_sum = self._rgb_count = None
-        self._counters = None                      # device {allocated slots, touched units of the chunk}
 
     # ------------------------------------------------------------------------------------------------------------ plumbing
     def _grid(self) -> Grid:
         return make_grid(self.voxel_size, self.sdf_trunc, 1.0, self.lo, self.dims)      # (depth_trunc: unused, positive)
-
-    def _cover(self, lo: np.ndarray, hi: np.ndarray) -> bool:
-        """Make the unit map cover units lo..hi (inclusive, clipped to the bounds), as ``TSDFVolume._cover``; False if there is
-        no map."""
-        if self.clip is not None:
-            lo, hi = np.maximum(lo, self.clip[0]), np.minimum(hi, self.clip[1])
-        if np.any(hi < lo):
-            return self.lo is not None
-        if self.lo is not None:
-            old_hi = self.lo + self.dims - 1
-            if np.all(lo >= self.lo) and np.all(hi <= old_hi):
-                return True
-            lo, hi = np.minimum(lo, self.lo), np.maximum(hi, old_hi)
-        dims, n = map_span("PointTSDFVolume", "the points and origins", lo, hi, self.max_units,
-                           "pass bounds= or a larger voxel_size")
-        slot_map = torch.full((n,), -1, dtype=torch.int32, device=self.device)
-        if self.n_units:                           # re-linearise the allocated units into the grown map
-            m = torch.nonzero(self._slot_map >= 0).squeeze(1)
-            nx, ny = int(self.dims[0]), int(self.dims[1])
-            cx, cy, cz = m % nx, (m // nx) % ny, m // (nx * ny)
-            o = self.lo - lo
-            lin = (cx + int(o[0])) + int(dims[0]) * ((cy + int(o[1])) + int(dims[1]) * (cz + int(o[2])))
-            slot_map[lin] = self._slot_map[m]
-        self.lo, self.dims = lo.astype(np.int64), dims.astype(np.int64)
-        self._slot_map = slot_map
-        self._words = torch.zeros(n, dtype=torch.int64, device=self.device)
-        self._touched = torch.empty(2 * n, dtype=torch.int32, device=self.device)
-        return True
 
     def _box_units(self, points: Tensor, origins: Tensor) -> Optional[Tuple[np.ndarray, np.ndarray]]:
         """Units overlapping the box of the rays that can take part (one host read); None if there is none."""
@@ -142,10 +109,7 @@ class PointTSDFVolume:
             raise ValueError(f"{name}: colors must be a floating-point tensor [{P},3] or None, got "
                              f"{tuple(colors.shape) if isinstance(colors, Tensor) else type(colors).__name__}")
         require_gpu(points, origin, colors)
-        if points.device != self.device and self.device.index is not None:
-            raise MisplatError(f"PointTSDFVolume on {self.device} got tensors on {points.device}")
-        if self.device.index is None:
-            self.device = points.device
+        self._adopt_device(points)
         self.n_rays += P
         if P == 0:
             return
@@ -159,9 +123,7 @@ class PointTSDFVolume:
         grid = self._grid()
         g = C.byref(grid)
         carve = int(self.space_carving)
-        if self._counters is None:
-            self._counters = torch.zeros(2, dtype=torch.int32, device=dev)
-        mark = _Stages(_timings)
+        mark = Stages(_timings)
         for c0 in range(0, P, CHUNK_RAYS):
             n = min(CHUNK_RAYS, P - c0)
             p, o = p32[c0:c0 + n], (o32[c0:c0 + n] if per_point else o32)
@@ -182,22 +144,14 @@ class PointTSDFVolume:
             E = C.c_int64(n_pairs)
             keys = torch.empty(n_pairs, dtype=torch.int32, device=dev)
             ids = torch.empty(n_pairs, dtype=torch.int32, device=dev)
-            self._words.zero_()
-            self._counters[1:].zero_()
+            self._begin_batch()
             check(lib.misplat_ptsdf_emit(g, ptr(p), ptr(o), stride, N, carve, ptr(pair_off), E, ptr(keys), ptr(ids),
                                          ptr(self._words), stream_ptr()), "misplat_ptsdf_emit")
-            check(lib.misplat_tsdf_alloc(g, ptr(self._words), ptr(self._slot_map), ptr(self._counters), ptr(self._touched),
-                                         stream_ptr()), "misplat_tsdf_alloc")
-            n_units, n_touched = (int(x) for x in self._counters.tolist())           # host read
+            n_units, n_touched = self._alloc(grid)                                   # host read
             self._grow_planes(n_units)
             self.n_units = n_units
             mark("emit_alloc")
-            ws = torch.empty(int(lib.misplat_ptsdf_workspace(C.c_int64(0), E)), dtype=torch.uint8, device=dev)
-            keys_sorted = torch.empty(n_pairs, dtype=torch.int32, device=dev)
-            ids_sorted = torch.empty(n_pairs, dtype=torch.int32, device=dev)
-            ranges = torch.zeros((n_units, 2), dtype=torch.int32, device=dev)
-            check(lib.misplat_ptsdf_lists(g, ptr(self._slot_map), ptr(keys), ptr(ids), E, n_units, ptr(ws), C.c_int64(ws.numel()),
-                                          ptr(keys_sorted), ptr(ids_sorted), ptr(ranges), stream_ptr()), "misplat_ptsdf_lists")
+            ids_sorted, ranges = unit_lists(grid, self._slot_map, keys, ids, n_pairs, n_units)
             mark("lists")
             ws = torch.empty(int(lib.misplat_ptsdf_workspace(C.c_int64(n_touched), C.c_int64(0))), dtype=torch.uint8, device=dev)
             check(lib.misplat_ptsdf_accumulate(g, ptr(self._touched), n_touched, ptr(p), ptr(o), stride, ptr(col), carve,
@@ -206,7 +160,7 @@ class PointTSDFVolume:
                   "misplat_ptsdf_accumulate")
             mark("accumulate")
             self.n_pairs += n_pairs
-            del keys, ids, keys_sorted, ids_sorted, ws
+            del keys, ids, ids_sorted, ws
 
     def integrate_depth(self, depths: Tensor, c2w: Tensor, intrinsics: Tensor, rgbs: Optional[Tensor] = None,
                         masks: Optional[Tensor] = None, _timings: Optional[dict] = None) -> None:
@@ -247,12 +201,8 @@ class PointTSDFVolume:
         ended within ``sdf_trunc`` of its two voxels.  The integer planes are not changed: any ``min_weight`` may follow."""
         if not isinstance(min_weight, (int, np.integer)) or isinstance(min_weight, bool) or not 0 <= min_weight < 1 << 31:
             raise ValueError(f"PointTSDFVolume.extract_mesh: min_weight must be an integer in 0..2^31-1, got {min_weight!r}")
-        dev = self.device
-        empty = (torch.zeros((0, 3), dtype=torch.float32, device=dev), torch.zeros((0, 3), dtype=torch.int32, device=dev),
-                 torch.zeros((0, 3), dtype=torch.float32, device=dev))
-        if self.n_units == 0:
-            return empty
-        return marching_cubes(self._grid(), self._slot_map, self.n_units, self._pool(int(min_weight))) or empty
+        mesh = marching_cubes(self._grid(), self._slot_map, self.n_units, self._pool(int(min_weight))) if self.n_units else None
+        return mesh or empty_mesh(self.device)
 
     def units(self):
         """The allocated units in map order, on the host (for tests and inspection): (coords [n,3] int64, sum_q [n,4096] int64,
@@ -260,31 +210,12 @@ class PointTSDFVolume:
         if self.n_units == 0:
             z = np.zeros((0, UNIT_VOXELS), np.int64)
             return np.zeros((0, 3), np.int64), z, z, np.zeros((0, UNIT_VOXELS, 3), np.int64), z
-        m = torch.nonzero(self._slot_map >= 0).squeeze(1)
+        m = self._map_order()
         slots = self._slot_map[m].long()
         host = lambda t: t[slots].cpu().numpy().astype(np.int64)                     # noqa: E731
         coords = unit_coords(m.cpu().numpy(), self.lo, self.dims)
         return (coords, host(self._sum_q), host(self._count), np.ascontiguousarray(host(self._rgb_sum).transpose(0, 2, 1)),
                 host(self._rgb_count))
-
-
-class _Stages:
-    """Seconds per stage added into a dict, each stage synchronised (scripts/pointtsdf_bench.py); nothing without a dict."""
-
-    def __init__(self, out: Optional[dict]):
-        self.out = out
-        if out is not None:
-            import time
-            self.clock = time.perf_counter
-            torch.cuda.synchronize()
-            self.t = self.clock()
-
-    def __call__(self, stage: str) -> None:
-        if self.out is not None:
-            torch.cuda.synchronize()
-            now = self.clock()
-            self.out[stage] = self.out.get(stage, 0.0) + (now - self.t)
-            self.t = now
 
 
 __all__ = ["PointTSDFVolume", "CHUNK_RAYS", "MAX_UNITS", "UNIT_BYTES", "MisplatError"]

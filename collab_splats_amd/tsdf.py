@@ -14,14 +14,14 @@ import numpy as np
 import torch
 from torch import Tensor
 
-from ._lib import MisplatError, check, load, ptr, require_gpu, stream_ptr
-from .unitvolume import (MAX_UNITS, UNIT, UNIT_VOXELS, Grid, _unit_range, make_grid, map_span, marching_cubes,  # noqa: F401
-                         unit_coords)
+from ._lib import MisplatError, check, load, ptr, require_gpu, stream_ptr  # noqa: F401
+from .unitvolume import (MAX_UNITS, UNIT, UNIT_VOXELS, Grid, GrowingVolume, _unit_range, empty_mesh, make_grid,  # noqa: F401
+                         map_span, marching_cubes, unit_coords)
 
 MAX_VIEWS = 64                       # views per kernel batch (bits of a unit's view word)
 
 
-class TSDFVolume:
+class TSDFVolume(GrowingVolume):
     """Scalable TSDF volume on the GPU.
 
     ``voxel_size`` / ``sdf_trunc`` / ``depth_trunc`` as Open3D's ``ScalableTSDFVolume(voxel_length, sdf_trunc)`` and
@@ -30,58 +30,26 @@ class TSDFVolume:
     cut at ``depth_trunc`` (padded by ``sdf_trunc``) and grows with them; more than ``max_units`` units raise ``MisplatError``.
     """
 
+    _name, _what = "TSDFVolume", "the views' frusta"
+    _advice = "pass bounds=, a smaller depth_trunc or a larger voxel_size"
+
     def __init__(self, voxel_size: float, sdf_trunc: float, depth_trunc: float = 3.0, bounds=None,
                  device=None, max_units: int = MAX_UNITS):
         if not (voxel_size > 0 and sdf_trunc > 0 and depth_trunc > 0):
             raise ValueError("TSDFVolume: voxel_size, sdf_trunc and depth_trunc must be positive")
-        self.device = torch.device(device) if device is not None else torch.device("cuda")
-        if self.device.type != "cuda":
-            raise MisplatError("TSDFVolume runs on the MI355X only: there is no CPU fallback")
-        self.voxel_size, self.sdf_trunc, self.depth_trunc = float(voxel_size), float(sdf_trunc), float(depth_trunc)
-        self.ulen = float(np.float32(self.voxel_size) * np.float32(UNIT))
-        self.max_units = min(int(max_units), MAX_UNITS)
-        self.clip = None
+        super().__init__(voxel_size, device, max_units)
+        self.sdf_trunc, self.depth_trunc = float(sdf_trunc), float(depth_trunc)
         if bounds is not None:
             b = np.asarray(bounds, np.float64).reshape(2, 3)
             if not np.all(b[1] >= b[0]):
                 raise ValueError("TSDFVolume: bounds must be [[min xyz], [max xyz]]")
             self.clip = _unit_range(b[0], b[1], self.ulen)
-        self.lo = self.dims = None                 # unit map (none before the first integrate)
-        self.n_units = 0                           # allocated units (= pool slots in use)
         self.n_views = 0
         self._pool = None
-        self._counters = None                      # device {allocated slots, touched units of the batch}
 
     # ------------------------------------------------------------------------------------------------------------ plumbing
     def _grid(self) -> Grid:
         return make_grid(self.voxel_size, self.sdf_trunc, self.depth_trunc, self.lo, self.dims)
-
-    def _cover(self, lo: np.ndarray, hi: np.ndarray) -> bool:
-        """Make the unit map cover units lo..hi (inclusive, clipped to the bounds); False if nothing is left."""
-        if self.clip is not None:
-            lo, hi = np.maximum(lo, self.clip[0]), np.minimum(hi, self.clip[1])
-        if np.any(hi < lo):
-            return self.lo is not None
-        if self.lo is not None:
-            old_hi = self.lo + self.dims - 1
-            if np.all(lo >= self.lo) and np.all(hi <= old_hi):
-                return True
-            lo, hi = np.minimum(lo, self.lo), np.maximum(hi, old_hi)
-        dims, n = map_span("TSDFVolume", "the views' frusta", lo, hi, self.max_units,
-                           "pass bounds=, a smaller depth_trunc or a larger voxel_size")
-        slot_map = torch.full((n,), -1, dtype=torch.int32, device=self.device)
-        if self.n_units:                           # re-linearise the allocated units into the grown map
-            m = torch.nonzero(self._slot_map >= 0).squeeze(1)
-            nx, ny = int(self.dims[0]), int(self.dims[1])
-            cx, cy, cz = m % nx, (m // nx) % ny, m // (nx * ny)
-            o = self.lo - lo
-            lin = (cx + int(o[0])) + int(dims[0]) * ((cy + int(o[1])) + int(dims[1]) * (cz + int(o[2])))
-            slot_map[lin] = self._slot_map[m]
-        self.lo, self.dims = lo.astype(np.int64), dims.astype(np.int64)
-        self._slot_map = slot_map
-        self._words = torch.zeros(n, dtype=torch.int64, device=self.device)
-        self._touched = torch.empty(2 * n, dtype=torch.int32, device=self.device)
-        return True
 
     def _frusta_units(self, viewmats: Tensor, Ks: Tensor, H: int, W: int) -> Tuple[np.ndarray, np.ndarray]:
         """Units overlapping the AABB of the views' frusta cut at depth_trunc, padded by sdf_trunc (one host read)."""
@@ -131,10 +99,7 @@ class TSDFVolume:
             if tuple(masks.shape) != (V, H, W):
                 raise ValueError(f"TSDFVolume.integrate: masks must be [{V},{H},{W}(,1)], got {tuple(masks.shape)}")
         require_gpu(depths, viewmats, Ks, rgbs, masks)
-        if depths.device != self.device and self.device.index is not None:
-            raise MisplatError(f"TSDFVolume on {self.device} got tensors on {depths.device}")
-        if self.device.index is None:
-            self.device = depths.device
+        self._adopt_device(depths)
         depths = depths.to(torch.float32).contiguous()
         viewmats = viewmats.to(torch.float32).contiguous()
         Ks = Ks.to(torch.float32).contiguous()
@@ -145,21 +110,15 @@ class TSDFVolume:
             return
         lib = load()
         grid = self._grid()
-        if self._counters is None:
-            self._counters = torch.zeros(2, dtype=torch.int32, device=self.device)
         for b in range(0, V, MAX_VIEWS):
             n = min(MAX_VIEWS, V - b)
             d, vm, k = depths[b:b + n], viewmats[b:b + n], Ks[b:b + n]
             c = rgbs[b:b + n] if rgbs is not None else None
             mk = masks[b:b + n] if masks is not None else None
-            self._words.zero_()
-            self._counters[1:].zero_()
-            s = stream_ptr()
-            check(lib.misplat_tsdf_mark(C.byref(grid), ptr(d), ptr(mk), n, H, W, ptr(vm), ptr(k), ptr(self._words), s),
+            self._begin_batch()
+            check(lib.misplat_tsdf_mark(C.byref(grid), ptr(d), ptr(mk), n, H, W, ptr(vm), ptr(k), ptr(self._words), stream_ptr()),
                   "misplat_tsdf_mark")
-            check(lib.misplat_tsdf_alloc(C.byref(grid), ptr(self._words), ptr(self._slot_map), ptr(self._counters),
-                                         ptr(self._touched), s), "misplat_tsdf_alloc")
-            n_units, n_touched = (int(x) for x in self._counters.tolist())     # the batch's one host read
+            n_units, n_touched = self._alloc(grid)                               # the batch's one host read
             if n_touched == 0:
                 continue
             self._grow_pool(n_units)
@@ -172,12 +131,8 @@ class TSDFVolume:
     def extract_mesh(self) -> Tuple[Tensor, Tensor, Tensor]:
         """Marching cubes over the allocated voxels: (vertices [M,3] fp32, triangles [T,3] int32, colors [M,3] fp32 in [0,1]),
         on the device, in the deterministic order of DESIGN.md section 14 (two host reads: nothing else)."""
-        dev = self.device
-        empty = (torch.zeros((0, 3), dtype=torch.float32, device=dev), torch.zeros((0, 3), dtype=torch.int32, device=dev),
-                 torch.zeros((0, 3), dtype=torch.float32, device=dev))
-        if self.n_units == 0:
-            return empty
-        return marching_cubes(self._grid(), self._slot_map, self.n_units, self._pool) or empty
+        mesh = marching_cubes(self._grid(), self._slot_map, self.n_units, self._pool) if self.n_units else None
+        return mesh or empty_mesh(self.device)
 
     def units(self):
         """The allocated units in map order, on the host (for tests and inspection): (coords [n,3] int64, tsdf [n,4096],
@@ -185,7 +140,7 @@ class TSDFVolume:
         if self.n_units == 0:
             z = np.zeros((0, UNIT_VOXELS), np.float32)
             return np.zeros((0, 3), np.int64), z, z, np.zeros((0, UNIT_VOXELS, 3), np.float32)
-        m = torch.nonzero(self._slot_map >= 0).squeeze(1)
+        m = self._map_order()
         slots = self._slot_map[m].long()
         data = self._pool[slots].cpu().numpy()
         coords = unit_coords(m.cpu().numpy(), self.lo, self.dims)

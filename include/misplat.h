@@ -732,6 +732,15 @@ int misplat_tsdf_mark(const misplat_tsdf_grid* grid, const float* depths, const 
  * (counters[1] zeroed by the caller). */
 int misplat_tsdf_alloc(const misplat_tsdf_grid* grid, const uint64_t* words, int32_t* slot_map, int32_t* counters,
                        int32_t* touched, misplat_stream_t stream);
+/* unit lists (csrc/unitlists.h, exported by csrc/density.hip), for the users that list items per unit
+ * (misplat_density_*, misplat_ptsdf_*): their n_pairs (unit map index, item) pairs, emitted while marking words, sorted by
+ * unit after alloc, stable (keys and ids are used as scratch): a unit's items keep their order of emission.  ranges [n_units,
+ * 2] = the part [begin, end) of ids_sorted that belongs to the unit in pool slot s, written for the units listed only.  Of the
+ * grid voxel_size, lo and dims are read.  workspace: misplat_density_workspace(0, n_pairs) = misplat_ptsdf_workspace(0,
+ * n_pairs) bytes. */
+int misplat_unit_lists(const misplat_tsdf_grid* grid, const int32_t* slot_map, int32_t* keys, int32_t* ids, int64_t n_pairs,
+                       int32_t n_units, void* workspace, int64_t workspace_bytes, int32_t* keys_sorted, int32_t* ids_sorted,
+                       int32_t* ranges, misplat_stream_t stream);
 /* integrate: the batch's views, in view order, into the voxels of the n_touched listed units. */
 int misplat_tsdf_integrate(const misplat_tsdf_grid* grid, const int32_t* touched, int32_t n_touched, const uint64_t* words,
                            const float* depths, const uint8_t* masks, const float* rgbs, int32_t n_views, int32_t height,
@@ -1071,11 +1080,13 @@ int misplat_bilagrid_tv_bwd(const float* grids, int32_t num, int32_t grid_w, int
  * per slot): of the grid only voxel_size, lo and dims are read.  A Gaussian is listed in a unit by a conservative fp32 test in
  * a fixed operation order (density.hip's head states it): the integer structures equal the restatement's bit for bit.
  * Order of calls: records; count (the host reads n_pairs); emit into zeroed words; misplat_tsdf_alloc (slot_map all -1,
- * counters zero: touched then lists the n_units allocated units); lists; accumulate; then query and misplat_tsdf_mc_* at will. */
+ * counters zero: touched then lists the n_units allocated units); misplat_unit_lists (every unit's list is then ascending in
+ * g); accumulate; then query and misplat_tsdf_mc_* at will. */
 #define MISPLAT_DENSITY_REC 16          /* floats per record: mu[3], A[9] row-major, o, E[3] (E = -1: takes no part) */
 #define MISPLAT_DENSITY_BATCH 64        /* records accumulate stages in LDS at a time */
 #define MISPLAT_DENSITY_MAX_CHANNELS 16 /* channels of query's values */
-/* workspace bytes that serve count (n_pairs = 0) or lists; -1 for sizes the library refuses (n_gauss, n_pairs < 2^31). */
+/* workspace bytes that serve count (n_pairs = 0) or misplat_unit_lists (n_gauss = 0); -1 for sizes the library refuses
+ * (n_gauss, n_pairs < 2^31). */
 int64_t misplat_density_workspace(int64_t n_gauss, int64_t n_pairs);
 /* records [N,16] (16-byte aligned); E_i = r sqrt(sum_a (R[i][a] s_a)^2), the half sides of the support's AABB. */
 int misplat_density_records(const float* means, const float* quats, const float* scales, const float* opacities,
@@ -1090,11 +1101,6 @@ int misplat_density_count(const misplat_tsdf_grid* grid, const float* means, con
 int misplat_density_emit(const misplat_tsdf_grid* grid, const float* means, const float* quats, const float* scales,
                          const float* opacities, int64_t n_gauss, float cutoff, float min_opacity, const int32_t* pair_off,
                          int64_t n_pairs, int32_t* keys, int32_t* ids, uint64_t* words, misplat_stream_t stream);
-/* lists: the pairs sorted by unit, stable (keys and ids are used as scratch): every unit's list is ascending in g;
- * ranges [n_units, 2] = the part [begin, end) of ids_sorted that belongs to the unit in pool slot s. */
-int misplat_density_lists(const misplat_tsdf_grid* grid, const int32_t* slot_map, int32_t* keys, int32_t* ids, int64_t n_pairs,
-                          int32_t n_units, void* workspace, int64_t workspace_bytes, int32_t* keys_sorted, int32_t* ids_sorted,
-                          int32_t* ranges, misplat_stream_t stream);
 /* accumulate: plane 0 of every listed unit = d at its voxel centres, terms added in list order (two runs are bitwise equal);
  * plane 1 = 1, planes 2..4 = 0.  touched: misplat_tsdf_alloc's {map index, slot} pairs.  flags bit 0: no sub-brick skipping (by
  * default a wave passes over a record whose slabs miss its 8 x 8 x 16 brick). */
@@ -1130,9 +1136,9 @@ int misplat_density_raycast(const misplat_tsdf_grid* grid, const int32_t* slot_m
  * 256 lz, zeroed by the caller when a slot is new.  Integer sums: the planes depend on no order of rays or calls.  A ray with a
  * non-finite coordinate, zero length or a coordinate at or beyond 2^22 voxels is skipped; a ray is walked only inside the map.
  * Order of calls per chunk of rays: count (the host reads n_pairs); emit into zeroed words; misplat_tsdf_alloc (the host reads
- * its counters and grows the planes); lists; accumulate.  Then finalize and misplat_tsdf_mc_* at will. */
-/* workspace bytes that serve count (n_pairs = 0), accumulate (n_rays = its n_touched, n_pairs = 0) or lists (n_rays = 0);
- * -1 for sizes the library refuses (both < 2^31). */
+ * its counters and grows the planes); misplat_unit_lists; accumulate.  Then finalize and misplat_tsdf_mc_* at will. */
+/* workspace bytes that serve count (n_pairs = 0), accumulate (n_rays = its n_touched, n_pairs = 0) or misplat_unit_lists
+ * (n_rays = 0); -1 for sizes the library refuses (both < 2^31). */
 int64_t misplat_ptsdf_workspace(int64_t n_rays, int64_t n_pairs);
 /* count: pair_off [N + 1] = the exclusive scan of the units each ray passes inside the map; n_pairs: DEVICE int64, their
  * number. */
@@ -1144,11 +1150,6 @@ int misplat_ptsdf_count(const misplat_tsdf_grid* grid, const float* points, cons
 int misplat_ptsdf_emit(const misplat_tsdf_grid* grid, const float* points, const float* origins, int32_t origin_stride,
                        int64_t n_rays, int32_t space_carving, const int32_t* pair_off, int64_t n_pairs, int32_t* keys, int32_t* ids,
                        uint64_t* words, misplat_stream_t stream);
-/* lists: the pairs sorted by unit, stable (keys and ids are used as scratch); ranges [n_units, 2]: the part [begin, end) of
- * ids_sorted of the unit in pool slot s, written for the units listed only. */
-int misplat_ptsdf_lists(const misplat_tsdf_grid* grid, const int32_t* slot_map, int32_t* keys, int32_t* ids, int64_t n_pairs,
-                        int32_t n_units, void* workspace, int64_t workspace_bytes, int32_t* keys_sorted, int32_t* ids_sorted,
-                        int32_t* ranges, misplat_stream_t stream);
 /* accumulate: the n_pairs listed rays into the planes of the n_touched units of touched (misplat_tsdf_alloc's {map index,
  * slot} pairs), one workgroup per 8192 rays of a unit's list.  colors [N,3] fp32 in [0,1], or NULL (black).  workspace:
  * misplat_ptsdf_workspace(n_touched, 0) bytes. */

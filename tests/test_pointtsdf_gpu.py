@@ -136,6 +136,39 @@ def test_map_grows_with_a_second_call():
     _check(vol, ref)
 
 
+@pytest.mark.parametrize("units, far, band", [
+    (((0, 0, 0), (256, 0, 0), (257, 0, 0)), (257, 0, 0), (257, 1 << 16)),
+    (((40, 37, 38), (28, 40, 39), (40, 40, 40)), (40, 40, 40), ((1 << 16) + 1, (1 << 24) - 1))])
+def test_lists_beyond_one_sort_pass(units, far, band):
+    """The shared list driver (misplat_unit_lists) under point TSDF with map indices above one byte: 12 short rays without
+    carving, four in each of three units, handed over unit by unit in turn, so the sort has to move every pair.  A map of 258
+    entries takes two radix passes (and the identity third), with map indices 0, 256 and 257; one of 41^3 three, with map
+    indices 65435 = 0xFF9B, 67227 = 0x1069B and 68920 on either side of 2^16.  The first two indices of each case share their
+    low byte: after the first pass their pairs alternate, and only the higher passes part the two units' lists.  The scenes
+    above never leave one pass.  A unit's rays run along +x through neighbouring voxel columns (2 x 2 in y, z), so the mesh is
+    not empty.  In the second case a thirteenth ray of length 0 in unit (0, 0, 0) stretches the map to the origin and is then
+    skipped: the restatement extracts densely over the box of the allocated units, which so stays 13 x 4 x 3 units while the
+    map has 41^3 entries."""
+    rng = np.random.default_rng(7)
+    units = np.array(units, np.float64)
+    yz = np.array([(0, j, k) for j in (0, 1) for k in (0, 1)], np.float64)
+    # points in voxels 8 .. 9 of their unit: with sdf_trunc 3 voxels and the map's pad of 4 nothing leaves the unit
+    p = (np.tile(units, (4, 1)) * 16 + 8.5 + np.repeat(yz, 3, 0) + rng.uniform(-0.2, 0.2, (12, 3))) * VS
+    o = p - np.array([0.5, 0.0, 0.0])
+    if units.min() > 0:
+        p, o = np.concatenate([p, [[8.5 * VS] * 3]]), np.concatenate([o, [[8.5 * VS] * 3]])
+    p, o = p.astype(np.float32), o.astype(np.float32)
+    vol, ref = _volume(False)
+    _both(vol, ref, p, o, rng.random(p.shape).astype(np.float32))
+    assert np.array_equal(vol.lo, np.zeros(3)) and np.array_equal(vol.dims, np.array(far) + 1)
+    assert band[0] <= int(np.prod(vol.dims)) <= band[1]
+    assert vol.n_units == 3 and vol.n_pairs == 12           # one call: every unit is listed, so one holds >= 2 rays (all hold 4)
+    m = (units[:, 0] + vol.dims[0] * (units[:, 1] + vol.dims[1] * units[:, 2])).astype(np.int64)
+    assert m[0] % 256 == m[1] % 256 and m[0] // 256 != m[1] // 256
+    assert np.array_equal(vol.units()[0], units[np.argsort(m)].astype(np.int64))
+    assert len(_check(vol, ref)[1]) > 0
+
+
 def test_empty_and_skipped_clouds():
     vol, ref = _volume(True)
     vol.integrate(torch.zeros((0, 3), device=DEV), torch.zeros(3, device=DEV))
