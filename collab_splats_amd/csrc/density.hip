@@ -161,7 +161,7 @@ __global__ __launch_bounds__(256) void density_pairs_kernel(Grid g, const float*
 // column lx = 8 (w & 1) + (l & 7), ly = 8 (w >> 1) + (l >> 3), all 16 z, in registers.  The unit's list is staged through LDS in
 // batches of kBatch records; every voxel adds its terms in list order.  SKIP: a wave passes over a record whose slabs miss its
 // brick (the test of the lists in the record's scaled form, on wave-uniform values, with a margin for its own rounding):
-// a skipped term is zero, or within rounding of the cut-off, where the term vanishes.
+// a skipped term is zero: SKIP = false gives the same bits (tests/test_density_regimes_gpu.py).
 template <bool SKIP>
 __global__ __launch_bounds__(256) void density_accumulate_kernel(Grid g, const int32_t* __restrict__ touched,
                                                                  const float* __restrict__ records, const int32_t* __restrict__ ids,

@@ -75,6 +75,22 @@ class Oracle:
         k = np.where(inside, self.o[None, :] * (e - self.ecut), 0.0)
         return k, t, inside, e
 
+    def scale(self, points, chunk=8192):
+        """S [P] = sum over g with m_g < r^2 (1 + 1e-3) of o_g (exp(-m_g / 2) (1 + m_g / 2) + exp(-r^2 / 2)): the size of the terms a
+        point's density is made of, each with the factor 1 + m / 2 by which a relative error of the exponent's argument grows
+        (d exp(-m / 2) = exp(-m / 2) (m / 2) dm / m).  The local scale an error at the point is measured against; 0 where no
+        Gaussian comes within a thousandth of its cut-off."""
+        p = np.asarray(points, np.float64).reshape(-1, 3)
+        out = np.zeros(p.shape[0])
+        if len(self.ids) == 0:
+            return out
+        for c0 in range(0, p.shape[0], chunk):
+            sl = slice(c0, min(c0 + chunk, p.shape[0]))
+            _, t, _, e = self.terms(p[sl])
+            m = (t * t).sum(-1)
+            out[sl] = np.where(m < self.r2 * (1.0 + 1e-3), self.o[None, :] * (e * (1.0 + 0.5 * m) + self.ecut), 0.0).sum(1)
+        return out
+
     def evaluate(self, points, values=None, chunk=16384):
         """dict: density [P], grad [P,3], dominant [P] int32 (the lowest g among equal largest terms; -1 where d = 0), best and
         second [P] (the largest and second largest term), min_m [P] (the smallest m_g), values [P,D] or None."""
@@ -235,6 +251,18 @@ class Restated:
             out[n] = self._sum_list(self.lists[m], x, y, z)[0]
         return out
 
+    def map_index(self, points):
+        """[P] int64: the map index of the unit of each point's voxel floor(p / h) (the fp32 division the kernel makes), -1 for
+        a non-finite point or one outside the map."""
+        p = np.ascontiguousarray(points, F).reshape(-1, 3)
+        with np.errstate(all="ignore"):
+            fin = np.isfinite(p).all(1)
+            vox = np.clip(np.floor(p / self.h), F(-3e7), F(3e7))
+            vox = np.where(np.isfinite(vox), vox, 0).astype(np.int64)
+        u = (vox >> 4) - self.lo[None, :]
+        inside = fin & (u >= 0).all(1) & (u < self.dims[None, :]).all(1)
+        return np.where(inside, u[:, 0] + self.dims[0] * (u[:, 1] + self.dims[1] * u[:, 2]), -1)
+
     def query(self, points, values=None):
         """fp32 (density, grad, values) at points, from the list of the unit of the point's voxel floor(p / h)."""
         p = np.ascontiguousarray(points, F).reshape(-1, 3)
@@ -245,14 +273,7 @@ class Restated:
         vals = None if v is None else np.zeros((P, v.shape[1]), F)
         if P == 0 or not self.lists:
             return d, grad, vals
-        with np.errstate(all="ignore"):
-            fin = np.isfinite(p).all(1)
-            vox = np.clip(np.floor(p / self.h), F(-3e7), F(3e7))
-            vox = np.where(np.isfinite(vox), vox, 0).astype(np.int64)
-        u = (vox >> 4) - self.lo[None, :]
-        inside = fin & (u >= 0).all(1) & (u < self.dims[None, :]).all(1)
-        m = u[:, 0] + self.dims[0] * (u[:, 1] + self.dims[1] * u[:, 2])
-        m = np.where(inside, m, -1)
+        m = self.map_index(p)
         for mi in np.unique(m):
             if mi < 0 or int(mi) not in self.lists:
                 continue

@@ -1,6 +1,7 @@
 """Scenes for the Gaussian density field: the smallest at which each mechanism can fail.  Every scene is
-a dict of fp32 numpy arrays (means, quats, scales, opacities), the voxel size h, optional bounds, and the isos its mesh is
-extracted at.  h = 0.02 throughout: a unit is 0.32 m."""
+a dict of fp32 numpy arrays (means, quats, scales, opacities), the voxel size h, optional bounds, the isos its mesh is
+extracted at, and the field's cutoff and min_opacity (the defaults here).  h = 0.02 throughout: a unit is 0.32 m.  The scenes
+off the defaults and at workload coordinates are density_regimes_scenes.py's; scene() knows their names too."""
 import functools
 
 import numpy as np
@@ -24,10 +25,10 @@ def _qmul(a, b):
                      w1 * y2 - x1 * z2 + y1 * w2 + z1 * x2, w1 * z2 + x1 * y2 - y1 * x2 + z1 * w2])
 
 
-def _scene(means, quats, scales, opacities, bounds=None, isos=(), h=H):
+def _scene(means, quats, scales, opacities, bounds=None, isos=(), h=H, cutoff=3.0, min_opacity=1.0 / 255.0):
     return dict(means=np.ascontiguousarray(means, F).reshape(-1, 3), quats=np.ascontiguousarray(quats, F).reshape(-1, 4),
                 scales=np.ascontiguousarray(scales, F).reshape(-1, 3), opacities=np.ascontiguousarray(opacities, F).reshape(-1),
-                h=h, bounds=bounds, isos=tuple(isos))
+                h=h, bounds=bounds, isos=tuple(isos), cutoff=float(cutoff), min_opacity=float(min_opacity))
 
 
 def _normalise32(q):
@@ -146,8 +147,12 @@ def wide_map(dims):
 def scene(name):
     if name.startswith("batches_"):
         return batches(int(name.split("_")[1]))
-    return {"single": single, "tilted_disc": tilted_disc, "tiny": tiny, "negative": negative, "clipped": clipped,
-            "culled": culled, "empty": empty, "random": random_scene}[name]()
+    own = {"single": single, "tilted_disc": tilted_disc, "tiny": tiny, "negative": negative, "clipped": clipped,
+           "culled": culled, "empty": empty, "random": random_scene}
+    if name in own:
+        return own[name]()
+    import density_regimes_scenes as RS                      # (imports this module: only here)
+    return RS.build(name)
 
 
 NAMES = ("single", "tilted_disc", "tiny") + tuple(f"batches_{n}" for n in BATCH_SIZES) + ("negative", "clipped", "culled",
@@ -159,14 +164,15 @@ MESH = tuple((n, iso) for n in ("single", "tiny", "random") for iso in scene(n)[
 def restated(name):
     from density_restatement import Restated
     sc = scene(name)
-    return Restated(sc["means"], sc["quats"], sc["scales"], sc["opacities"], sc["h"], bounds=sc["bounds"])
+    return Restated(sc["means"], sc["quats"], sc["scales"], sc["opacities"], sc["h"], cutoff=sc["cutoff"],
+                    min_opacity=sc["min_opacity"], bounds=sc["bounds"])
 
 
 @functools.lru_cache(maxsize=None)
 def oracle(name):
     from density_restatement import Oracle
     sc = scene(name)
-    return Oracle(sc["means"], sc["quats"], sc["scales"], sc["opacities"])
+    return Oracle(sc["means"], sc["quats"], sc["scales"], sc["opacities"], cutoff=sc["cutoff"], min_opacity=sc["min_opacity"])
 
 
 @functools.lru_cache(maxsize=None)

@@ -31,7 +31,7 @@ def _field(name):
         from collab_splats_amd import DensityField
         sc = S.scene(name)
         _FIELDS[name] = DensityField(_t(sc["means"]), _t(sc["quats"]), _t(sc["scales"]), _t(sc["opacities"]), sc["h"],
-                                     bounds=sc["bounds"])
+                                     cutoff=sc["cutoff"], min_opacity=sc["min_opacity"], bounds=sc["bounds"])
     return _FIELDS[name]
 
 

@@ -31,7 +31,7 @@ def _field(name):
         from collab_splats_amd import DensityField
         sc = S.scene(name)
         _FIELDS[name] = DensityField(_t(sc["means"]), _t(sc["quats"]), _t(sc["scales"]), _t(sc["opacities"]), sc["h"],
-                                     bounds=sc["bounds"])
+                                     cutoff=sc["cutoff"], min_opacity=sc["min_opacity"], bounds=sc["bounds"])
     return _FIELDS[name]
 
 
@@ -103,15 +103,21 @@ def test_raycast_equals_the_composition_of_queries(name, kind, levels):
     assert all(0 < x for x in n) if kind == "long" else n[-2 if len(levels) == 3 else 0] > 0.9 * len(rays["t0"])
 
 
-@pytest.mark.parametrize("name", ["batches_193", "clipped", "culled", "tiny"])
+@pytest.mark.parametrize("name", ["batches_193", "clipped", "culled", "tiny", "bench_corner_r1.5", "bench_corner_r6"])
 def test_raycast_equals_the_composition_on_the_small_scenes(name):
-    """One list of 193 entries; a map of one unit with a Gaussian wider than it; culled Gaussians; a Gaussian smaller than a voxel.
+    """One list of 193 entries; a map of one unit with a Gaussian wider than it; culled Gaussians; a Gaussian smaller than a voxel;
+    a cut-off of 1.5 and of 6 (density_regimes_scenes.py: two units at the bench's voxel size, 7 to 12 m from the origin).
     A fan from outside the scene's box through its middle (4 degrees wide for `tiny`, whose support is 0.018 across: the 35
-    degree fan's rays all pass it by); the levels sit below the scene's own maximum."""
+    degree fan's rays all pass it by; 20 degrees for the two-unit maps, 0.32 x 0.16 x 0.16 m, aimed at the map's centre);
+    the levels sit below the scene's own maximum."""
     f = _field(name)
     sc = S.scene(name)
-    centre = sc["means"][np.isfinite(sc["means"]).all(1) & (np.abs(sc["means"]) < 1.5).all(1)].mean(0)
-    o, v = LS.fan(centre - np.array([0.03, 0.05, 0.6], np.float32), centre, res=16, fov_deg=4.0 if name == "tiny" else 35.0)
+    if name.startswith("bench_corner"):
+        centre = ((f.lo + 0.5 * f.dims) * f.ulen).astype(np.float32)
+    else:
+        centre = sc["means"][np.isfinite(sc["means"]).all(1) & (np.abs(sc["means"]) < 1.5).all(1)].mean(0)
+    fov = 4.0 if name == "tiny" else 20.0 if name.startswith("bench_corner") else 35.0
+    o, v = LS.fan(centre - np.array([0.03, 0.05, 0.6], np.float32), centre, res=16, fov_deg=fov)
     rays = dict(origins=o, dirs=v, t0=np.full(256, 0.2, np.float32), t1=np.full(256, 1.0, np.float32))
     top = float(f._pool[:, 0].max())
     levels = (0.02 * top, 0.3 * top, 0.8 * top)
