@@ -30,6 +30,8 @@ from .poisson import (poisson_grid, poisson_reconstruct, poisson_solve, poisson_
                       poisson_trim)
 from .density import DensityField, gaussian_density, gaussian_density_grad, level_surface_points  # noqa: F401
 from .pointtsdf import PointTSDFVolume  # noqa: F401
+from .identity import (IdentityField, IdentityNeighbours, identity_3d_loss, identity_labels, identity_loss,  # noqa: F401
+                       identity_neighbours)
 from .grouping import FrontGaussians, MemoryBank, convert_matched_mask, front_gaussians, project_gaussians  # noqa: F401
 
 __version__ = "0.1.0"

@@ -168,6 +168,9 @@ SYMBOLS = {
     "misplat_density_raycast": (C.c_int, 19),
     "misplat_ptsdf_workspace": (C.c_int64, 2), "misplat_ptsdf_count": (C.c_int, 11), "misplat_ptsdf_emit": (C.c_int, 12),
     "misplat_ptsdf_accumulate": (C.c_int, 18), "misplat_ptsdf_finalize": (C.c_int, 8),
+    "misplat_identity_scratch_floats": (C.c_int64, 4), "misplat_identity_loss_fwd": (C.c_int, 13),
+    "misplat_identity_loss_bwd": (C.c_int, 16), "misplat_identity_labels": (C.c_int, 10),
+    "misplat_identity_3d_fwd": (C.c_int, 14), "misplat_identity_3d_bwd": (C.c_int, 19),
     "misplat_version": (C.c_char_p, 0),
 }
 

@@ -71,6 +71,8 @@ SOURCES = {
     "meshtri.hip": ["-ffp-contract=off"],
     # pointtsdf.hip: the same: the rays' voxel walks and fixed-point sdf terms, hence the integer planes, equal the restatement (tests/)
     "pointtsdf.hip": ["-ffp-contract=off"],
+    # identity.hip: contraction allowed, as featloss.hip (the logits are multiply-add chains; the test oracle is fp64)
+    "identity.hip": [],
 }
 
 

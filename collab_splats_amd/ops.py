@@ -1095,13 +1095,13 @@ def _upstream(P: Params, cd: int, dev, v_render, v_alpha, v_exp_depth, v_med_dep
             for t, w in zip((v_render, v_alpha, v_exp_depth, v_med_depth, v_normal), widths)]
 
 # ----------------------------------------------------------------------------- the other nodes
-# The stage-by-stage nodes live in ops_stages.py, the model-level ones in ops_epilogue.py, featureloss.py, textquery.py and bilagrid.py; ``ops.X`` resolves there on first use
+# The stage-by-stage nodes live in ops_stages.py, the model-level ones in ops_epilogue.py, featureloss.py, textquery.py, bilagrid.py and identity.py; ``ops.X`` resolves there on first use
 # (lazily: ops_stages reads this module's switches, so neither can import the other's names at import time).
 def __getattr__(name: str):
     if name.startswith("__"):
         raise AttributeError(name)
-    from . import bilagrid, featureloss, ops_epilogue, ops_stages, textquery
-    for m in (ops_stages, ops_epilogue, featureloss, textquery, bilagrid):
+    from . import bilagrid, featureloss, identity, ops_epilogue, ops_stages, textquery
+    for m in (ops_stages, ops_epilogue, featureloss, textquery, bilagrid, identity):
         if name in m.__dict__:
             return m.__dict__[name]
     raise AttributeError(f"module 'collab_splats_amd.ops' has no attribute {name!r}")

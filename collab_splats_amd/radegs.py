@@ -1115,6 +1115,64 @@ class RadegsModel(nn.Module):
             self.train(was_training)
         return bank, labels, matched
 
+    def render_identities(self, camera, field) -> Tensor:
+        """[H, W, D]: ``field.identities`` composited as pass-through colours (``sh_degree=None``, ``render_mode="RGB"``) over
+        the model's own Gaussians, which are detached -- the result is attached to ``field.identities`` only.  The camera is
+        handled as ``get_outputs`` does in evaluation (the stored pose, no resolution schedule).  The crop box must be unset, as
+        in ``associate_masks``: the field indexes all Gaussians.  DESIGN.md section 33."""
+        if self.crop_box is not None:
+            raise ValueError("render_identities: unset the crop box first (set_crop(None)): the field indexes all Gaussians")
+        if field.identities.shape[0] != self.means.shape[0]:
+            raise ValueError(f"render_identities: the field holds {field.identities.shape[0]} identities, the model "
+                             f"{self.means.shape[0]} Gaussians")
+        camera = camera.to(self.device) if hasattr(camera, "to") else camera
+        cp = self._get_camera_parameters(camera)
+        render = rasterization(
+            means=self.means.detach(), quats=self.quats.detach(), scales=self.scales.detach(), scales_are_log=True,
+            opacities=self.opacities.detach().squeeze(-1), opacities_are_logit=True, colors=field.identities,
+            viewmats=cp["viewmats"].detach(), Ks=cp["Ks"], width=int(cp["image_width"]), height=int(cp["image_height"]),
+            packed=False, near_plane=0.01, far_plane=1e10, render_mode="RGB", sh_degree=None, sparse_grad=False,
+            absgrad=False, rasterize_mode=self.config.rasterize_mode)[0]
+        return render[0]
+
+    def identity_neighbours(self, num_samples: int = 1000, k: int = 5, radius: float = 1.0, seed: int = 0):
+        """The pairs of the 3-D identity loss over the model's means (``identity.identity_neighbours``).  ``num_samples`` = 1000
+        and ``k`` = 5 are the Gaussian Grouping paper's; ``radius`` (scene units, the kNN's cut-off) is this project's."""
+        from .identity import identity_neighbours
+        return identity_neighbours(self.means.detach(), num_samples, k, radius, seed)
+
+    def fit_identities(self, cameras: Sequence, matched: Sequence, num_classes: int, steps: int, lr: float = 5e-4,
+                       lambda_3d: float = 2.0, every_3d: int = 5, field=None, identity_dim: int = 16, radius: float = 1.0):
+        """Identity training after ``associate_masks``: a plain loop over the views in order -- ``render_identities``, the 2-D
+        cross-entropy against ``matched[i]``, on every ``every_3d``-th step ``lambda_3d`` times the 3-D consistency loss, one
+        ``FusedAdam`` step over the field's parameters -- and the trained ``identity.IdentityField`` comes back.
+        ``identity_dim`` = 16, ``lambda_3d`` = 2.0 and the 3-D loss's 1000 samples of 5 neighbours are the Gaussian Grouping
+        paper's; ``lr`` = 5e-4 is its released configuration's classifier rate; ``every_3d`` and ``radius`` are this project's
+        (the paper does not state them).  The reference has no such loop (grouping.py:110-136 stops at ``setup_train``)."""
+        from .identity import IdentityField
+        from .optim import FusedAdam
+        cameras, matched = list(cameras), list(matched)
+        if not cameras or len(cameras) != len(matched):
+            raise ValueError(f"fit_identities: {len(cameras)} cameras but {len(matched)} matched images")
+        if int(steps) < 0 or int(every_3d) < 1:
+            raise ValueError(f"fit_identities: steps >= 0 and every_3d >= 1, got {steps} and {every_3d}")
+        if field is None:
+            field = IdentityField(int(self.means.shape[0]), int(num_classes), identity_dim).to(self.device)
+        elif field.num_classes != int(num_classes):
+            raise ValueError(f"fit_identities: the field classifies onto {field.num_classes} classes, not {num_classes}")
+        optimizer = FusedAdam(list(field.parameters()), lr=lr)
+        neighbours = self.identity_neighbours(radius=radius) if lambda_3d > 0 else None
+        matched = [m.to(self.device) for m in matched]
+        for step in range(int(steps)):
+            i = step % len(cameras)
+            optimizer.zero_grad(set_to_none=True)
+            loss = field.loss_2d(self.render_identities(cameras[i], field), matched[i])
+            if neighbours is not None and step % int(every_3d) == 0:
+                loss = loss + lambda_3d * field.loss_3d(neighbours)
+            loss.backward()
+            optimizer.step()
+        return field
+
     def _scale_reg(self, dev) -> Tensor:
         """Splatfacto's scale regularisation: 0.1 * mean(max(max(s) / min(s), max_gauss_ratio) - max_gauss_ratio) of the
         activated scales, every 10th step; 0 otherwise [UNVERIFIED-UPSTREAM]."""

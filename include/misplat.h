@@ -1318,6 +1318,43 @@ int misplat_meshtri_flip_round(const float* vertices, int64_t n_vertices, int32_
                                const uint8_t* region, double min_violation, void* workspace, int64_t workspace_bytes, int32_t* counts,
                                misplat_stream_t stream);
 
+/* ---- identity training for Gaussian grouping (Gaussian Grouping / Gaga; the reference's unfinished setup_train,
+ * utils/grouping.py:110-136, restated from the published method): csrc/identity.hip.  A linear classifier weight [classes, dim],
+ * bias [classes] (dim 1..32, classes 1..4096) over rendered identity images or the Gaussians' identity vectors.
+ *   2-D: z = W x + b per pixel, ce = logsumexp(z) - z[target - 1], loss = sum_labelled ce / max(n_labelled, 1); target [H, W]
+ *   int32, 0 = unlabelled, t in 1..classes = class t - 1, anything else counts as unlabelled and is reported in counts[1].
+ *   3-D: loss = sum_pairs KL(softmax(W e_s + b) || softmax(W e_t + b)) / max(n_pairs, 1) over the pairs (sample[j], table[j][i])
+ *   whose entry is neither -1 nor its own sample.
+ * features [H, W, dim] float32 with its pixels pix_stride >= dim floats apart.  scratch: misplat_identity_scratch_floats(rows,
+ * dim, classes, mode) floats (mode 0: rows = H * W pixels; mode 1: rows = n_samples * k pairs; -1 outside the limits, rows at
+ * most 2^28): per-row scalars and the weight gradient's partial sums per row split (at most 64 splits), written by the forward,
+ * read and written by the backward.  counts: device int32 [2] = (labelled pixels or valid pairs, targets out of range).  No
+ * [classes, rows] buffer exists; every sum runs in a fixed order, the last stage in fp64; no atomics. */
+int64_t misplat_identity_scratch_floats(int64_t rows, int32_t dim, int32_t classes, int32_t mode);
+int misplat_identity_loss_fwd(int32_t height, int32_t width, int32_t dim, int32_t pix_stride, const float* features,
+                              int32_t classes, const float* weight, const float* bias, const int32_t* target, float* scratch,
+                              int32_t* counts, float* loss, misplat_stream_t stream);
+/* g_loss: the upstream gradient as a DEVICE scalar (or NULL = 0).  v_features [H, W, dim] contiguous, every element written
+ * (exact zeros at unlabelled pixels), v_weight [classes, dim], v_bias [classes]. */
+int misplat_identity_loss_bwd(int32_t height, int32_t width, int32_t dim, int32_t pix_stride, const float* features,
+                              int32_t classes, const float* weight, const float* bias, const int32_t* target, float* scratch,
+                              const int32_t* counts, const float* g_loss, float* v_features, float* v_weight, float* v_bias,
+                              misplat_stream_t stream);
+/* Inference, one launch: labels [rows] = argmax class + 1 (ties: the smallest class), confidence (or NULL) [rows] = the
+ * largest softmax probability. */
+int misplat_identity_labels(int64_t rows, int32_t dim, int32_t pix_stride, const float* features, int32_t classes,
+                            const float* weight, const float* bias, int32_t* labels, float* confidence, misplat_stream_t stream);
+/* identities [n_rows, dim]; sample [n_samples] int64; table [n_samples, k] int32, k 1..16. */
+int misplat_identity_3d_fwd(int64_t n_rows, int32_t dim, const float* identities, int32_t classes, const float* weight,
+                            const float* bias, int32_t n_samples, int32_t k, const int64_t* sample, const int32_t* table,
+                            float* scratch, int32_t* counts, float* loss, misplat_stream_t stream);
+/* rev_offsets [n_rows + 1] int64 / rev_slots int32: a CSR over rows of the slots (2 * pair + side; side 0 the sample, 1 the
+ * table entry) that name the row, ascending within a row; v_identities [n_rows, dim], every element written. */
+int misplat_identity_3d_bwd(int64_t n_rows, int32_t dim, const float* identities, int32_t classes, const float* weight,
+                            const float* bias, int32_t n_samples, int32_t k, const int64_t* sample, const int32_t* table,
+                            const int64_t* rev_offsets, const int32_t* rev_slots, float* scratch, const int32_t* counts,
+                            const float* g_loss, float* v_identities, float* v_weight, float* v_bias, misplat_stream_t stream);
+
 /* Library identification ("misplat <version> gfx950"). */
 const char* misplat_version(void);
 
