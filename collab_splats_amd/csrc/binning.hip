@@ -653,7 +653,6 @@ inline int grid_for(int64_t n, int block) {
     if (b < 1) b = 1;
     return (int)b;
 }
-inline int check_launch() { return hipGetLastError() == hipSuccess ? MISPLAT_OK : MISPLAT_ELAUNCH; }
 
 }  // namespace
 
@@ -671,7 +670,7 @@ extern "C" int misplat_pack(int64_t n_rows, int32_t color_dim, const float* mean
     hipLaunchKernelGGL(pack_kernel, dim3(grid_for(n_rows, 256)), dim3(256), 0, (hipStream_t)stream, n_rows,
                        color_dim, means2d, conics, opacities_eff, ray_ts, ray_planes, normals, colors,
                        (float4*)grec);
-    return check_launch();
+    return launched();
 }
 
 
@@ -682,7 +681,7 @@ extern "C" int misplat_isect_ids(const uint32_t* tiles_sorted, const int32_t* fl
     if (n_isects == 0) return MISPLAT_OK;
     hipLaunchKernelGGL(isect_ids_kernel, dim3(grid_for(n_isects, 256)), dim3(256), 0, (hipStream_t)stream,
                        tiles_sorted, flatten_ids, depths, n_isects, isect_ids);
-    return check_launch();
+    return launched();
 }
 
 
@@ -826,7 +825,7 @@ static int launch_tile_sort(const int32_t* offsets, int32_t n_tiles, int64_t n_i
     }
     hipLaunchKernelGGL((tile_sort_rest_kernel<MAP, UNORDERED>), dim3(few), dim3(1024), 0, s, offsets, n_tiles, n_isects,
                        covered, depths, isect_gid, payload, flatten_ids, scratch, sel);
-    return check_launch();
+    return launched();
 }
 
 // Front-only ordering, first part: the front kernel, then the regular size classes for the tiles it left undone.
@@ -839,7 +838,7 @@ int misplat_internal::tile_sort_front(const int32_t* offsets, int32_t n_tiles, i
     const int grid = n_tiles < 65536 ? n_tiles : 65536;
     hipLaunchKernelGGL(tile_sort_front_kernel, dim3(grid), dim3(64 * kFrontWaves), 0, s, offsets, n_tiles, n_isects, depths,
                        row_map, (const int32_t*)payload, flatten_ids, F);
-    if (n_isects == 0) return check_launch();
+    if (n_isects == 0) return launched();
     return launch_tile_sort<2, true>(offsets, n_tiles, n_isects, depths, row_map, payload, flatten_ids, scratch, 1, s,
                                      TileSel{F.front_n, 1}, false, est_isects);
 }

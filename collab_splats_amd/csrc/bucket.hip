@@ -558,8 +558,6 @@ __global__ __launch_bounds__(kRowsPerWg) void bucket_tile_fill_kernel(
     }
 }
 
-inline int check_launch() { return hipGetLastError() == hipSuccess ? MISPLAT_OK : MISPLAT_ELAUNCH; }
-
 }  // namespace
 
 extern "C" int misplat_bucket_plan(const misplat_params* p, int32_t* n_cells, int32_t* n_blocks) {
@@ -591,7 +589,7 @@ extern "C" int misplat_bucket_count(const misplat_params* p, const float* means2
         hipLaunchKernelGGL(bucket_count_kernel, dim3(g.n_blocks), dim3(kCountThreads), 0, s, total, p->n_gauss, p->tile_w,
                            p->tile_h, g.shift, g.cells_x, g.cells_x * g.cells_y, g.n_cells, g.rows_per_block, means2d, radii,
                            tiles_per_gauss, (uint2*)rect2, cellhist, cell_count, (unsigned long long*)counters);
-    return check_launch();
+    return launched();
 }
 
 extern "C" int misplat_bucket_rows(const misplat_params* p, const int32_t* tiles_per_gauss, const uint32_t* rect2,
@@ -631,7 +629,7 @@ int misplat_internal::bucket_rows(const misplat_params* p, const int32_t* tiles_
     else
         hipLaunchKernelGGL(bucket_rows_empty_kernel, dim3(1), dim3(256), 0, s, g.n_cells, cell_offs, counters,
                            (long long*)n_isects_host);
-    return check_launch();
+    return launched();
 }
 
 extern "C" int misplat_bucket_tiles(const misplat_params* p, const int32_t* order, const uint32_t* rect_sorted,
@@ -674,5 +672,5 @@ int misplat_internal::bucket_tiles(const misplat_params* p, const int32_t* order
                                tiles_per_cam, counters, order, (const uint2*)rect_sorted, offsets, tile_count, cum, cap_isects,
                                payload, isect_gid, depth_sorted);
     }
-    return check_launch();
+    return launched();
 }

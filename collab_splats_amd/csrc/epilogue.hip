@@ -194,8 +194,6 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(int64_t n_pix, const floa
     }
 }
 
-inline int check_launch() { return hipGetLastError() == hipSuccess ? MISPLAT_OK : MISPLAT_ELAUNCH; }
-
 }  // namespace
 
 extern "C" int misplat_outputs_fwd(int64_t n_pix, int32_t color_dim, const float* background3_host,
@@ -216,7 +214,7 @@ extern "C" int misplat_outputs_fwd(int64_t n_pix, int32_t color_dim, const float
     hipLaunchKernelGGL(outputs_fwd_kernel, dim3(grid_for(n_pix, 256)), dim3(256), 0, s, n_pix, color_dim,
                        background3_host[0], background3_host[1], background3_host[2], render, alpha, exp_depth,
                        med_depth, exp_normal, maxes4, rgb, depth, median_depth, normals, depth_im);
-    return check_launch();
+    return launched();
 }
 
 extern "C" int misplat_outputs_bwd(int64_t n_pix, int32_t color_dim, const float* background3_host,
@@ -230,7 +228,7 @@ extern "C" int misplat_outputs_bwd(int64_t n_pix, int32_t color_dim, const float
                        color_dim, background3_host[0], background3_host[1], background3_host[2], render, alpha, v_rgb,
                        v_depth, v_median_depth, v_normals, v_depth_im, v_render, v_alpha, v_exp_depth, v_med_depth,
                        v_exp_normal);
-    return check_launch();
+    return launched();
 }
 
 extern "C" int misplat_loss_fwd(int64_t n_pix, const float* rgb, const float* gt, const float* err_exp, const float* err_med,
@@ -243,7 +241,7 @@ extern "C" int misplat_loss_fwd(int64_t n_pix, const float* rgb, const float* gt
     hipLaunchKernelGGL(loss_partial_kernel, dim3(kLossBlocks), dim3(256), 0, s, n_pix, rgb, gt, err_exp, err_med, partials);
     hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(256), 0, s, kLossBlocks, partials, 1.0 / (3.0 * (double)n_pix),
                        1.0 / (double)n_pix, depth_ratio, depth_normal_lambda, gt ? rgb_loss : nullptr, err_exp ? dn_loss : nullptr);
-    return check_launch();
+    return launched();
 }
 
 extern "C" int misplat_loss_bwd(int64_t n_pix, const float* rgb, const float* gt, const float* g_rgb_loss, const float* g_dn_loss,
@@ -257,5 +255,5 @@ extern "C" int misplat_loss_bwd(int64_t n_pix, const float* rgb, const float* gt
     hipLaunchKernelGGL(loss_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n_pix, rgb, gt, g_rgb_loss,
                        g_dn_loss, (float)(1.0 / (3.0 * (double)n_pix)), depth_normal_lambda * (1.0f - depth_ratio) * inv_n,
                        depth_normal_lambda * depth_ratio * inv_n, v_rgb, v_err_exp, v_err_med);
-    return check_launch();
+    return launched();
 }

@@ -24,6 +24,8 @@
 
 #include "bilinear.h"
 #include "misplat.h"
+#include "rowlinear.h"
+#include "wgprims.h"
 
 namespace {
 
@@ -62,19 +64,6 @@ struct Plan {
     int max_tiles, max_S, max_units, max_PS, max_blk;
 };
 
-// the destinations whose taps can touch source index i: source coordinate in (i - 1, i + 1), one more on each side for
-// rounding; every candidate is then tested with taps() itself, so the gather is the exact transpose of the sampling
-__device__ __forceinline__ void touching(int i, int n_out, double inv_scale, int* lo, int* hi) {
-    const double a = ((double)i - 0.5) * inv_scale - 0.5, b = ((double)i + 1.5) * inv_scale - 0.5;
-    const double l = floor(a) - 1.0, h = ceil(b) + 1.0, last = (double)(n_out - 1);
-    *lo = (int)(l < 0.0 ? 0.0 : (l > last ? last : l));
-    *hi = (int)(h > last ? last : (h < 0.0 ? 0.0 : h));
-}
-
-__device__ __forceinline__ float tap_weight(const Taps& t, int i) {
-    return (t.i0 == i ? t.l0 : 0.f) + (t.i1 == i ? t.l1 : 0.f);
-}
-
 // ---- x and h on the main map.  One workgroup = 16 pixels: x through LDS, then one (pixel, hidden unit) per thread.
 __global__ __launch_bounds__(256) void hidden_fwd_kernel(Plan pl, int H, int W, int pix_stride, const float* __restrict__ features,
                                                          const float* __restrict__ wh, const float* __restrict__ bh,
@@ -91,7 +80,7 @@ __global__ __launch_bounds__(256) void hidden_fwd_kernel(Plan pl, int H, int W, 
             const float* f = features + l;
             const float v00 = f[((size_t)ty.i0 * W + tx.i0) * pix_stride], v01 = f[((size_t)ty.i0 * W + tx.i1) * pix_stride];
             const float v10 = f[((size_t)ty.i1 * W + tx.i0) * pix_stride], v11 = f[((size_t)ty.i1 * W + tx.i1) * pix_stride];
-            v = ty.l0 * (tx.l0 * v00 + tx.l1 * v01) + ty.l1 * (tx.l0 * v10 + tx.l1 * v11);
+            v = bilerp(ty, tx, v00, v01, v10, v11);
             scratch[pl.x + (size_t)m * L + l] = v;
         }
         sx[pix][l] = v;
@@ -121,14 +110,14 @@ __global__ __launch_bounds__(256) void resample_kernel(Plan pl, float* __restric
     const float* h = scratch + pl.hP + j;
     const float v00 = h[((size_t)ty.i0 * pl.Wm + tx.i0) * Hd], v01 = h[((size_t)ty.i0 * pl.Wm + tx.i1) * Hd];
     const float v10 = h[((size_t)ty.i1 * pl.Wm + tx.i0) * Hd], v11 = h[((size_t)ty.i1 * pl.Wm + tx.i1) * Hd];
-    const float v = ty.l0 * (tx.l0 * v00 + tx.l1 * v01) + ty.l1 * (tx.l0 * v10 + tx.l1 * v11);
+    const float v = bilerp(ty, tx, v00, v01, v10, v11);
     scratch[br.hqP + e] = v;
     scratch[br.hqT + (size_t)j * P + q] = v;
 }
 
 // One channel's prediction at one pixel, p = bias + <row of w_out, h_b(q)>.  The row is wave-uniform: it comes through scalar
 // loads.  kH64 (Hd == 64, the default): the pixel's hidden vector stays in 64 registers for all channels (two chains of
-// multiply-adds); any other Hd: it is read per channel (hT [Hd, P]: one coalesced load per hidden unit).
+// multiply-adds, rowlinear.h's dot2); any other Hd: it is read per channel (hT [Hd, P]: one coalesced load per hidden unit).
 template <bool kH64>
 __device__ __forceinline__ void load_hidden(float (&hv)[kJ], const float* __restrict__ hT, size_t P, size_t q) {
 #pragma unroll
@@ -137,12 +126,7 @@ __device__ __forceinline__ void load_hidden(float (&hv)[kJ], const float* __rest
 template <bool kH64>
 __device__ __forceinline__ float predict(const float* __restrict__ wr, float bias, const float (&hv)[kJ], const float* __restrict__ hT,
                                          size_t P, size_t q, int Hd) {
-    if (kH64) {
-        float a0 = bias, a1 = 0.f;
-#pragma unroll
-        for (int jj = 0; jj < kJ; jj += 2) { a0 = fmaf(wr[jj], hv[jj], a0); a1 = fmaf(wr[jj + 1], hv[jj + 1], a1); }
-        return a0 + a1;
-    }
+    if (kH64) return dot2<kJ, true>(wr, bias, hv, kJ);
     float a = bias;
     for (int j = 0; j < Hd; j++) a = fmaf(wr[j], hT[(size_t)j * P + q], a);
     return a;
@@ -528,8 +512,6 @@ __global__ __launch_bounds__(256) void branch_decode_kernel(Plan pl, int channel
     }
 }
 
-inline int check_launch() { return hipGetLastError() == hipSuccess ? MISPLAT_OK : MISPLAT_ELAUNCH; }
-
 // The scratch layout and the launch shapes: a function of the sizes alone.  decode_only: the buffers of x, h and the
 // resampled h only.  Returns false for sizes outside the documented limits.
 bool make_plan(int L, int Hd, int Hm, int Wm, int n, const int32_t* dims, bool decode_only, Plan* pl) {
@@ -623,7 +605,7 @@ extern "C" int misplat_featloss_fwd(int32_t height, int32_t width, int32_t laten
     else hipLaunchKernelGGL(branch_fwd_kernel<false>, grid, dim3(256), 0, s, pl, scratch);
     hipLaunchKernelGGL(pixel_stats_kernel, dim3(pl.max_blk, pl.n), dim3(256), 0, s, pl, scratch);
     hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(1024), 0, s, pl, scratch, branch_sums, features_loss);
-    return check_launch();
+    return launched();
 }
 
 extern "C" int misplat_featloss_bwd(int32_t height, int32_t width, int32_t latent, int32_t hidden, const float* w_hidden,
@@ -659,7 +641,7 @@ extern "C" int misplat_featloss_bwd(int32_t height, int32_t width, int32_t laten
     const dim3 grid_f((unsigned)(((int64_t)width * latent + 255) / 256), (unsigned)std::min<int32_t>(height, 65535));
     hipLaunchKernelGGL(features_bwd_kernel, grid_f, dim3(256), 0, s, pl, (int)height, (int)width, (double)height / main_h,
                        (double)width / main_w, (double)main_h / height, (double)main_w / width, scratch, v_features);
-    return check_launch();
+    return launched();
 }
 
 extern "C" int misplat_feature_decode(int32_t height, int32_t width, int32_t latent, int32_t pix_stride, const float* features,
@@ -680,5 +662,5 @@ extern "C" int misplat_feature_decode(int32_t height, int32_t width, int32_t lat
     const dim3 grid(pl.max_tiles, pl.max_S, pl.n);
     if (hidden == kJ) hipLaunchKernelGGL(branch_decode_kernel<true>, grid, dim3(256), 0, s, pl, channels_last, scratch);
     else hipLaunchKernelGGL(branch_decode_kernel<false>, grid, dim3(256), 0, s, pl, channels_last, scratch);
-    return check_launch();
+    return launched();
 }

@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "misplat.h"
+#include "rowlinear.h"
 #include "wgprims.h"
 
 namespace {
@@ -31,23 +32,7 @@ constexpr int kRS = kUnit + 4;                  // LDS row strides (floats), 16-
 constexpr int64_t kMaxRows = (int64_t)1 << 28;
 
 // ---------------------------------------------------------------------------------------------------- the contraction
-template <int DP, bool kFull>
-__device__ __forceinline__ void load_row(float (&x)[DP], const float* __restrict__ src, int D) {
-#pragma unroll
-    for (int d = 0; d < DP; d++) x[d] = (kFull || d < D) ? src[d] : 0.f;
-}
-
-// one logit: bias + <row of W, x>, two chains of multiply-adds.  wr is wave-uniform.
-template <int DP, bool kFull>
-__device__ __forceinline__ float logit(const float* __restrict__ wr, float bias, const float (&x)[DP], int D) {
-    float a0 = bias, a1 = 0.f;
-#pragma unroll
-    for (int d = 0; d + 1 < DP; d += 2) {
-        if (kFull || d < D) a0 = fmaf(wr[d], x[d], a0);
-        if (kFull || d + 1 < D) a1 = fmaf(wr[d + 1], x[d + 1], a1);
-    }
-    return a0 + a1;
-}
+// A lane's row and one logit, bias + <row of W, x>: load_row and dot2 of rowlinear.h.
 
 // log-sum-exp over the K classes, the maximum subtracted; *zt = the logit of class t (unchanged if t is not in 0 .. K - 1);
 // *best = the first class that attains the maximum
@@ -63,7 +48,7 @@ __device__ __forceinline__ void lse_walk(const float* __restrict__ W, const floa
             const int k = k0 + u;
             z[u] = -INFINITY;
             if (k < K) {
-                z[u] = logit<DP, kFull>(W + (size_t)k * D, b[k], x, D);
+                z[u] = dot2<DP, kFull>(W + (size_t)k * D, b[k], x, D);
                 zsel = k == t ? z[u] : zsel;
                 arg = z[u] > cm ? k : arg;
                 cm = fmaxf(cm, z[u]);
@@ -144,7 +129,7 @@ __global__ __launch_bounds__(256) void ce_bwd_dx_kernel(int64_t P, int D, int K,
 #pragma unroll 2
         for (int k = 0; k < K; k++) {
             const float* wr = W + (size_t)k * D;
-            const float z = logit<DP, kFull>(wr, b[k], x, D);
+            const float z = dot2<DP, kFull>(wr, b[k], x, D);
             const float r = (expf(z - l) - (k == t - 1 ? 1.f : 0.f)) * ws;
 #pragma unroll
             for (int d = 0; d < DP; d++)
@@ -194,7 +179,7 @@ __global__ __launch_bounds__(256) void kl_fwd_kernel(Pairs pr, int D, int K, con
 #pragma unroll 2
         for (int k = 0; k < K; k++) {
             const float* wr = W + (size_t)k * D;
-            const float ps = logit<DP, kFull>(wr, b[k], xs, D) - ls, pt = logit<DP, kFull>(wr, b[k], xt, D) - lt;
+            const float ps = dot2<DP, kFull>(wr, b[k], xs, D) - ls, pt = dot2<DP, kFull>(wr, b[k], xt, D) - lt;
             kl = fmaf(expf(ps), ps - pt, kl);
         }
     }
@@ -233,7 +218,7 @@ __global__ __launch_bounds__(256) void kl_bwd_rows_kernel(Pairs pr, int D, int K
 #pragma unroll 2
         for (int k = 0; k < K; k++) {
             const float* wr = W + (size_t)k * D;
-            const float r = pair_dz(side, logit<DP, kFull>(wr, b[k], xs, D) - ls, logit<DP, kFull>(wr, b[k], xt, D) - lt, kl, ws);
+            const float r = pair_dz(side, dot2<DP, kFull>(wr, b[k], xs, D) - ls, dot2<DP, kFull>(wr, b[k], xt, D) - lt, kl, ws);
 #pragma unroll
             for (int d = 0; d < DP; d++)
                 if (kFull || d < D) de[d] = fmaf(wr[d], r, de[d]);
@@ -312,7 +297,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(Src src, int64_t rows, int D
                 for (int u = 0; u < kUnit; u++) {
                     const int k = c0 + u;
                     if (k < K) {
-                        const float z = logit<DP, kFull>(W + (size_t)k * D, b[k], x, D);
+                        const float z = dot2<DP, kFull>(W + (size_t)k * D, b[k], x, D);
                         dz[u] = lab ? (expf(z - l) - (k == t - 1 ? 1.f : 0.f)) * ws : 0.f;
                     }
                 }
@@ -336,7 +321,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(Src src, int64_t rows, int D
                     const int k = c0 + u;
                     if (k < K) {
                         const float* wr = W + (size_t)k * D;
-                        const float zo = logit<DP, kFull>(wr, b[k], x, D), zx = logit<DP, kFull>(wr, b[k], xo, D);
+                        const float zo = dot2<DP, kFull>(wr, b[k], x, D), zx = dot2<DP, kFull>(wr, b[k], xo, D);
                         const float lps = (side ? zx : zo) - ls, lpt = (side ? zo : zx) - lt;
                         dz[u] = valid ? pair_dz(side, lps, lpt, kl, ws) : 0.f;
                     }

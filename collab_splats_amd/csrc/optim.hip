@@ -111,7 +111,7 @@ extern "C" int misplat_adam_step(int32_t n_tensors, float* const* params, const 
     if (blocks > 0x7fffffffLL) return MISPLAT_EINVAL;
     hipLaunchKernelGGL(adam_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, T,
                        (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps);
-    return hipGetLastError() == hipSuccess ? MISPLAT_OK : MISPLAT_ELAUNCH;
+    return launched();
 }
 
 // ---- shared-Gaussian gradient reduce that moves only the rows that HAVE a gradient (parallel.GradientBuckets; SURVEY.md
@@ -231,7 +231,7 @@ int rows_move(bool pack, int32_t n_tensors, float* const* tensors, const int32_t
     if (blocks > 16384) blocks = 16384;
     if (pack) hipLaunchKernelGGL(rows_move_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, T, ids, n_ids, count_dev, packed);
     else hipLaunchKernelGGL(rows_move_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, T, ids, n_ids, count_dev, packed);
-    return hipGetLastError() == hipSuccess ? MISPLAT_OK : MISPLAT_ELAUNCH;
+    return launched();
 }
 
 }  // namespace
@@ -242,7 +242,7 @@ extern "C" int misplat_touched_bits(const uint8_t* flags, int64_t n_rows, uint8_
     if (nbytes == 0) return MISPLAT_OK;
     hipLaunchKernelGGL(touched_bits_kernel, dim3((unsigned)((nbytes + 255) / 256)), dim3(256), 0, (hipStream_t)stream, flags, n_rows,
                        bits, nbytes);
-    return hipGetLastError() == hipSuccess ? MISPLAT_OK : MISPLAT_ELAUNCH;
+    return launched();
 }
 
 extern "C" int misplat_union_count(const uint8_t* gathered, int32_t world, int64_t nbytes, int32_t* block_counts,
@@ -251,7 +251,7 @@ extern "C" int misplat_union_count(const uint8_t* gathered, int32_t world, int64
     if (nbytes == 0) return MISPLAT_OK;
     hipLaunchKernelGGL(union_count_kernel, dim3((unsigned)((nbytes + kBitsBlock - 1) / kBitsBlock)), dim3(256), 0,
                        (hipStream_t)stream, gathered, (int)world, nbytes, block_counts);
-    return hipGetLastError() == hipSuccess ? MISPLAT_OK : MISPLAT_ELAUNCH;
+    return launched();
 }
 
 extern "C" int misplat_union_scan(const int32_t* block_counts, int64_t n_blocks, int64_t* block_offsets, int64_t* total,
@@ -262,7 +262,7 @@ extern "C" int misplat_union_scan(const int32_t* block_counts, int64_t n_blocks,
     // torch op behind the backward's launch blocked the autograd thread for 0.9 ms per step at 5 M Gaussians).
     hipLaunchKernelGGL((carry_scan_kernel<int32_t, int64_t>), dim3(1), dim3(kScanBlock), 0, (hipStream_t)stream, block_counts, n_blocks,
                        n_blocks, block_offsets, total);
-    return hipGetLastError() == hipSuccess ? MISPLAT_OK : MISPLAT_ELAUNCH;
+    return launched();
 }
 
 extern "C" int misplat_union_ids(const uint8_t* gathered, int32_t world, int64_t nbytes, const int64_t* block_offsets,
@@ -271,7 +271,7 @@ extern "C" int misplat_union_ids(const uint8_t* gathered, int32_t world, int64_t
     if (nbytes == 0) return MISPLAT_OK;
     hipLaunchKernelGGL(union_ids_kernel, dim3((unsigned)((nbytes + kBitsBlock - 1) / kBitsBlock)), dim3(256), 0,
                        (hipStream_t)stream, gathered, (int)world, nbytes, block_offsets, ids, ids_cap);
-    return hipGetLastError() == hipSuccess ? MISPLAT_OK : MISPLAT_ELAUNCH;
+    return launched();
 }
 
 extern "C" int misplat_rows_pack(int32_t n_tensors, const float* const* srcs, const int32_t* widths, const int32_t* ids,

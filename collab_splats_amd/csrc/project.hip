@@ -1734,7 +1734,6 @@ inline int grid_for(int64_t n, int block) {
     if (b < 1) b = 1;
     return (int)b;
 }
-inline int check_launch() { return hipGetLastError() == hipSuccess ? MISPLAT_OK : MISPLAT_ELAUNCH; }
 
 }  // namespace
 
@@ -1745,7 +1744,7 @@ int misplat_internal::zero_fill(float* dst, int64_t n_floats, int max_blocks, hi
     int g = grid_for(n4, 256);
     if (max_blocks > 0 && g > max_blocks) g = max_blocks;
     hipLaunchKernelGGL(zero_fill_kernel, dim3(g), dim3(256), 0, s, (float4*)dst, n4, dst + 4 * n4, (int)(n_floats - 4 * n4));
-    return check_launch();
+    return launched();
 }
 
 extern "C" int misplat_project_fwd(const misplat_params* p, const float* means, const float* quats,
@@ -1759,7 +1758,7 @@ extern "C" int misplat_project_fwd(const misplat_params* p, const float* means, 
     hipLaunchKernelGGL(project_fwd_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, *p,
                        means, quats, scales, opacities, viewmats, Ks, radii, means2d, depths, conics,
                        compensations, ray_ts, ray_planes, normals);
-    return check_launch();
+    return launched();
 }
 
 extern "C" int misplat_project_bwd(const misplat_params* p, const float* means, const float* quats,
@@ -1774,7 +1773,7 @@ extern "C" int misplat_project_bwd(const misplat_params* p, const float* means, 
     hipLaunchKernelGGL(project_bwd_kernel, dim3(grid_for(p->n_gauss, 256)), dim3(256), 0, (hipStream_t)stream,
                        *p, means, quats, scales, viewmats, Ks, radii, v_means2d, v_depths, v_conics,
                        v_compensations, v_ray_ts, v_ray_planes, v_normals, v_means, v_quats, v_scales);
-    return check_launch();
+    return launched();
 }
 
 extern "C" int64_t misplat_project_bwd_pose_workspace(int32_t n_gauss, int32_t n_cams) {
@@ -1795,11 +1794,11 @@ extern "C" int misplat_project_bwd_pose(const misplat_params* p, const float* me
         hipLaunchKernelGGL(project_bwd_pose_kernel, dim3(nb, p->n_cams), dim3(kPoseBlock), 0, (hipStream_t)stream,
                            *p, means, quats, scales, viewmats, Ks, radii, v_means2d, v_depths, v_conics,
                            v_compensations, v_ray_ts, v_ray_planes, v_normals, (double*)workspace);
-        if (check_launch() != MISPLAT_OK) return MISPLAT_ELAUNCH;
+        if (launched() != MISPLAT_OK) return MISPLAT_ELAUNCH;
     }
     hipLaunchKernelGGL(project_bwd_pose_final_kernel, dim3(p->n_cams), dim3(kPoseBlock), 0, (hipStream_t)stream,
                        (const double*)workspace, nb, v_viewmats);
-    return check_launch();
+    return launched();
 }
 
 extern "C" int misplat_sh_fwd(int32_t n_gauss, int32_t n_cams, int32_t K, int32_t degree,
@@ -1810,7 +1809,7 @@ extern "C" int misplat_sh_fwd(int32_t n_gauss, int32_t n_cams, int32_t K, int32_
     if (total == 0) return MISPLAT_OK;
     hipLaunchKernelGGL(sh_fwd_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, n_gauss,
                        n_cams, K, degree, dirs, coeffs, radii, colors);
-    return check_launch();
+    return launched();
 }
 
 extern "C" int misplat_sh_bwd(int32_t n_gauss, int32_t n_cams, int32_t K, int32_t degree,
@@ -1821,7 +1820,7 @@ extern "C" int misplat_sh_bwd(int32_t n_gauss, int32_t n_cams, int32_t K, int32_
     if (n_gauss == 0) return MISPLAT_OK;
     hipLaunchKernelGGL(sh_bwd_kernel, dim3(grid_for(n_gauss, 256)), dim3(256), 0, (hipStream_t)stream, n_gauss,
                        n_cams, K, degree, dirs, coeffs, radii, v_colors, v_coeffs, v_dirs);
-    return check_launch();
+    return launched();
 }
 
 // ------------------------------------------------------------------ fused path entry points
@@ -1852,7 +1851,7 @@ int misplat_internal::project_pack_fwd(const misplat_params* p, const float* mea
                        means, quats, scales, opacities, viewmats, Ks, radii, means2d, depths, compensations,
                        (float4*)grec, zero_words, n_zero, (float4*)lazy_rows, (float2*)abs_rows, (int)clear_lazy_rows,
                        order_table, order_sel, (int)order_slots, (int)order_stride);
-    return check_launch();
+    return launched();
 }
 
 extern "C" int misplat_color_fwd(const misplat_params* p, int32_t sh_degree, int32_t K_or_D, int32_t n_color,
@@ -1900,7 +1899,7 @@ int misplat_internal::color_fwd(const misplat_params* p, int32_t sh_degree, int3
         hipLaunchKernelGGL(color_copy_kernel, dim3(grid_for(total, 256)), dim3(256), 0, s, *p, K_or_D, n_color,
                            per_cam, depth_channel, coeffs_or_colors, radii, depths, grec, (float4*)zero_rows);
     }
-    return check_launch();
+    return launched();
 }
 
 extern "C" int misplat_color_bwd(const misplat_params* p, int32_t sh_degree, int32_t K_or_D, int32_t n_color,
@@ -1937,7 +1936,7 @@ extern "C" int misplat_color_bwd(const misplat_params* p, int32_t sh_degree, int
             else
                 hipLaunchKernelGGL(color_sh_bwd_sparse_kernel<false>, dim3(grid), dim3(64), 0, s, *p, sh_degree, means, viewmats,
                                    coeffs_or_colors, coeffs_rest, radii, v_grec, v_coeffs_or_colors, v_coeffs_rest, v_means_dir);
-            return check_launch();
+            return launched();
         }
 #define LAUNCH_SH_BWD(MULTI_, AUX_, KC_, SPLIT_)                                                                     \
     hipLaunchKernelGGL((color_sh_kernel<true, BLK, MULTI_, AUX_, KC_, SPLIT_>),                                       \
@@ -1965,7 +1964,7 @@ extern "C" int misplat_color_bwd(const misplat_params* p, int32_t sh_degree, int
         hipLaunchKernelGGL(color_copy_bwd_kernel, dim3(grid_for(rows, 256)), dim3(256), 0, s, *p, K_or_D, n_color,
                            per_cam, radii, v_grec, v_coeffs_or_colors);
     }
-    return check_launch();
+    return launched();
 }
 
 int misplat_internal::gauss_bwd_sparse(const misplat_params* p, int32_t sh_degree, int32_t depth_slot, const float* means,
@@ -2001,7 +2000,7 @@ int misplat_internal::gauss_bwd_sparse(const misplat_params* p, int32_t sh_degre
     if (coeffs_rest) { if (fine) LAUNCH_SPARSE(true, 4); else LAUNCH_SPARSE(true, 8); }
     else { if (fine) LAUNCH_SPARSE(false, 4); else LAUNCH_SPARSE(false, 8); }
 #undef LAUNCH_SPARSE
-    return check_launch();
+    return launched();
 }
 
 extern "C" int misplat_project_pack_bwd(const misplat_params* p, int32_t depth_slot, const float* means,
@@ -2023,12 +2022,12 @@ extern "C" int misplat_project_pack_bwd(const misplat_params* p, int32_t depth_s
         hipLaunchKernelGGL(project_pack_bwd_sparse_kernel, dim3((unsigned)waves), dim3(64), 0, (hipStream_t)stream, *p, depth_slot,
                            means, quats, scales, opacities, viewmats, Ks, radii, compensations, v_means2d, v_grec, v_means_dir,
                            v_means, v_quats, v_scales, v_opacities, v_depth_rows, (int)v_depth_stride);
-        return check_launch();
+        return launched();
     }
     hipLaunchKernelGGL(project_pack_bwd_kernel, dim3(grid_for(p->n_gauss, 256)), dim3(256), 0, (hipStream_t)stream,
                        *p, depth_slot, means, quats, scales, opacities, viewmats, Ks, radii, compensations, v_means2d,
                        v_grec, v_means_dir, v_means, v_quats, v_scales, v_opacities, v_depth_rows, (int)v_depth_stride);
-    return check_launch();
+    return launched();
 }
 
 extern "C" int misplat_color_fwd_x(const misplat_params* p, int32_t D, int32_t per_cam, int32_t depth_channel,
@@ -2048,7 +2047,7 @@ int misplat_internal::color_fwd_x(const misplat_params* p, int32_t D, int32_t n_
     if (total == 0) return MISPLAT_OK;
     hipLaunchKernelGGL(color_copy_x_kernel, dim3(grid_for(total * (1 + nxq), 256)), dim3(256), 0, stream, *p, D, (int)n_pre,
                        per_cam, depth_channel, nxq, colors, radii, depths, grec, featx, (float4*)zero_grec, (float4*)zero_featx);
-    return check_launch();
+    return launched();
 }
 
 extern "C" int misplat_color_bwd_x(const misplat_params* p, int32_t D, int32_t per_cam, int32_t nxq,
@@ -2065,5 +2064,5 @@ int misplat_internal::color_bwd_x(const misplat_params* p, int32_t D, int32_t n_
     if (rows == 0) return MISPLAT_OK;
     hipLaunchKernelGGL(color_copy_x_bwd_kernel, dim3(grid_for(rows * ((D + 3) / 4), 256)), dim3(256), 0, stream, *p,
                        D, (int)n_pre, per_cam, nxq, radii, v_grec, v_featx, v_colors);
-    return check_launch();
+    return launched();
 }

@@ -303,7 +303,6 @@ __global__ __launch_bounds__(256) void ssim_bwd_kernel(int H, int Wd, const floa
     }
 }
 
-inline int check_launch() { return hipGetLastError() == hipSuccess ? MISPLAT_OK : MISPLAT_ELAUNCH; }
 inline bool shape_ok(int32_t h, int32_t w) { return h >= kWin && w >= kWin && (int64_t)h * w <= (1 << 28); }
 
 }  // namespace
@@ -329,7 +328,7 @@ extern "C" int misplat_ssim_fwd(int32_t height, int32_t width, const float* rgb,
     hipLaunchKernelGGL(ssim_final_kernel, dim3(1), dim3(1024), 0, s, (int)(grid.x * grid.y), partials,
                        1.0 / (3.0 * (double)OH * (double)OW), 1.0 / (3.0 * (double)height * (double)width), l1_loss,
                        ssim_lambda, ssim, main_loss);
-    return check_launch();
+    return launched();
 }
 
 extern "C" int misplat_ssim_bwd(int32_t height, int32_t width, const float* rgb, const float* gt, const float* scratch,
@@ -341,5 +340,5 @@ extern "C" int misplat_ssim_bwd(int32_t height, int32_t width, const float* rgb,
     const float w_ssim = (float)((double)ssim_lambda / (3.0 * (double)OH * (double)OW));
     hipLaunchKernelGGL(ssim_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, (int)height, (int)width, rgb, gt, scratch,
                        make_window(), g_main, w_l1, w_ssim, v_rgb);
-    return check_launch();
+    return launched();
 }

@@ -19,6 +19,7 @@
 
 #include "bilinear.h"
 #include "misplat.h"
+#include "wgprims.h"
 
 namespace {
 
@@ -144,7 +145,7 @@ __global__ __launch_bounds__(256) void similarity_kernel(Query qy, int H, int W,
         const float* f11 = features + ((size_t)ty.i1 * W + tx.i1) * pix_stride;
 #pragma unroll
         for (int l = 0; l < kMaxLatent; l++) {
-            if (l < L) x[l] = ty.l0 * (tx.l0 * f00[l] + tx.l1 * f01[l]) + ty.l1 * (tx.l0 * f10[l] + tx.l1 * f11[l]);
+            if (l < L) x[l] = bilerp(ty, tx, f00[l], f01[l], f10[l], f11[l]);
         }
     }
     out[m] = similarity<kQ>(qy, x);
@@ -157,10 +158,8 @@ __global__ __launch_bounds__(256) void upsample_kernel(int h, int w, const float
     const Taps ty = taps((int)(m / W), h, (double)h / H), tx = taps((int)(m % W), w, (double)w / W);
     const float v00 = in[(size_t)ty.i0 * w + tx.i0], v01 = in[(size_t)ty.i0 * w + tx.i1];
     const float v10 = in[(size_t)ty.i1 * w + tx.i0], v11 = in[(size_t)ty.i1 * w + tx.i1];
-    out[m] = ty.l0 * (tx.l0 * v00 + tx.l1 * v01) + ty.l1 * (tx.l0 * v10 + tx.l1 * v11);
+    out[m] = bilerp(ty, tx, v00, v01, v10, v11);
 }
-
-inline int check_launch() { return hipGetLastError() == hipSuccess ? MISPLAT_OK : MISPLAT_ELAUNCH; }
 
 bool make_query(int32_t latent, int32_t hidden, const float* w_hidden, const float* b_hidden, int32_t n_queries, int32_t n_positive,
                 const float* A, const float* c, int32_t method, float softmax_temp, Query* qy) {
@@ -178,7 +177,7 @@ int launch_similarity(const Query& qy, int H, int W, int pix_stride, const float
     const int identity = h == H && w == W;
     if (qy.Q <= kFewQueries) hipLaunchKernelGGL(similarity_kernel<kFewQueries>, grid, dim3(256), 0, s, qy, H, W, pix_stride, features, h, w, identity, out);
     else hipLaunchKernelGGL(similarity_kernel<kMaxQuery>, grid, dim3(256), 0, s, qy, H, W, pix_stride, features, h, w, identity, out);
-    return check_launch();
+    return launched();
 }
 
 }  // namespace
@@ -191,7 +190,7 @@ extern "C" int misplat_textquery_fold(int32_t n_queries, int32_t channels, int32
     const int n = n_queries * (hidden + 1);
     hipLaunchKernelGGL(fold_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, (int)n_queries, (int)channels, (int)hidden,
                        embeddings, w_out, b_out, A, c);
-    return check_launch();
+    return launched();
 }
 
 extern "C" int misplat_textquery_map(int32_t height, int32_t width, int32_t latent, int32_t pix_stride, const float* features,
@@ -226,5 +225,5 @@ extern "C" int misplat_textquery_upsample(int32_t in_h, int32_t in_w, const floa
     const size_t P = (size_t)out_h * out_w;
     hipLaunchKernelGGL(upsample_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (int)in_h, (int)in_w, in,
                        (int)out_h, (int)out_w, out);
-    return check_launch();
+    return launched();
 }
