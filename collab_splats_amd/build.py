@@ -73,6 +73,9 @@ SOURCES = {
     "pointtsdf.hip": ["-ffp-contract=off"],
     # identity.hip: contraction allowed, as featloss.hip (the logits are multiply-add chains; the test oracle is fp64)
     "identity.hip": [],
+    # evalmetrics.hip: contraction allowed, as ssim.hip, whose filter it runs (multiply-add chains; the test oracle is fp64);
+    # the per-pixel normal and depth arithmetic is fp64 and the integer counts do not depend on it
+    "evalmetrics.hip": [],
 }
 
 

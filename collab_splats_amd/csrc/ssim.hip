@@ -25,28 +25,10 @@
 #include <cstdint>
 
 #include "misplat.h"
+#include "ssimwin.h"                            // kTile, kWin, kPatch, Window, make_window(), kSsimC1 / kSsimC2
 #include "wgprims.h"
 
 namespace {
-
-constexpr int kTile = 16;
-constexpr int kWin = 11;
-constexpr int kPatch = kTile + kWin - 1;        // 26
-
-struct Window { float w[kWin]; };
-
-// pytorch_msssim._fspecial_gauss_1d(11, 1.5): float32 exp of -(c^2) / (2 sigma^2), normalised by the float32 sum
-Window make_window() {
-    Window W;
-    float sum = 0.f;
-    for (int i = 0; i < kWin; i++) {
-        const float c = (float)(i - kWin / 2);
-        W.w[i] = expf(-(c * c) / (2.0f * 1.5f * 1.5f));
-        sum += W.w[i];
-    }
-    for (int i = 0; i < kWin; i++) W.w[i] /= sum;
-    return W;
-}
 
 // maps: [3][3 channels][OH][OW] (d ssim / d E[x], / d E[xx], / d E[xy]); partials: one float per workgroup.
 // One workgroup = one 16 x 16 tile of window positions, ALL THREE channels: the 26 x 26 x 3 patch of each image is read
@@ -54,10 +36,7 @@ Window make_window() {
 // not by memory (one output per thread and pass: 77 LDS reads per output, 84 us at 1080p), so both passes are register
 // tiled: a thread filters FOUR adjacent outputs from 14 values it reads once (row pass: 312 (channel, row, column-quad)
 // items; column pass: 192 (channel, row-quad, column) items) -- 2.5 x fewer LDS operations, three barriers per workgroup.
-constexpr int kRow3 = 3 * kPatch;               // 78 floats of a patch row
-constexpr int kRowS = kRow3 + 1;                // LDS row stride (odd: the stride-3 channel walk stays conflict-free)
-constexpr int kHzS = 20;                        // row stride of the row-pass results: row quads 16 banks apart
-constexpr int kQuads = kTile / 4;
+// (the LDS layout constants kRow3, kRowS, kHzS, kQuads: ssimwin.h)
 __global__ __launch_bounds__(256) void ssim_fwd_kernel(int H, int Wd, const float* __restrict__ rgb, const float* __restrict__ gt,
                                                        Window win, float C1, float C2, float* __restrict__ maps,
                                                        float* __restrict__ partials) {
@@ -323,8 +302,8 @@ extern "C" int misplat_ssim_fwd(int32_t height, int32_t width, const float* rgb,
     float* maps = scratch;
     float* partials = scratch + 9 * (size_t)OH * OW;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(ssim_fwd_kernel, grid, dim3(256), 0, s, (int)height, (int)width, rgb, gt, make_window(), 0.01f * 0.01f,
-                       0.03f * 0.03f, maps, partials);
+    hipLaunchKernelGGL(ssim_fwd_kernel, grid, dim3(256), 0, s, (int)height, (int)width, rgb, gt, make_window(), kSsimC1,
+                       kSsimC2, maps, partials);
     hipLaunchKernelGGL(ssim_final_kernel, dim3(1), dim3(1024), 0, s, (int)(grid.x * grid.y), partials,
                        1.0 / (3.0 * (double)OH * (double)OW), 1.0 / (3.0 * (double)height * (double)width), l1_loss,
                        ssim_lambda, ssim, main_loss);

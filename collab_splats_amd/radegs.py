@@ -1248,6 +1248,97 @@ class RadegsModel(nn.Module):
             loss_dict["tv_loss"] = 10 * ops.bilagrid_tv_loss(self.bil_grids.grids)
         return loss_dict
 
+    # ------------------------------------------------------------------------------------------------------- evaluation
+    @property
+    def num_points(self) -> int:
+        return int(self.means.shape[0])
+
+    def composite_with_background(self, image: Tensor, background: Tensor) -> Tensor:
+        """Splatfacto's ``composite_with_background`` [UNVERIFIED-UPSTREAM]: an RGBA ground truth goes over the background
+        the render was composited on (alpha * rgb + (1 - alpha) * background); an RGB one is returned as it is."""
+        if image.shape[-1] == 4:
+            alpha = image[..., 3:4]
+            return alpha * image[..., :3] + (1 - alpha) * background.to(image.device)
+        return image
+
+    def _eval_pair(self, outputs, batch) -> Tuple[Tensor, Tensor]:
+        """(rgb, gt): the render and the ground truth it is scored against, float32 [H, W, 3] on the render's device."""
+        rgb = outputs["rgb"]
+        gt = self.composite_with_background(self.get_gt_img(batch["image"].to(rgb.device)), outputs["background"])
+        return rgb.detach().to(torch.float32).contiguous(), gt.detach().to(torch.float32).contiguous()
+
+    @torch.no_grad()
+    def get_metrics_dict(self, outputs, batch) -> Dict[str, Union[Tensor, int]]:
+        """Splatfacto's ``get_metrics_dict`` [UNVERIFIED-UPSTREAM], which it calls on every training step: ``psnr`` (a device
+        scalar: ``metrics.image_metrics(..., ssim=False)``, two launches, no host read) of the render against the ground
+        truth over the render's background, ``gaussian_count``, and the camera optimizer's entries when there is one."""
+        from .metrics import image_metrics
+        rgb, gt = self._eval_pair(outputs, batch)
+        metrics_dict: Dict[str, Union[Tensor, int]] = {"psnr": image_metrics(rgb, gt, ssim=False)["psnr"][0],
+                                                       "gaussian_count": self.num_points}
+        if self.config.camera_optimizer_mode != "off":
+            self.camera_optimizer.get_metrics_dict(metrics_dict)
+        return metrics_dict
+
+    @torch.no_grad()
+    def get_image_metrics_and_images(self, outputs, batch) -> Tuple[Dict[str, float], Dict[str, Tensor]]:
+        """Splatfacto's ``get_image_metrics_and_images`` [UNVERIFIED-UPSTREAM], what an evaluation run calls for each view:
+        ``({"psnr", "ssim"} as floats, {"img": the ground truth and the render side by side, [H, 2 W, 3]})``.  One fused
+        metric call and one host read.  There is no ``"lpips"`` key: LPIPS is a trained network whose weights are not
+        part of this package, and nothing is downloaded."""
+        from .metrics import image_metrics
+        rgb, gt = self._eval_pair(outputs, batch)
+        m = image_metrics(rgb, gt, ssim=True)
+        psnr, ssim = torch.stack((m["psnr"][0], m["ssim"][0])).tolist()
+        return {"psnr": float(psnr), "ssim": float(ssim)}, {"img": torch.cat([gt, rgb], dim=1)}
+
+    @torch.no_grad()
+    def evaluate_views(self, cameras: Sequence, images: Sequence, normals: Optional[Sequence] = None,
+                       depths: Optional[Sequence] = None, valid: Optional[Sequence] = None, batch_size: int = 4) -> Dict[str, Dict]:
+        """Scores the model on ``cameras`` against their ground truth: ``batch_size`` views at a time are rendered by
+        ``render_views`` and scored on the device (``metrics.image_metrics`` / ``normal_metrics`` / ``depth_metrics``); the
+        one host read is at the end.  ``images`` [V] of [H, W, 3 or 4] (uint8 or float; RGBA goes over the model's background);
+        ``normals`` (or None) [V] of [H, W, 3] maps in the 0..1 encoding of the model's ``normals`` output; ``depths`` (or
+        None) [V] of [H, W] or [H, W, 1], compared with the rendered ``depth``; ``valid`` (or None) [V] of [H, W] bool masks for
+        the normal and depth scores.  Returns ``{"per_view": {name: [V] device tensor}, "mean": {name: float}}`` with the
+        names ``psnr ssim mse l1``, ``normal_mean normal_a11.25 normal_a22.5 normal_a30 normal_count`` and ``depth_abs_rel
+        depth_sq_rel depth_rmse depth_rmse_log depth_delta1 depth_delta2 depth_delta3 depth_count``.  A view's scores do not
+        depend on the batch it was in."""
+        from .metrics import depth_metrics, image_metrics, normal_metrics
+        cameras = list(cameras)
+        V, bs = len(cameras), max(1, int(batch_size))
+        for name, seq in (("images", images), ("normals", normals), ("depths", depths), ("valid", valid)):
+            if seq is not None and len(seq) != V:
+                raise ValueError(f"evaluate_views: {V} cameras but {len(seq)} {name}")
+        if V == 0:
+            raise ValueError("evaluate_views: no cameras")
+        dev = self.device
+        background = self._get_background_color()
+
+        def stack(seq, lo, hi, prepare):
+            return torch.stack([prepare(seq[i].to(dev)) for i in range(lo, hi)]).contiguous()
+
+        per_view: Dict[str, List[Tensor]] = {}
+        for lo in range(0, V, bs):
+            hi = min(lo + bs, V)
+            maps = self.render_views(cameras[lo:hi], batch_size=bs)
+            gt = stack(images, lo, hi, lambda t: self.composite_with_background(self.get_gt_img(t), background).to(torch.float32))
+            scores = dict(image_metrics(maps["rgb"], gt, ssim=True))
+            mask = None if valid is None else stack(valid, lo, hi, lambda t: t.reshape(t.shape[0], t.shape[1]).bool())
+            if normals is not None:
+                n = normal_metrics(maps["normals"], stack(normals, lo, hi, lambda t: t.to(torch.float32)), mask, encoded=True)
+                scores.update({"normal_" + k: v for k, v in n.items()})
+            if depths is not None:
+                d = depth_metrics(maps["depth"], stack(depths, lo, hi, lambda t: t.to(torch.float32).reshape(t.shape[0], t.shape[1])),
+                                  mask)
+                scores.update({"depth_" + k: v for k, v in d.items()})
+            for k, v in scores.items():
+                per_view.setdefault(k, []).append(v)
+        result = {k: torch.cat(v) for k, v in per_view.items()}
+        names = list(result)
+        means = torch.stack([result[k].mean() for k in names]).tolist()                 # the one host read
+        return {"per_view": result, "mean": {k: float(m) for k, m in zip(names, means)}}
+
     def get_gaussian_param_groups(self) -> Dict[str, List[nn.Parameter]]:
         """One optimizer group per Gaussian parameter (Splatfacto's ``get_gaussian_param_groups``)."""
         return {name: [self.gauss_params[name]] for name in self.gauss_params.keys()}

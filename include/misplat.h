@@ -1355,6 +1355,32 @@ int misplat_identity_3d_bwd(int64_t n_rows, int32_t dim, const float* identities
                             const int64_t* rev_offsets, const int32_t* rev_slots, float* scratch, const int32_t* counts,
                             const float* g_loss, float* v_identities, float* v_weight, float* v_bias, misplat_stream_t stream);
 
+/* ---- Evaluation metrics (csrc/evalmetrics.hip): per-view scores of B stacked views, two launches
+ * each (per-workgroup partial sums, then one workgroup per view adds them in fp64 in an order that depends on H and W
+ * only), no atomics, no host read.  All: 1 <= n_views <= 65535, height * width < 2^31, NULL where not allowed or a
+ * size outside that is MISPLAT_EINVAL.  Images are [B, H, W, C] fp32, channel-interleaved.
+ *
+ * Image scores: out [B, 4] = {mse, l1, ssim, psnr}: means over the 3 H W values of (pred - gt)^2 and |pred - gt|; the
+ * valid-region SSIM of the training loss (11-tap gaussian window, sigma 1.5, (H - 10) x (W - 10) positions, C1 = 0.01^2,
+ * C2 = 0.03^2), NaN when want_ssim == 0; psnr = -10 log10(mse) (+inf for mse == 0).  want_ssim needs H, W >= 11.
+ * scratch: the floats the _scratch_floats call returns (-1 for sizes out of range). */
+int64_t misplat_eval_image_scratch_floats(int32_t n_views, int32_t height, int32_t width);
+int misplat_eval_image(int32_t n_views, int32_t height, int32_t width, const float* pred, const float* gt, int32_t want_ssim,
+                       float* scratch, float* out, misplat_stream_t stream);
+/* Normals: pred, gt [B, H, W, 3]; valid (or NULL) [B, H, W] bytes, 0 = excluded; encoded: v <- 2 v - 1 first; normalize:
+ * both vectors scaled to unit length, a pixel with a squared length <= 1e-12 excluded.  theta = acos(clamp(dot, -1, 1)).
+ * out [B, 5] = {mean theta (radians), fraction theta < 11.25 deg, < 22.5 deg, < 30 deg, count}; NaN means and fractions for
+ * count == 0.  map (or NULL) [B, H, W]: every pixel's theta, NaN where excluded.  Depth: pred, gt [B, H, W]; a pixel counts
+ * where valid (or NULL) is non-zero, both depths are finite and > 0 and gt <= max_depth (max_depth <= 0: no limit).
+ * out [B, 8] = {abs_rel, sq_rel, rmse, rmse_log, delta < 1.25, < 1.25^2, < 1.25^3, count} (Eigen et al. 2014).
+ * scratch: the floats the one _scratch_floats call returns, 8-byte aligned. */
+int64_t misplat_eval_pixels_scratch_floats(int32_t n_views, int32_t height, int32_t width);
+int misplat_eval_normals(int32_t n_views, int32_t height, int32_t width, const float* pred, const float* gt,
+                         const uint8_t* valid, int32_t encoded, int32_t normalize, float* map, float* scratch, float* out,
+                         misplat_stream_t stream);
+int misplat_eval_depth(int32_t n_views, int32_t height, int32_t width, const float* pred, const float* gt,
+                       const uint8_t* valid, float max_depth, float* scratch, float* out, misplat_stream_t stream);
+
 /* Library identification ("misplat <version> gfx950"). */
 const char* misplat_version(void);
 
