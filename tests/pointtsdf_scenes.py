@@ -15,19 +15,22 @@ def opengl_c2w(M):
     return (np.linalg.inv(np.asarray(M, np.float64)) @ np.diag([1.0, -1.0, -1.0, 1.0]))[:3, :4].astype(np.float32)
 
 
-def sphere_scan(n=8, W=48, H=36, centre=(0.1, -0.05, 0.2), radius=0.5, dist=1.6):
+def sphere_scan(n=8, W=48, H=36, centre=(0.1, -0.05, 0.2), radius=0.5, dist=1.6, shift=(0.0, 0.0, 0.0)):
     """n views of a sphere: dict(depths [n,H,W,1], c2w [n,3,4], intr [n,4], rgbs [n,H,W,3], views: [(points, origin, colours)])
-    with the points lifted analytically (origin + ray * depth in float64, then float32)."""
+    with the points lifted analytically (origin + ray * depth in float64, then float32).  ``shift``: the views' points and
+    origins and ``centre`` translated by it, in float64 before the cast (the maps and the poses stay where they are)."""
     d, vms, Ks, rgb = S.sphere_views(n, W, H, centre=centre, radius=radius, dist=dist)
+    shift = np.asarray(shift, np.float64)
     views = []
     for k in range(n):
         o, dirs = S._rays(vms[k].astype(np.float64), Ks[k].astype(np.float64), W, H)
+        o = o + shift
         dep = d[k, ..., 0].astype(np.float64)
         hit = dep > 0
         views.append(((o + dirs[hit] * dep[hit][:, None]).astype(np.float32), o.astype(np.float32), rgb[k][hit]))
     intr = np.stack([Ks[:, 0, 0], Ks[:, 1, 1], Ks[:, 0, 2], Ks[:, 1, 2]], 1).astype(np.float32)
     return dict(depths=d, c2w=np.stack([opengl_c2w(M) for M in vms]), intr=intr, rgbs=rgb, views=views,
-                centre=np.asarray(centre), radius=radius, vms=vms, Ks=Ks)
+                centre=np.asarray(centre) + shift, radius=radius, vms=vms, Ks=Ks)
 
 
 def clump(scan, view=0, at=0.2, n=20, side=0.05, seed=3):
@@ -53,6 +56,15 @@ def column_rays(vs, repeat, nx=6, ny=6, length=12, at=(3, -2, 5)):
     p = np.concatenate([xy, np.full((len(xy), 1), (at[2] + 0.5) * vs)], 1)
     o = p + np.array([0.0, 0.0, length * vs])
     return np.repeat(p, repeat, 0).astype(np.float32), np.repeat(o, repeat, 0).astype(np.float32)
+
+
+def fan(vs, n, seed=7):
+    """n rays from one origin (voxel (2, 4, 7) of unit (0, 0, 0)) into one small patch 30 voxels away, with colours: every ray
+    passes the origin's voxel, so that voxel counts exactly n and its unit's list holds n rays.  (points, origin [3], colours)."""
+    rng = np.random.default_rng(seed)
+    o = (np.array([2.3, 4.6, 7.2]) * vs).astype(np.float32)
+    p = (o + np.array([30.0, 22.0, 17.0]) * vs + rng.uniform(-2, 2, (n, 3)) * vs).astype(np.float32)
+    return p, o, rng.random((n, 3)).astype(np.float32)
 
 
 def edge_rays(vs, n=320, reach=24.0, offset=0.0, seed=0):

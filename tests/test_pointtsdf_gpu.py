@@ -198,11 +198,9 @@ def test_flush_boundary_of_the_lds_sums():
     partial sum may hold, so its list is flushed in several pieces (of 8192 rays, by integer atomics); the origin's voxel counts
     exactly 70 000 and every integer equals the restatement's."""
     n = 70000
-    rng = np.random.default_rng(7)
-    o = (np.array([2.3, 4.6, 7.2]) * VS).astype(np.float32)
-    p = (o + np.array([30.0, 22.0, 17.0]) * VS + rng.uniform(-2, 2, (n, 3)) * VS).astype(np.float32)
+    p, o, c = PS.fan(VS, n)
     vol, ref = _volume(True)
-    _both(vol, ref, p, o, rng.random((n, 3)).astype(np.float32))
+    _both(vol, ref, p, o, c)
     coords, sum_q, count = vol.units()[:3]
     k = int(np.nonzero((coords == 0).all(1))[0][0])
     i = 2 | (4 << 4) | (7 << 8)
