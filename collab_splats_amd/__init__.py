@@ -32,7 +32,8 @@ from .density import DensityField, gaussian_density, gaussian_density_grad, leve
 from .pointtsdf import PointTSDFVolume  # noqa: F401
 from .identity import (IdentityField, IdentityNeighbours, identity_3d_loss, identity_labels, identity_loss,  # noqa: F401
                        identity_neighbours)
-from .metrics import depth_metrics, image_metrics, mean_angular_error, normal_metrics, psnr, ssim  # noqa: F401
+from .metrics import (color_correct, color_corrected_metrics, depth_metrics, image_metrics, mean_angular_error,  # noqa: F401
+                      normal_metrics, psnr, ssim)
 from .grouping import FrontGaussians, MemoryBank, convert_matched_mask, front_gaussians, project_gaussians  # noqa: F401
 
 __version__ = "0.1.0"

@@ -173,6 +173,7 @@ SYMBOLS = {
     "misplat_identity_3d_fwd": (C.c_int, 14), "misplat_identity_3d_bwd": (C.c_int, 19),
     "misplat_eval_image_scratch_floats": (C.c_int64, 3), "misplat_eval_image": (C.c_int, 9),
     "misplat_eval_pixels_scratch_floats": (C.c_int64, 3), "misplat_eval_normals": (C.c_int, 12), "misplat_eval_depth": (C.c_int, 10),
+    "misplat_colorcorrect_scratch_floats": (C.c_int64, 3), "misplat_colorcorrect": (C.c_int, 12),
     "misplat_version": (C.c_char_p, 0),
 }
 

@@ -76,6 +76,10 @@ SOURCES = {
     # evalmetrics.hip: contraction allowed, as ssim.hip, whose filter it runs (multiply-add chains; the test oracle is fp64);
     # the per-pixel normal and depth arithmetic is fp64 and the integer counts do not depend on it
     "evalmetrics.hip": [],
+    # colorcorrect.hip: fixed IEEE operation order: the warp's sum ((a0 w0 + a1 w1) + a2 w2) + ... rounds every product and sum
+    # on its own, so the numpy fp64 restatement (tests/) reproduces the image bit for bit from the device's fit; the
+    # accumulation's multiply-adds are written as explicit fma
+    "colorcorrect.hip": ["-ffp-contract=off"],
 }
 
 

@@ -6,8 +6,11 @@ nerfstudio's Splatfacto reports from ``get_metrics_dict`` and ``get_image_metric
 ``PeakSignalNoiseRatio(data_range=1.0)`` and ``structural_similarity_index_measure``) [UNVERIFIED-UPSTREAM]; the SSIM is the
 training loss's valid-region index.  ``mean_angular_error`` is collab_splats/utils/utils.py:63-81.  DESIGN.md section 34.
 
-Every function is two launches on the current stream and returns device tensors; none reads anything back to the host.
-There is no CPU fallback.
+``color_correct`` / ``color_corrected_metrics`` (csrc/colorcorrect.hip) warp a render onto its ground
+truth's colours before it is scored: Splatfacto's ``color_corrected_metrics``, for models trained with the bilateral grid.
+
+Every metric is two launches on the current stream (the colour correction three per round) and returns device tensors; none
+reads anything back to the host.  There is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -177,3 +180,49 @@ def depth_metrics(pred: Tensor, gt: Tensor, valid: Optional[Tensor] = None, max_
           "misplat_eval_depth")
     names = ("abs_rel", "sq_rel", "rmse", "rmse_log", "delta1", "delta2", "delta3", "count")
     return {k: out[:, i] for i, k in enumerate(names)}
+
+
+# ------------------------------------------------------------------------------------------- colour-corrected metrics
+MAX_COLOR_ITERS = 64
+
+
+@torch.no_grad()
+def color_correct(pred: Tensor, gt: Tensor, num_iters: int = 5, eps: float = 0.5 / 255, return_fit: bool = False):
+    """``pred`` warped onto ``gt``'s colours (csrc/colorcorrect.hip): multinerf's ``color_correct`` as
+    nerfstudio carries it for Splatfacto's ``color_corrected_metrics``, restated from the published method
+    [UNVERIFIED-UPSTREAM].  Both [B, H, W, 3] or [H, W, 3] float32 on the GPU with values in 0..1; the result has ``pred``'s
+    shape.  ``num_iters`` times, per view and output channel: a least-squares fit of gt's channel on the 10 monomials (r^2,
+    rg, rb, g^2, gb, b^2, r, g, b, 1) of the current image over the pixels where pred's channel, the current image's and
+    gt's all lie in [eps, 1 - eps] (fp64 normal equations, eigenvalues <= 2^-46 of the largest dropped, minimum norm), then
+    the fit applied to every pixel and clipped to 0..1.  ``num_iters=0`` returns a copy of ``pred``.
+
+    With ``return_fit``: ``(corrected, {"warps": [B, num_iters, 10, 3] float64, "counts": [B, num_iters, 3] int64})``, every
+    round's coefficients and the number of pixels that counted.  Three launches per round, no host read."""
+    what = "color_correct"
+    single = isinstance(pred, Tensor) and pred.dim() == 3
+    pred, gt = _views(pred, 3, what, "pred"), _views(gt, 3, what, "gt")
+    B, H, W = _sizes(pred, gt, what)
+    if isinstance(num_iters, bool) or not isinstance(num_iters, int) or not 0 <= num_iters <= MAX_COLOR_ITERS:
+        raise ValueError(f"{what}: num_iters must be an int in 0..{MAX_COLOR_ITERS}, got {num_iters!r}")
+    eps = float(eps)
+    if not 0.0 <= eps < 0.5:
+        raise ValueError(f"{what}: eps must be in [0, 0.5), got {eps}")
+    require_gpu(pred, gt)
+    lib = _lib.load()
+    pred, gt = pred.detach().contiguous(), gt.detach().contiguous()
+    scratch = _scratch(lib.misplat_colorcorrect_scratch_floats, B, H, W, pred.device, what)
+    out = torch.empty_like(pred)
+    warps = torch.empty(B, num_iters, 10, 3, device=pred.device, dtype=torch.float64)
+    counts = torch.empty(B, num_iters, 3, device=pred.device, dtype=torch.int64)
+    check(lib.misplat_colorcorrect(C.c_int32(B), C.c_int32(H), C.c_int32(W), ptr(pred), ptr(gt), C.c_int32(num_iters),
+                                   C.c_float(eps), ptr(scratch), ptr(out), ptr(warps), ptr(counts), stream_ptr()),
+          "misplat_colorcorrect")
+    if single:
+        out = out[0]
+    return (out, {"warps": warps, "counts": counts}) if return_fit else out
+
+
+def color_corrected_metrics(pred: Tensor, gt: Tensor, ssim: bool = True, num_iters: int = 5, eps: float = 0.5 / 255) -> Dict[str, Tensor]:
+    """Per-view ``{"cc_psnr", "cc_ssim", "cc_mse", "cc_l1"}`` ([B] float32 device tensors; no ``"cc_ssim"`` with
+    ``ssim=False``): ``image_metrics(color_correct(pred, gt, num_iters, eps), gt, ssim)`` under Splatfacto's names."""
+    return {"cc_" + k: v for k, v in image_metrics(color_correct(pred, gt, num_iters, eps), gt, ssim).items()}

@@ -228,6 +228,10 @@ class RadegsModelConfig:
     camera_optimizer_mode: str = "off"
     camera_opt_trans_l2_penalty: float = 1e-2
     camera_opt_rot_l2_penalty: float = 1e-3
+    # Splatfacto's ``color_corrected_metrics`` [UNVERIFIED-UPSTREAM]: evaluation also reports cc_psnr / cc_ssim, the scores of
+    # the render after ``metrics.color_correct`` has warped it onto the ground truth's colours (what a model trained with
+    # ``use_bilateral_grid`` is judged by: no grid applies to a held-out view)
+    color_corrected_metrics: bool = False
 
 
 class RadegsModel(nn.Module):
@@ -1284,17 +1288,24 @@ class RadegsModel(nn.Module):
     def get_image_metrics_and_images(self, outputs, batch) -> Tuple[Dict[str, float], Dict[str, Tensor]]:
         """Splatfacto's ``get_image_metrics_and_images`` [UNVERIFIED-UPSTREAM], what an evaluation run calls for each view:
         ``({"psnr", "ssim"} as floats, {"img": the ground truth and the render side by side, [H, 2 W, 3]})``.  One fused
-        metric call and one host read.  There is no ``"lpips"`` key: LPIPS is a trained network whose weights are not
-        part of this package, and nothing is downloaded."""
-        from .metrics import image_metrics
+        metric call and one host read.  With the config's ``color_corrected_metrics`` also ``"cc_psnr"`` and ``"cc_ssim"``
+        (``metrics.color_corrected_metrics``), in the same host read.  There is no ``"lpips"`` key: LPIPS is a trained
+        network whose weights are not part of this package, and nothing is downloaded."""
+        from .metrics import color_corrected_metrics, image_metrics
         rgb, gt = self._eval_pair(outputs, batch)
         m = image_metrics(rgb, gt, ssim=True)
-        psnr, ssim = torch.stack((m["psnr"][0], m["ssim"][0])).tolist()
-        return {"psnr": float(psnr), "ssim": float(ssim)}, {"img": torch.cat([gt, rgb], dim=1)}
+        names, values = ["psnr", "ssim"], [m["psnr"][0], m["ssim"][0]]
+        if self.config.color_corrected_metrics:
+            cc = color_corrected_metrics(rgb, gt, ssim=True)
+            names += ["cc_psnr", "cc_ssim"]
+            values += [cc["cc_psnr"][0], cc["cc_ssim"][0]]
+        scores = torch.stack(values).tolist()                                          # the one host read
+        return {k: float(v) for k, v in zip(names, scores)}, {"img": torch.cat([gt, rgb], dim=1)}
 
     @torch.no_grad()
     def evaluate_views(self, cameras: Sequence, images: Sequence, normals: Optional[Sequence] = None,
-                       depths: Optional[Sequence] = None, valid: Optional[Sequence] = None, batch_size: int = 4) -> Dict[str, Dict]:
+                       depths: Optional[Sequence] = None, valid: Optional[Sequence] = None, batch_size: int = 4,
+                       color_correct: Optional[bool] = None) -> Dict[str, Dict]:
         """Scores the model on ``cameras`` against their ground truth: ``batch_size`` views at a time are rendered by
         ``render_views`` and scored on the device (``metrics.image_metrics`` / ``normal_metrics`` / ``depth_metrics``); the
         one host read is at the end.  ``images`` [V] of [H, W, 3 or 4] (uint8 or float; RGBA goes over the model's background);
@@ -1302,9 +1313,12 @@ class RadegsModel(nn.Module):
         None) [V] of [H, W] or [H, W, 1], compared with the rendered ``depth``; ``valid`` (or None) [V] of [H, W] bool masks for
         the normal and depth scores.  Returns ``{"per_view": {name: [V] device tensor}, "mean": {name: float}}`` with the
         names ``psnr ssim mse l1``, ``normal_mean normal_a11.25 normal_a22.5 normal_a30 normal_count`` and ``depth_abs_rel
-        depth_sq_rel depth_rmse depth_rmse_log depth_delta1 depth_delta2 depth_delta3 depth_count``.  A view's scores do not
-        depend on the batch it was in."""
-        from .metrics import depth_metrics, image_metrics, normal_metrics
+        depth_sq_rel depth_rmse depth_rmse_log depth_delta1 depth_delta2 depth_delta3 depth_count``, and with ``color_correct``
+        (None: the config's ``color_corrected_metrics``) ``cc_psnr cc_ssim cc_mse cc_l1``, the image scores of the
+        colour-corrected render.  A view's scores do not depend on the batch it was in."""
+        from .metrics import color_corrected_metrics, depth_metrics, image_metrics, normal_metrics
+        if color_correct is None:
+            color_correct = self.config.color_corrected_metrics
         cameras = list(cameras)
         V, bs = len(cameras), max(1, int(batch_size))
         for name, seq in (("images", images), ("normals", normals), ("depths", depths), ("valid", valid)):
@@ -1324,6 +1338,8 @@ class RadegsModel(nn.Module):
             maps = self.render_views(cameras[lo:hi], batch_size=bs)
             gt = stack(images, lo, hi, lambda t: self.composite_with_background(self.get_gt_img(t), background).to(torch.float32))
             scores = dict(image_metrics(maps["rgb"], gt, ssim=True))
+            if color_correct:
+                scores.update(color_corrected_metrics(maps["rgb"], gt, ssim=True))
             mask = None if valid is None else stack(valid, lo, hi, lambda t: t.reshape(t.shape[0], t.shape[1]).bool())
             if normals is not None:
                 n = normal_metrics(maps["normals"], stack(normals, lo, hi, lambda t: t.to(torch.float32)), mask, encoded=True)

@@ -1381,6 +1381,20 @@ int misplat_eval_normals(int32_t n_views, int32_t height, int32_t width, const f
 int misplat_eval_depth(int32_t n_views, int32_t height, int32_t width, const float* pred, const float* gt,
                        const uint8_t* valid, float max_depth, float* scratch, float* out, misplat_stream_t stream);
 
+/* ---- Colour-corrected evaluation (csrc/colorcorrect.hip): pred [B, H, W, 3] fp32 is warped onto gt's
+ * colours by num_iters rounds of a masked least-squares fit of the 10 quadratic monomials (r^2, rg, rb, g^2, gb, b^2, r, g,
+ * b, 1) per output channel: fp64 normal equations, symmetric eigensolve, eigenvalues <= 2^-46 lambda_max dropped; a pixel
+ * counts for channel c where pred_c, the current image's c and gt_c all lie in [eps, 1 - eps] (fp32 comparisons); the
+ * warp is applied to every pixel and clipped to 0..1.  Three launches per round, no atomics, no host read; a view's
+ * result does not depend on n_views.  corrected [B, H, W, 3] fp32 (not pred or gt; pred's bits for num_iters == 0);
+ * warps [B, num_iters, 10, 3] fp64 and counts [B, num_iters, 3] int64: each round's fit and mask counts (may be NULL for
+ * num_iters == 0).  1 <= n_views <= 65535, height * width < 2^31, 0 <= num_iters <= 64, 0 <= eps < 0.5: anything else is
+ * MISPLAT_EINVAL before any launch.  scratch: the floats the _scratch_floats call returns (-1 for sizes out of range), 8-byte
+ * aligned. */
+int64_t misplat_colorcorrect_scratch_floats(int32_t n_views, int32_t height, int32_t width);
+int misplat_colorcorrect(int32_t n_views, int32_t height, int32_t width, const float* pred, const float* gt, int32_t num_iters,
+                         float eps, float* scratch, float* corrected, double* warps, int64_t* counts, misplat_stream_t stream);
+
 /* Library identification ("misplat <version> gfx950"). */
 const char* misplat_version(void);
 
