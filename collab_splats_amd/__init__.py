@@ -9,6 +9,8 @@ from ._lib import MisplatError, load as load_library  # noqa: F401
 from .rendering import rasterization  # noqa: F401
 from .wrapper import fully_fused_projection, spherical_harmonics  # noqa: F401
 from .strategy import DefaultStrategy, MCMCStrategy  # noqa: F401
+from .mcmc import (RelocationStrategy, compute_relocation, inject_noise_to_position, relocate, sample_add,  # noqa: F401
+                   sample_by_opacity)
 from .ops import set_deterministic  # noqa: F401
 from .optim import FusedAdam, step_all as fused_adam_step_all  # noqa: F401
 from .tsdf import TSDFVolume, write_ply  # noqa: F401

@@ -174,6 +174,8 @@ SYMBOLS = {
     "misplat_eval_image_scratch_floats": (C.c_int64, 3), "misplat_eval_image": (C.c_int, 9),
     "misplat_eval_pixels_scratch_floats": (C.c_int64, 3), "misplat_eval_normals": (C.c_int, 12), "misplat_eval_depth": (C.c_int, 10),
     "misplat_colorcorrect_scratch_floats": (C.c_int64, 3), "misplat_colorcorrect": (C.c_int, 12),
+    "misplat_mcmc_noise": (C.c_int, 9), "misplat_mcmc_sample_workspace_bytes": (C.c_int64, 1),
+    "misplat_mcmc_sample": (C.c_int, 13), "misplat_mcmc_relocation": (C.c_int, 9),
     "misplat_version": (C.c_char_p, 0),
 }
 

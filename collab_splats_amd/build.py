@@ -80,6 +80,9 @@ SOURCES = {
     # on its own, so the numpy fp64 restatement (tests/) reproduces the image bit for bit from the device's fit; the
     # accumulation's multiply-adds are written as explicit fma
     "colorcorrect.hip": ["-ffp-contract=off"],
+    # mcmc.hip: fixed IEEE operation order: the noise step rounds its displacement d to fp32 on its own and then adds it, so
+    # the update equals fl32(mean + d) bit for bit; the sampler is integer work and the relocation's sums are fp64 in written order
+    "mcmc.hip": ["-ffp-contract=off"],
 }
 
 

@@ -1,6 +1,6 @@
-// hashmix.h -- the counter-based 32-bit hash shared by meshclean.hip (RANSAC draws) and depthcloud.hip
-// (pixel sampling keys, section 19): two rounds of a 32-bit finaliser over (seed, i, draw).  The restatements under tests/
-// hold the same arithmetic in uint32.
+// hashmix.h -- the counter-based 32-bit hash shared by meshclean.hip (RANSAC draws), depthcloud.hip
+// (pixel sampling keys, section 19) and mcmc.hip (noise and sampling draws, section 36): two rounds of a 32-bit finaliser over
+// (seed, i, draw).  The restatements under tests/ hold the same arithmetic in uint32.
 #pragma once
 #include <stdint.h>
 

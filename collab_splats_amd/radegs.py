@@ -232,6 +232,18 @@ class RadegsModelConfig:
     # the render after ``metrics.color_correct`` has warped it onto the ground truth's colours (what a model trained with
     # ``use_bilateral_grid`` is judged by: no grid applies to a held-out view)
     color_corrected_metrics: bool = False
+    # Splatfacto's ``strategy`` field and its MCMC settings [UNVERIFIED-UPSTREAM]: "default" (adaptive density control,
+    # strategy.DefaultStrategy) | "mcmc" (fixed budget ``cap_max``, mcmc.RelocationStrategy), with the two
+    # regularisers the MCMC method trains under: mcmc_opacity_reg * mean(opacity) and mcmc_scale_reg * mean(scale)
+    strategy: str = "default"
+    cap_max: int = 1_000_000
+    noise_lr: float = 5e5
+    mcmc_opacity_reg: float = 0.01
+    mcmc_scale_reg: float = 0.01
+
+    def __post_init__(self):
+        if self.strategy not in ("default", "mcmc"):
+            raise ValueError(f"RadegsModelConfig: strategy must be 'default' or 'mcmc', got {self.strategy!r}")
 
 
 class RadegsModel(nn.Module):
@@ -267,7 +279,13 @@ class RadegsModel(nn.Module):
             "opacities": nn.Parameter(opacities.reshape(-1, 1)), "features_dc": nn.Parameter(features_dc),
             "features_rest": nn.Parameter(features_rest)})
         self.step = 0
-        self.strategy = DefaultStrategy(absgrad=config.absgrad)
+        if config.strategy == "default":
+            self.strategy = DefaultStrategy(absgrad=config.absgrad)
+        elif config.strategy == "mcmc":
+            from .mcmc import RelocationStrategy
+            self.strategy = RelocationStrategy(cap_max=int(config.cap_max), noise_lr=float(config.noise_lr))
+        else:
+            raise ValueError(f"RadegsModel: strategy must be 'default' or 'mcmc', got {config.strategy!r}")
         self.strategy_state = self.strategy.initialize_state()
         self.optimizers: Dict = {}
         self.info: Dict = {}
@@ -1225,7 +1243,7 @@ class RadegsModel(nn.Module):
                 loss_dict["scale_reg"] = self._scale_reg(rgb.device)
             if with_dn:
                 loss_dict["depth_normal_loss"] = dn_loss
-            return self._add_camera_opt_loss(self._add_tv_loss(loss_dict))
+            return self._add_mcmc_reg(self._add_camera_opt_loss(self._add_tv_loss(loss_dict)))
         if gt is not None:
             if self.config.ssim_lambda > 0:
                 raise MisplatError(f"get_loss_dict: main_loss (L1 + SSIM) takes float32 images of equal shape on the GPU; got "
@@ -1236,7 +1254,17 @@ class RadegsModel(nn.Module):
         if with_dn:
             depth_normal_loss = ((1 - self.config.depth_ratio) * e1.mean() + self.config.depth_ratio * e2.mean())
             loss_dict["depth_normal_loss"] = self.config.depth_normal_lambda * depth_normal_loss
-        return self._add_camera_opt_loss(self._add_tv_loss(loss_dict))
+        return self._add_mcmc_reg(self._add_camera_opt_loss(self._add_tv_loss(loss_dict)))
+
+    def _add_mcmc_reg(self, loss_dict: Dict[str, Tensor]) -> Dict[str, Tensor]:
+        """Splatfacto's MCMC regularisers [UNVERIFIED-UPSTREAM] (Kheradmand et al. 2024, section 4.3), while training with
+        ``strategy="mcmc"``: ``opacity_reg`` = mcmc_opacity_reg * mean(sigmoid(opacities)) and mcmc_scale_reg *
+        mean(exp(scales)) added to ``scale_reg``; otherwise the dict as it is.  Two plain reductions a step."""
+        if self.config.strategy == "mcmc" and self.training:
+            loss_dict["opacity_reg"] = self.config.mcmc_opacity_reg * torch.sigmoid(self.opacities).mean()
+            scale_reg = self.config.mcmc_scale_reg * torch.exp(self.scales).mean()
+            loss_dict["scale_reg"] = loss_dict["scale_reg"] + scale_reg if "scale_reg" in loss_dict else scale_reg
+        return loss_dict
 
     def _add_camera_opt_loss(self, loss_dict: Dict[str, Tensor]) -> Dict[str, Tensor]:
         """Splatfacto's ``camera_optimizer.get_loss_dict`` [UNVERIFIED-UPSTREAM]: the L2 regulariser of the pose adjustments,

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Minimal training loop on the MI355X: RadegsModel (host mirror of the reference's rade-gs model) +
 one (fused) Adam optimizer per parameter group (learning rates of collab_splats/configs/rade_gs_method.py:44-71)
-+ DefaultStrategy densification, fitting renders of a hidden synthetic scene from a ring of cameras.
++ DefaultStrategy densification (or, with ``--strategy mcmc``, the fixed-budget RelocationStrategy: relocation, growth up to
+1.5 x the initial count and position noise), fitting renders of a hidden synthetic scene from a ring of cameras.
 
-    python examples/train_synthetic.py [--steps 300] [--gaussians 20000] [--width 320] [--height 200]
+    python examples/train_synthetic.py [--steps 300] [--gaussians 20000] [--width 320] [--height 200] [--strategy mcmc]
 """
 import argparse
 import math
@@ -42,11 +43,12 @@ LRS = {"means": 1.6e-4 * 10, "features_dc": 2.5e-3, "features_rest": 2.5e-3 / 20
        "quats": 1e-3}
 
 
-def train(steps=300, n=20000, W=320, H=200, n_views=8, refine_every=50, seed=0, verbose=True):
+def train(steps=300, n=20000, W=320, H=200, n_views=8, refine_every=50, seed=0, verbose=True, strategy="default"):
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(seed)
     sc = random_scene(n, W, H, seed=42 + seed)
-    cfg = radegs.RadegsModelConfig(rasterize_mode="antialiased", sh_degree_interval=1, regularization_from_iter=steps // 2)
+    cfg = radegs.RadegsModelConfig(rasterize_mode="antialiased", sh_degree_interval=1, regularization_from_iter=steps // 2,
+                                   strategy=strategy, cap_max=int(1.5 * n))
     truth = build_model(sc, cfg, dev).eval()
     cams = [ring_camera(i, n_views, W, H) for i in range(n_views)]
     with torch.no_grad():
@@ -55,7 +57,11 @@ def train(steps=300, n=20000, W=320, H=200, n_views=8, refine_every=50, seed=0, 
                         generator=g).train()
     model.step = 10                                    # all SH degrees active
     model.strategy.refine_start_iter, model.strategy.refine_every = 0, refine_every
-    model.strategy.grow_grad2d, model.strategy.refine_stop_iter = 2e-4, steps
+    model.strategy.refine_stop_iter = steps
+    if strategy == "default":
+        model.strategy.grow_grad2d = 2e-4
+    else:
+        model.strategy.seed = seed
     # one FusedAdam per parameter group (the interface the strategy edits), all stepped by ONE kernel launch
     model.optimizers = {k: FusedAdam([v], lr=LRS[k], eps=1e-15) for k, v in model.gauss_params.items()}
     log = []
@@ -70,11 +76,15 @@ def train(steps=300, n=20000, W=320, H=200, n_views=8, refine_every=50, seed=0, 
         loss = sum(losses.values())
         loss.backward()
         fused_adam_step_all(model.optimizers)
-        counts = model.strategy.step_post_backward(model.gauss_params, model.optimizers, model.strategy_state, it + 1, model.info)
+        # (the MCMC controller scales its position noise by the means group's current learning rate)
+        post = {"lr": model.optimizers["means"].param_groups[0]["lr"]} if strategy == "mcmc" else {}
+        counts = model.strategy.step_post_backward(model.gauss_params, model.optimizers, model.strategy_state, it + 1, model.info,
+                                                   **post)
         log.append((losses["main_loss"].item(), model.means.shape[0], counts))
         if verbose and (it % 50 == 0 or it == steps - 1):
             extra = "".join(f"  {k} {v.item():.5f}" for k, v in losses.items())
-            print(f"step {it:4d}{extra}  gaussians {model.means.shape[0]}  dup/split/prune {counts}")
+            what = "dup/split/prune" if strategy == "default" else "relocated/added"
+            print(f"step {it:4d}{extra}  gaussians {model.means.shape[0]}  {what} {counts}")
     torch.cuda.synchronize()
     if verbose:
         print(f"{steps} steps in {time.perf_counter() - t0:.2f} s")
@@ -87,5 +97,6 @@ if __name__ == "__main__":
     ap.add_argument("--gaussians", type=int, default=20000)
     ap.add_argument("--width", type=int, default=320)
     ap.add_argument("--height", type=int, default=200)
+    ap.add_argument("--strategy", choices=("default", "mcmc"), default="default")
     a = ap.parse_args()
-    train(a.steps, a.gaussians, a.width, a.height)
+    train(a.steps, a.gaussians, a.width, a.height, strategy=a.strategy)

@@ -1395,6 +1395,39 @@ int64_t misplat_colorcorrect_scratch_floats(int32_t n_views, int32_t height, int
 int misplat_colorcorrect(int32_t n_views, int32_t height, int32_t width, const float* pred, const float* gt, int32_t num_iters,
                          float eps, float* scratch, float* corrected, double* warps, int64_t* counts, misplat_stream_t stream);
 
+/* ---- MCMC densification (csrc/mcmc.hip): Kheradmand et al. 2024, restated from the published method.
+ * seed and step are the two words of the counter-based generator (csrc/hashmix.h): the same pair gives the same bits in
+ * every run, on every rank and under any launch shape.  All: 1 <= n, m < 2^31, a NULL where none is allowed is
+ * MISPLAT_EINVAL before any launch.
+ *
+ * Noise, every training step, in place on means [n, 3]: with o = sigmoid(opacities[i]) (logits), s = exp(scales[i]) (logs),
+ * R the rotation of the normalised wxyz quats[i] (16-byte aligned), g = 1 / (1 + exp(-100 ((1 - o) - 0.995))) and z three
+ * standard normals (Box-Muller over the words mix32(mix32(seed, step, 1), i, 0..3)):
+ * means[i] += fl32(R diag(s^2) R^T (z g scaler)).  One launch. */
+#define MISPLAT_MCMC_N_MAX 51    /* the largest ratio of the relocation; binoms is at most [51, 51] */
+#define MISPLAT_MCMC_NOTHING 1   /* *status of misplat_mcmc_sample: every weight is 0 */
+int misplat_mcmc_noise(int64_t n, float* means, const float* opacities, const float* scales, const float* quats, float scaler,
+                       uint32_t seed, uint32_t step, misplat_stream_t stream);
+/* Sampling: m draws with replacement from the n ACTIVATED opacities [n] fp32, in exact integer arithmetic.  Row i weighs
+ * q_i = (uint32)(min(o_i, 1) 2^24), 0 for o_i <= 0 or NaN and, when has_min_opacity, for o_i <= min_opacity; draw j is the
+ * first i with incl[i] > (u_j total) >> 64, incl the int64 inclusive sum of q, total = incl[n - 1], u_j the 64 bits
+ * mix32(k, j, 0) << 32 | mix32(k, j, 1), k = mix32(seed, step, 2).  A row of weight 0 is never drawn.  idx [m] int64;
+ * counts (or NULL) [n] int32 = how often each row was drawn (zeroed here, then integer atomics: order-independent);
+ * status [1] int32 on the device = 0, or MISPLAT_MCMC_NOTHING when total == 0 (idx is then -1 throughout and counts 0;
+ * nothing is divided).  workspace: misplat_mcmc_sample_workspace_bytes(n) bytes (-1 for n out of range), 8-byte aligned. */
+int64_t misplat_mcmc_sample_workspace_bytes(int64_t n);
+int misplat_mcmc_sample(int64_t n, const float* opacities, int32_t has_min_opacity, float min_opacity, int64_t m, uint32_t seed,
+                        uint32_t step, void* workspace, int64_t workspace_bytes, int64_t* idx, int32_t* counts, int32_t* status,
+                        misplat_stream_t stream);
+/* Relocation (the paper's Eq. 9) of m entries: opacities [m] (activated), scales [m, 3] (activated), ratios [m] int32, clamped
+ * to 1 .. n_max here; binoms [n_max, n_max] fp64, binoms[i][k] = C(i, k) (0 for k > i), 1 <= n_max <= MISPLAT_MCMC_N_MAX.
+ *   o' = 1 - (1 - o)^(1 / n)   (as -expm1(log1p(-o) / n));
+ *   D = sum_{i = 1..n} sum_{k = 0..i-1} C(i - 1, k) (-1)^k / sqrt(k + 1) o'^(k + 1), in fp64 in this order;
+ *   s' = (o / D) s   (s for o <= 0).
+ * new_opacities [m] = o', new_scales [m, 3] = s', each rounded to fp32 once. */
+int misplat_mcmc_relocation(int64_t m, const float* opacities, const float* scales, const int32_t* ratios, const double* binoms,
+                            int32_t n_max, float* new_opacities, float* new_scales, misplat_stream_t stream);
+
 /* Library identification ("misplat <version> gfx950"). */
 const char* misplat_version(void);
 
