@@ -13,6 +13,7 @@ from .mcmc import (RelocationStrategy, compute_relocation, inject_noise_to_posit
                    sample_by_opacity)
 from .ops import set_deterministic  # noqa: F401
 from .optim import FusedAdam, step_all as fused_adam_step_all  # noqa: F401
+from .optim import SelectiveAdam, selective_step_all as selective_adam_step_all, visibility_from_radii  # noqa: F401
 from .tsdf import TSDFVolume, write_ply  # noqa: F401
 from .meshmap import features2vertex, normals2vertex  # noqa: F401
 from .meshquery import cluster_labels, mesh_clustering, query_similarity, similarity_colors  # noqa: F401

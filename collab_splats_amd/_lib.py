@@ -120,6 +120,7 @@ SYMBOLS = {
     "misplat_graph_cache_destroy": (None, 1), "misplat_graph_cache_stats": (C.c_int, 3), "misplat_wait_count": (C.c_int64, 2), "misplat_zero_bytes": (C.c_int, 3), "misplat_stream_copy": (C.c_int, 5),
     "misplat_touched_bits": (C.c_int, 4), "misplat_union_count": (C.c_int, 5), "misplat_union_scan": (C.c_int, 5), "misplat_union_ids": (C.c_int, 7),
     "misplat_rows_pack": (C.c_int, 8), "misplat_rows_unpack": (C.c_int, 8),
+    "misplat_adam_step_rows": (C.c_int, 16), "misplat_visible_rows": (C.c_int, 5),
     "misplat_debug_memset_replay": (C.c_int, 5),
     "misplat_tsdf_mark": (C.c_int, 10), "misplat_tsdf_alloc": (C.c_int, 6), "misplat_tsdf_integrate": (C.c_int, 14),
     "misplat_unit_lists": (C.c_int, 12),

@@ -283,3 +283,142 @@ extern "C" int misplat_rows_unpack(int32_t n_tensors, float* const* dsts, const 
                                    int64_t n_ids, const int64_t* count_dev, const float* packed, misplat_stream_t stream) {
     return rows_move(false, n_tensors, dsts, widths, ids, n_ids, count_dev, (float*)packed, (hipStream_t)stream);
 }
+
+// ---- row-selective Adam (optim.SelectiveAdam; gsplat users know it as SelectiveAdam / visible_adam) -------------------------
+// Only the rows of an ascending id list are stepped (the Gaussians visible in the step's views; the list comes from
+// misplat_visible_rows or any other byte-per-row flags through touched_bits / union_count / union_scan / union_ids with
+// world = 1); every other row keeps p, exp_avg and exp_avg_sq bit for bit.  One launch covers up to MISPLAT_ADAM_MAX_TENSORS
+// tensors of different widths, one pass per tensor: a grid-stride loop over count x width elements, lanes consecutive along
+// a row and on into the next listed row, so neighbouring ids make one contiguous stream.  (One loop over count x W packed
+// columns, rows_move_kernel's mapping, looks every lane's tensor up per element: 9 loads beside the 7 of the step itself, and
+// 2.1 TB/s at full density at 5 M rows where this form reaches 4.9.)  The count lives on the device.  The host-side scalars are
+// misplat_adam_step's and the arithmetic is adam_kernel's (adam_as_dense): a selected row gets the bits the dense kernel
+// gives it.  Rows of width 3 are not 16-byte aligned: plain dword loads and stores, no atomics.
+namespace {
+
+// adam_one as adam_kernel's code object evaluates it.  This file allows contraction and the compiler takes it where it finds
+// it: in the float4 body both moment updates are fused multiply-adds (v_pk_fma_f32: m = fma(g - m, 1 - b1, m),
+// v = fma((1 - b2) g, g, b2 v)); in the scalar tail -- the last numel % 4 elements of a tensor -- the two products of an
+// element are packed into one v_pk_mul_f32 first, which leaves nothing to fuse.  The parameter update is an fma in both.
+// Inlined into a third kernel adam_one is contracted a third way, so the row kernel spells out which of the two an element
+// gets in the dense kernel; tests/test_selective_adam_gpu.py holds the two kernels to the same bits, tail elements included.
+__device__ __forceinline__ void adam_as_dense(bool tail, float& p, float g, float& m, float& v, float omb1, float b2, float omb2,
+                                              float eps, float step_size, float sb2) {
+#pragma clang fp contract(off)
+    if (tail) {
+        m = m + (g - m) * omb1;
+        v = b2 * v + omb2 * g * g;
+    } else {
+        m = __builtin_fmaf(g - m, omb1, m);
+        v = __builtin_fmaf(omb2 * g, g, b2 * v);
+    }
+    const float denom = sqrtf(v) / sb2 + eps;
+    p = __builtin_fmaf(-step_size, m / denom, p);
+}
+
+struct AdamRowTable {
+    float* p[MISPLAT_ADAM_MAX_TENSORS];
+    const float* g[MISPLAT_ADAM_MAX_TENSORS];
+    float* m[MISPLAT_ADAM_MAX_TENSORS];
+    float* v[MISPLAT_ADAM_MAX_TENSORS];
+    int32_t width[MISPLAT_ADAM_MAX_TENSORS];
+    float step_size[MISPLAT_ADAM_MAX_TENSORS];
+    float sqrt_bias2[MISPLAT_ADAM_MAX_TENSORS];
+    int32_t count;
+};
+
+constexpr int kRowsBlock = 256;
+constexpr int64_t kRowsMaxBlocks = 16384;
+
+__global__ __launch_bounds__(kRowsBlock) void adam_rows_kernel(AdamRowTable T, const int32_t* __restrict__ ids, int64_t ids_cap,
+                                                               const int64_t* __restrict__ count_dev, int64_t n_rows, float omb1,
+                                                               float b2, float omb2, float eps) {
+    int64_t have = *count_dev;
+    if (have > ids_cap) have = ids_cap;                   // (a count the list cannot hold: never read past the list)
+    // The tensors one after the other (pointers, width and scalars of a pass are uniform: SGPRs); inside a pass a grid-stride
+    // loop over have x width elements, lanes consecutive along a row and on into the next listed row.  (slot u, column c) of
+    // a lane's element and the grid's stride are carried in that form: one 32-bit division per lane and pass, none per element.
+    const uint32_t lanes = gridDim.x * kRowsBlock, i0 = blockIdx.x * kRowsBlock + threadIdx.x;     // (at most 2^22)
+    for (int t = 0; t < T.count; t++) {
+        float* __restrict__ p = T.p[t];
+        const float* __restrict__ g = T.g[t];
+        float* __restrict__ m = T.m[t];
+        float* __restrict__ v = T.v[t];
+        const uint32_t w = (uint32_t)T.width[t];
+        const float ss = T.step_size[t], sb2 = T.sqrt_bias2[t];
+        const int64_t tail_from = (n_rows * w) & ~(int64_t)3;      // (from here on the dense kernel runs its scalar tail)
+        const uint32_t du = lanes / w, dc = lanes - du * w;
+        int64_t u = i0 / w;
+        uint32_t c = i0 - (uint32_t)u * w;
+        for (; u < have; u += du) {
+            const int64_t row = ids[u];
+            if (row >= 0 && row < n_rows) {               // (an id outside the tensors is skipped, never dereferenced)
+                const int64_t j = row * w + c;
+                float pp = p[j], mm = m[j], vv = v[j];
+                adam_as_dense(j >= tail_from, pp, g[j], mm, vv, omb1, b2, omb2, eps, ss, sb2);
+                p[j] = pp; m[j] = mm; v[j] = vv;
+            }
+            c += dc;
+            if (c >= w) { c -= w; u++; }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void visible_rows_kernel(const int2* __restrict__ radii, int32_t n_cams, int64_t n_rows,
+                                                           uint8_t* __restrict__ flags) {
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= n_rows) return;
+    uint8_t f = 0;
+    for (int cam = 0; cam < n_cams; cam++) {
+        const int2 q = radii[(int64_t)cam * n_rows + r];
+        if (q.x > 0 && q.y > 0) f = 1;
+    }
+    flags[r] = f;
+}
+
+}  // namespace
+
+extern "C" int misplat_adam_step_rows(int32_t n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,
+                                      float* const* exp_avg_sq, const int32_t* widths, int64_t n_rows, const float* lr,
+                                      const int64_t* step, double beta1, double beta2, double eps, const int32_t* ids,
+                                      int64_t ids_cap, const int64_t* count_dev, misplat_stream_t stream) {
+    if (n_tensors < 0 || n_tensors > MISPLAT_ADAM_MAX_TENSORS || n_rows < 0 || n_rows > 0x7fffffffLL || ids_cap < 0 ||
+        ids_cap > n_rows)
+        return MISPLAT_EINVAL;
+    if (n_tensors == 0) return MISPLAT_OK;
+    if (!params || !grads || !exp_avg || !exp_avg_sq || !widths || !lr || !step) return MISPLAT_EINVAL;
+    AdamRowTable T;
+    int64_t widest = 0;
+    for (int i = 0; i < n_tensors; i++) {
+        if (widths[i] < 1 || widths[i] > 0x3fffffff || step[i] < 1) return MISPLAT_EINVAL;   // (two columns add up in 32 bits)
+        if (n_rows > 0 && (!params[i] || !grads[i] || !exp_avg[i] || !exp_avg_sq[i])) return MISPLAT_EINVAL;
+        T.p[i] = params[i]; T.g[i] = grads[i]; T.m[i] = exp_avg[i]; T.v[i] = exp_avg_sq[i];
+        T.width[i] = widths[i];
+        const double bias1 = 1.0 - pow(beta1, (double)step[i]);
+        const double bias2 = 1.0 - pow(beta2, (double)step[i]);
+        T.step_size[i] = (float)((double)lr[i] / bias1);
+        T.sqrt_bias2[i] = (float)sqrt(bias2);
+        if (widths[i] > widest) widest = widths[i];
+    }
+    if (ids_cap == 0) return MISPLAT_OK;
+    if (!ids || !count_dev) return MISPLAT_EINVAL;
+    for (int i = n_tensors; i < MISPLAT_ADAM_MAX_TENSORS; i++) {
+        T.p[i] = T.m[i] = T.v[i] = nullptr; T.g[i] = nullptr; T.width[i] = 0; T.step_size[i] = T.sqrt_bias2[i] = 0.f;
+    }
+    T.count = n_tensors;
+    int64_t blocks = (ids_cap * widest + kRowsBlock - 1) / kRowsBlock;          // (both below 2^31)
+    if (blocks > kRowsMaxBlocks) blocks = kRowsMaxBlocks;
+    hipLaunchKernelGGL(adam_rows_kernel, dim3((unsigned)blocks), dim3(kRowsBlock), 0, (hipStream_t)stream, T, ids, ids_cap, count_dev,
+                       n_rows, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps);
+    return launched();
+}
+
+extern "C" int misplat_visible_rows(const int32_t* radii, int32_t n_cams, int64_t n_rows, uint8_t* flags, misplat_stream_t stream) {
+    if (n_cams < 1 || n_rows < 0 || (n_rows > 0 && (!radii || !flags)) || (((uintptr_t)radii) & 7)) return MISPLAT_EINVAL;
+    if (n_rows == 0) return MISPLAT_OK;
+    const int64_t blocks = (n_rows + 255) / 256;
+    if (blocks > 0x7fffffffLL) return MISPLAT_EINVAL;
+    hipLaunchKernelGGL(visible_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const int2*>(radii), n_cams, n_rows, flags);
+    return launched();
+}

@@ -5,6 +5,10 @@ The reference trains with one ``torch.optim.Adam`` per parameter group (nerfstud
 keeps that interface (``param_groups``, ``state[p]["exp_avg"|"exp_avg_sq"|"step"]``, so the densification
 strategy's optimizer-state surgery works unchanged) and ``step_all`` updates every group of every optimizer in
 ONE kernel launch (``misplat_adam_step``) instead of ~6 x 5 elementwise kernels.
+
+``SelectiveAdam`` is the same optimizer stepped under a row mask (the Gaussians visible in the step's views,
+``visibility_from_radii``): ``selective_step_all`` lists the flagged rows on the device and ``misplat_adam_step_rows`` steps
+those rows only -- DESIGN.md section 37.
 """
 from __future__ import annotations
 
@@ -99,3 +103,134 @@ def _launch(entries: List[tuple]) -> None:
             for _, st, _, _, _, _ in chunk:              # a refused launch has stepped nothing: the counts stay too
                 st["step"] += 1
             del keep
+
+
+# ---- row-selective Adam: only the Gaussians visible in the step's views are stepped ----------------------------------------
+
+class SelectiveAdam(FusedAdam):
+    """A ``FusedAdam`` (same hyper-parameters, same ``state`` layout, so the densification strategies edit it unchanged) whose
+    ``step`` takes a row mask: ``visibility`` is a bool or uint8 GPU tensor ``[N]`` and every parameter that has a gradient
+    has ``shape[0] == N``.  Rows with flag 1 get the bits ``FusedAdam`` gives them; rows with flag 0 keep the parameter,
+    ``exp_avg`` and ``exp_avg_sq`` bit for bit.  ``state["step"]`` advances by one for every parameter that has a gradient,
+    whatever the mask, and the bias correction uses that count (the convention of ``torch.optim.SparseAdam``).  gsplat
+    users know the idea as ``SelectiveAdam`` / ``visible_adam``; parity with its kernel is unpinned.
+    Data-parallel replicas must pass the same mask to stay identical."""
+
+    @torch.no_grad()
+    def step(self, visibility, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        _launch_rows(self._entries(), visibility)
+        return loss
+
+
+@torch.no_grad()
+def selective_step_all(optimizers: Iterable[SelectiveAdam] | Dict[str, SelectiveAdam], visibility: torch.Tensor) -> None:
+    """Step all parameters of several ``SelectiveAdam`` instances under one row mask: the id list is built once, then one row
+    launch per distinct (betas, eps) and per chunk of 8 tensors."""
+    if isinstance(optimizers, dict):
+        optimizers = optimizers.values()
+    entries: List[tuple] = []
+    for opt in optimizers:
+        if not isinstance(opt, SelectiveAdam):
+            raise TypeError("selective_step_all() takes SelectiveAdam optimizers")
+        entries += opt._entries()
+    _launch_rows(entries, visibility)
+
+
+@torch.no_grad()
+def visibility_from_radii(radii: torch.Tensor) -> torch.Tensor:
+    """uint8 ``[N]`` from the projection's ``info["radii"]`` (int32 ``[C, N, 2]``): 1 where both radii are positive for some
+    camera, i.e. ``(radii > 0).all(-1).any(0)``."""
+    if not isinstance(radii, torch.Tensor) or not radii.is_cuda:
+        raise _lib.MisplatError("visibility_from_radii: radii must be a tensor on the GPU (no CPU fallback)")
+    if radii.dtype != torch.int32 or radii.dim() != 3 or radii.shape[0] < 1 or radii.shape[2] != 2:
+        raise _lib.MisplatError("visibility_from_radii: radii must be int32 [C, N, 2] with C >= 1")
+    radii = radii.contiguous()
+    n = radii.shape[1]
+    flags = torch.empty(n, device=radii.device, dtype=torch.uint8)
+    with torch.cuda.device(radii.device):
+        check(_lib.load().misplat_visible_rows(_lib.ptr(radii), C.c_int32(radii.shape[0]), C.c_int64(n), _lib.ptr(flags),
+                                               stream_ptr()), "misplat_visible_rows")
+    return flags
+
+
+_row_ws: Dict[torch.device, dict] = {}                   # the row list's work arrays, one set per device, kept from step to step
+
+
+def _row_list(visibility: torch.Tensor):
+    """(ids, count): the ascending ids of the flagged rows in an int32 list of capacity N and their number, which stays on the
+    device.  Four small launches over work arrays that live from step to step (as ``parallel.GradientBuckets._ws``)."""
+    lib = _lib.load()
+    n, dev = visibility.numel(), visibility.device
+    nbytes = (n + 7) // 8
+    n_blocks = (nbytes + 255) // 256
+    ws = _row_ws.get(dev)
+    if ws is None or ws["n"] != n:
+        ws = _row_ws[dev] = dict(n=n, flags=torch.empty(n, device=dev, dtype=torch.uint8),
+                                 bits=torch.empty(nbytes, device=dev, dtype=torch.uint8),
+                                 counts=torch.empty(n_blocks, device=dev, dtype=torch.int32),
+                                 offs=torch.empty(n_blocks, device=dev, dtype=torch.int64),
+                                 total=torch.empty(1, device=dev, dtype=torch.int64),
+                                 ids=torch.empty(n, device=dev, dtype=torch.int32))
+    flags = visibility
+    if not flags.is_contiguous() or flags.data_ptr() % 8:   # (misplat_touched_bits reads 8 flags at a time)
+        flags = ws["flags"].copy_(visibility)
+    s = stream_ptr()
+    check(lib.misplat_touched_bits(C.c_void_p(flags.data_ptr()), C.c_int64(n), _lib.ptr(ws["bits"]), s), "misplat_touched_bits")
+    check(lib.misplat_union_count(_lib.ptr(ws["bits"]), C.c_int32(1), C.c_int64(nbytes), _lib.ptr(ws["counts"]), s),
+          "misplat_union_count")
+    check(lib.misplat_union_scan(_lib.ptr(ws["counts"]), C.c_int64(n_blocks), _lib.ptr(ws["offs"]), _lib.ptr(ws["total"]), s),
+          "misplat_union_scan")
+    check(lib.misplat_union_ids(_lib.ptr(ws["bits"]), C.c_int32(1), C.c_int64(nbytes), _lib.ptr(ws["offs"]), _lib.ptr(ws["ids"]),
+                                C.c_int64(n), s), "misplat_union_ids")
+    return ws["ids"], ws["total"]
+
+
+def _launch_rows(entries: List[tuple], visibility) -> None:
+    # everything is checked before anything is launched: a refused step moves neither a row nor a step count
+    if not isinstance(visibility, torch.Tensor) or not visibility.is_cuda:
+        raise _lib.MisplatError("SelectiveAdam: visibility must be a tensor on the GPU (no CPU fallback)")
+    if visibility.dtype not in (torch.bool, torch.uint8) or visibility.dim() != 1:
+        raise _lib.MisplatError("SelectiveAdam: visibility must be a bool or uint8 tensor [N]")
+    if not entries:
+        return
+    n = visibility.numel()
+    grads = []
+    for p, st, _, _, _, _ in entries:
+        if p.dim() < 1 or p.shape[0] != n:
+            raise _lib.MisplatError(f"SelectiveAdam: a parameter of shape {tuple(p.shape)} under a mask of {n} rows")
+        if p.device != visibility.device:
+            raise _lib.MisplatError("SelectiveAdam: parameters and visibility must be on the same device")
+        if not p.is_contiguous() or not st["exp_avg"].is_contiguous() or not st["exp_avg_sq"].is_contiguous():
+            raise _lib.MisplatError("SelectiveAdam: parameters and their moments must be contiguous")
+        if st["exp_avg"].shape != p.shape or st["exp_avg_sq"].shape != p.shape:
+            raise _lib.MisplatError("SelectiveAdam: the moments must have the parameter's shape")
+        if p.grad.dtype != torch.float32 or p.grad.shape != p.shape:
+            raise _lib.MisplatError("SelectiveAdam: gradient must be float32 with the parameter's shape")
+        grads.append(p.grad if p.grad.is_contiguous() else p.grad.contiguous())   # (the copies outlive the launches)
+    by_hyper: Dict[tuple, List[tuple]] = {}
+    for e, g in zip(entries, grads):
+        if e[0].numel():
+            by_hyper.setdefault(e[3:], []).append(e + (g,))
+        else:                                            # (a tensor of no elements has nothing to step but its count)
+            e[1]["step"] += 1
+    lib = _lib.load()
+    with torch.cuda.device(visibility.device):
+        if by_hyper:
+            ids, count = _row_list(visibility)
+        for (b1, b2, eps), es in by_hyper.items():
+            for i in range(0, len(es), MAX_TENSORS):
+                chunk = es[i:i + MAX_TENSORS]
+                k = len(chunk)
+                vp = C.c_void_p * k
+                check(lib.misplat_adam_step_rows(
+                    C.c_int32(k), vp(*[e[0].data_ptr() for e in chunk]), vp(*[e[6].data_ptr() for e in chunk]),
+                    vp(*[e[1]["exp_avg"].data_ptr() for e in chunk]), vp(*[e[1]["exp_avg_sq"].data_ptr() for e in chunk]),
+                    (C.c_int32 * k)(*[e[0].numel() // n for e in chunk]), C.c_int64(n), (C.c_float * k)(*[e[2] for e in chunk]),
+                    (C.c_int64 * k)(*[int(e[1]["step"].item()) + 1 for e in chunk]), C.c_double(b1), C.c_double(b2),
+                    C.c_double(eps), _lib.ptr(ids), C.c_int64(n), _lib.ptr(count), stream_ptr()), "misplat_adam_step_rows")
+                for e in chunk:                          # (whatever the mask holds: the count is the step's, not the row's)
+                    e[1]["step"] += 1

@@ -5,6 +5,9 @@ one (fused) Adam optimizer per parameter group (learning rates of collab_splats/
 1.5 x the initial count and position noise), fitting renders of a hidden synthetic scene from a ring of cameras.
 
     python examples/train_synthetic.py [--steps 300] [--gaussians 20000] [--width 320] [--height 200] [--strategy mcmc]
+                                       [--visible-adam]
+
+``--visible-adam``: the groups are ``SelectiveAdam`` and a step updates only the Gaussians visible in its view.
 """
 import argparse
 import math
@@ -15,7 +18,8 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from collab_splats_amd import FusedAdam, fused_adam_step_all, radegs  # noqa: E402
+from collab_splats_amd import (FusedAdam, SelectiveAdam, fused_adam_step_all, radegs, selective_adam_step_all,  # noqa: E402
+                               visibility_from_radii)
 from collab_splats_amd.synthetic import random_scene  # noqa: E402
 
 
@@ -43,7 +47,8 @@ LRS = {"means": 1.6e-4 * 10, "features_dc": 2.5e-3, "features_rest": 2.5e-3 / 20
        "quats": 1e-3}
 
 
-def train(steps=300, n=20000, W=320, H=200, n_views=8, refine_every=50, seed=0, verbose=True, strategy="default"):
+def train(steps=300, n=20000, W=320, H=200, n_views=8, refine_every=50, seed=0, verbose=True, strategy="default",
+          visible_adam=False):
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(seed)
     sc = random_scene(n, W, H, seed=42 + seed)
@@ -63,7 +68,8 @@ def train(steps=300, n=20000, W=320, H=200, n_views=8, refine_every=50, seed=0, 
     else:
         model.strategy.seed = seed
     # one FusedAdam per parameter group (the interface the strategy edits), all stepped by ONE kernel launch
-    model.optimizers = {k: FusedAdam([v], lr=LRS[k], eps=1e-15) for k, v in model.gauss_params.items()}
+    Adam = SelectiveAdam if visible_adam else FusedAdam
+    model.optimizers = {k: Adam([v], lr=LRS[k], eps=1e-15) for k, v in model.gauss_params.items()}
     log = []
     t0 = time.perf_counter()
     for it in range(steps):
@@ -75,7 +81,10 @@ def train(steps=300, n=20000, W=320, H=200, n_views=8, refine_every=50, seed=0, 
         losses = model.get_loss_dict(out, {"image": tgt})
         loss = sum(losses.values())
         loss.backward()
-        fused_adam_step_all(model.optimizers)
+        if visible_adam:
+            selective_adam_step_all(model.optimizers, visibility_from_radii(model.info["radii"]))
+        else:
+            fused_adam_step_all(model.optimizers)
         # (the MCMC controller scales its position noise by the means group's current learning rate)
         post = {"lr": model.optimizers["means"].param_groups[0]["lr"]} if strategy == "mcmc" else {}
         counts = model.strategy.step_post_backward(model.gauss_params, model.optimizers, model.strategy_state, it + 1, model.info,
@@ -98,5 +107,6 @@ if __name__ == "__main__":
     ap.add_argument("--width", type=int, default=320)
     ap.add_argument("--height", type=int, default=200)
     ap.add_argument("--strategy", choices=("default", "mcmc"), default="default")
+    ap.add_argument("--visible-adam", action="store_true")
     a = ap.parse_args()
-    train(a.steps, a.gaussians, a.width, a.height, strategy=a.strategy)
+    train(a.steps, a.gaussians, a.width, a.height, strategy=a.strategy, visible_adam=a.visible_adam)

@@ -670,6 +670,20 @@ int misplat_adam_step(int32_t n_tensors, float* const* params, const float* cons
                       const float* lr, const int64_t* step, double beta1, double beta2, double eps,
                       misplat_stream_t stream);
 
+/* ---- row-selective Adam (optim.SelectiveAdam): the same step on the rows of an id list only (the Gaussians visible in the
+ * step's views); every other row keeps its parameter and both moments bit for bit.  n_tensors (<= 8) row-major tensors of
+ * n_rows rows and widths[i] floats per row; ids[ids_cap] (device, ids_cap <= n_rows): ascending row ids, of which the first
+ * *count_dev (device, never read on the host) are valid -- union_ids / union_scan below write both.  lr, step (t >= 1, already
+ * incremented -- for every tensor, whatever the list holds: torch SparseAdam's convention), beta1 / beta2 / eps as
+ * misplat_adam_step; a listed row gets the bits misplat_adam_step gives it.  One launch, no host read, no allocation.
+ * visible_rows: flags[r] = 1 where both radii of radii[n_cams][n_rows][2] (int32, 8-byte aligned) are positive for some
+ * camera, else 0 -- the flags touched_bits takes. */
+int misplat_adam_step_rows(int32_t n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,
+                           float* const* exp_avg_sq, const int32_t* widths, int64_t n_rows, const float* lr,
+                           const int64_t* step, double beta1, double beta2, double eps, const int32_t* ids, int64_t ids_cap,
+                           const int64_t* count_dev, misplat_stream_t stream);
+int misplat_visible_rows(const int32_t* radii, int32_t n_cams, int64_t n_rows, uint8_t* flags, misplat_stream_t stream);
+
 /* ---- shared-Gaussian gradient reduce that moves only the rows that have a gradient (the gradient
  * set of collab_splats/configs/rade_gs_method.py:44-71; csrc/optim.hip, driven by collab_splats_amd/parallel.py).
  *   touched_bits  bits[ceil(n_rows / 8)]: bit (r & 7) of byte r >> 3 = flags[r] != 0 (flags: misplat_params.touched, 8-byte
