@@ -1,5 +1,10 @@
 """ctypes binding of libmisplat.so (the C ABI declared in include/misplat.h).
 
+``SYMBOLS`` holds the signature of every entry point; ``load()`` sets ``restype`` and ``argtypes`` from it, so call sites pass
+plain Python values and ctypes converts each to the C type the header declares (a float for an ``int64_t`` raises).  ``run``
+calls an entry that returns a status on the current stream.  A new entry point needs its prototype in the header and its
+signature string here; tests/test_abi.py derives the strings from the header and requires the two equal.
+
 There is NO fallback: if the HIP library is missing or a call fails this module raises.  The
 CPU restatements under ``oracle/`` are test infrastructure and are never imported from here.
 """
@@ -94,90 +99,97 @@ def make_params(n_gauss: int, n_cams: int, width: int, height: int, tile_size: i
                   int(ed_slot), 0, None, None, None)
 
 
-# name -> (restype, n_args); every symbol include/misplat.h declares
+# The signature of every symbol include/misplat.h declares: one letter for the return, a space, one letter per argument.
+#   arguments: p pointer, s misplat_stream_t, i int / int32_t, q int64_t, f float, d double, u uint32_t, Q size_t
+#   returns:   i status, q int64_t, p pointer, v void, z const char*
+# tests/test_abi.py derives the same strings from the header's prototypes and requires them equal.
+_ARG = {"p": C.c_void_p, "s": C.c_void_p, "i": C.c_int32, "q": C.c_int64, "f": C.c_float, "d": C.c_double,
+        "u": C.c_uint32, "Q": C.c_uint64}
+_RET = {"i": C.c_int, "q": C.c_int64, "p": C.c_void_p, "v": None, "z": C.c_char_p}
 SYMBOLS = {
-    "misplat_project_fwd": (C.c_int, 16), "misplat_project_bwd": (C.c_int, 18),
-    "misplat_project_bwd_pose_workspace": (C.c_int64, 2), "misplat_project_bwd_pose": (C.c_int, 17),
-    "misplat_project_pack_fwd": (C.c_int, 17), "misplat_color_fwd": (C.c_int, 16),
-    "misplat_color_bwd": (C.c_int, 16), "misplat_project_pack_bwd": (C.c_int, 20),
-    "misplat_sh_fwd": (C.c_int, 9), "misplat_sh_bwd": (C.c_int, 11),
-    "misplat_isect_ids": (C.c_int, 6), "misplat_tile_sort": (C.c_int, 10),
-    "misplat_adam_step": (C.c_int, 12), "misplat_pack": (C.c_int, 11),
-    "misplat_blend_fwd": (C.c_int, 15), "misplat_blend_fwd_lazy": (C.c_int, 23), "misplat_blend_bwd": (C.c_int, 21),
-    "misplat_color_fwd_x": (C.c_int, 11), "misplat_color_bwd_x": (C.c_int, 9),
-    "misplat_blend_fwd_x": (C.c_int, 17), "misplat_blend_bwd_x_atomic": (C.c_int, 22),
-    "misplat_blend_planes": (C.c_int, 1), "misplat_blend_bwd_atomic": (C.c_int, 20), "misplat_slab_reduce": (C.c_int, 11), "misplat_depth_normal_fwd": (C.c_int, 10),
-    "misplat_depth_normal_bwd": (C.c_int, 14), "misplat_outputs_fwd": (C.c_int, 15), "misplat_outputs_bwd": (C.c_int, 16),
-    "misplat_loss_fwd": (C.c_int, 11), "misplat_loss_bwd": (C.c_int, 11),
-    "misplat_ssim_scratch_floats": (C.c_int64, 2), "misplat_ssim_fwd": (C.c_int, 10), "misplat_ssim_bwd": (C.c_int, 9),
-    "misplat_featloss_scratch_floats": (C.c_int64, 7), "misplat_featloss_fwd": (C.c_int, 21), "misplat_featloss_bwd": (C.c_int, 22),
-    "misplat_feature_decode": (C.c_int, 18),
-    "misplat_textquery_fold": (C.c_int, 9), "misplat_textquery_map": (C.c_int, 18), "misplat_textquery_rows": (C.c_int, 15),
-    "misplat_textquery_upsample": (C.c_int, 7),
-    "misplat_bucket_plan": (C.c_int, 3), "misplat_bucket_count": (C.c_int, 10), "misplat_bucket_rows": (C.c_int, 14),
-    "misplat_bucket_tiles": (C.c_int, 11),
-    "misplat_unit_order": (C.c_int, 4), "misplat_raster_fwd": (C.c_int, 5), "misplat_raster_bwd": (C.c_int, 4), "misplat_raster_bwd_plan": (C.c_int, 2), "misplat_graph_cache_create": (C.c_void_p, 1),
-    "misplat_graph_cache_destroy": (None, 1), "misplat_graph_cache_stats": (C.c_int, 3), "misplat_wait_count": (C.c_int64, 2), "misplat_zero_bytes": (C.c_int, 3), "misplat_stream_copy": (C.c_int, 5),
-    "misplat_touched_bits": (C.c_int, 4), "misplat_union_count": (C.c_int, 5), "misplat_union_scan": (C.c_int, 5), "misplat_union_ids": (C.c_int, 7),
-    "misplat_rows_pack": (C.c_int, 8), "misplat_rows_unpack": (C.c_int, 8),
-    "misplat_adam_step_rows": (C.c_int, 16), "misplat_visible_rows": (C.c_int, 5),
-    "misplat_debug_memset_replay": (C.c_int, 5),
-    "misplat_tsdf_mark": (C.c_int, 10), "misplat_tsdf_alloc": (C.c_int, 6), "misplat_tsdf_integrate": (C.c_int, 14),
-    "misplat_unit_lists": (C.c_int, 12),
-    "misplat_tsdf_order": (C.c_int, 5), "misplat_tsdf_mc_count": (C.c_int, 11), "misplat_tsdf_mc_emit": (C.c_int, 13),
-    "misplat_meshmap_workspace": (C.c_int64, 4), "misplat_meshmap_knn": (C.c_int, 12),
-    "misplat_meshmap_aggregate": (C.c_int, 13),
-    "misplat_cluster_workspace": (C.c_int64, 1), "misplat_cluster_radius": (C.c_int, 11),
-    "misplat_pointcloud_workspace": (C.c_int64, 2), "misplat_pointcloud_cells": (C.c_int, 7),
-    "misplat_pointcloud_knn": (C.c_int, 12), "misplat_pointcloud_radius_count": (C.c_int, 9),
-    "misplat_pointcloud_outlier_mask": (C.c_int, 7), "misplat_pointcloud_voxel_group": (C.c_int, 12),
-    "misplat_pointcloud_voxel_mean": (C.c_int, 8),
-    "misplat_meshclean_workspace": (C.c_int64, 3), "misplat_meshclean_edge_stats": (C.c_int, 9),
-    "misplat_meshclean_components": (C.c_int, 9), "misplat_meshclean_holes": (C.c_int, 11),
-    "misplat_meshclean_segment_sum": (C.c_int, 6), "misplat_meshclean_smooth": (C.c_int, 15),
-    "misplat_meshclean_plane_build": (C.c_int, 8),
-    "misplat_meshclean_plane_count": (C.c_int, 8), "misplat_meshclean_plane_moments": (C.c_int, 9),
-    "misplat_decimate_workspace": (C.c_int64, 2), "misplat_decimate_round": (C.c_int, 12),
-    "misplat_decimate_apply": (C.c_int, 15), "misplat_decimate_resolve": (C.c_int, 4),
-    "misplat_meshfill_workspace": (C.c_int64, 2), "misplat_meshfill_round": (C.c_int, 10), "misplat_meshfill_apply": (C.c_int, 14),
-    "misplat_meshfill_fair_workspace": (C.c_int64, 4), "misplat_meshfill_fair_count": (C.c_int, 8),
-    "misplat_meshfill_fair_build": (C.c_int, 11), "misplat_meshfill_fair_step": (C.c_int, 16),
-    "misplat_meshfill_fair_lds": (C.c_int, 13), "misplat_meshfill_fair_finish": (C.c_int, 5),
-    "misplat_meshfill_curv_patches": (C.c_int, 8), "misplat_meshfill_curv_workspace": (C.c_int64, 2),
-    "misplat_meshfill_curv_solve": (C.c_int, 23),
-    "misplat_meshtri_order": (C.c_int, 9), "misplat_meshtri_workspace": (C.c_int64, 1), "misplat_meshtri_dp": (C.c_int, 18),
-    "misplat_meshtri_rim_workspace": (C.c_int64, 1), "misplat_meshtri_order_rim": (C.c_int, 14),
-    "misplat_meshtri_angle_workspace": (C.c_int64, 1), "misplat_meshtri_angle_dp": (C.c_int, 20),
-    "misplat_meshtri_flip_workspace": (C.c_int64, 2), "misplat_meshtri_flip_round": (C.c_int, 10),
-    "misplat_depthcloud_workspace": (C.c_int64, 4), "misplat_depthcloud_edges": (C.c_int, 10),
-    "misplat_depthcloud_candidates": (C.c_int, 7), "misplat_depthcloud_sample": (C.c_int, 15),
-    "misplat_depthcloud_backproject": (C.c_int, 15), "misplat_depthcloud_gaussian_filter": (C.c_int, 10),
-    "misplat_poisson_workspace": (C.c_int64, 2), "misplat_poisson_splat": (C.c_int, 13),
-    "misplat_poisson_system": (C.c_int, 10), "misplat_poisson_cg_init": (C.c_int, 11),
-    "misplat_poisson_cg_iterate": (C.c_int, 13), "misplat_poisson_sample": (C.c_int, 11),
-    "misplat_poisson_mean": (C.c_int, 6), "misplat_poisson_mc_pool": (C.c_int, 5),
-    "misplat_grouping_workspace": (C.c_int64, 1), "misplat_grouping_project": (C.c_int, 8),
-    "misplat_grouping_mask_ids": (C.c_int, 7), "misplat_grouping_front": (C.c_int, 15),
-    "misplat_grouping_relabel": (C.c_int, 7), "misplat_grouping_overlap": (C.c_int, 8),
-    "misplat_grouping_assign": (C.c_int, 8), "misplat_grouping_merge_count": (C.c_int, 10),
-    "misplat_grouping_merge_copy": (C.c_int, 12), "misplat_grouping_members": (C.c_int, 6),
-    "misplat_bilagrid_scratch_floats": (C.c_int64, 5), "misplat_bilagrid_slice_fwd": (C.c_int, 9),
-    "misplat_bilagrid_slice_bwd": (C.c_int, 14), "misplat_bilagrid_tv_fwd": (C.c_int, 8), "misplat_bilagrid_tv_bwd": (C.c_int, 8),
-    "misplat_density_workspace": (C.c_int64, 2), "misplat_density_records": (C.c_int, 9),
-    "misplat_density_count": (C.c_int, 13), "misplat_density_emit": (C.c_int, 14),
-    "misplat_density_accumulate": (C.c_int, 10), "misplat_density_query": (C.c_int, 15),
-    "misplat_density_raycast": (C.c_int, 19),
-    "misplat_ptsdf_workspace": (C.c_int64, 2), "misplat_ptsdf_count": (C.c_int, 11), "misplat_ptsdf_emit": (C.c_int, 12),
-    "misplat_ptsdf_accumulate": (C.c_int, 18), "misplat_ptsdf_finalize": (C.c_int, 8),
-    "misplat_identity_scratch_floats": (C.c_int64, 4), "misplat_identity_loss_fwd": (C.c_int, 13),
-    "misplat_identity_loss_bwd": (C.c_int, 16), "misplat_identity_labels": (C.c_int, 10),
-    "misplat_identity_3d_fwd": (C.c_int, 14), "misplat_identity_3d_bwd": (C.c_int, 19),
-    "misplat_eval_image_scratch_floats": (C.c_int64, 3), "misplat_eval_image": (C.c_int, 9),
-    "misplat_eval_pixels_scratch_floats": (C.c_int64, 3), "misplat_eval_normals": (C.c_int, 12), "misplat_eval_depth": (C.c_int, 10),
-    "misplat_colorcorrect_scratch_floats": (C.c_int64, 3), "misplat_colorcorrect": (C.c_int, 12),
-    "misplat_mcmc_noise": (C.c_int, 9), "misplat_mcmc_sample_workspace_bytes": (C.c_int64, 1),
-    "misplat_mcmc_sample": (C.c_int, 13), "misplat_mcmc_relocation": (C.c_int, 9),
-    "misplat_version": (C.c_char_p, 0),
+    "misplat_project_fwd": "i ppppppppppppppps", "misplat_project_bwd": "i ppppppppppppppppps",
+    "misplat_project_bwd_pose_workspace": "q ii", "misplat_project_bwd_pose": "i pppppppppppppppps",
+    "misplat_project_pack_fwd": "i pppppppppppppipps", "misplat_color_fwd": "i piiiiippppppppps",
+    "misplat_color_bwd": "i piiiipppppppppps", "misplat_project_pack_bwd": "i pippppppppppppppppis",
+    "misplat_sh_fwd": "i iiiipppps", "misplat_sh_bwd": "i iiiipppppps", "misplat_isect_ids": "i pppqps",
+    "misplat_tile_sort": "i piqpppppis", "misplat_adam_step": "i ipppppppddds", "misplat_pack": "i qipppppppps",
+    "misplat_blend_fwd": "i pippppqppppppps", "misplat_blend_fwd_lazy": "i pippppqpppppppppppiipps",
+    "misplat_blend_bwd": "i pipppppqpppppppppppps", "misplat_color_fwd_x": "i piiiippppps",
+    "misplat_color_bwd_x": "i piiipppps", "misplat_blend_fwd_x": "i piipppppqppppppps",
+    "misplat_blend_bwd_x_atomic": "i piipppppqpppppppppppps", "misplat_blend_planes": "i p",
+    "misplat_blend_bwd_atomic": "i pippppqpppppppppppis", "misplat_slab_reduce": "i pqqppppppps",
+    "misplat_depth_normal_fwd": "i iiffppppps", "misplat_depth_normal_bwd": "i iiffppppppppis",
+    "misplat_outputs_fwd": "i qipppppppppppps", "misplat_outputs_bwd": "i qippppppppppppps",
+    "misplat_loss_fwd": "i qppppffppps", "misplat_loss_bwd": "i qppppffppps", "misplat_ssim_scratch_floats": "q ii",
+    "misplat_ssim_fwd": "i iippppfpps", "misplat_ssim_bwd": "i iippppfps",
+    "misplat_featloss_scratch_floats": "q iiiiipi", "misplat_featloss_fwd": "i iiiipippiiipppppfppps",
+    "misplat_featloss_bwd": "i iiiipiiipppppfppppppps", "misplat_feature_decode": "i iiiipippiiippppips",
+    "misplat_textquery_fold": "i iiippppps", "misplat_textquery_map": "i iiiipippiippifiips",
+    "misplat_textquery_rows": "i qiipippiippifps", "misplat_textquery_upsample": "i iipiips",
+    "misplat_bucket_plan": "i ppp", "misplat_bucket_count": "i ppppppppis", "misplat_bucket_rows": "i ppppppppppppis",
+    "misplat_bucket_tiles": "i pppppppqpps", "misplat_unit_order": "i ppps", "misplat_raster_fwd": "i ppisp",
+    "misplat_raster_bwd": "i ppsp", "misplat_raster_bwd_plan": "i pp", "misplat_graph_cache_create": "p i",
+    "misplat_graph_cache_destroy": "v p", "misplat_graph_cache_stats": "i ppp", "misplat_wait_count": "q pq",
+    "misplat_zero_bytes": "i pQs", "misplat_stream_copy": "i ppqis", "misplat_touched_bits": "i pqps",
+    "misplat_union_count": "i piqps", "misplat_union_scan": "i pqpps", "misplat_union_ids": "i piqppqs",
+    "misplat_rows_pack": "i ipppqpps", "misplat_rows_unpack": "i ipppqpps",
+    "misplat_adam_step_rows": "i ipppppqppdddpqps", "misplat_visible_rows": "i piqps",
+    "misplat_debug_memset_replay": "i ppips", "misplat_tsdf_mark": "i pppiiippps", "misplat_tsdf_alloc": "i ppppps",
+    "misplat_tsdf_integrate": "i ppippppiiippps", "misplat_unit_lists": "i ppppqipqppps",
+    "misplat_tsdf_order": "i pppps", "misplat_tsdf_mc_count": "i pppipppppps",
+    "misplat_tsdf_mc_emit": "i pppipppppppps", "misplat_meshmap_workspace": "q qqii",
+    "misplat_meshmap_knn": "i pqpqifpqppps", "misplat_meshmap_aggregate": "i qqippppiipqps",
+    "misplat_cluster_workspace": "q q", "misplat_cluster_radius": "i pqpfipqppps",
+    "misplat_pointcloud_workspace": "q qi", "misplat_pointcloud_cells": "i pqfpqps",
+    "misplat_pointcloud_knn": "i pqpqifipqpps", "misplat_pointcloud_radius_count": "i pqpqfpqps",
+    "misplat_pointcloud_outlier_mask": "i pqdpqps", "misplat_pointcloud_voxel_group": "i pqddddpqppps",
+    "misplat_pointcloud_voxel_mean": "i pqippqps", "misplat_meshclean_workspace": "q qqi",
+    "misplat_meshclean_edge_stats": "i pqpqpqpps", "misplat_meshclean_components": "i pqqpqppps",
+    "misplat_meshclean_holes": "i pqpqpqpppps", "misplat_meshclean_segment_sum": "i pppqps",
+    "misplat_meshclean_smooth": "i pqpqpiidpqpppps", "misplat_meshclean_plane_build": "i pqpuipps",
+    "misplat_meshclean_plane_count": "i pqpifips", "misplat_meshclean_plane_moments": "i pqpfpqpps",
+    "misplat_decimate_workspace": "q qq", "misplat_decimate_round": "i pqpqpqpipqps",
+    "misplat_decimate_apply": "i pqpqpqpippqqpqs", "misplat_decimate_resolve": "i pqps",
+    "misplat_meshfill_workspace": "q qq", "misplat_meshfill_round": "i pqpqpfpqps",
+    "misplat_meshfill_apply": "i pqpqpppiqqpqps", "misplat_meshfill_fair_workspace": "q qqqq",
+    "misplat_meshfill_fair_count": "i pqpqpqps", "misplat_meshfill_fair_build": "i pqpqqqpqpps",
+    "misplat_meshfill_fair_step": "i ppqqiqqiifipqpps", "misplat_meshfill_fair_lds": "i pqqqqifipqpps",
+    "misplat_meshfill_fair_finish": "i qipps", "misplat_meshfill_curv_patches": "i ppqpqpps",
+    "misplat_meshfill_curv_workspace": "q qq", "misplat_meshfill_curv_solve": "i ppqpppppppqqqpidipqppps",
+    "misplat_meshtri_order": "i ppppqqpps", "misplat_meshtri_workspace": "q q",
+    "misplat_meshtri_dp": "i pqpppqipqpqpqpqpps", "misplat_meshtri_rim_workspace": "q q",
+    "misplat_meshtri_order_rim": "i ppppqqpqpqppps", "misplat_meshtri_angle_workspace": "q q",
+    "misplat_meshtri_angle_dp": "i pqppppqipqpqpqpqppps", "misplat_meshtri_flip_workspace": "q qq",
+    "misplat_meshtri_flip_round": "i pqpqpdpqps", "misplat_depthcloud_workspace": "q qqqi",
+    "misplat_depthcloud_edges": "i piiifipqps", "misplat_depthcloud_candidates": "i ppppqps",
+    "misplat_depthcloud_sample": "i ppiiiiuupqpppps", "misplat_depthcloud_backproject": "i pppppiiippqppps",
+    "misplat_depthcloud_gaussian_filter": "i pqpppiiips", "misplat_poisson_workspace": "q iq",
+    "misplat_poisson_splat": "i pppqiffffppps", "misplat_poisson_system": "i ppifpqppps",
+    "misplat_poisson_cg_init": "i ppiipqpppps", "misplat_poisson_cg_iterate": "i piidipqppppps",
+    "misplat_poisson_sample": "i piiffffpqps", "misplat_poisson_mean": "i pqpqps",
+    "misplat_poisson_mc_pool": "i pifps", "misplat_grouping_workspace": "q q",
+    "misplat_grouping_project": "i ppqiipps", "misplat_grouping_mask_ids": "i pqpqpps",
+    "misplat_grouping_front": "i pppqpiiiidpqpps", "misplat_grouping_relabel": "i pqpqpps",
+    "misplat_grouping_overlap": "i pqppiips", "misplat_grouping_assign": "i ppiifpps",
+    "misplat_grouping_merge_count": "i pqpipppqps", "misplat_grouping_merge_copy": "i pqpipppqppis",
+    "misplat_grouping_members": "i ppqips", "misplat_bilagrid_scratch_floats": "q iiiii",
+    "misplat_bilagrid_slice_fwd": "i iippiiips", "misplat_bilagrid_slice_bwd": "i iippiiiiipppps",
+    "misplat_bilagrid_tv_fwd": "i piiiipps", "misplat_bilagrid_tv_bwd": "i piiiipps",
+    "misplat_density_workspace": "q qq", "misplat_density_records": "i ppppqffps",
+    "misplat_density_count": "i pppppqffpqpps", "misplat_density_emit": "i pppppqffpqppps",
+    "misplat_density_accumulate": "i ppipppfips", "misplat_density_query": "i pppppfpqpipppps",
+    "misplat_density_raycast": "i pppppfppppqffffipps", "misplat_ptsdf_workspace": "q qq",
+    "misplat_ptsdf_count": "i pppiqipqpps", "misplat_ptsdf_emit": "i pppiqipqppps",
+    "misplat_ptsdf_accumulate": "i ppippipippqpqpppps", "misplat_ptsdf_finalize": "i ippppips",
+    "misplat_identity_scratch_floats": "q qiii", "misplat_identity_loss_fwd": "i iiiipipppppps",
+    "misplat_identity_loss_bwd": "i iiiipippppppppps", "misplat_identity_labels": "i qiipipppps",
+    "misplat_identity_3d_fwd": "i qipippiippppps", "misplat_identity_3d_bwd": "i qipippiipppppppppps",
+    "misplat_eval_image_scratch_floats": "q iii", "misplat_eval_image": "i iiippipps",
+    "misplat_eval_pixels_scratch_floats": "q iii", "misplat_eval_normals": "i iiipppiippps",
+    "misplat_eval_depth": "i iiipppfpps", "misplat_colorcorrect_scratch_floats": "q iii",
+    "misplat_colorcorrect": "i iiippifpppps", "misplat_mcmc_noise": "i qppppfuus",
+    "misplat_mcmc_sample_workspace_bytes": "q q", "misplat_mcmc_sample": "i qpifquupqppps",
+    "misplat_mcmc_relocation": "i qppppipps", "misplat_version": "z",
 }
 
 _lib: Optional[C.CDLL] = None
@@ -194,18 +206,18 @@ def load() -> C.CDLL:
             f"{path} not found: build it with `python -m collab_splats_amd.build` "
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
     lib = C.CDLL(path)
-    for name, (res, n_args) in SYMBOLS.items():
+    for name, sig in SYMBOLS.items():
         fn = getattr(lib, name)
-        fn.restype = res
-        setattr(lib, name, _arity_checked(name, fn, n_args))
+        fn.restype = _RET[sig[0]]
+        fn.argtypes = [_ARG[k] for k in sig[2:]]
+        setattr(lib, name, _counted(name, fn, len(fn.argtypes)))
     _lib = lib
     return lib
 
 
-def _arity_checked(name: str, fn, n_args: int):
-    """ctypes without argtypes cannot tell a call with a missing argument from a correct one (the stream pointer
-    would silently land in the wrong slot): every entry point is called through this check of the argument count
-    that tests/test_abi.py keeps equal to include/misplat.h."""
+def _counted(name: str, fn, n_args: int):
+    """``argtypes`` converts every argument to the C type of the signature, but a cdecl call with one argument too many
+    passes ctypes unnoticed: every entry point is called through this check of the count."""
     def call(*args):
         if len(args) != n_args:
             raise MisplatError(f"{name}: {len(args)} arguments passed, the C ABI takes {n_args}")
@@ -236,6 +248,14 @@ def ptr(t: Optional[torch.Tensor]) -> C.c_void_p:
 def check(code: int, what: str) -> None:
     if code != 0:
         raise MisplatError(f"{what} failed: {_ERR.get(code, code)}")
+
+
+def run(name: str, *args) -> None:
+    """Call the entry point ``name``, which returns a status, and raise unless that is 0.  The current stream is appended
+    where the signature ends in one.  The entry is looked up on every call: a test that patches it is honoured."""
+    if SYMBOLS[name][-1] == "s":
+        args += (stream_ptr(),)
+    check(getattr(load(), name)(*args), name)
 
 
 def require_gpu(*tensors: torch.Tensor) -> None:

@@ -18,7 +18,7 @@ import torch
 from torch import Tensor, nn
 
 from . import _lib
-from ._lib import MisplatError, check, ptr, require_gpu, stream_ptr
+from ._lib import MisplatError, ptr, require_gpu, run
 
 MAX_GRID_XY = 256
 MAX_GRID_L = 16
@@ -88,13 +88,11 @@ class _Slice(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rgb, grids, cam, geo):
-        lib = _lib.load()
         H, W, num, L, GH, GW = geo
         out = torch.empty_like(rgb)
         per_cam = 12 * L * GH * GW
         grid = C.c_void_p(grids.data_ptr() + 4 * per_cam * cam)
-        check(lib.misplat_bilagrid_slice_fwd(C.c_int32(H), C.c_int32(W), ptr(rgb), grid, C.c_int32(GW), C.c_int32(GH), C.c_int32(L),
-                                             ptr(out), stream_ptr()), "misplat_bilagrid_slice_fwd")
+        run("misplat_bilagrid_slice_fwd", H, W, ptr(rgb), grid, GW, GH, L, ptr(out))
         ctx.save_for_backward(rgb, grids)
         ctx.cam, ctx.geo = cam, geo
         ctx.set_materialize_grads(False)
@@ -108,14 +106,13 @@ class _Slice(torch.autograd.Function):
         rgb, grids = ctx.saved_tensors
         H, W, num, L, GH, GW = ctx.geo
         v_out = v_out.to(torch.float32).contiguous()
-        n = int(lib.misplat_bilagrid_scratch_floats(C.c_int32(H), C.c_int32(W), C.c_int32(GW), C.c_int32(GH), C.c_int32(L)))
+        n = int(lib.misplat_bilagrid_scratch_floats(H, W, GW, GH, L))
         if n < 0:
             raise MisplatError(f"bilagrid_slice: sizes outside the kernels' limits (image {(H, W)}, grid {(GW, GH, L)})")
         scratch = torch.empty(n, device=rgb.device, dtype=torch.float32)
         v_rgb, v_grids = torch.empty_like(rgb), torch.empty_like(grids)
-        check(lib.misplat_bilagrid_slice_bwd(C.c_int32(H), C.c_int32(W), ptr(rgb), ptr(grids), C.c_int32(num), C.c_int32(ctx.cam),
-                                             C.c_int32(GW), C.c_int32(GH), C.c_int32(L), ptr(v_out), ptr(v_rgb), ptr(v_grids),
-                                             ptr(scratch), stream_ptr()), "misplat_bilagrid_slice_bwd")
+        run("misplat_bilagrid_slice_bwd", H, W, ptr(rgb), ptr(grids), num, ctx.cam, GW, GH, L, ptr(v_out), ptr(v_rgb),
+            ptr(v_grids), ptr(scratch))
         return v_rgb, v_grids, None, None
 
 
@@ -152,12 +149,10 @@ class _TvLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, grids, geo):
-        lib = _lib.load()
         num, L, GH, GW = geo
         partials = torch.empty(3 * TV_BLOCKS, device=grids.device, dtype=torch.float64)
         loss = torch.empty((), device=grids.device, dtype=torch.float32)
-        check(lib.misplat_bilagrid_tv_fwd(ptr(grids), C.c_int32(num), C.c_int32(GW), C.c_int32(GH), C.c_int32(L), ptr(partials),
-                                          ptr(loss), stream_ptr()), "misplat_bilagrid_tv_fwd")
+        run("misplat_bilagrid_tv_fwd", ptr(grids), num, GW, GH, L, ptr(partials), ptr(loss))
         ctx.save_for_backward(grids)
         ctx.geo = geo
         ctx.set_materialize_grads(False)
@@ -167,13 +162,11 @@ class _TvLoss(torch.autograd.Function):
     def backward(ctx, g):
         if g is None:
             return None, None
-        lib = _lib.load()
         (grids,) = ctx.saved_tensors
         num, L, GH, GW = ctx.geo
         g = g.to(torch.float32).contiguous()
         v_grids = torch.empty_like(grids)
-        check(lib.misplat_bilagrid_tv_bwd(ptr(grids), C.c_int32(num), C.c_int32(GW), C.c_int32(GH), C.c_int32(L), ptr(g),
-                                          ptr(v_grids), stream_ptr()), "misplat_bilagrid_tv_bwd")
+        run("misplat_bilagrid_tv_bwd", ptr(grids), num, GW, GH, L, ptr(g), ptr(v_grids))
         return v_grids, None
 
 

@@ -9,13 +9,12 @@ tests/decimate_restatement.py, bit for bit.  There is no CPU fallback.
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Sequence, Tuple
 
 import torch
 from torch import Tensor
 
-from ._lib import MisplatError, check, load, ptr, require_gpu, stream_ptr
+from ._lib import MisplatError, load, ptr, require_gpu, run
 from .meshclean import _attributes, _mesh
 from .meshmap import _prep
 
@@ -64,16 +63,15 @@ def simplify_quadric_decimation(vertices: Tensor, triangles: Tensor, target_tria
     n_alive = int(alive.sum()) if n_slots else 0                    # the host read before the first round
     rounds = 0
     if n_alive > target_triangles and max_rounds > 0:
-        b = int(lib.misplat_decimate_workspace(C.c_int64(m), C.c_int64(n_slots)))
+        b = int(lib.misplat_decimate_workspace(m, n_slots))
         if b < 0:
             raise ValueError(f"{name}: {n_slots} triangles over {m} vertices are beyond the library's limits")
         ws = torch.empty(b, dtype=torch.uint8, device=dev)
         quadrics = torch.empty((m, 10), dtype=torch.float64, device=dev)
         counts = torch.empty(3, dtype=torch.int32, device=dev)
         while rounds < max_rounds and n_alive > target_triangles:
-            check(lib.misplat_decimate_round(ptr(pos), C.c_int64(m), ptr(tri), C.c_int64(n_slots), ptr(alive), C.c_int64(n_alive),
-                                             ptr(quadrics), int(rounds == 0), ptr(ws), C.c_int64(b), ptr(counts), stream_ptr()),
-                  "misplat_decimate_round")
+            run("misplat_decimate_round", ptr(pos), m, ptr(tri), n_slots, ptr(alive), n_alive, ptr(quadrics), int(rounds == 0),
+                ptr(ws), b, ptr(counts))
             found, n_selected, n_removed = counts.tolist()          # the round's host read
             if found != n_alive:
                 raise MisplatError(f"{name}: {found} live faces found where {n_alive} were expected")
@@ -82,16 +80,14 @@ def simplify_quadric_decimation(vertices: Tensor, triangles: Tensor, target_tria
             rounds += 1
             need = n_alive - target_triangles
             last = n_removed > need
-            check(lib.misplat_decimate_apply(ptr(pos), C.c_int64(m), ptr(tri), C.c_int64(n_slots), ptr(alive), C.c_int64(n_alive),
-                                             ptr(att), d, ptr(quadrics), ptr(into), C.c_int64(n_selected),
-                                             C.c_int64(need if last else -1), ptr(ws), C.c_int64(b), stream_ptr()),
-                  "misplat_decimate_apply")
+            run("misplat_decimate_apply", ptr(pos), m, ptr(tri), n_slots, ptr(alive), n_alive, ptr(att), d, ptr(quadrics),
+                ptr(into), n_selected, need if last else -1, ptr(ws), b)
             if last:
                 break
             n_alive -= n_removed
     # the output: the live faces and the vertices they reference, both in their original order
     root = torch.empty(m, dtype=torch.int32, device=dev)
-    check(lib.misplat_decimate_resolve(ptr(into), C.c_int64(m), ptr(root), stream_ptr()), "misplat_decimate_resolve")
+    run("misplat_decimate_resolve", ptr(into), m, ptr(root))
     kept = tri[alive.bool()].long()
     used = torch.zeros(m, dtype=torch.bool, device=dev)
     used[kept.reshape(-1)] = True

@@ -24,7 +24,7 @@ import numpy as np
 import torch
 from torch import Tensor
 
-from ._lib import MisplatError, check, load, ptr, require_gpu, stream_ptr
+from ._lib import MisplatError, load, ptr, require_gpu, run
 from .meshmap import _prep
 from .unitvolume import (MAX_UNITS, UNIT, UNIT_VOXELS, Grid, Stages, _unit_range, alloc_units, empty_mesh, make_grid, map_order,
                          map_span, marching_cubes, unit_coords, unit_lists)
@@ -157,9 +157,7 @@ class DensityField:
         dev = self.device
         mark = Stages(_timings)                                # (scripts/density_bench.py: seconds per stage, synchronised)
         mu, q, s, o = _prep(means), _prep(quats), _prep(scales), _prep(opacities)
-        cr, cmo = C.c_float(r), C.c_float(mo)
-        check(lib.misplat_density_records(ptr(mu), ptr(q), ptr(s), ptr(o), C.c_int64(self.n_gauss), cr, cmo, ptr(self._records),
-                                          stream_ptr()), "misplat_density_records")
+        run("misplat_density_records", ptr(mu), ptr(q), ptr(s), ptr(o), self.n_gauss, r, mo, ptr(self._records))
         mark("records")
         if clip is None:
             e = self._records[:, 13:16]
@@ -176,12 +174,11 @@ class DensityField:
         self.lo, self.dims = lo.astype(np.int64), dims
         mark("bounds")
         grid = self._grid()
-        N = C.c_int64(self.n_gauss)
-        ws = torch.empty(int(lib.misplat_density_workspace(N, C.c_int64(0))), dtype=torch.uint8, device=dev)
+        ws = torch.empty(int(lib.misplat_density_workspace(self.n_gauss, 0)), dtype=torch.uint8, device=dev)
         pair_off = torch.empty(self.n_gauss + 1, dtype=torch.int32, device=dev)
         total = torch.empty(1, dtype=torch.int64, device=dev)
-        check(lib.misplat_density_count(C.byref(grid), ptr(mu), ptr(q), ptr(s), ptr(o), N, cr, cmo, ptr(ws), C.c_int64(ws.numel()),
-                                        ptr(pair_off), ptr(total), stream_ptr()), "misplat_density_count")
+        run("misplat_density_count", C.byref(grid), ptr(mu), ptr(q), ptr(s), ptr(o), self.n_gauss, r, mo, ptr(ws), ws.numel(),
+            ptr(pair_off), ptr(total))
         n_pairs = int(total.item())                                                  # host read
         self._slot_map = torch.full((n_map,), -1, dtype=torch.int32, device=dev)
         mark("count")
@@ -190,12 +187,11 @@ class DensityField:
         if n_pairs >= MAX_PAIRS:
             raise MisplatError(f"{name}: {n_pairs} (unit, Gaussian) pairs, above the cap of {MAX_PAIRS}: pass bounds= or a larger "
                                f"voxel_size")
-        E = C.c_int64(n_pairs)
         keys = torch.empty(n_pairs, dtype=torch.int32, device=dev)
         ids = torch.empty(n_pairs, dtype=torch.int32, device=dev)
         words = torch.zeros(n_map, dtype=torch.int64, device=dev)
-        check(lib.misplat_density_emit(C.byref(grid), ptr(mu), ptr(q), ptr(s), ptr(o), N, cr, cmo, ptr(pair_off), E, ptr(keys),
-                                       ptr(ids), ptr(words), stream_ptr()), "misplat_density_emit")
+        run("misplat_density_emit", C.byref(grid), ptr(mu), ptr(q), ptr(s), ptr(o), self.n_gauss, r, mo, ptr(pair_off), n_pairs,
+            ptr(keys), ptr(ids), ptr(words))
         counters = torch.zeros(2, dtype=torch.int32, device=dev)
         touched = torch.empty(2 * min(n_map, n_pairs), dtype=torch.int32, device=dev)
         n_units, _ = alloc_units(grid, words, self._slot_map, counters, touched)    # host read: the pool's size
@@ -206,9 +202,8 @@ class DensityField:
         del keys, ids, ws
         self._touched = touched
         self._pool = torch.empty((n_units, 5, UNIT_VOXELS), dtype=torch.float32, device=dev)
-        check(lib.misplat_density_accumulate(C.byref(grid), ptr(touched), n_units, ptr(self._records), ptr(self._ids),
-                                             ptr(self._ranges), cr, int(_flags), ptr(self._pool), stream_ptr()),
-              "misplat_density_accumulate")
+        run("misplat_density_accumulate", C.byref(grid), ptr(touched), n_units, ptr(self._records), ptr(self._ids),
+            ptr(self._ranges), r, int(_flags), ptr(self._pool))
         mark("accumulate")
         self.n_units, self.n_pairs = n_units, n_pairs
 
@@ -269,10 +264,9 @@ class DensityField:
         p32 = _prep(points)
         v32 = None if values is None else _prep(values)
         grid = self._grid()
-        check(load().misplat_density_query(C.byref(grid), ptr(self._slot_map), ptr(self._records), ptr(self._ids), ptr(self._ranges),
-                                           C.c_float(self.cutoff), ptr(p32), C.c_int64(P), ptr(v32),
-                                           0 if v32 is None else int(v32.shape[1]), ptr(out["density"]), ptr(out["grad"]),
-                                           ptr(out["dominant"]), ptr(out["values"]), stream_ptr()), "misplat_density_query")
+        run("misplat_density_query", C.byref(grid), ptr(self._slot_map), ptr(self._records), ptr(self._ids), ptr(self._ranges),
+            self.cutoff, ptr(p32), P, ptr(v32), 0 if v32 is None else int(v32.shape[1]), ptr(out["density"]), ptr(out["grad"]),
+            ptr(out["dominant"]), ptr(out["values"]))
         return out
 
     def raycast(self, origins: Tensor, dirs: Tensor, t_near: Tensor, t_far: Tensor, levels) -> Dict[str, Tensor]:
@@ -295,10 +289,9 @@ class DensityField:
         o32, v32, a32, b32 = _prep(origins), _prep(dirs), _prep(t_near), _prep(t_far)
         grid = self._grid()
         lv4 = lv + (lv[-1],) * (MAX_LEVELS - len(lv))
-        check(load().misplat_density_raycast(C.byref(grid), ptr(self._slot_map), ptr(self._records), ptr(self._ids),
-                                             ptr(self._ranges), C.c_float(self.cutoff), ptr(o32), ptr(v32), ptr(a32), ptr(b32),
-                                             C.c_int64(M), C.c_float(lv4[0]), C.c_float(lv4[1]), C.c_float(lv4[2]), C.c_float(lv4[3]),
-                                             len(lv), ptr(t), ptr(hit), stream_ptr()), "misplat_density_raycast")
+        run("misplat_density_raycast", C.byref(grid), ptr(self._slot_map), ptr(self._records), ptr(self._ids),
+            ptr(self._ranges), self.cutoff, ptr(o32), ptr(v32), ptr(a32), ptr(b32), M, lv4[0], lv4[1], lv4[2], lv4[3], len(lv),
+            ptr(t), ptr(hit))
         return {"t": t, "hit": hit.view(torch.bool)}
 
     def extract_mesh(self, iso: float = 0.5, values: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Optional[Tensor]]:

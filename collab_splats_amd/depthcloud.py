@@ -16,13 +16,12 @@ altogether, so masked pixels and holes become points at the camera centre there.
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, Optional, Tuple
 
 import torch
 from torch import Tensor
 
-from ._lib import MisplatError, check, load, ptr, require_gpu, stream_ptr
+from ._lib import MisplatError, load, ptr, require_gpu, run
 from .meshmap import _prep
 from .pointcloud import _cloud
 
@@ -75,7 +74,7 @@ def _u32(name: str, what: str, v) -> int:
 
 
 def _workspace(shape: Tuple[int, int, int], kind: int, device) -> Tensor:
-    b = int(load().misplat_depthcloud_workspace(C.c_int64(shape[0]), C.c_int64(shape[1]), C.c_int64(shape[2]), kind))
+    b = int(load().misplat_depthcloud_workspace(shape[0], shape[1], shape[2], kind))
     if b < 0:
         raise ValueError(f"depthcloud: maps of shape {shape} are beyond the library's limits (V <= 65535, H W < 2^31)")
     return torch.empty(b, dtype=torch.uint8, device=device)
@@ -97,8 +96,7 @@ def _check_edges(name: str, threshold, dilation_itr) -> float:
 def _edges(d: Tensor, shape, threshold: float, dilation: int) -> Tensor:
     out = torch.empty(shape, dtype=torch.uint8, device=d.device)
     ws = _workspace(shape, _EDGES, d.device)
-    check(load().misplat_depthcloud_edges(ptr(d), shape[0], shape[1], shape[2], C.c_float(threshold), dilation, ptr(ws),
-                                          C.c_int64(ws.numel()), ptr(out), stream_ptr()), "misplat_depthcloud_edges")
+    run("misplat_depthcloud_edges", ptr(d), shape[0], shape[1], shape[2], threshold, dilation, ptr(ws), ws.numel(), ptr(out))
     return out
 
 
@@ -126,9 +124,8 @@ def _sample(cand: Tensor, keys: Optional[Tensor], shape, s: int, seed: int, fram
     counts = torch.empty(v, dtype=torch.int32, device=dev)
     base = torch.empty(v + 1, dtype=torch.int32, device=dev)
     ws = _workspace(shape, _SAMPLE, dev)
-    check(load().misplat_depthcloud_sample(ptr(cand), ptr(keys), shape[0], shape[1], shape[2], s, C.c_uint32(seed),
-                                           C.c_uint32(frame_offset), ptr(ws), C.c_int64(ws.numel()), ptr(frame_ids), ptr(pixel_ids),
-                                           ptr(counts), ptr(base), stream_ptr()), "misplat_depthcloud_sample")
+    run("misplat_depthcloud_sample", ptr(cand), ptr(keys), shape[0], shape[1], shape[2], s, seed, frame_offset, ptr(ws),
+        ws.numel(), ptr(frame_ids), ptr(pixel_ids), ptr(counts), ptr(base))
     total = int(base[v].item())                                     # the call's host read
     return frame_ids[:total], pixel_ids[:total], counts
 
@@ -180,9 +177,8 @@ def _backproject(d, rgb, nrm, c2w, intr, shape, f, p):
     points = torch.empty((n, 3), dtype=torch.float32, device=dev)
     colors = torch.empty((n, 3), dtype=torch.float32, device=dev)
     normals = None if nrm is None else torch.empty((n, 3), dtype=torch.float32, device=dev)
-    check(load().misplat_depthcloud_backproject(ptr(d), ptr(rgb), ptr(nrm), ptr(c2w), ptr(intr), shape[0], shape[1], shape[2], ptr(f),
-                                                ptr(p), C.c_int64(n), ptr(points), ptr(normals), ptr(colors), stream_ptr()),
-          "misplat_depthcloud_backproject")
+    run("misplat_depthcloud_backproject", ptr(d), ptr(rgb), ptr(nrm), ptr(c2w), ptr(intr), shape[0], shape[1], shape[2], ptr(f),
+        ptr(p), n, ptr(points), ptr(normals), ptr(colors))
     return points, normals, colors
 
 
@@ -235,8 +231,7 @@ def depth_normal_cloud(depth: Tensor, rgb: Tensor, normals: Optional[Tensor], c2
     require_gpu(depth, rgb, normals, c2w, intrinsics, masks, valid)
     edges = _edges(d, shape, t, edge_dilation) if filter_edges else None
     cand = torch.empty(shape, dtype=torch.uint8, device=d.device)
-    check(load().misplat_depthcloud_candidates(ptr(d), ptr(m), ptr(ok), ptr(edges), C.c_int64(cand.numel()), ptr(cand), stream_ptr()),
-          "misplat_depthcloud_candidates")
+    run("misplat_depthcloud_candidates", ptr(d), ptr(m), ptr(ok), ptr(edges), cand.numel(), ptr(cand))
     f, p, counts = _sample(cand, None, shape, samples_per_frame, seed, frame_offset)
     points, out_normals, colors = _backproject(d, rgb_, nrm, pose, intr, shape, f, p)
     return {"points": points, "normals": out_normals, "colors": colors, "frame_ids": f, "pixel_ids": p, "counts": counts}
@@ -258,8 +253,8 @@ def gaussian_mask_filter(means: Tensor, c2w: Tensor, intrinsics: Tensor, masks: 
     require_gpu(means, c2w, intrinsics, masks)
     p = _prep(means)
     keep = torch.empty(p.shape[0], dtype=torch.uint8, device=p.device)
-    check(load().misplat_depthcloud_gaussian_filter(ptr(p), C.c_int64(p.shape[0]), ptr(pose), ptr(intr), ptr(m), shape[0], shape[1],
-                                                    shape[2], ptr(keep), stream_ptr()), "misplat_depthcloud_gaussian_filter")
+    run("misplat_depthcloud_gaussian_filter", ptr(p), p.shape[0], ptr(pose), ptr(intr), ptr(m), shape[0], shape[1], shape[2],
+        ptr(keep))
     return keep.view(torch.bool)
 
 

@@ -15,7 +15,7 @@ import torch.nn.functional as F
 from torch import Tensor, nn
 
 from . import _lib
-from ._lib import check, ptr, require_gpu, stream_ptr
+from ._lib import ptr, require_gpu, run
 
 MAX_LATENT = 32
 MAX_HIDDEN = 256
@@ -149,9 +149,8 @@ def _dims_array(dlist):
 
 
 def _scratch(lib, latent, hidden, main_hw, dlist, decode_only: bool, dev, what: str) -> Tensor:
-    n = int(lib.misplat_featloss_scratch_floats(C.c_int32(latent), C.c_int32(hidden), C.c_int32(int(main_hw[0])),
-                                                C.c_int32(int(main_hw[1])), C.c_int32(len(dlist)), _dims_array(dlist),
-                                                C.c_int32(int(decode_only))))
+    n = int(lib.misplat_featloss_scratch_floats(latent, hidden, int(main_hw[0]), int(main_hw[1]), len(dlist), _dims_array(dlist),
+                                                int(decode_only)))
     if n < 0:
         raise ValueError(f"{what}: sizes outside the kernels' limits (main map {tuple(main_hw)}, branches {dlist})")
     return torch.empty(n, device=dev, dtype=torch.float32)
@@ -177,10 +176,9 @@ class _FeatureLoss(torch.autograd.Function):
         loss = torch.empty((), device=dev, dtype=torch.float32)
         sums = torch.empty(nb, device=dev, dtype=torch.float32)
         wts = (C.c_float * nb)(*weights)
-        check(lib.misplat_featloss_fwd(C.c_int32(H), C.c_int32(W), C.c_int32(L), C.c_int32(stride), C.c_void_p(features.data_ptr()),
-                                       C.c_int32(hidden), ptr(w_h), ptr(b_h), C.c_int32(main_hw[0]), C.c_int32(main_hw[1]),
-                                       C.c_int32(nb), _dims_array(dlist), _ptr_array(ws), _ptr_array(bs), _ptr_array(gts), wts,
-                                       C.c_float(lam), ptr(scratch), ptr(sums), ptr(loss), stream_ptr()), "misplat_featloss_fwd")
+        run("misplat_featloss_fwd", H, W, L, stride, C.c_void_p(features.data_ptr()), hidden, ptr(w_h), ptr(b_h), main_hw[0],
+            main_hw[1], nb, _dims_array(dlist), _ptr_array(ws), _ptr_array(bs), _ptr_array(gts), wts, lam, ptr(scratch),
+            ptr(sums), ptr(loss))
         ctx.save_for_backward(w_h, scratch, *ws, *bs, *gts)
         ctx.meta = (H, W, L, hidden, nb, dlist, tuple(main_hw), tuple(weights), float(lam))
         ctx.branch_sums = sums
@@ -193,7 +191,6 @@ class _FeatureLoss(torch.autograd.Function):
         none = (None,) * (5 + 3 * nb)
         if g is None:
             return none
-        lib = _lib.load()
         saved = ctx.saved_tensors
         w_h, scratch = saved[0], saved[1]
         ws, bs, gts = saved[2:2 + nb], saved[2 + nb:2 + 2 * nb], saved[2 + 2 * nb:]
@@ -203,10 +200,9 @@ class _FeatureLoss(torch.autograd.Function):
         v_wh, v_bh = torch.empty_like(w_h), torch.empty(hidden, device=dev, dtype=torch.float32)
         v_ws, v_bs = [torch.empty_like(t) for t in ws], [torch.empty_like(t) for t in bs]
         wts = (C.c_float * nb)(*weights)
-        check(lib.misplat_featloss_bwd(C.c_int32(H), C.c_int32(W), C.c_int32(L), C.c_int32(hidden), ptr(w_h), C.c_int32(main_hw[0]),
-                                       C.c_int32(main_hw[1]), C.c_int32(nb), _dims_array(dlist), _ptr_array(ws), _ptr_array(bs),
-                                       _ptr_array(gts), wts, C.c_float(lam), ptr(scratch), ptr(g), ptr(v_features), ptr(v_wh),
-                                       ptr(v_bh), _ptr_array(v_ws), _ptr_array(v_bs), stream_ptr()), "misplat_featloss_bwd")
+        run("misplat_featloss_bwd", H, W, L, hidden, ptr(w_h), main_hw[0], main_hw[1], nb, _dims_array(dlist), _ptr_array(ws),
+            _ptr_array(bs), _ptr_array(gts), wts, lam, ptr(scratch), ptr(g), ptr(v_features), ptr(v_wh), ptr(v_bh),
+            _ptr_array(v_ws), _ptr_array(v_bs))
         return (v_features, None, None, v_wh, v_bh, *v_ws, *v_bs, *((None,) * nb))
 
 
@@ -254,8 +250,7 @@ def feature_decode(features: Tensor, decoder: Decoder, dims: Mapping[str, Sequen
     ws, bs = [t.detach().contiguous() for t in ws], [t.detach().contiguous() for t in bs]
     scratch = _scratch(lib, L, hidden, main_hw, dlist, True, dev, "feature_decode")
     outs = [torch.empty((d[1] * d[2], d[0]) if channels_last else d, device=dev, dtype=torch.float32) for d in dlist]
-    check(lib.misplat_feature_decode(C.c_int32(H), C.c_int32(W), C.c_int32(L), C.c_int32(stride), C.c_void_p(feats.data_ptr()),
-                                     C.c_int32(hidden), ptr(w_h), ptr(b_h), C.c_int32(int(main_hw[0])), C.c_int32(int(main_hw[1])),
-                                     C.c_int32(len(names)), _dims_array(dlist), _ptr_array(ws), _ptr_array(bs), _ptr_array(outs),
-                                     C.c_int32(int(channels_last)), ptr(scratch), stream_ptr()), "misplat_feature_decode")
+    run("misplat_feature_decode", H, W, L, stride, C.c_void_p(feats.data_ptr()), hidden, ptr(w_h), ptr(b_h), int(main_hw[0]),
+        int(main_hw[1]), len(names), _dims_array(dlist), _ptr_array(ws), _ptr_array(bs), _ptr_array(outs), int(channels_last),
+        ptr(scratch))
     return dict(zip(names, outs))

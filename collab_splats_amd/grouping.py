@@ -15,14 +15,13 @@ reference's loop ends with a stray ``break`` after the first frame).
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, List, Optional, Tuple, Union
 
 import numpy as np
 import torch
 from torch import Tensor
 
-from ._lib import check, load, ptr, require_gpu, stream_ptr
+from ._lib import load, ptr, require_gpu, run
 
 MAX_PATCHES = 128
 MAX_MASK_ID = 65535
@@ -72,8 +71,7 @@ def _project(radii: Tensor, means2d: Tensor, depths: Tensor, w: int, h: int) -> 
     means2d = means2d.detach().to(torch.float32).contiguous()
     flat = torch.empty(n, dtype=torch.int32, device=depths.device)
     valid = torch.empty(n, dtype=torch.uint8, device=depths.device)
-    check(load().misplat_grouping_project(ptr(radii), ptr(means2d), C.c_int64(n), w, h, ptr(flat), ptr(valid), stream_ptr()),
-          "misplat_grouping_project")
+    run("misplat_grouping_project", ptr(radii), ptr(means2d), n, w, h, ptr(flat), ptr(valid))
     return flat, valid, depths.detach().to(torch.float32).contiguous()
 
 
@@ -117,7 +115,7 @@ def _mask_device(m, device) -> Tensor:
 
 
 def _workspace(n: int, device) -> Tensor:
-    b = int(load().misplat_grouping_workspace(C.c_int64(n)))
+    b = int(load().misplat_grouping_workspace(n))
     if b < 0:
         raise ValueError(f"grouping: {n} Gaussians are beyond the library's limits (< 2^31)")
     return torch.empty(b, dtype=torch.uint8, device=device)
@@ -127,8 +125,7 @@ def _mask_ids(mask: Tensor, ws: Tensor) -> Tensor:
     """The ascending positive ids of the image (one host read: their number); leaves the id -> rank table in ws."""
     ids = torch.empty(MAX_MASK_ID, dtype=torch.int32, device=mask.device)
     n = torch.empty(1, dtype=torch.int32, device=mask.device)
-    check(load().misplat_grouping_mask_ids(ptr(mask), C.c_int64(mask.numel()), ptr(ws), C.c_int64(ws.numel()), ptr(ids), ptr(n),
-                                           stream_ptr()), "misplat_grouping_mask_ids")
+    run("misplat_grouping_mask_ids", ptr(mask), mask.numel(), ptr(ws), ws.numel(), ptr(ids), ptr(n))
     return ids[:int(n.item())]
 
 
@@ -202,9 +199,8 @@ def front_gaussians(meta_or_proj: Dict, composite_mask, front_percentage: float 
     m = int(ids.shape[0])
     mask_of = torch.empty(n, dtype=torch.int32, device=dev)
     counts = torch.empty(m, dtype=torch.int32, device=dev)
-    check(load().misplat_grouping_front(ptr(flat), ptr(valid), ptr(depths), C.c_int64(n), ptr(mask), w, h, num_patches, m,
-                                        C.c_double(fp), ptr(ws), C.c_int64(ws.numel()), ptr(mask_of), ptr(counts), stream_ptr()),
-          "misplat_grouping_front")
+    run("misplat_grouping_front", ptr(flat), ptr(valid), ptr(depths), n, ptr(mask), w, h, num_patches, m, fp, ptr(ws),
+        ws.numel(), ptr(mask_of), ptr(counts))
     return FrontGaussians(mask_of, ids, counts)
 
 
@@ -224,8 +220,7 @@ def convert_matched_mask(labels: Tensor, composite_mask) -> Tensor:
     out = torch.zeros(h, w, dtype=torch.int32, device=labels.device)
     if m > 0:
         labels = labels.to(torch.int64).contiguous()
-        check(load().misplat_grouping_relabel(ptr(mask), C.c_int64(h * w), ptr(ws), C.c_int64(ws.numel()), ptr(labels), ptr(out),
-                                              stream_ptr()), "misplat_grouping_relabel")
+        run("misplat_grouping_relabel", ptr(mask), h * w, ptr(ws), ws.numel(), ptr(labels), ptr(out))
     return out
 
 
@@ -287,11 +282,10 @@ class MemoryBank:
         count = None
         if l > 0:
             count = torch.empty(m * l, dtype=torch.int32, device=dev)
-            check(load().misplat_grouping_overlap(ptr(front.mask_of), C.c_int64(self.num_gaussians), ptr(self._off), ptr(self._lab),
-                                                  m, l, ptr(count), stream_ptr()), "misplat_grouping_overlap")
+            run("misplat_grouping_overlap", ptr(front.mask_of), self.num_gaussians, ptr(self._off), ptr(self._lab), m, l,
+                ptr(count))
         n_new = torch.empty(1, dtype=torch.int32, device=dev)
-        check(load().misplat_grouping_assign(ptr(count), ptr(front.counts), m, l, C.c_float(self.iou_threshold), ptr(labels),
-                                             ptr(n_new), stream_ptr()), "misplat_grouping_assign")
+        run("misplat_grouping_assign", ptr(count), ptr(front.counts), m, l, self.iou_threshold, ptr(labels), ptr(n_new))
         return labels
 
     def update(self, labels: Tensor, front: FrontGaussians) -> None:
@@ -310,10 +304,8 @@ class MemoryBank:
         self._state(dev)
         labels = labels.to(torch.int64).contiguous()
         new_off = torch.empty(n + 1, dtype=torch.int32, device=dev)
-        lib = load()
-        check(lib.misplat_grouping_merge_count(ptr(front.mask_of), C.c_int64(n), ptr(labels), m, ptr(self._off), ptr(self._lab),
-                                               ptr(self._ws), C.c_int64(self._ws.numel()), ptr(new_off), stream_ptr()),
-              "misplat_grouping_merge_count")
+        run("misplat_grouping_merge_count", ptr(front.mask_of), n, ptr(labels), m, ptr(self._off), ptr(self._lab),
+            ptr(self._ws), self._ws.numel(), ptr(new_off))
         lo, hi = torch.aminmax(labels)
         pairs, lo, hi = torch.stack((new_off[n].to(torch.int64), lo, hi)).tolist()      # the call's host read
         if lo < 0 or hi >= self.total_masks + m:
@@ -323,9 +315,8 @@ class MemoryBank:
         sizes = torch.zeros(total, dtype=torch.int32, device=dev)
         sizes[:self.total_masks] = self._sizes
         new_lab = torch.empty(pairs, dtype=torch.int32, device=dev) if pairs > 0 else torch.zeros(1, dtype=torch.int32, device=dev)
-        check(lib.misplat_grouping_merge_copy(ptr(front.mask_of), C.c_int64(n), ptr(labels), m, ptr(self._off), ptr(self._lab),
-                                              ptr(new_off), C.c_int64(pairs), ptr(new_lab), ptr(sizes), total, stream_ptr()),
-              "misplat_grouping_merge_copy")
+        run("misplat_grouping_merge_copy", ptr(front.mask_of), n, ptr(labels), m, ptr(self._off), ptr(self._lab), ptr(new_off),
+            pairs, ptr(new_lab), ptr(sizes), total)
         self._off, self._lab, self._sizes, self._pairs, self.total_masks = new_off, new_lab, sizes, pairs, total
 
     def associate(self, front: FrontGaussians) -> Tensor:
@@ -345,6 +336,5 @@ class MemoryBank:
         if not isinstance(label, int) or isinstance(label, bool) or not 0 <= label < self.total_masks:
             raise ValueError(f"MemoryBank.members: label must be in 0..{self.total_masks - 1}, got {label!r}")
         flags = torch.empty(self.num_gaussians, dtype=torch.uint8, device=self._off.device)
-        check(load().misplat_grouping_members(ptr(self._off), ptr(self._lab), C.c_int64(self.num_gaussians), label, ptr(flags),
-                                              stream_ptr()), "misplat_grouping_members")
+        run("misplat_grouping_members", ptr(self._off), ptr(self._lab), self.num_gaussians, label, ptr(flags))
         return flags.view(torch.bool).nonzero(as_tuple=False).squeeze(-1)

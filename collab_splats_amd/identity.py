@@ -20,7 +20,7 @@ import torch
 from torch import Tensor, nn
 
 from . import _lib
-from ._lib import check, ptr, require_gpu, stream_ptr
+from ._lib import ptr, require_gpu, run
 from .featureloss import _features_view
 
 MAX_DIM = 32
@@ -158,7 +158,7 @@ def _flat(classifier: Classifier, dim: int, what: str) -> Tuple[Tensor, Tensor]:
 
 
 def _scratch(lib, rows: int, dim: int, classes: int, mode: int, dev, what: str) -> Tensor:
-    n = int(lib.misplat_identity_scratch_floats(C.c_int64(rows), C.c_int32(dim), C.c_int32(classes), C.c_int32(mode)))
+    n = int(lib.misplat_identity_scratch_floats(rows, dim, classes, mode))
     if n < 0:
         raise ValueError(f"{what}: sizes outside the kernels' limits ({rows} rows, width {dim}, {classes} classes)")
     return torch.empty(n, device=dev, dtype=torch.float32)
@@ -178,9 +178,8 @@ class _IdentityLoss(torch.autograd.Function):
         scratch = _scratch(lib, H * W, D, K, 0, dev, "identity_loss")
         counts = torch.empty(2, device=dev, dtype=torch.int32)
         loss = torch.empty((), device=dev, dtype=torch.float32)
-        check(lib.misplat_identity_loss_fwd(C.c_int32(H), C.c_int32(W), C.c_int32(D), C.c_int32(stride),
-                                            C.c_void_p(features.data_ptr()), C.c_int32(K), ptr(weight), ptr(bias), ptr(target),
-                                            ptr(scratch), ptr(counts), ptr(loss), stream_ptr()), "misplat_identity_loss_fwd")
+        run("misplat_identity_loss_fwd", H, W, D, stride, C.c_void_p(features.data_ptr()), K, ptr(weight), ptr(bias),
+            ptr(target), ptr(scratch), ptr(counts), ptr(loss))
         if validate:
             n_bad = int(counts.tolist()[1])                                   # the call's one host read
             if n_bad:
@@ -195,16 +194,13 @@ class _IdentityLoss(torch.autograd.Function):
         if g is None:
             return (None,) * 6
         H, W, D, K, stride = ctx.meta
-        lib = _lib.load()
         features, weight, bias, target, scratch, counts = ctx.saved_tensors
         dev = weight.device
         g = g.to(torch.float32).contiguous()
         v_features = torch.empty(H, W, D, device=dev, dtype=torch.float32)
         v_w, v_b = torch.empty_like(weight), torch.empty_like(bias)
-        check(lib.misplat_identity_loss_bwd(C.c_int32(H), C.c_int32(W), C.c_int32(D), C.c_int32(stride),
-                                            C.c_void_p(features.data_ptr()), C.c_int32(K), ptr(weight), ptr(bias), ptr(target),
-                                            ptr(scratch), ptr(counts), ptr(g), ptr(v_features), ptr(v_w), ptr(v_b), stream_ptr()),
-              "misplat_identity_loss_bwd")
+        run("misplat_identity_loss_bwd", H, W, D, stride, C.c_void_p(features.data_ptr()), K, ptr(weight), ptr(bias),
+            ptr(target), ptr(scratch), ptr(counts), ptr(g), ptr(v_features), ptr(v_w), ptr(v_b))
         return v_features, None, None, v_w, v_b, None
 
 
@@ -240,14 +236,12 @@ def identity_labels(features: Tensor, classifier: Classifier, return_confidence:
     feats, stride = _features_view(features, what)
     w, b = _flat(classifier, feats.shape[2], what)
     require_gpu(feats, w, b)
-    lib = _lib.load()
     H, W, D = (int(v) for v in feats.shape)
     w, b = w.detach().contiguous(), b.detach().contiguous()
     labels = torch.empty(H, W, device=feats.device, dtype=torch.int32)
     conf = torch.empty(H, W, device=feats.device, dtype=torch.float32) if return_confidence else None
-    check(lib.misplat_identity_labels(C.c_int64(H * W), C.c_int32(D), C.c_int32(stride), C.c_void_p(feats.data_ptr()),
-                                      C.c_int32(int(w.shape[0])), ptr(w), ptr(b), ptr(labels), ptr(conf), stream_ptr()),
-          "misplat_identity_labels")
+    run("misplat_identity_labels", H * W, D, stride, C.c_void_p(feats.data_ptr()), int(w.shape[0]), ptr(w), ptr(b), ptr(labels),
+        ptr(conf))
     return (labels, conf) if return_confidence else labels
 
 
@@ -266,9 +260,8 @@ class _Identity3DLoss(torch.autograd.Function):
         scratch = _scratch(lib, M * k, D, K, 1, dev, "identity_3d_loss")
         counts = torch.empty(2, device=dev, dtype=torch.int32)
         loss = torch.empty((), device=dev, dtype=torch.float32)
-        check(lib.misplat_identity_3d_fwd(C.c_int64(N), C.c_int32(D), ptr(identities), C.c_int32(K), ptr(weight), ptr(bias),
-                                          C.c_int32(M), C.c_int32(k), ptr(nb.sample), ptr(nb.table), ptr(scratch), ptr(counts),
-                                          ptr(loss), stream_ptr()), "misplat_identity_3d_fwd")
+        run("misplat_identity_3d_fwd", N, D, ptr(identities), K, ptr(weight), ptr(bias), M, k, ptr(nb.sample), ptr(nb.table),
+            ptr(scratch), ptr(counts), ptr(loss))
         ctx.save_for_backward(identities, weight, bias, scratch, counts)
         ctx.nb = nb
         ctx.set_materialize_grads(False)
@@ -278,17 +271,15 @@ class _Identity3DLoss(torch.autograd.Function):
     def backward(ctx, g):
         if g is None:
             return None, None, None, None
-        lib = _lib.load()
         identities, weight, bias, scratch, counts = ctx.saved_tensors
         nb = ctx.nb
         N, D = (int(v) for v in identities.shape)
         M, k = (int(v) for v in nb.table.shape)
         g = g.to(torch.float32).contiguous()
         v_e, v_w, v_b = torch.empty_like(identities), torch.empty_like(weight), torch.empty_like(bias)
-        check(lib.misplat_identity_3d_bwd(C.c_int64(N), C.c_int32(D), ptr(identities), C.c_int32(int(weight.shape[0])), ptr(weight),
-                                          ptr(bias), C.c_int32(M), C.c_int32(k), ptr(nb.sample), ptr(nb.table), ptr(nb.rev_offsets),
-                                          ptr(nb.rev_slots), ptr(scratch), ptr(counts), ptr(g), ptr(v_e), ptr(v_w), ptr(v_b),
-                                          stream_ptr()), "misplat_identity_3d_bwd")
+        run("misplat_identity_3d_bwd", N, D, ptr(identities), int(weight.shape[0]), ptr(weight), ptr(bias), M, k,
+            ptr(nb.sample), ptr(nb.table), ptr(nb.rev_offsets), ptr(nb.rev_slots), ptr(scratch), ptr(counts), ptr(g), ptr(v_e),
+            ptr(v_w), ptr(v_b))
         return v_e, v_w, v_b, None
 
 

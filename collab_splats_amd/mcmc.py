@@ -12,7 +12,6 @@ view-sharded data parallelism -- and the sampler has no 2^24 limit on the number
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from dataclasses import dataclass
 from typing import Any, Dict, Optional, Tuple
@@ -20,7 +19,7 @@ from typing import Any, Dict, Optional, Tuple
 import torch
 from torch import Tensor
 
-from ._lib import MisplatError, check, load, ptr, require_gpu, stream_ptr
+from ._lib import MisplatError, load, ptr, require_gpu, run
 from .strategy import _update_param_with_optimizer
 
 N_MAX = 51                      # MISPLAT_MCMC_N_MAX: the largest ratio of the relocation
@@ -30,10 +29,6 @@ _ADD_STREAM = 0x5851F42D        # sample_add's draws of a step use seed + this: 
 
 class NothingToSample(MisplatError):
     """Every weight handed to ``sample_by_opacity`` is zero."""
-
-
-def _u32(v: int) -> C.c_uint32:
-    return C.c_uint32(int(v) & 0xFFFFFFFF)
 
 
 def binomial_table(n_max: int = N_MAX, device=None) -> Tensor:
@@ -60,7 +55,7 @@ def sample_by_opacity(opacities: Tensor, m: int, seed: int, step: int, min_opaci
     if n < 1 or m < 1:
         raise ValueError(f"sample_by_opacity: needs N >= 1 rows and m >= 1 draws, got N = {n}, m = {m}")
     lib = load()
-    nbytes = int(lib.misplat_mcmc_sample_workspace_bytes(C.c_int64(n)))
+    nbytes = int(lib.misplat_mcmc_sample_workspace_bytes(n))
     if nbytes < 0:
         raise MisplatError(f"sample_by_opacity: N = {n} out of range")
     dev = opacities.device
@@ -68,10 +63,8 @@ def sample_by_opacity(opacities: Tensor, m: int, seed: int, step: int, min_opaci
     idx = torch.empty(m, device=dev, dtype=torch.int64)
     counts = torch.empty(n, device=dev, dtype=torch.int32)
     status = torch.empty(1, device=dev, dtype=torch.int32)
-    check(lib.misplat_mcmc_sample(C.c_int64(n), ptr(opacities), C.c_int32(min_opacity is not None),
-                                  C.c_float(0.0 if min_opacity is None else min_opacity), C.c_int64(m), _u32(seed), _u32(step),
-                                  ptr(work), C.c_int64(work.numel() * 8), ptr(idx), ptr(counts), ptr(status), stream_ptr()),
-          "misplat_mcmc_sample")
+    run("misplat_mcmc_sample", n, ptr(opacities), min_opacity is not None, 0.0 if min_opacity is None else min_opacity, m, seed,
+        step, ptr(work), work.numel() * 8, ptr(idx), ptr(counts), ptr(status))
     if int(status.item()) == _NOTHING:
         raise NothingToSample("sample_by_opacity: every weight is zero, nothing to sample")
     return idx, counts
@@ -96,8 +89,7 @@ def compute_relocation(opacities: Tensor, scales: Tensor, ratios: Tensor, binoms
     s = scales.detach().to(torch.float32).contiguous()
     r = ratios.detach().reshape(-1).to(torch.int32).contiguous()
     new_o, new_s = torch.empty_like(o), torch.empty_like(s)
-    check(load().misplat_mcmc_relocation(C.c_int64(m), ptr(o), ptr(s), ptr(r), ptr(binoms), C.c_int32(binoms.shape[0]),
-                                         ptr(new_o), ptr(new_s), stream_ptr()), "misplat_mcmc_relocation")
+    run("misplat_mcmc_relocation", m, ptr(o), ptr(s), ptr(r), ptr(binoms), binoms.shape[0], ptr(new_o), ptr(new_s))
     return new_o.reshape(opacities.shape), new_s
 
 
@@ -116,8 +108,7 @@ def inject_noise_to_position(params, optimizers, state: Dict[str, Any], scaler: 
                                f"{tuple(t.shape)} {t.dtype}")
     if opac.numel() != n or opac.dtype != torch.float32 or not opac.is_contiguous():
         raise MisplatError(f"inject_noise_to_position: opacities must hold {n} contiguous float32 logits")
-    check(load().misplat_mcmc_noise(C.c_int64(n), ptr(means), ptr(opac), ptr(scales), ptr(quats), C.c_float(scaler), _u32(seed),
-                                    _u32(step), stream_ptr()), "misplat_mcmc_noise")
+    run("misplat_mcmc_noise", n, ptr(means), ptr(opac), ptr(scales), ptr(quats), scaler, seed, step)
 
 
 def _relocated_values(params, idx: Tensor, counts: Tensor, min_opacity: float, binoms) -> Tuple[Tensor, Tensor]:

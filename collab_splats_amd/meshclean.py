@@ -16,14 +16,13 @@ cannot triangulate.
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import Optional, Sequence, Tuple, Union
 
 import torch
 from torch import Tensor
 
-from ._lib import MisplatError, check, load, ptr, require_gpu, stream_ptr
+from ._lib import MisplatError, load, ptr, require_gpu, run
 from .meshmap import _prep
 from .pointcloud import _cloud, _positive32
 
@@ -64,7 +63,7 @@ def _attributes(name: str, attributes: Sequence[Tensor], m: int, floating: bool)
 
 
 def _workspace(n_vertices: int, n_triangles: int, kind: int, device) -> Tensor:
-    b = int(load().misplat_meshclean_workspace(C.c_int64(n_vertices), C.c_int64(n_triangles), kind))
+    b = int(load().misplat_meshclean_workspace(n_vertices, n_triangles, kind))
     if b < 0:
         raise ValueError(f"meshclean: {n_triangles} triangles / {n_vertices} vertices or points are beyond the library's limits")
     return torch.empty(b, dtype=torch.uint8, device=device)
@@ -81,9 +80,7 @@ def mesh_edge_stats(vertices: Tensor, triangles: Tensor) -> dict:
     counts = torch.empty(3, dtype=torch.int32, device=v.device)
     mean = torch.empty(1, dtype=torch.float64, device=v.device)
     ws = _workspace(v.shape[0], t.shape[0], _STATS, v.device)
-    check(load().misplat_meshclean_edge_stats(ptr(v), C.c_int64(v.shape[0]), ptr(t), C.c_int64(t.shape[0]), ptr(ws),
-                                              C.c_int64(ws.numel()), ptr(counts), ptr(mean), stream_ptr()),
-          "misplat_meshclean_edge_stats")
+    run("misplat_meshclean_edge_stats", ptr(v), v.shape[0], ptr(t), t.shape[0], ptr(ws), ws.numel(), ptr(counts), ptr(mean))
     e, b, nm = counts.tolist()
     return {"n_edges": e, "n_boundary": b, "n_nonmanifold": nm, "mean_edge_length": float(mean.item())}
 
@@ -104,8 +101,7 @@ def _components(v: Tensor, t: Tensor) -> Tuple[Tensor, Tensor]:
     sizes = torch.empty(n, dtype=torch.int32, device=v.device)
     count = torch.empty(1, dtype=torch.int32, device=v.device)
     ws = _workspace(v.shape[0], n, _COMPONENTS, v.device)
-    check(load().misplat_meshclean_components(ptr(t), C.c_int64(v.shape[0]), C.c_int64(n), ptr(ws), C.c_int64(ws.numel()),
-                                              ptr(labels), ptr(sizes), ptr(count), stream_ptr()), "misplat_meshclean_components")
+    run("misplat_meshclean_components", ptr(t), v.shape[0], n, ptr(ws), ws.numel(), ptr(labels), ptr(sizes), ptr(count))
     return labels, sizes[:int(count.item())].clone()
 
 
@@ -168,8 +164,7 @@ def mesh_holes(vertices: Tensor, triangles: Tensor) -> Tuple[Tensor, Tensor, Ten
 
 def _segment_sum(values: Tensor, order: Tensor, offsets: Tensor, n: int) -> Tensor:
     out = torch.empty(n, dtype=torch.float64, device=values.device)
-    check(load().misplat_meshclean_segment_sum(ptr(values), ptr(order), ptr(offsets), C.c_int64(n), ptr(out), stream_ptr()),
-          "misplat_meshclean_segment_sum")
+    run("misplat_meshclean_segment_sum", ptr(values), ptr(order), ptr(offsets), n, ptr(out))
     return out
 
 
@@ -181,8 +176,8 @@ def _holes(v: Tensor, t: Tensor):
     length = torch.empty(3 * n, dtype=torch.float32, device=dev)
     counts = torch.empty(2, dtype=torch.int32, device=dev)
     ws = _workspace(v.shape[0], n, _HOLES, dev)
-    check(load().misplat_meshclean_holes(ptr(v), C.c_int64(v.shape[0]), ptr(t), C.c_int64(n), ptr(ws), C.c_int64(ws.numel()),
-                                         ptr(edges), ptr(loop), ptr(length), ptr(counts), stream_ptr()), "misplat_meshclean_holes")
+    run("misplat_meshclean_holes", ptr(v), v.shape[0], ptr(t), n, ptr(ws), ws.numel(), ptr(edges), ptr(loop), ptr(length),
+        ptr(counts))
     b, n_loops = counts.tolist()                                    # the call's host read
     edges, loop, length = edges[:b].clone(), loop[:b].clone(), length[:b].clone()
     order = torch.sort(loop, stable=True).indices.to(torch.int32)   # edges by loop, in list order inside a loop
@@ -255,8 +250,7 @@ def _fan_patches(v: Tensor, attributes: Tuple[Tensor, ...], loop: Tensor, edges:
     outs = []
     for x in (v,) + attributes:
         mean = torch.empty((n_fill, x.shape[1]), dtype=torch.float32, device=v.device)
-        check(load().misplat_pointcloud_voxel_mean(ptr(x), C.c_int64(m), x.shape[1], ptr(members), ptr(offsets), C.c_int64(n_fill),
-                                                   ptr(mean), stream_ptr()), "misplat_pointcloud_voxel_mean")
+        run("misplat_pointcloud_voxel_mean", ptr(x), m, x.shape[1], ptr(members), ptr(offsets), n_fill, ptr(mean))
         outs.append(torch.cat([x, mean]))
     return fans, new_id[l], outs
 
@@ -297,9 +291,8 @@ def smooth_laplacian(vertices: Tensor, triangles: Tensor, iterations: int = 1, l
     v_tmp = torch.empty_like(v) if iterations > 1 else None
     a_tmp = torch.empty_like(att) if iterations > 1 and att is not None else None
     ws = _workspace(m, n, _SMOOTH, dev)
-    check(load().misplat_meshclean_smooth(ptr(v), C.c_int64(m), ptr(t), C.c_int64(n), ptr(att), d, iterations, C.c_double(lam),
-                                          ptr(ws), C.c_int64(ws.numel()), ptr(v_out), ptr(a_out), ptr(v_tmp), ptr(a_tmp),
-                                          stream_ptr()), "misplat_meshclean_smooth")
+    run("misplat_meshclean_smooth", ptr(v), m, ptr(t), n, ptr(att), d, iterations, lam, ptr(ws), ws.numel(), ptr(v_out),
+        ptr(a_out), ptr(v_tmp), ptr(a_tmp))
     return v_out, (tuple(x.contiguous() for x in torch.split(a_out, widths, 1)) if d else ())
 
 
@@ -331,8 +324,7 @@ def plane_inlier_counts(points: Tensor, planes: Tensor, distance_threshold: floa
 
 def _plane_counts(p: Tensor, pl: Tensor, t: float) -> Tensor:
     counts = torch.empty(pl.shape[0], dtype=torch.int32, device=p.device)
-    check(load().misplat_meshclean_plane_count(ptr(p), C.c_int64(p.shape[0]), ptr(pl), pl.shape[0], C.c_float(t), PLANE_TILE,
-                                               ptr(counts), stream_ptr()), "misplat_meshclean_plane_count")
+    run("misplat_meshclean_plane_count", ptr(p), p.shape[0], ptr(pl), pl.shape[0], t, PLANE_TILE, ptr(counts))
     return counts
 
 
@@ -368,9 +360,7 @@ def ransac_planes(points: Tensor, num_iterations: int = 1000, seed: int = 0, tri
     given = None if triples is None else triples.detach().to(torch.int32).contiguous()
     out = given if given is not None else torch.empty((h, 3), dtype=torch.int32, device=p.device)
     planes = torch.empty((h, 4), dtype=torch.float32, device=p.device)
-    check(load().misplat_meshclean_plane_build(ptr(p), C.c_int64(n), ptr(given), C.c_uint32(seed), h,
-                                               ptr(None if given is not None else out), ptr(planes), stream_ptr()),
-          "misplat_meshclean_plane_build")
+    run("misplat_meshclean_plane_build", ptr(p), n, ptr(given), seed, h, ptr(None if given is not None else out), ptr(planes))
     return out, planes
 
 
@@ -398,8 +388,7 @@ def segment_plane(points: Tensor, distance_threshold: float = 0.02, ransac_n: in
     mask = torch.empty(n, dtype=torch.uint8, device=p.device)
     moments = torch.empty(10, dtype=torch.float64, device=p.device)
     ws = _workspace(n, 0, _MOMENTS, p.device)
-    check(load().misplat_meshclean_plane_moments(ptr(p), C.c_int64(n), ptr(planes[best]), C.c_float(t), ptr(ws), C.c_int64(ws.numel()),
-                                                 ptr(mask), ptr(moments), stream_ptr()), "misplat_meshclean_plane_moments")
+    run("misplat_meshclean_plane_moments", ptr(p), n, ptr(planes[best]), t, ptr(ws), ws.numel(), ptr(mask), ptr(moments))
     host = torch.cat([moments, planes[best].double(), best[None].double()]).tolist()       # the call's host read
     mom, hyp, index = host[:10], host[10:14], int(host[14])
     if mom[0] < 3 or any(math.isnan(x) for x in hyp):

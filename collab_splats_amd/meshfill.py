@@ -15,14 +15,13 @@ tests/meshtri_restatement.py and tests/meshsmooth_restatement.py, bit for bit.  
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import Optional, Sequence, Tuple
 
 import torch
 from torch import Tensor
 
-from ._lib import check, load, ptr, require_gpu, stream_ptr
+from ._lib import load, ptr, require_gpu, run
 from .meshclean import _attributes, _fan_patches, _fans, _holes, _limit, _mesh, mesh_edge_stats
 from .meshmap import _prep
 from .pointcloud import _positive32
@@ -120,11 +119,10 @@ def subdivide_mesh(vertices: Tensor, triangles: Tensor, max_edge_len: float, max
         while rounds < max_rounds and n_splits < budget:
             if ws is None or n > ws_faces:
                 ws_faces = 2 * n
-                ws = torch.empty(int(lib.misplat_meshfill_workspace(C.c_int64(m), C.c_int64(ws_faces))), dtype=torch.uint8, device=dev)
+                ws = torch.empty(int(lib.misplat_meshfill_workspace(m, ws_faces)), dtype=torch.uint8, device=dev)
             # (the workspace is carved for the current n: both calls of a round see the same layout)
-            b = int(lib.misplat_meshfill_workspace(C.c_int64(m), C.c_int64(n)))
-            check(lib.misplat_meshfill_round(ptr(pos), C.c_int64(m), ptr(tri), C.c_int64(n), ptr(reg), C.c_float(max_len), ptr(ws),
-                                             C.c_int64(b), ptr(counts), stream_ptr()), "misplat_meshfill_round")
+            b = int(lib.misplat_meshfill_workspace(m, n))
+            run("misplat_meshfill_round", ptr(pos), m, ptr(tri), n, ptr(reg), max_len, ptr(ws), b, ptr(counts))
             n_sel, n_faces = counts.tolist()                        # the round's host read
             if n_sel == 0:
                 break
@@ -136,9 +134,8 @@ def subdivide_mesh(vertices: Tensor, triangles: Tensor, max_edge_len: float, max
             reg, origin = _grown(reg, tri.shape[0]), _grown(origin, tri.shape[0])
             if d:
                 att = _grown(att, pos.shape[0])
-            check(lib.misplat_meshfill_apply(ptr(pos), C.c_int64(m), ptr(tri), C.c_int64(n), ptr(reg), ptr(origin), ptr(att), d,
-                                             C.c_int64(n_sel), C.c_int64(take if cut else -1), ptr(ws), C.c_int64(b), ptr(counts),
-                                             stream_ptr()), "misplat_meshfill_apply")
+            run("misplat_meshfill_apply", ptr(pos), m, ptr(tri), n, ptr(reg), ptr(origin), ptr(att), d, n_sel,
+                take if cut else -1, ptr(ws), b, ptr(counts))
             if cut:
                 n_faces = counts.tolist()[1]                        # the faces the edges that fitted split
             m, n, n_splits = m + take, n + n_faces, n_splits + take
@@ -187,44 +184,37 @@ def fair_vertices(vertices: Tensor, triangles: Tensor, free: Tensor, tolerance: 
     counts = torch.zeros(4, dtype=torch.int32, device=dev)
 
     def workspace(n_free, n_edges):
-        return torch.empty(int(lib.misplat_meshfill_fair_workspace(C.c_int64(m), C.c_int64(n), C.c_int64(n_free), C.c_int64(n_edges))),
-                           dtype=torch.uint8, device=dev)
+        return torch.empty(int(lib.misplat_meshfill_fair_workspace(m, n, n_free, n_edges)), dtype=torch.uint8, device=dev)
 
     ws = workspace(0, 0)
-    check(lib.misplat_meshfill_fair_count(ptr(t), C.c_int64(n), ptr(fr), C.c_int64(m), ptr(ws), C.c_int64(ws.numel()), ptr(counts),
-                                          stream_ptr()), "misplat_meshfill_fair_count")
+    run("misplat_meshfill_fair_count", ptr(t), n, ptr(fr), m, ptr(ws), ws.numel(), ptr(counts))
     n_free, n_edges = counts.tolist()[:2]                           # the free vertices and the directed edges that leave them
     if n_free == 0:
         return v.clone(), tuple(a.clone() for a in attributes), none
     ws = workspace(n_free, n_edges)
     iters = torch.empty(n_free, dtype=torch.int32, device=dev)
-    sizes = (C.c_int64(m), C.c_int64(n))
-    check(lib.misplat_meshfill_fair_build(ptr(t), sizes[1], ptr(fr), sizes[0], C.c_int64(n_free), C.c_int64(n_edges), ptr(ws),
-                                          C.c_int64(ws.numel()), ptr(iters), ptr(counts), stream_ptr()), "misplat_meshfill_fair_build")
+    run("misplat_meshfill_fair_build", ptr(t), n, ptr(fr), m, n_free, n_edges, ptr(ws), ws.numel(), ptr(iters), ptr(counts))
 
-    def run(a, b, first, count, fixed):
+    def step(a, b, first, count, fixed):
         """Iterations first .. first + count - 1: an odd one reads a and writes b, an even one the other way."""
-        check(lib.misplat_meshfill_fair_step(ptr(a), ptr(b), sizes[0], sizes[1], a.shape[1], C.c_int64(n_free), C.c_int64(n_edges),
-                                             first, count, C.c_float(tol), int(fixed), ptr(ws), C.c_int64(ws.numel()), ptr(iters),
-                                             ptr(counts), stream_ptr()), "misplat_meshfill_fair_step")
+        run("misplat_meshfill_fair_step", ptr(a), ptr(b), m, n, a.shape[1], n_free, n_edges, first, count, tol,
+            int(fixed), ptr(ws), ws.numel(), ptr(iters), ptr(counts))
 
     pos = v.clone()
     n_patches = counts.tolist()[2]
     left = n_patches                                                # the patches that still have to run
     if ENABLE_LDS_FAIR and max_iterations > 0:
-        check(lib.misplat_meshfill_fair_lds(ptr(pos), sizes[0], sizes[1], C.c_int64(n_free), C.c_int64(n_edges), n_patches,
-                                            C.c_float(tol), max_iterations, ptr(ws), C.c_int64(ws.numel()), ptr(iters), ptr(counts),
-                                            stream_ptr()), "misplat_meshfill_fair_lds")
+        run("misplat_meshfill_fair_lds", ptr(pos), m, n, n_free, n_edges, n_patches, tol, max_iterations, ptr(ws),
+            ws.numel(), ptr(iters), ptr(counts))
         left = counts.tolist()[3]                                   # the patches too large for a workgroup's LDS
     done = 0
     other = pos.clone() if left and max_iterations > 0 else None    # (after the LDS path: what it has finished is in both)
     while left and done < max_iterations:
         batch = min(32, max_iterations - done)
-        run(pos, other, done + 1, batch, False)
+        step(pos, other, done + 1, batch, False)
         done += batch
         left = counts.tolist()[3]                                   # the patches that are still running
-    check(lib.misplat_meshfill_fair_finish(C.c_int64(n_free), done, ptr(iters), ptr(counts), stream_ptr()),
-          "misplat_meshfill_fair_finish")
+    run("misplat_meshfill_fair_finish", n_free, done, ptr(iters), ptr(counts))
     if done & 1:
         pos = other
     iterations = iters[:n_patches].clone()
@@ -234,7 +224,7 @@ def fair_vertices(vertices: Tensor, triangles: Tensor, free: Tensor, tolerance: 
         a = a.clone()
         b = a.clone() if most else None
         for first in range(1, most + 1, 1024):
-            run(a, b, first, min(1024, most - first + 1), True)
+            step(a, b, first, min(1024, most - first + 1), True)
         out.append(b if most & 1 else a)
     return pos, tuple(out), iterations
 
@@ -305,8 +295,7 @@ def fair_vertices_curvature(vertices: Tensor, triangles: Tensor, free: Tensor, r
     n_entries = es.shape[0]
     parent = torch.arange(m, **i32)
     root = torch.empty(m, **i32)
-    check(lib.misplat_meshfill_curv_patches(ptr(es), ptr(et), C.c_int64(n_entries), ptr(fr.view(torch.uint8)), C.c_int64(m), ptr(parent),
-                                            ptr(root), stream_ptr()), "misplat_meshfill_curv_patches")
+    run("misplat_meshfill_curv_patches", ptr(es), ptr(et), n_entries, ptr(fr.view(torch.uint8)), m, ptr(parent), ptr(root))
     # patches by their smallest free vertex; the free vertices and the rows of R by patch and then by vertex
     roots, of_free = torch.unique(root[flist].long(), return_inverse=True)
     n_patches = roots.shape[0]
@@ -330,18 +319,16 @@ def fair_vertices_curvature(vertices: Tensor, triangles: Tensor, free: Tensor, r
     has_degree = torch.zeros(n_patches, dtype=torch.bool, device=dev)
     has_degree[pf[degree_of[torch.nonzero(fr).view(-1)] > 0]] = True
     code = torch.where(~has_degree, 1, torch.where(n_r == 0, 2, torch.where(n_f > CG_VERTICES, 3, 0))).to(torch.int32)
-    ws = torch.empty(int(lib.misplat_meshfill_curv_workspace(C.c_int64(n_free), C.c_int64(n_rows))), dtype=torch.uint8, device=dev)
+    ws = torch.empty(int(lib.misplat_meshfill_curv_workspace(n_free, n_rows)), dtype=torch.uint8, device=dev)
     out = v.clone()
     iterations = torch.empty(n_patches, **i32)
     converged = torch.empty(n_patches, dtype=torch.uint8, device=dev)
     residual = torch.empty(n_patches, dtype=torch.float64, device=dev)
     vertex, row, degree = slist.to(torch.int32), start_of[slist].to(torch.int32), degree_of[slist].to(torch.int32)
     place = place_of[et.long()].contiguous()
-    check(lib.misplat_meshfill_curv_solve(ptr(v), ptr(out), C.c_int64(m), ptr(foff), ptr(roff), ptr(vertex), ptr(row), ptr(degree),
-                                          ptr(et), ptr(place), C.c_int64(n_free), C.c_int64(n_rows), C.c_int64(n_entries), ptr(code),
-                                          n_patches, C.c_double(rtol), -1 if max_iterations is None else max_iterations, ptr(ws),
-                                          C.c_int64(ws.numel()), ptr(iterations), ptr(converged), ptr(residual), stream_ptr()),
-          "misplat_meshfill_curv_solve")
+    run("misplat_meshfill_curv_solve", ptr(v), ptr(out), m, ptr(foff), ptr(roff), ptr(vertex), ptr(row), ptr(degree), ptr(et),
+        ptr(place), n_free, n_rows, n_entries, ptr(code), n_patches, rtol, -1 if max_iterations is None else max_iterations,
+        ptr(ws), ws.numel(), ptr(iterations), ptr(converged), ptr(residual))
     return out, {"iterations": iterations, "converged": converged.bool(), "residual": residual, "code": code}
 
 
@@ -511,13 +498,12 @@ def _triangulated(v: Tensor, t: Tensor, attributes: Tuple[Tensor, ...], limit: f
         if 6 * t.shape[0] >= (1 << 31) - 4096:
             raise ValueError(f"triangulate_holes: {t.shape[0]} triangles are beyond the library's limits (6 T < 2^31 - 4096)")
         rim = torch.empty(n_boundary, dtype=torch.int32, device=dev)
-        ws = torch.empty(int(lib.misplat_meshtri_rim_workspace(C.c_int64(t.shape[0]))), dtype=torch.uint8, device=dev)
-        check(lib.misplat_meshtri_order_rim(ptr(edges), ptr(order), ptr(offsets), ptr(fill.view(torch.uint8)), C.c_int64(n_boundary),
-                                            C.c_int64(n_loops), ptr(t), C.c_int64(t.shape[0]), ptr(ws), C.c_int64(ws.numel()),
-                                            ptr(code), ptr(polygon), ptr(rim), stream_ptr()), "misplat_meshtri_order_rim")
+        ws = torch.empty(int(lib.misplat_meshtri_rim_workspace(t.shape[0])), dtype=torch.uint8, device=dev)
+        run("misplat_meshtri_order_rim", ptr(edges), ptr(order), ptr(offsets), ptr(fill.view(torch.uint8)), n_boundary, n_loops,
+            ptr(t), t.shape[0], ptr(ws), ws.numel(), ptr(code), ptr(polygon), ptr(rim))
     else:
-        check(lib.misplat_meshtri_order(ptr(edges), ptr(order), ptr(offsets), ptr(fill.view(torch.uint8)), C.c_int64(n_boundary),
-                                        C.c_int64(n_loops), ptr(code), ptr(polygon), stream_ptr()), "misplat_meshtri_order")
+        run("misplat_meshtri_order", ptr(edges), ptr(order), ptr(offsets), ptr(fill.view(torch.uint8)), n_boundary, n_loops,
+            ptr(code), ptr(polygon))
     lds_loop = ANGLE_LDS_LOOP if angle else LDS_LOOP
     n = n_edges.long()
     tri, fan = code == 0, code > 0
@@ -539,18 +525,15 @@ def _triangulated(v: Tensor, t: Tensor, attributes: Tuple[Tensor, ...], limit: f
         ws = None
         if n_entries:
             size = lib.misplat_meshtri_angle_workspace if angle else lib.misplat_meshtri_workspace
-            ws = torch.empty(int(size(C.c_int64(n_entries))), dtype=torch.uint8, device=dev)
+            ws = torch.empty(int(size(n_entries)), dtype=torch.uint8, device=dev)
     if n_tri and angle:
-        check(lib.misplat_meshtri_angle_dp(ptr(v), C.c_int64(v.shape[0]), ptr(polygon), ptr(rim), ptr(offsets), ptr(code),
-                                           C.c_int64(n_loops), paths, ptr(slab_offset), C.c_int64(n_entries), ptr(ws),
-                                           C.c_int64(ws.numel() if n_entries else 0), ptr(face_base), C.c_int64(n_faces),
-                                           ptr(area_slot), C.c_int64(n_tri), ptr(faces), ptr(area), ptr(badness), stream_ptr()),
-              "misplat_meshtri_angle_dp")
+        run("misplat_meshtri_angle_dp", ptr(v), v.shape[0], ptr(polygon), ptr(rim), ptr(offsets), ptr(code), n_loops, paths,
+            ptr(slab_offset), n_entries, ptr(ws), ws.numel() if n_entries else 0, ptr(face_base), n_faces, ptr(area_slot),
+            n_tri, ptr(faces), ptr(area), ptr(badness))
     elif n_tri:
-        check(lib.misplat_meshtri_dp(ptr(v), C.c_int64(v.shape[0]), ptr(polygon), ptr(offsets), ptr(code), C.c_int64(n_loops), paths,
-                                     ptr(slab_offset), C.c_int64(n_entries), ptr(ws), C.c_int64(ws.numel() if n_entries else 0),
-                                     ptr(face_base), C.c_int64(n_faces), ptr(area_slot), C.c_int64(n_tri), ptr(faces), ptr(area),
-                                     stream_ptr()), "misplat_meshtri_dp")
+        run("misplat_meshtri_dp", ptr(v), v.shape[0], ptr(polygon), ptr(offsets), ptr(code), n_loops, paths, ptr(slab_offset),
+            n_entries, ptr(ws), ws.numel() if n_entries else 0, ptr(face_base), n_faces, ptr(area_slot), n_tri, ptr(faces),
+            ptr(area))
     outs = [v, *attributes]
     if n_fans:
         fans, fan_of, outs = _fan_patches(v, attributes, loop, edges, order, fan, n_fans)
@@ -603,10 +586,9 @@ def flip_edges(vertices: Tensor, triangles: Tensor, region: Optional[Tensor] = N
         dev = v.device
         reg = (torch.ones(n, dtype=torch.uint8, device=dev) if region is None else region.detach().to(torch.uint8)).contiguous()
         counts = torch.empty(1, dtype=torch.int32, device=dev)
-        ws = torch.empty(int(lib.misplat_meshtri_flip_workspace(C.c_int64(m), C.c_int64(n))), dtype=torch.uint8, device=dev)
+        ws = torch.empty(int(lib.misplat_meshtri_flip_workspace(m, n)), dtype=torch.uint8, device=dev)
         while rounds < max_rounds:
-            check(lib.misplat_meshtri_flip_round(ptr(v), C.c_int64(m), ptr(tri), C.c_int64(n), ptr(reg), C.c_double(min_violation),
-                                                 ptr(ws), C.c_int64(ws.numel()), ptr(counts), stream_ptr()), "misplat_meshtri_flip_round")
+            run("misplat_meshtri_flip_round", ptr(v), m, ptr(tri), n, ptr(reg), min_violation, ptr(ws), ws.numel(), ptr(counts))
             k = int(counts.item())                                  # the round's host read
             if k == 0:
                 break

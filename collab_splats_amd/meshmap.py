@@ -8,13 +8,12 @@ holds the weighted mean of what it received (0 if nothing).  Everything stays on
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Tuple
 
 import torch
 from torch import Tensor
 
-from ._lib import MisplatError, check, load, ptr, require_gpu, stream_ptr
+from ._lib import MisplatError, load, ptr, require_gpu, run
 
 MAX_K = 16
 COORD_CELLS = 2.0 ** 18              # every vertex: |x| / sdf_trunc < 2^18 per axis (csrc/meshmap.hip kCoordCells)
@@ -38,7 +37,7 @@ def _check(name: str, mesh_vertices: Tensor, points: Tensor, values, k: int, sdf
 
 
 def _workspace(M: int, N: int, k: int, D: int, device) -> Tensor:
-    n = int(load().misplat_meshmap_workspace(C.c_int64(M), C.c_int64(N), k, D))
+    n = int(load().misplat_meshmap_workspace(M, N, k, D))
     if n < 0:
         raise ValueError(f"meshmap: sizes M={M}, N={N}, k={k}, D={D} are beyond the library's limits")
     return torch.empty(n, dtype=torch.uint8, device=device)
@@ -53,8 +52,8 @@ def _knn_ws(vertices: Tensor, points: Tensor, k: int, sdf_trunc: float, ws: Tens
     idx = torch.empty((N, k), dtype=torch.int32, device=dev)
     dist = torch.empty((N, k), dtype=torch.float32, device=dev)
     valid = torch.empty(N, dtype=torch.uint8, device=dev)
-    check(load().misplat_meshmap_knn(ptr(vertices), C.c_int64(M), ptr(points), C.c_int64(N), k, C.c_float(sdf_trunc), ptr(ws),
-                                     C.c_int64(ws.numel()), ptr(idx), ptr(dist), ptr(valid), stream_ptr()), "misplat_meshmap_knn")
+    run("misplat_meshmap_knn", ptr(vertices), M, ptr(points), N, k, sdf_trunc, ptr(ws), ws.numel(), ptr(idx), ptr(dist),
+        ptr(valid))
     return idx, dist, valid
 
 
@@ -76,8 +75,8 @@ def _aggregate(M: int, idx: Tensor, dist: Tensor, valid: Tensor, values: Tensor,
     N, k = idx.shape
     D = values.shape[1]
     out = torch.empty((M, D), dtype=torch.float32, device=values.device)
-    check(load().misplat_meshmap_aggregate(C.c_int64(M), C.c_int64(N), k, ptr(idx), ptr(dist), ptr(valid), ptr(values), D, n_unit,
-                                           ptr(ws), C.c_int64(ws.numel()), ptr(out), stream_ptr()), "misplat_meshmap_aggregate")
+    run("misplat_meshmap_aggregate", M, N, k, ptr(idx), ptr(dist), ptr(valid), ptr(values), D, n_unit, ptr(ws), ws.numel(),
+        ptr(out))
     return out
 
 

@@ -13,7 +13,6 @@ There is no CPU fallback for the clustering.
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import List, Optional, Sequence, Tuple
 
@@ -21,7 +20,7 @@ import torch
 import torch.nn.functional as F
 from torch import Tensor
 
-from ._lib import MisplatError, check, load, ptr, require_gpu, stream_ptr
+from ._lib import MisplatError, load, ptr, require_gpu, run
 from .meshmap import COORD_CELLS, _prep
 
 
@@ -115,14 +114,13 @@ def _cluster(vertices: Tensor, mask: Tensor, radius: float, min_cluster_size: in
     sizes = torch.empty(M, dtype=torch.int32, device=dev)
     if M == 0:
         return labels, sizes, 0
-    n = int(load().misplat_cluster_workspace(C.c_int64(M)))
+    n = int(load().misplat_cluster_workspace(M))
     if n < 0:
         raise ValueError(f"meshquery: {M} vertices are beyond the library's limits")
     ws = torch.empty(n, dtype=torch.uint8, device=dev)
     count = torch.empty(1, dtype=torch.int32, device=dev)
-    check(load().misplat_cluster_radius(ptr(vertices), C.c_int64(M), ptr(mask), C.c_float(radius), min_cluster_size, ptr(ws),
-                                        C.c_int64(ws.numel()), ptr(labels), ptr(sizes), ptr(count), stream_ptr()),
-          "misplat_cluster_radius")
+    run("misplat_cluster_radius", ptr(vertices), M, ptr(mask), radius, min_cluster_size, ptr(ws), ws.numel(), ptr(labels),
+        ptr(sizes), ptr(count))
     return labels, sizes, int(count.item())                     # host read 2 of 2
 
 

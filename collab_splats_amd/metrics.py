@@ -14,14 +14,13 @@ reads anything back to the host.  There is no CPU fallback.
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, Optional, Tuple
 
 import torch
 from torch import Tensor
 
 from . import _lib
-from ._lib import check, ptr, require_gpu, stream_ptr
+from ._lib import ptr, require_gpu, run
 
 MAX_VIEWS = 65535
 SSIM_WINDOW = 11
@@ -74,7 +73,7 @@ def _valid(valid: Optional[Tensor], shape, what: str) -> Optional[Tensor]:
 
 
 def _scratch(fn, B: int, H: int, W: int, dev, what: str) -> Tensor:
-    n = int(fn(C.c_int32(B), C.c_int32(H), C.c_int32(W)))
+    n = int(fn(B, H, W))
     if n < 0:
         raise ValueError(f"{what}: sizes outside the kernels' limits ({B} views of {H} x {W})")
     return torch.empty(n, device=dev, dtype=torch.float32)
@@ -99,8 +98,7 @@ def image_metrics(pred: Tensor, gt: Tensor, ssim: bool = True) -> Dict[str, Tens
     pred, gt = pred.detach().contiguous(), gt.detach().contiguous()
     scratch = _scratch(lib.misplat_eval_image_scratch_floats, B, H, W, pred.device, what)
     out = torch.empty(B, 4, device=pred.device, dtype=torch.float32)
-    check(lib.misplat_eval_image(C.c_int32(B), C.c_int32(H), C.c_int32(W), ptr(pred), ptr(gt), C.c_int32(int(bool(ssim))),
-                                 ptr(scratch), ptr(out), stream_ptr()), "misplat_eval_image")
+    run("misplat_eval_image", B, H, W, ptr(pred), ptr(gt), int(bool(ssim)), ptr(scratch), ptr(out))
     res = {"psnr": out[:, 3], "mse": out[:, 0], "l1": out[:, 1]}
     if ssim:
         res["ssim"] = out[:, 2]
@@ -137,9 +135,8 @@ def normal_metrics(pred: Tensor, gt: Tensor, valid: Optional[Tensor] = None, enc
     scratch = _scratch(lib.misplat_eval_pixels_scratch_floats, B, H, W, pred.device, what)
     out = torch.empty(B, 5, device=pred.device, dtype=torch.float32)
     amap = torch.empty(B, H, W, device=pred.device, dtype=torch.float32) if return_map else None
-    check(lib.misplat_eval_normals(C.c_int32(B), C.c_int32(H), C.c_int32(W), ptr(pred), ptr(gt), ptr(valid),
-                                   C.c_int32(int(bool(encoded))), C.c_int32(int(bool(normalize))), ptr(amap), ptr(scratch),
-                                   ptr(out), stream_ptr()), "misplat_eval_normals")
+    run("misplat_eval_normals", B, H, W, ptr(pred), ptr(gt), ptr(valid), int(bool(encoded)), int(bool(normalize)), ptr(amap),
+        ptr(scratch), ptr(out))
     res = {"mean": out[:, 0], "a11.25": out[:, 1], "a22.5": out[:, 2], "a30": out[:, 3], "count": out[:, 4]}
     if return_map:
         res["map"] = amap
@@ -175,9 +172,8 @@ def depth_metrics(pred: Tensor, gt: Tensor, valid: Optional[Tensor] = None, max_
     pred, gt = pred.detach().contiguous(), gt.detach().contiguous()
     scratch = _scratch(lib.misplat_eval_pixels_scratch_floats, B, H, W, pred.device, what)
     out = torch.empty(B, 8, device=pred.device, dtype=torch.float32)
-    check(lib.misplat_eval_depth(C.c_int32(B), C.c_int32(H), C.c_int32(W), ptr(pred), ptr(gt), ptr(valid),
-                                 C.c_float(0.0 if max_depth is None else float(max_depth)), ptr(scratch), ptr(out), stream_ptr()),
-          "misplat_eval_depth")
+    run("misplat_eval_depth", B, H, W, ptr(pred), ptr(gt), ptr(valid), 0.0 if max_depth is None else float(max_depth),
+        ptr(scratch), ptr(out))
     names = ("abs_rel", "sq_rel", "rmse", "rmse_log", "delta1", "delta2", "delta3", "count")
     return {k: out[:, i] for i, k in enumerate(names)}
 
@@ -214,9 +210,7 @@ def color_correct(pred: Tensor, gt: Tensor, num_iters: int = 5, eps: float = 0.5
     out = torch.empty_like(pred)
     warps = torch.empty(B, num_iters, 10, 3, device=pred.device, dtype=torch.float64)
     counts = torch.empty(B, num_iters, 3, device=pred.device, dtype=torch.int64)
-    check(lib.misplat_colorcorrect(C.c_int32(B), C.c_int32(H), C.c_int32(W), ptr(pred), ptr(gt), C.c_int32(num_iters),
-                                   C.c_float(eps), ptr(scratch), ptr(out), ptr(warps), ptr(counts), stream_ptr()),
-          "misplat_colorcorrect")
+    run("misplat_colorcorrect", B, H, W, ptr(pred), ptr(gt), num_iters, eps, ptr(scratch), ptr(out), ptr(warps), ptr(counts))
     if single:
         out = out[0]
     return (out, {"warps": warps, "counts": counts}) if return_fit else out

@@ -17,7 +17,7 @@ import torch
 from torch import Tensor
 
 from . import _lib, arena
-from ._lib import MISPLAT_REC, Params, RasterArgs, RasterBwdArgs, check, ptr, require_gpu, stream_ptr
+from ._lib import MISPLAT_REC, Params, RasterArgs, RasterBwdArgs, check, ptr, require_gpu, run, stream_ptr
 
 
 # False (default): every (band, Gaussian) gradient row is added into the per-Gaussian gradient with
@@ -133,7 +133,7 @@ class _UnitSchedule:
         P.unit_perm, P.unit_work = None, None
         if not self.on:
             return
-        check(_lib.load().misplat_unit_order(C.byref(P), ptr(self.work), ptr(self.perm), stream_ptr()), "misplat_unit_order")
+        run("misplat_unit_order", C.byref(P), ptr(self.work), ptr(self.perm))
         _LAST_ORDER[self.key] = self.perm
         self.perm_bwd = self.perm
 
@@ -236,7 +236,7 @@ def bucket_plan(P: Params) -> Tuple[int, int]:
     key = (P.n_gauss, P.n_cams, P.tile_w, P.tile_h)
     if key not in _PLAN_CACHE:
         nc, nb = C.c_int32(0), C.c_int32(0)
-        check(_lib.load().misplat_bucket_plan(C.byref(P), C.byref(nc), C.byref(nb)), "misplat_bucket_plan")
+        run("misplat_bucket_plan", C.byref(P), C.byref(nc), C.byref(nb))
         _PLAN_CACHE[key] = (int(nc.value), int(nb.value))
     return _PLAN_CACHE[key]
 
@@ -317,7 +317,7 @@ def _graph_cache(dev: torch.device):
         return None                                     # (the caller is capturing the whole step: plain launches)
     idx = dev.index if dev.index is not None else torch.cuda.current_device()
     if idx not in _GRAPH_CACHE:
-        h = _lib.load().misplat_graph_cache_create(C.c_int32(GRAPH_CACHE_ENTRIES))
+        h = _lib.load().misplat_graph_cache_create(GRAPH_CACHE_ENTRIES)
         if not h:
             raise _lib.MisplatError("misplat_graph_cache_create failed")
         _GRAPH_CACHE[idx] = h
@@ -339,12 +339,12 @@ def graph_cache_stats(dev: Optional[torch.device] = None) -> Dict[str, int]:
     if idx not in _GRAPH_CACHE:
         return dict(hits=0, captures=0)
     h, c = C.c_int64(0), C.c_int64(0)
-    check(_lib.load().misplat_graph_cache_stats(C.c_void_p(_GRAPH_CACHE[idx]), C.byref(h), C.byref(c)), "misplat_graph_cache_stats")
+    run("misplat_graph_cache_stats", C.c_void_p(_GRAPH_CACHE[idx]), C.byref(h), C.byref(c))
     return dict(hits=int(h.value), captures=int(c.value))
 
 
 def _wait_count(host: Tensor) -> int:
-    n = int(_lib.load().misplat_wait_count(C.c_void_p(host.data_ptr()), C.c_int64(20_000_000)))
+    n = int(_lib.load().misplat_wait_count(C.c_void_p(host.data_ptr()), 20_000_000))
     if n < 0:
         raise _lib.MisplatError("timed out waiting for the intersection count (GPU hung?)")
     return n
@@ -560,7 +560,7 @@ def _raster_phase_a(P: Params, means, quats, scales, opacities, colors, colors_r
                                                                      _order_slots(order[0], order[2]), order[2])
     PATH_STATS["forward_rows_on_touch"] += int(rows_on_touch)
     if not defer:
-        check(lib.misplat_raster_fwd(C.byref(P), C.byref(a), C.c_int32(1), stream_ptr(), _graph_cache(dev)),
+        check(lib.misplat_raster_fwd(C.byref(P), C.byref(a), 1, stream_ptr(), _graph_cache(dev)),
               "misplat_raster_fwd(A)")
     state = dict(args=a, host=host, tiles_per_gauss=tiles_per_gauss, depths=depths, v_grec_zero=v_grec_zero, v_abs_zero=v_abs_zero,
                  deferred=defer, rows_on_touch=rows_on_touch, order=order, carver=cv, featx=featx, v_featx_zero=v_featx_zero,
@@ -667,7 +667,7 @@ def _phase_b_launch(P: Params, state: dict, prep: dict, cd: int, cv):
         with _timed("raster_fwd_B"):
             if KEY_TRACE is not None:
                 KEY_TRACE.append(("fwd%d" % phases, bytes(P) + bytes(a)))
-            check(lib.misplat_raster_fwd(C.byref(P), C.byref(a), C.c_int32(phases), stream_ptr(), _graph_cache(dev)),
+            check(lib.misplat_raster_fwd(C.byref(P), C.byref(a), phases, stream_ptr(), _graph_cache(dev)),
                   "misplat_raster_fwd(B)")
         a.ev_blend_begin, a.ev_blend_end = None, None
         phases = 2
@@ -682,7 +682,7 @@ def _phase_b_launch(P: Params, state: dict, prep: dict, cd: int, cv):
         prep["overflow"] = True
         PATH_STATS["capacity_redo"] += 1
         tc = state["keep"][6]                                         # tile_count: phase B expects it cleared
-        check(lib.misplat_zero_bytes(ptr(tc), C.c_size_t(4 * tc.numel()), stream_ptr()), "misplat_zero_bytes")
+        check(lib.misplat_zero_bytes(ptr(tc), 4 * tc.numel(), stream_ptr()), "misplat_zero_bytes")
         if cap >= 2 ** 31:
             raise _lib.MisplatError(f"{cap} tile intersections exceed int32 indexing")
         payload, flatten_ids, scratch = _isect_buffers(dev, cv, cap)
@@ -1029,26 +1029,20 @@ class _RasterFused(torch.autograd.Function):
             if by_view is not None:
                 P.unit_perm, P.unit_sel, P.unit_stride = by_view[0].data_ptr(), by_view[1].data_ptr(), by_view[2]
                 P.unit_slots = _order_slots(by_view[0], by_view[2])
-            check(lib.misplat_blend_bwd_atomic(C.byref(P), C.c_int32(cd), ptr(Ks), ptr(grec), ptr(bins["flatten_ids"]),
-                                               ptr(bins["isect_offsets"]), C.c_int64(bins["n_isects"]), ptr(alpha),
-                                               ptr(last_ids), ptr(median_ids), ptr(render), *[ptr(t) for t in ups],
-                                               ptr(v_grec), ptr(v_abs), C.c_int32(flags), stream_ptr()),
-                  "misplat_blend_bwd_atomic")
+            run("misplat_blend_bwd_atomic", C.byref(P), cd, ptr(Ks), ptr(grec), ptr(bins["flatten_ids"]),
+                ptr(bins["isect_offsets"]), bins["n_isects"], ptr(alpha), ptr(last_ids), ptr(median_ids), ptr(render),
+                *[ptr(t) for t in ups], ptr(v_grec), ptr(v_abs), flags)
             P.unit_perm, P.unit_sel, P.unit_stride, P.unit_slots = None, None, 0, 0
-            check(lib.misplat_color_bwd(C.byref(P), C.c_int32(deg), C.c_int32(kd), C.c_int32(n_color),
-                                        C.c_int32(per_cam), ptr(means), ptr(viewmats), ptr(colors), ptr(colors_rest),
-                                        ptr(radii), ptr(v_grec), ptr(v_colors), ptr(v_colors_rest), ptr(v_means_dir),
-                                        ptr(sh_aux), stream_ptr()), "misplat_color_bwd")
+            run("misplat_color_bwd", C.byref(P), deg, kd, n_color, per_cam, ptr(means), ptr(viewmats), ptr(colors),
+                ptr(colors_rest), ptr(radii), ptr(v_grec), ptr(v_colors), ptr(v_colors_rest), ptr(v_means_dir), ptr(sh_aux))
             if GRAD_SINK is not None:
                 GRAD_SINK.colour_ready()
             vm2d = None
             if v_means2d_in is not None:
                 vm2d = (v_grec.view(P.n_cams, P.n_gauss, MISPLAT_REC)[..., 0:2] + v_means2d_in).contiguous()
-            check(lib.misplat_project_pack_bwd(C.byref(P), C.c_int32(ctx.depth_slot), ptr(means), ptr(quats),
-                                               ptr(scales), ptr(opacities), ptr(viewmats), ptr(Ks), ptr(radii),
-                                               ptr(comps), ptr(vm2d), ptr(v_grec), ptr(v_means_dir), ptr(v_means),
-                                               ptr(v_quats), ptr(v_scales), ptr(v_opac), None, C.c_int32(0), stream_ptr()),
-                  "misplat_project_pack_bwd")
+            run("misplat_project_pack_bwd", C.byref(P), ctx.depth_slot, ptr(means), ptr(quats), ptr(scales), ptr(opacities),
+                ptr(viewmats), ptr(Ks), ptr(radii), ptr(comps), ptr(vm2d), ptr(v_grec), ptr(v_means_dir), ptr(v_means),
+                ptr(v_quats), ptr(v_scales), ptr(v_opac), None, 0)
         cvb.done()
         # gsplat's contract: the screen-space gradient rides on meta["means2d"]
         m2d = ctx.means2d_ref()

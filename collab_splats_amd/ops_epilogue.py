@@ -11,7 +11,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._lib import check, ptr, require_gpu, stream_ptr
+from ._lib import ptr, require_gpu, run
 
 
 def _c(t: Optional[Tensor]) -> Optional[Tensor]:
@@ -30,29 +30,23 @@ def _f32(t: Tensor, name: str) -> Tensor:
 class _DepthNormal(torch.autograd.Function):
     @staticmethod
     def forward(ctx, exp_depth, med_depth, n_render, fx: float, fy: float):
-        lib = _lib.load()
         require_gpu(exp_depth, med_depth, n_render)
         H, W = exp_depth.shape[-2], exp_depth.shape[-1]
         dev = exp_depth.device
         normals2 = torch.empty(2, H, W, 3, device=dev, dtype=torch.float32)
         err = torch.empty(2, H, W, device=dev, dtype=torch.float32)
-        check(lib.misplat_depth_normal_fwd(C.c_int32(W), C.c_int32(H), C.c_float(fx), C.c_float(fy),
-                                           ptr(exp_depth), ptr(med_depth), ptr(n_render), ptr(normals2),
-                                           ptr(err), stream_ptr()), "misplat_depth_normal_fwd")
+        run("misplat_depth_normal_fwd", W, H, fx, fy, ptr(exp_depth), ptr(med_depth), ptr(n_render), ptr(normals2), ptr(err))
         ctx.save_for_backward(exp_depth, med_depth, n_render)
         ctx.fx, ctx.fy = fx, fy
         return normals2, err
 
     @staticmethod
     def backward(ctx, v_normals2, v_err):
-        lib = _lib.load()
         ed, md, nr = ctx.saved_tensors
         H, W = ed.shape[-2], ed.shape[-1]
         v_ed, v_md, v_nr = torch.empty_like(ed), torch.empty_like(md), torch.empty_like(nr)
-        check(lib.misplat_depth_normal_bwd(C.c_int32(W), C.c_int32(H), C.c_float(ctx.fx), C.c_float(ctx.fy),
-                                           ptr(ed), ptr(md), ptr(nr), ptr(_c(v_normals2)), ptr(_c(v_err)),
-                                           ptr(v_ed), ptr(v_md), ptr(v_nr), C.c_int32(0), stream_ptr()),
-              "misplat_depth_normal_bwd")
+        run("misplat_depth_normal_bwd", W, H, ctx.fx, ctx.fy, ptr(ed), ptr(md), ptr(nr), ptr(_c(v_normals2)), ptr(_c(v_err)),
+            ptr(v_ed), ptr(v_md), ptr(v_nr), 0)
         return v_ed, v_md, v_nr, None, None
 
 
@@ -68,7 +62,6 @@ def depth_normal(exp_depth: Tensor, med_depth: Tensor, n_render: Tensor, fx: flo
 class _Outputs(torch.autograd.Function):
     @staticmethod
     def forward(ctx, render, alpha, exp_depth, med_depth, exp_normal, bg, want_depth_im: bool):
-        lib = _lib.load()
         require_gpu(render, alpha, exp_depth, med_depth, exp_normal)
         cd = render.shape[-1]
         n_pix = alpha.numel()
@@ -80,9 +73,8 @@ class _Outputs(torch.autograd.Function):
         depth_im = torch.empty_like(alpha) if want_depth_im else None
         maxes = torch.empty(4, **f)
         bg_c = (C.c_float * 3)(*[float(b) for b in bg])
-        check(lib.misplat_outputs_fwd(C.c_int64(n_pix), C.c_int32(cd), bg_c, ptr(render), ptr(alpha), ptr(exp_depth),
-                                      ptr(med_depth), ptr(exp_normal), ptr(maxes), ptr(rgb), ptr(depth), ptr(median),
-                                      ptr(normals), ptr(depth_im), stream_ptr()), "misplat_outputs_fwd")
+        run("misplat_outputs_fwd", n_pix, cd, bg_c, ptr(render), ptr(alpha), ptr(exp_depth), ptr(med_depth), ptr(exp_normal),
+            ptr(maxes), ptr(rgb), ptr(depth), ptr(median), ptr(normals), ptr(depth_im))
         ctx.save_for_backward(render, alpha)
         ctx.bg, ctx.cd, ctx.want_depth_im = bg_c, cd, want_depth_im
         if want_depth_im:
@@ -91,16 +83,14 @@ class _Outputs(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, v_rgb, v_depth, v_median, v_normals, v_depth_im=None):
-        lib = _lib.load()
         render, alpha = ctx.saved_tensors
         v_render = torch.empty_like(render)
         v_alpha, v_ed, v_md = torch.empty_like(alpha), torch.empty_like(alpha), torch.empty_like(alpha)
         v_nr = torch.empty_like(v_normals)
         ups = [_c(t) for t in (v_rgb, v_depth, v_median, v_normals)]
         vdi = _c(v_depth_im) if ctx.want_depth_im else None
-        check(lib.misplat_outputs_bwd(C.c_int64(alpha.numel()), C.c_int32(ctx.cd), ctx.bg, ptr(render), ptr(alpha),
-                                      *[ptr(t) for t in ups], ptr(vdi), ptr(v_render), ptr(v_alpha), ptr(v_ed),
-                                      ptr(v_md), ptr(v_nr), stream_ptr()), "misplat_outputs_bwd")
+        run("misplat_outputs_bwd", alpha.numel(), ctx.cd, ctx.bg, ptr(render), ptr(alpha), *[ptr(t) for t in ups], ptr(vdi),
+            ptr(v_render), ptr(v_alpha), ptr(v_ed), ptr(v_md), ptr(v_nr))
         return v_render, v_alpha, v_ed, v_md, v_nr, None, None
 
 
@@ -122,7 +112,6 @@ class _GetOutputs(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, render, alpha, exp_depth, med_depth, exp_normal, bg, want_depth_im: bool, fx: float, fy: float):
-        lib = _lib.load()
         require_gpu(render, alpha, exp_depth, med_depth, exp_normal)
         if alpha.shape[0] != 1:
             raise ValueError("get_outputs epilogue: one camera per call (rade_gs_model.py:94-95)")
@@ -137,12 +126,9 @@ class _GetOutputs(torch.autograd.Function):
         err = torch.empty(2, H, W, **f)
         normals2 = torch.empty(2, H, W, 3, **f)
         bg_c = (C.c_float * 3)(*[float(b) for b in bg])
-        check(lib.misplat_depth_normal_fwd(C.c_int32(W), C.c_int32(H), C.c_float(fx), C.c_float(fy), ptr(exp_depth),
-                                           ptr(med_depth), ptr(exp_normal), ptr(normals2), ptr(err), stream_ptr()),
-              "misplat_depth_normal_fwd")
-        check(lib.misplat_outputs_fwd(C.c_int64(H * W), C.c_int32(cd), bg_c, ptr(render), ptr(alpha), ptr(exp_depth),
-                                      ptr(med_depth), ptr(exp_normal), ptr(maxes), ptr(rgb), ptr(depth), ptr(median),
-                                      ptr(normals), ptr(depth_im), stream_ptr()), "misplat_outputs_fwd")
+        run("misplat_depth_normal_fwd", W, H, fx, fy, ptr(exp_depth), ptr(med_depth), ptr(exp_normal), ptr(normals2), ptr(err))
+        run("misplat_outputs_fwd", H * W, cd, bg_c, ptr(render), ptr(alpha), ptr(exp_depth), ptr(med_depth), ptr(exp_normal),
+            ptr(maxes), ptr(rgb), ptr(depth), ptr(median), ptr(normals), ptr(depth_im))
         ctx.save_for_backward(render, alpha, exp_depth, med_depth, exp_normal)
         ctx.bg, ctx.cd, ctx.want_depth_im, ctx.fx, ctx.fy = bg_c, cd, want_depth_im, fx, fy
         ctx.set_materialize_grads(False)
@@ -152,21 +138,17 @@ class _GetOutputs(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, v_rgb, v_depth, v_median, v_normals, v_err, v_depth_im=None):
-        lib = _lib.load()
         render, alpha, ed, md, nr = ctx.saved_tensors
         H, W = alpha.shape[1], alpha.shape[2]
         v_render = torch.empty_like(render)
         v_alpha, v_ed, v_md = torch.empty_like(alpha), torch.empty_like(alpha), torch.empty_like(alpha)
         v_nr = torch.empty_like(nr)
-        check(lib.misplat_outputs_bwd(C.c_int64(H * W), C.c_int32(ctx.cd), ctx.bg, ptr(render), ptr(alpha),
-                                      ptr(_c(v_rgb)), ptr(_c(v_depth)), ptr(_c(v_median)), ptr(_c(v_normals)),
-                                      ptr(_c(v_depth_im) if ctx.want_depth_im else None), ptr(v_render), ptr(v_alpha),
-                                      ptr(v_ed), ptr(v_md), ptr(v_nr), stream_ptr()), "misplat_outputs_bwd")
+        run("misplat_outputs_bwd", H * W, ctx.cd, ctx.bg, ptr(render), ptr(alpha), ptr(_c(v_rgb)), ptr(_c(v_depth)),
+            ptr(_c(v_median)), ptr(_c(v_normals)), ptr(_c(v_depth_im) if ctx.want_depth_im else None), ptr(v_render),
+            ptr(v_alpha), ptr(v_ed), ptr(v_md), ptr(v_nr))
         if v_err is not None:
-            check(lib.misplat_depth_normal_bwd(C.c_int32(W), C.c_int32(H), C.c_float(ctx.fx), C.c_float(ctx.fy),
-                                               ptr(ed), ptr(md), ptr(nr), ptr(None), ptr(_c(v_err)), ptr(v_ed),
-                                               ptr(v_md), ptr(v_nr), C.c_int32(1), stream_ptr()),
-                  "misplat_depth_normal_bwd")
+            run("misplat_depth_normal_bwd", W, H, ctx.fx, ctx.fy, ptr(ed), ptr(md), ptr(nr), ptr(None), ptr(_c(v_err)),
+                ptr(v_ed), ptr(v_md), ptr(v_nr), 1)
         return v_render, v_alpha, v_ed, v_md, v_nr, None, None, None, None
 
 
@@ -207,9 +189,9 @@ class _MeanLosses(torch.autograd.Function):
         dn_loss = torch.empty((), device=dev, dtype=torch.float32) if with_dn else None
         if l1_here or with_dn:
             partials = torch.empty(LOSS_PARTIALS, device=dev, dtype=torch.float32)
-            check(lib.misplat_loss_fwd(C.c_int64(n_pix), ptr(rgb if l1_here else None), ptr(gt if l1_here else None),
-                                       ptr(e1 if with_dn else None), ptr(e2 if with_dn else None), C.c_float(depth_ratio),
-                                       C.c_float(lam), ptr(partials), ptr(rgb_loss), ptr(dn_loss), stream_ptr()), "misplat_loss_fwd")
+            run("misplat_loss_fwd", n_pix, ptr(rgb if l1_here else None), ptr(gt if l1_here else None),
+                ptr(e1 if with_dn else None), ptr(e2 if with_dn else None), depth_ratio, lam, ptr(partials), ptr(rgb_loss),
+                ptr(dn_loss))
         # the base model's image loss (Splatfacto: (1 - l) L1 + l (1 - SSIM)): two launches that sum both terms tile by tile
         # and leave the derivative maps of the SSIM for the backward
         ctx.ssim = None
@@ -217,13 +199,12 @@ class _MeanLosses(torch.autograd.Function):
             H, W = int(rgb.shape[-3]), int(rgb.shape[-2])
             if rgb.shape[-1] != 3 or rgb.numel() != 3 * H * W:
                 raise ValueError("mean_losses: the SSIM term takes one [H,W,3] image")
-            n_scratch = int(lib.misplat_ssim_scratch_floats(C.c_int32(H), C.c_int32(W)))
+            n_scratch = int(lib.misplat_ssim_scratch_floats(H, W))
             if n_scratch < 0:
                 raise ValueError(f"mean_losses: the SSIM window needs an image of at least 11 x 11 pixels (got {H} x {W})")
             scratch = torch.empty(n_scratch, device=dev, dtype=torch.float32)
             main = torch.empty((), device=dev, dtype=torch.float32)
-            check(lib.misplat_ssim_fwd(C.c_int32(H), C.c_int32(W), ptr(rgb), ptr(gt), ptr(scratch), None,
-                                       C.c_float(ssim_lambda), None, ptr(main), stream_ptr()), "misplat_ssim_fwd")
+            run("misplat_ssim_fwd", H, W, ptr(rgb), ptr(gt), ptr(scratch), None, ssim_lambda, None, ptr(main))
             ctx.ssim = (H, W, scratch, float(ssim_lambda))
             rgb_loss = main
         ctx.save_for_backward(*(t for t in (rgb, gt) if with_rgb))
@@ -236,7 +217,6 @@ class _MeanLosses(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_rgb, g_dn):
-        lib = _lib.load()
         rgb, gt = ctx.saved_tensors if ctx.with_rgb else (None, None)
         want_rgb = ctx.with_rgb and ctx.needs_input_grad[0] and g_rgb is not None
         want_dn = ctx.with_dn and g_dn is not None and (ctx.needs_input_grad[2] if ctx.packed
@@ -255,12 +235,11 @@ class _MeanLosses(torch.autograd.Function):
         l1_here = want_rgb and ctx.ssim is None
         if want_rgb and ctx.ssim is not None:                         # both halves of the image term in one launch
             H, W, scratch, ssim_lambda = ctx.ssim
-            check(lib.misplat_ssim_bwd(C.c_int32(H), C.c_int32(W), ptr(rgb), ptr(gt), ptr(scratch), ptr(g1),
-                                       C.c_float(ssim_lambda), ptr(v_rgb), stream_ptr()), "misplat_ssim_bwd")
+            run("misplat_ssim_bwd", H, W, ptr(rgb), ptr(gt), ptr(scratch), ptr(g1), ssim_lambda, ptr(v_rgb))
         if l1_here or want_dn:
-            check(lib.misplat_loss_bwd(C.c_int64(ctx.n_pix), ptr(rgb if l1_here else None), ptr(gt if l1_here else None),
-                                       ptr(g1 if l1_here else None), ptr(g2), C.c_float(ctx.k[0]), C.c_float(ctx.k[1]),
-                                       ptr(v_rgb if l1_here else None), ptr(v_e1), ptr(v_e2), stream_ptr()), "misplat_loss_bwd")
+            run("misplat_loss_bwd", ctx.n_pix, ptr(rgb if l1_here else None), ptr(gt if l1_here else None),
+                ptr(g1 if l1_here else None), ptr(g2), ctx.k[0], ctx.k[1], ptr(v_rgb if l1_here else None), ptr(v_e1),
+                ptr(v_e2))
         if ctx.packed:
             return v_rgb, None, v_err, None, None, None, None, None
         return v_rgb, None, None, v_e1, v_e2, None, None, None

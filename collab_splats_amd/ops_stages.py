@@ -17,14 +17,13 @@ from torch import Tensor
 
 from . import _lib, arena
 from . import ops as _o
-from ._lib import MISPLAT_REC, Params, check, ptr, require_gpu, stream_ptr
+from ._lib import MISPLAT_REC, Params, ptr, require_gpu, run
 
 # ----------------------------------------------------------------------------- projection
 
 class _Project(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means, quats, scales, opacities, viewmats, Ks, P: Params):
-        lib = _lib.load()
         require_gpu(means, quats, scales, viewmats, Ks)
         N, Cn = P.n_gauss, P.n_cams
         dev = means.device
@@ -37,10 +36,8 @@ class _Project(torch.autograd.Function):
         ray_ts = torch.empty(Cn, N, **f)
         ray_planes = torch.empty(Cn, N, 2, **f)
         normals = torch.empty(Cn, N, 3, **f)
-        check(lib.misplat_project_fwd(C.byref(P), ptr(means), ptr(quats), ptr(scales), ptr(opacities),
-                                      ptr(viewmats), ptr(Ks), ptr(radii), ptr(means2d), ptr(depths),
-                                      ptr(conics), ptr(comps), ptr(ray_ts), ptr(ray_planes), ptr(normals),
-                                      stream_ptr()), "misplat_project_fwd")
+        run("misplat_project_fwd", C.byref(P), ptr(means), ptr(quats), ptr(scales), ptr(opacities), ptr(viewmats), ptr(Ks),
+            ptr(radii), ptr(means2d), ptr(depths), ptr(conics), ptr(comps), ptr(ray_ts), ptr(ray_planes), ptr(normals))
         ctx.P = P
         ctx.save_for_backward(means, quats, scales, viewmats, Ks, radii)
         ctx.mark_non_differentiable(radii)
@@ -55,18 +52,16 @@ class _Project(torch.autograd.Function):
         v_quats = torch.empty_like(quats)
         v_scales = torch.empty_like(scales)
         g = [_o._c(t) for t in (v_means2d, v_depths, v_conics, v_comps, v_ray_ts, v_ray_planes, v_normals)]
-        check(lib.misplat_project_bwd(C.byref(P), ptr(means), ptr(quats), ptr(scales), ptr(viewmats), ptr(Ks),
-                                      ptr(radii), *[ptr(t) for t in g], ptr(v_means), ptr(v_quats),
-                                      ptr(v_scales), stream_ptr()), "misplat_project_bwd")
+        run("misplat_project_bwd", C.byref(P), ptr(means), ptr(quats), ptr(scales), ptr(viewmats), ptr(Ks), ptr(radii),
+            *[ptr(t) for t in g], ptr(v_means), ptr(v_quats), ptr(v_scales))
         v_viewmats = None
         if ctx.needs_input_grad[4]:
             # camera pose gradient (csrc/project.hip: project_bwd_pose_kernel): the same gradient rows once more, summed per camera
-            nbytes = int(lib.misplat_project_bwd_pose_workspace(C.c_int32(P.n_gauss), C.c_int32(P.n_cams)))
+            nbytes = int(lib.misplat_project_bwd_pose_workspace(P.n_gauss, P.n_cams))
             work = torch.empty(nbytes, device=means.device, dtype=torch.uint8)
             v_viewmats = torch.empty_like(viewmats)
-            check(lib.misplat_project_bwd_pose(C.byref(P), ptr(means), ptr(quats), ptr(scales), ptr(viewmats), ptr(Ks),
-                                               ptr(radii), *[ptr(t) for t in g], ptr(work), ptr(v_viewmats),
-                                               stream_ptr()), "misplat_project_bwd_pose")
+            run("misplat_project_bwd_pose", C.byref(P), ptr(means), ptr(quats), ptr(scales), ptr(viewmats), ptr(Ks), ptr(radii),
+                *[ptr(t) for t in g], ptr(work), ptr(v_viewmats))
         return v_means, v_quats, v_scales, None, v_viewmats, None, None
 
 
@@ -84,27 +79,23 @@ def project(means: Tensor, quats: Tensor, scales: Tensor, opacities: Optional[Te
 class _SphericalHarmonics(torch.autograd.Function):
     @staticmethod
     def forward(ctx, dirs, coeffs, degree: int, radii):
-        lib = _lib.load()
         require_gpu(dirs, coeffs)
         N, K = coeffs.shape[0], coeffs.shape[1]
         Cn = dirs.numel() // (3 * N) if N > 0 else 1
         colors = torch.empty(dirs.shape[:-1] + (3,), device=dirs.device, dtype=torch.float32)
-        check(lib.misplat_sh_fwd(C.c_int32(N), C.c_int32(Cn), C.c_int32(K), C.c_int32(degree), ptr(dirs),
-                                 ptr(coeffs), ptr(radii), ptr(colors), stream_ptr()), "misplat_sh_fwd")
+        run("misplat_sh_fwd", N, Cn, K, degree, ptr(dirs), ptr(coeffs), ptr(radii), ptr(colors))
         ctx.save_for_backward(dirs, coeffs, radii)
         ctx.degree, ctx.Cn = degree, Cn
         return colors
 
     @staticmethod
     def backward(ctx, v_colors):
-        lib = _lib.load()
         dirs, coeffs, radii = ctx.saved_tensors
         N, K = coeffs.shape[0], coeffs.shape[1]
         v_coeffs = torch.empty_like(coeffs)
         v_dirs = torch.empty_like(dirs)
-        check(lib.misplat_sh_bwd(C.c_int32(N), C.c_int32(ctx.Cn), C.c_int32(K), C.c_int32(ctx.degree),
-                                 ptr(dirs), ptr(coeffs), ptr(radii), ptr(_o._c(v_colors)), ptr(v_coeffs),
-                                 ptr(v_dirs), stream_ptr()), "misplat_sh_bwd")
+        run("misplat_sh_bwd", N, ctx.Cn, K, ctx.degree, ptr(dirs), ptr(coeffs), ptr(radii), ptr(_o._c(v_colors)), ptr(v_coeffs),
+            ptr(v_dirs))
         return v_dirs, v_coeffs, None, None
 
 
@@ -142,7 +133,6 @@ def start_binning(P: Params, means2d: Tensor, radii: Tensor) -> Dict[str, Tensor
     counts, the cell ordering of the rows), and an ASYNCHRONOUS read-back of that number.  Called right
     after the projection kernel, before the colour kernel is launched, so that the host's wait for n_isects -- the one
     sync of the step -- and the launches that follow it are hidden behind the colour kernel instead of idling the GPU."""
-    lib = _lib.load()
     dev = means2d.device
     total = P.n_gauss * P.n_cams
     n_tiles = P.tile_w * P.tile_h * P.n_cams
@@ -150,13 +140,11 @@ def start_binning(P: Params, means2d: Tensor, radii: Tensor) -> Dict[str, Tensor
     tiles_per_gauss, rect2, cellhist, cell_count, cell_cursor, cell_offs, order, rect_sorted, counters, tile_count = _o._carve(
         dev, (total, 2 * total, n_blocks * n_cells, n_cells, n_cells, n_cells + 1, total, 2 * total, 4, n_tiles + 1))
     counters = counters.view(torch.int64)
-    check(lib.misplat_bucket_count(C.byref(P), ptr(means2d), ptr(radii), ptr(tiles_per_gauss), ptr(rect2),
-                                   ptr(cellhist), ptr(cell_count), ptr(counters), C.c_int32(0), stream_ptr()),
-          "misplat_bucket_count")
+    run("misplat_bucket_count", C.byref(P), ptr(means2d), ptr(radii), ptr(tiles_per_gauss), ptr(rect2), ptr(cellhist),
+        ptr(cell_count), ptr(counters), 0)
     pend = _read_back(counters[0:1])
-    check(lib.misplat_bucket_rows(C.byref(P), ptr(tiles_per_gauss), ptr(rect2), ptr(cellhist), ptr(cell_count),
-                                  ptr(cell_cursor), ptr(cell_offs), ptr(order), ptr(rect_sorted), ptr(counters),
-                                  ptr(tile_count), ptr(None), C.c_int32(0), stream_ptr()), "misplat_bucket_rows")
+    run("misplat_bucket_rows", C.byref(P), ptr(tiles_per_gauss), ptr(rect2), ptr(cellhist), ptr(cell_count), ptr(cell_cursor),
+        ptr(cell_offs), ptr(order), ptr(rect_sorted), ptr(counters), ptr(tile_count), ptr(None), 0)
     pend.update(tiles_per_gauss=tiles_per_gauss, rect2=rect_sorted, order=order, counters=counters, tile_count=tile_count)
     return pend
 
@@ -169,7 +157,6 @@ def bin_tiles(P: Params, means2d: Tensor, radii: Tensor, depths: Tensor,
     Result: ``flatten_ids[n_isects]`` (Gaussian rows in (tile, depth, id) order), ``isect_offsets[n_tiles + 1]`` (the
     last entry is n_isects), ``tiles_per_gauss``; in deterministic mode also ``slots`` (the emission slot of every
     sorted intersection: the row of the gradient slab)."""
-    lib = _lib.load()
     dev = means2d.device
     total = P.n_gauss * P.n_cams
     n_tiles = P.tile_w * P.tile_h * P.n_cams
@@ -190,13 +177,11 @@ def bin_tiles(P: Params, means2d: Tensor, radii: Tensor, depths: Tensor,
         out["cum"] = cum
     else:
         isect_gid = None
-    check(lib.misplat_bucket_tiles(C.byref(P), ptr(pend["order"]), ptr(pend["rect2"]), ptr(pend["counters"]),
-                                   ptr(pend["tile_count"]), ptr(offsets), ptr(cum), C.c_int64(n_isects), ptr(payload),
-                                   ptr(isect_gid), stream_ptr()), "misplat_bucket_tiles")
+    run("misplat_bucket_tiles", C.byref(P), ptr(pend["order"]), ptr(pend["rect2"]), ptr(pend["counters"]),
+        ptr(pend["tile_count"]), ptr(offsets), ptr(cum), n_isects, ptr(payload), ptr(isect_gid))
     if n_isects > 0:
-        check(lib.misplat_tile_sort(ptr(offsets), C.c_int32(n_tiles), C.c_int64(n_isects), ptr(depths), ptr(isect_gid),
-                                    ptr(payload), ptr(flatten_ids), ptr(scratch), C.c_int32(3), stream_ptr()),
-              "misplat_tile_sort")
+        run("misplat_tile_sort", ptr(offsets), n_tiles, n_isects, ptr(depths), ptr(isect_gid), ptr(payload), ptr(flatten_ids),
+            ptr(scratch), 3)
     out.update(slots=payload if deterministic else None, flatten_ids=flatten_ids, isect_offsets=offsets[:n_tiles + 1])
     return out
 
@@ -212,10 +197,8 @@ def complete_bins(bins: Dict[str, Tensor]) -> Tensor:
         n_tiles = bins["n_tiles"]
         if part["cap"] > 0:
             # (the bucket entries are positions in the cell-ordered row list: flags bit 2)
-            check(_lib.load().misplat_tile_sort(ptr(part["offsets"]), C.c_int32(n_tiles), C.c_int64(part["cap"]),
-                                                ptr(part["depth_sorted"]), ptr(part["row_map"]), ptr(part["payload"]),
-                                                ptr(part["flatten_ids"]), ptr(part["scratch"]), C.c_int32(7), stream_ptr()),
-                  "misplat_tile_sort")
+            run("misplat_tile_sort", ptr(part["offsets"]), n_tiles, part["cap"], ptr(part["depth_sorted"]),
+                ptr(part["row_map"]), ptr(part["payload"]), ptr(part["flatten_ids"]), ptr(part["scratch"]), 7)
         bins["partial"] = None
         _o.PATH_STATS["bins_completed"] += 1
     return bins["flatten_ids"]
@@ -224,15 +207,13 @@ def complete_bins(bins: Dict[str, Tensor]) -> Tensor:
 @torch.no_grad()
 def isect_ids(bins: Dict[str, Tensor]) -> Tensor:
     """gsplat's ``meta["isect_ids"]``: the sorted 64-bit keys (tile << 32 | depth bits), on demand."""
-    lib = _lib.load()
     complete_bins(bins)
     n = bins["n_isects"]
     out = torch.empty(n, device=bins["flatten_ids"].device, dtype=torch.int64)
     if bins["tile_ids"] is None:                       # no sorted tile-id array exists: rebuild it from the offsets
         cnt = torch.diff(bins["isect_offsets"].long())
         bins["tile_ids"] = torch.repeat_interleave(torch.arange(cnt.numel(), device=cnt.device, dtype=torch.int32), cnt)
-    check(lib.misplat_isect_ids(ptr(bins["tile_ids"]), ptr(bins["flatten_ids"]), ptr(bins["depths"]),
-                                C.c_int64(n), ptr(out), stream_ptr()), "misplat_isect_ids")
+    run("misplat_isect_ids", ptr(bins["tile_ids"]), ptr(bins["flatten_ids"]), ptr(bins["depths"]), n, ptr(out))
     return out
 
 
@@ -252,7 +233,6 @@ class _Blend(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means2d, conics, opac, colors, ray_ts, ray_planes, normals, Ks, P: Params,
                 bins: Dict[str, Tensor], absgrad: bool, pass_index: int = 0):
-        lib = _lib.load()
         ctx.pass_index = pass_index
         require_gpu(means2d)
         Cn, N, H, W = P.n_cams, P.n_gauss, P.height, P.width
@@ -260,9 +240,8 @@ class _Blend(torch.autograd.Function):
         dev = means2d.device
         rows = Cn * N
         grec = torch.empty(rows, MISPLAT_REC, device=dev, dtype=torch.float32)
-        check(lib.misplat_pack(C.c_int64(rows), C.c_int32(cd), ptr(means2d), ptr(conics), ptr(opac),
-                               ptr(ray_ts), ptr(ray_planes), ptr(normals), ptr(colors), ptr(grec),
-                               stream_ptr()), "misplat_pack")
+        run("misplat_pack", rows, cd, ptr(means2d), ptr(conics), ptr(opac), ptr(ray_ts), ptr(ray_planes), ptr(normals),
+            ptr(colors), ptr(grec))
         f = dict(device=dev, dtype=torch.float32)
         render = torch.empty(Cn, H, W, cd, **f)
         alpha = torch.empty(Cn, H, W, 1, **f)
@@ -274,10 +253,9 @@ class _Blend(torch.autograd.Function):
         sched = _o._UnitSchedule(P, dev)
         with _o._timed("blend_fwd"):
             sched.before_forward(P)
-            check(lib.misplat_blend_fwd(C.byref(P), C.c_int32(cd), ptr(Ks), ptr(grec), ptr(bins["flatten_ids"]),
-                                        ptr(bins["isect_offsets"]), C.c_int64(bins["n_isects"]), ptr(render),
-                                        ptr(alpha), ptr(exp_depth), ptr(med_depth), ptr(normal), ptr(last_ids),
-                                        ptr(median_ids), stream_ptr()), "misplat_blend_fwd")
+            run("misplat_blend_fwd", C.byref(P), cd, ptr(Ks), ptr(grec), ptr(bins["flatten_ids"]), ptr(bins["isect_offsets"]),
+                bins["n_isects"], ptr(render), ptr(alpha), ptr(exp_depth), ptr(med_depth), ptr(normal), ptr(last_ids),
+                ptr(median_ids))
         sched.after_forward(P)
         ctx.sched = sched
         ctx.P, ctx.bins, ctx.absgrad, ctx.cd = P, bins, absgrad, cd
@@ -356,7 +334,6 @@ class _ProjectPack(torch.autograd.Function):
                 depth_channel: bool, prebin: Optional[dict] = None):
         if ctx.needs_input_grad[6]:
             raise NotImplementedError(_o.POSE_GRAD_MESSAGE.format(node="_ProjectPack"))
-        lib = _lib.load()
         require_gpu(means, quats, scales, opacities, colors, viewmats, Ks)
         N, Cn = P.n_gauss, P.n_cams
         dev = means.device
@@ -389,10 +366,8 @@ class _ProjectPack(torch.autograd.Function):
         depths = torch.empty(Cn, N, device=dev, dtype=torch.float32)
         comps = torch.empty(Cn, N, device=dev, dtype=torch.float32)
         grec = torch.empty(Cn * N, MISPLAT_REC, device=dev, dtype=torch.float32)
-        check(lib.misplat_project_pack_fwd(C.byref(P), ptr(means), ptr(quats), ptr(scales), ptr(opacities),
-                                           ptr(viewmats), ptr(Ks), ptr(radii), ptr(means2d), ptr(depths),
-                                           ptr(comps), ptr(grec), ptr(None), C.c_int32(0), ptr(None), ptr(None), stream_ptr()),
-              "misplat_project_pack_fwd")
+        run("misplat_project_pack_fwd", C.byref(P), ptr(means), ptr(quats), ptr(scales), ptr(opacities), ptr(viewmats), ptr(Ks),
+            ptr(radii), ptr(means2d), ptr(depths), ptr(comps), ptr(grec), ptr(None), 0, ptr(None), ptr(None))
         if prebin is not None:                         # count tiles + start the n_isects read-back before the colours
             prebin["pending"] = start_binning(P, means2d, radii)
         # SH + a backward to come: keep d rgb / d dir (48 B per (camera, Gaussian)) so that the backward does not
@@ -400,10 +375,8 @@ class _ProjectPack(torch.autograd.Function):
         sh_aux = None
         if deg >= 0 and any(ctx.needs_input_grad[:6]):
             sh_aux = torch.empty(Cn * N, 12, device=dev, dtype=torch.float32)
-        check(lib.misplat_color_fwd(C.byref(P), C.c_int32(deg), C.c_int32(kd), C.c_int32(n_color),
-                                    C.c_int32(per_cam), C.c_int32(int(depth_channel)), ptr(means), ptr(viewmats),
-                                    ptr(colors), ptr(colors_rest), ptr(radii), ptr(depths), ptr(grec), ptr(sh_aux),
-                                    ptr(None), stream_ptr()), "misplat_color_fwd")
+        run("misplat_color_fwd", C.byref(P), deg, kd, n_color, per_cam, int(depth_channel), ptr(means), ptr(viewmats),
+            ptr(colors), ptr(colors_rest), ptr(radii), ptr(depths), ptr(grec), ptr(sh_aux), ptr(None))
         ctx.P, ctx.color_args = P, (deg, kd, n_color, per_cam)
         ctx.depth_slot = 12 + n_color if depth_channel else -1
         ctx.has_rest = colors_rest is not None
@@ -417,7 +390,6 @@ class _ProjectPack(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, _v_radii, v_means2d, _v_depths, _v_comps, v_grec):
-        lib = _lib.load()
         means, quats, scales, opacities, colors, viewmats, Ks, radii, comps, colors_rest, sh_aux = ctx.saved_tensors
         if not ctx.has_rest:
             colors_rest = None
@@ -429,19 +401,15 @@ class _ProjectPack(torch.autograd.Function):
         v_colors = _o._grad_out(colors)
         v_colors_rest = _o._grad_out(colors_rest) if colors_rest is not None else None
         v_means_dir = torch.empty_like(means) if deg >= 0 else None
-        check(lib.misplat_color_bwd(C.byref(P), C.c_int32(deg), C.c_int32(kd), C.c_int32(n_color),
-                                    C.c_int32(per_cam), ptr(means), ptr(viewmats), ptr(colors), ptr(colors_rest),
-                                    ptr(radii), ptr(v_grec), ptr(v_colors), ptr(v_colors_rest), ptr(v_means_dir),
-                                    ptr(sh_aux), stream_ptr()), "misplat_color_bwd")
+        run("misplat_color_bwd", C.byref(P), deg, kd, n_color, per_cam, ptr(means), ptr(viewmats), ptr(colors),
+            ptr(colors_rest), ptr(radii), ptr(v_grec), ptr(v_colors), ptr(v_colors_rest), ptr(v_means_dir), ptr(sh_aux))
         if _o.GRAD_SINK is not None:
             _o.GRAD_SINK.colour_ready()                   # the colour bucket's all-reduce starts now, overlapped with the rest
         v_means, v_quats = _o._grad_out(means), _o._grad_out(quats)
         v_scales, v_opac = _o._grad_out(scales), _o._grad_out(opacities)
-        check(lib.misplat_project_pack_bwd(C.byref(P), C.c_int32(ctx.depth_slot), ptr(means), ptr(quats),
-                                           ptr(scales), ptr(opacities), ptr(viewmats), ptr(Ks), ptr(radii),
-                                           ptr(comps), ptr(v_means2d), ptr(v_grec), ptr(v_means_dir), ptr(v_means),
-                                           ptr(v_quats), ptr(v_scales), ptr(v_opac), None, C.c_int32(0), stream_ptr()),
-              "misplat_project_pack_bwd")
+        run("misplat_project_pack_bwd", C.byref(P), ctx.depth_slot, ptr(means), ptr(quats), ptr(scales), ptr(opacities),
+            ptr(viewmats), ptr(Ks), ptr(radii), ptr(comps), ptr(v_means2d), ptr(v_grec), ptr(v_means_dir), ptr(v_means),
+            ptr(v_quats), ptr(v_scales), ptr(v_opac), None, 0)
         return v_means, v_quats, v_scales, v_opac, v_colors, v_colors_rest, None, None, None, None, None, None
 
 
@@ -464,7 +432,6 @@ class _BlendPacked(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means2d, grec, Ks, P: Params, bins: Dict[str, Tensor], absgrad: bool, cd: int):
-        lib = _lib.load()
         Cn, H, W = P.n_cams, P.height, P.width
         dev = grec.device
         if "args" in bins:                             # phase-A state of the one-entry path: buckets, sort, compositing
@@ -490,10 +457,9 @@ class _BlendPacked(torch.autograd.Function):
         sched = _o._UnitSchedule(P, dev)
         with _o._timed("blend_fwd"):
             sched.before_forward(P)
-            check(lib.misplat_blend_fwd(C.byref(P), C.c_int32(cd), ptr(Ks), ptr(grec), ptr(bins["flatten_ids"]),
-                                        ptr(bins["isect_offsets"]), C.c_int64(bins["n_isects"]), ptr(render),
-                                        ptr(alpha), ptr(exp_depth), ptr(med_depth), ptr(normal), ptr(last_ids),
-                                        ptr(median_ids), stream_ptr()), "misplat_blend_fwd")
+            run("misplat_blend_fwd", C.byref(P), cd, ptr(Ks), ptr(grec), ptr(bins["flatten_ids"]), ptr(bins["isect_offsets"]),
+                bins["n_isects"], ptr(render), ptr(alpha), ptr(exp_depth), ptr(med_depth), ptr(normal), ptr(last_ids),
+                ptr(median_ids))
         sched.after_forward(P)
         ctx.sched = sched
         ctx.P, ctx.bins, ctx.absgrad, ctx.cd = P, bins, absgrad, cd
@@ -531,11 +497,9 @@ def _blend_backward(ctx, v_render, v_alpha, v_exp_depth, v_med_depth, v_normal):
             v_grec = torch.empty(rows, MISPLAT_REC, device=dev, dtype=torch.float32)
         v_abs = torch.empty(rows, 2, device=dev, dtype=torch.float32) if ctx.absgrad else None
         with _o._timed("blend_bwd"):
-            check(lib.misplat_blend_bwd_atomic(C.byref(P), C.c_int32(cd), ptr(Ks), ptr(grec), ptr(bins["flatten_ids"]),
-                                               ptr(bins["isect_offsets"]), C.c_int64(n_isects), ptr(alpha),
-                                               ptr(last_ids), ptr(median_ids), ptr(render), *[ptr(t) for t in ups],
-                                               ptr(v_grec), ptr(v_abs), C.c_int32(int(prezeroed)), stream_ptr()),
-                  "misplat_blend_bwd_atomic")
+            run("misplat_blend_bwd_atomic", C.byref(P), cd, ptr(Ks), ptr(grec), ptr(bins["flatten_ids"]),
+                ptr(bins["isect_offsets"]), n_isects, ptr(alpha), ptr(last_ids), ptr(median_ids), ptr(render),
+                *[ptr(t) for t in ups], ptr(v_grec), ptr(v_abs), int(prezeroed))
         return v_grec, v_abs
     planes = int(lib.misplat_blend_planes(C.byref(P)))
     rows_s = max(n_isects, 1) * planes
@@ -543,16 +507,14 @@ def _blend_backward(ctx, v_render, v_alpha, v_exp_depth, v_med_depth, v_normal):
     slab_abs = torch.empty(rows_s, 2, device=dev, dtype=torch.float32) if ctx.absgrad else None
     slab_valid = torch.empty(rows_s, device=dev, dtype=torch.uint8)
     with _o._timed("blend_bwd"):
-        check(lib.misplat_blend_bwd(C.byref(P), C.c_int32(cd), ptr(Ks), ptr(grec), ptr(bins["flatten_ids"]),
-                                    ptr(bins["slots"]), ptr(bins["isect_offsets"]), C.c_int64(n_isects),
-                                    ptr(alpha), ptr(last_ids), ptr(median_ids), ptr(render), *[ptr(t) for t in ups],
-                                    ptr(slab), ptr(slab_abs), ptr(slab_valid), stream_ptr()), "misplat_blend_bwd")
+        run("misplat_blend_bwd", C.byref(P), cd, ptr(Ks), ptr(grec), ptr(bins["flatten_ids"]), ptr(bins["slots"]),
+            ptr(bins["isect_offsets"]), n_isects, ptr(alpha), ptr(last_ids), ptr(median_ids), ptr(render),
+            *[ptr(t) for t in ups], ptr(slab), ptr(slab_abs), ptr(slab_valid))
     v_grec = torch.empty(rows, MISPLAT_REC, device=dev, dtype=torch.float32)
     v_abs = torch.empty(rows, 2, device=dev, dtype=torch.float32) if ctx.absgrad else None
     with _o._timed("slab_reduce"):
-        check(lib.misplat_slab_reduce(C.byref(P), C.c_int64(rows), C.c_int64(n_isects), ptr(_cum_by_row(bins)),
-                                      ptr(bins["tiles_per_gauss"]), ptr(slab), ptr(slab_abs), ptr(slab_valid),
-                                      ptr(v_grec), ptr(v_abs), stream_ptr()), "misplat_slab_reduce")
+        run("misplat_slab_reduce", C.byref(P), rows, n_isects, ptr(_cum_by_row(bins)), ptr(bins["tiles_per_gauss"]), ptr(slab),
+            ptr(slab_abs), ptr(slab_valid), ptr(v_grec), ptr(v_abs))
     return v_grec, v_abs
 
 
@@ -572,7 +534,6 @@ class _ProjectPackX(torch.autograd.Function):
     def forward(ctx, means, quats, scales, opacities, colors, viewmats, Ks, P: Params, depth_channel: bool, nxq: int):
         if ctx.needs_input_grad[5]:
             raise NotImplementedError(_o.POSE_GRAD_MESSAGE.format(node="_ProjectPackX"))
-        lib = _lib.load()
         require_gpu(means, quats, scales, opacities, colors, viewmats, Ks)
         N, Cn = P.n_gauss, P.n_cams
         dev = means.device
@@ -582,14 +543,11 @@ class _ProjectPackX(torch.autograd.Function):
         comps = torch.empty(Cn, N, device=dev, dtype=torch.float32)
         grec = torch.empty(Cn * N, MISPLAT_REC, device=dev, dtype=torch.float32)
         featx = torch.empty(Cn * N, 4 * nxq, device=dev, dtype=torch.float32)
-        check(lib.misplat_project_pack_fwd(C.byref(P), ptr(means), ptr(quats), ptr(scales), ptr(opacities),
-                                           ptr(viewmats), ptr(Ks), ptr(radii), ptr(means2d), ptr(depths),
-                                           ptr(comps), ptr(grec), ptr(None), C.c_int32(0), ptr(None), ptr(None), stream_ptr()),
-              "misplat_project_pack_fwd")
+        run("misplat_project_pack_fwd", C.byref(P), ptr(means), ptr(quats), ptr(scales), ptr(opacities), ptr(viewmats), ptr(Ks),
+            ptr(radii), ptr(means2d), ptr(depths), ptr(comps), ptr(grec), ptr(None), 0, ptr(None), ptr(None))
         D, per_cam = colors.shape[-1], int(colors.dim() == 3)
-        check(lib.misplat_color_fwd_x(C.byref(P), C.c_int32(D), C.c_int32(per_cam), C.c_int32(int(depth_channel)),
-                                      C.c_int32(nxq), ptr(colors), ptr(radii), ptr(depths), ptr(grec), ptr(featx),
-                                      stream_ptr()), "misplat_color_fwd_x")
+        run("misplat_color_fwd_x", C.byref(P), D, per_cam, int(depth_channel), nxq, ptr(colors), ptr(radii), ptr(depths),
+            ptr(grec), ptr(featx))
         ctx.P, ctx.D, ctx.per_cam, ctx.nxq, ctx.depth_channel = P, D, per_cam, nxq, depth_channel
         ctx.save_for_backward(means, quats, scales, opacities, colors, viewmats, Ks, radii, comps)
         ctx.mark_non_differentiable(radii, depths, comps)
@@ -598,14 +556,12 @@ class _ProjectPackX(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, _v_radii, v_means2d, _v_depths, _v_comps, v_grec, v_featx):
-        lib = _lib.load()
         means, quats, scales, opacities, colors, viewmats, Ks, radii, comps = ctx.saved_tensors
         P, D, nxq = ctx.P, ctx.D, ctx.nxq
         v_means2d, v_grec = _grads_of_pack(P, v_means2d, v_grec)
         v_featx = _o._c(v_featx) if v_featx is not None else torch.zeros(v_grec.shape[0], 4 * nxq, device=v_grec.device)
         v_colors = torch.empty_like(colors)
-        check(lib.misplat_color_bwd_x(C.byref(P), C.c_int32(D), C.c_int32(ctx.per_cam), C.c_int32(nxq), ptr(radii),
-                                      ptr(v_grec), ptr(v_featx), ptr(v_colors), stream_ptr()), "misplat_color_bwd_x")
+        run("misplat_color_bwd_x", C.byref(P), D, ctx.per_cam, nxq, ptr(radii), ptr(v_grec), ptr(v_featx), ptr(v_colors))
         depth_slot, v_depth_rows, v_depth_stride = -1, None, 0
         if ctx.depth_channel:                       # channel D carries the depth
             if D < 4:
@@ -616,11 +572,9 @@ class _ProjectPackX(torch.autograd.Function):
                 v_depth_stride = 4 * nxq
         v_means, v_quats = torch.empty_like(means), torch.empty_like(quats)
         v_scales, v_opac = torch.empty_like(scales), torch.empty_like(opacities)
-        check(lib.misplat_project_pack_bwd(C.byref(P), C.c_int32(depth_slot), ptr(means), ptr(quats), ptr(scales),
-                                           ptr(opacities), ptr(viewmats), ptr(Ks), ptr(radii), ptr(comps),
-                                           ptr(v_means2d), ptr(v_grec), ptr(None), ptr(v_means), ptr(v_quats),
-                                           ptr(v_scales), ptr(v_opac), v_depth_rows, C.c_int32(v_depth_stride), stream_ptr()),
-              "misplat_project_pack_bwd")
+        run("misplat_project_pack_bwd", C.byref(P), depth_slot, ptr(means), ptr(quats), ptr(scales), ptr(opacities),
+            ptr(viewmats), ptr(Ks), ptr(radii), ptr(comps), ptr(v_means2d), ptr(v_grec), ptr(None), ptr(v_means), ptr(v_quats),
+            ptr(v_scales), ptr(v_opac), v_depth_rows, v_depth_stride)
         return v_means, v_quats, v_scales, v_opac, v_colors, None, None, None, None, None
 
 
@@ -636,7 +590,6 @@ class _BlendPackedX(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means2d, grec, featx, Ks, P: Params, bins: Dict[str, Tensor], absgrad: bool, n_channels: int,
                 nxq: int):
-        lib = _lib.load()
         Cn, H, W = P.n_cams, P.height, P.width
         dev = grec.device
         f = dict(device=dev, dtype=torch.float32)
@@ -651,11 +604,9 @@ class _BlendPackedX(torch.autograd.Function):
         ctx.sched = sched
         with _o._timed("blend_fwd"):
             sched.before_forward(P)
-            check(lib.misplat_blend_fwd_x(C.byref(P), C.c_int32(n_channels), C.c_int32(nxq), ptr(Ks), ptr(grec),
-                                          ptr(featx), ptr(bins["flatten_ids"]), ptr(bins["isect_offsets"]),
-                                          C.c_int64(bins["n_isects"]), ptr(render), ptr(alpha), ptr(exp_depth),
-                                          ptr(med_depth), ptr(normal), ptr(last_ids), ptr(median_ids), stream_ptr()),
-                  "misplat_blend_fwd_x")
+            run("misplat_blend_fwd_x", C.byref(P), n_channels, nxq, ptr(Ks), ptr(grec), ptr(featx), ptr(bins["flatten_ids"]),
+                ptr(bins["isect_offsets"]), bins["n_isects"], ptr(render), ptr(alpha), ptr(exp_depth), ptr(med_depth),
+                ptr(normal), ptr(last_ids), ptr(median_ids))
         sched.after_forward(P)
         ctx.P, ctx.bins, ctx.absgrad, ctx.n_channels, ctx.nxq = P, bins, absgrad, n_channels, nxq
         ctx.means2d_ref = means2d if absgrad else None
@@ -666,7 +617,6 @@ class _BlendPackedX(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, v_render, v_alpha, v_exp_depth, v_med_depth, v_normal, _l, _m):
-        lib = _lib.load()
         grec, featx, Ks, alpha, last_ids, median_ids, render = ctx.saved_tensors
         P, bins = ctx.P, ctx.bins
         rows = P.n_cams * P.n_gauss
@@ -677,12 +627,9 @@ class _BlendPackedX(torch.autograd.Function):
         ups = _o._upstream(P, ctx.n_channels, dev, v_render, v_alpha, v_exp_depth, v_med_depth, v_normal)
         ctx.sched.before_backward(P)
         with _o._timed("blend_bwd"):
-            check(lib.misplat_blend_bwd_x_atomic(C.byref(P), C.c_int32(ctx.n_channels), C.c_int32(ctx.nxq), ptr(Ks),
-                                                 ptr(grec), ptr(featx), ptr(bins["flatten_ids"]),
-                                                 ptr(bins["isect_offsets"]), C.c_int64(bins["n_isects"]), ptr(alpha),
-                                                 ptr(last_ids), ptr(median_ids), ptr(render), *[ptr(t) for t in ups],
-                                                 ptr(v_grec), ptr(v_featx), ptr(v_abs), stream_ptr()),
-                  "misplat_blend_bwd_x_atomic")
+            run("misplat_blend_bwd_x_atomic", C.byref(P), ctx.n_channels, ctx.nxq, ptr(Ks), ptr(grec), ptr(featx),
+                ptr(bins["flatten_ids"]), ptr(bins["isect_offsets"]), bins["n_isects"], ptr(alpha), ptr(last_ids),
+                ptr(median_ids), ptr(render), *[ptr(t) for t in ups], ptr(v_grec), ptr(v_featx), ptr(v_abs))
         _o._UnitSchedule.done(P)
         if ctx.absgrad:
             ctx.means2d_ref.absgrad = v_abs.view(P.n_cams, P.n_gauss, 2)

@@ -18,7 +18,7 @@ from typing import Dict, Iterable, List, Tuple
 import torch
 
 from . import _lib
-from ._lib import check, stream_ptr
+from ._lib import run
 
 MAX_TENSORS = 8                                  # MISPLAT_ADAM_MAX_TENSORS
 
@@ -76,7 +76,6 @@ def step_all(optimizers: Iterable[FusedAdam] | Dict[str, FusedAdam]) -> None:
 def _launch(entries: List[tuple]) -> None:
     if not entries:
         return
-    lib = _lib.load()
     by_hyper: Dict[tuple, List[tuple]] = {}
     for e in entries:
         by_hyper.setdefault(e[3:], []).append(e)
@@ -97,9 +96,8 @@ def _launch(entries: List[tuple]) -> None:
                 ms.append(st["exp_avg"].data_ptr()); vs.append(st["exp_avg_sq"].data_ptr())
                 numel.append(p.numel()); lrs.append(lr); steps.append(int(st["step"].item()) + 1)
             vp = C.c_void_p * n
-            check(lib.misplat_adam_step(C.c_int32(n), vp(*ps), vp(*gs), vp(*ms), vp(*vs), (C.c_int64 * n)(*numel),
-                                        (C.c_float * n)(*lrs), (C.c_int64 * n)(*steps), C.c_double(b1), C.c_double(b2),
-                                        C.c_double(eps), stream_ptr()), "misplat_adam_step")
+            run("misplat_adam_step", n, vp(*ps), vp(*gs), vp(*ms), vp(*vs), (C.c_int64 * n)(*numel), (C.c_float * n)(*lrs),
+                (C.c_int64 * n)(*steps), b1, b2, eps)
             for _, st, _, _, _, _ in chunk:              # a refused launch has stepped nothing: the counts stay too
                 st["step"] += 1
             del keep
@@ -152,8 +150,7 @@ def visibility_from_radii(radii: torch.Tensor) -> torch.Tensor:
     n = radii.shape[1]
     flags = torch.empty(n, device=radii.device, dtype=torch.uint8)
     with torch.cuda.device(radii.device):
-        check(_lib.load().misplat_visible_rows(_lib.ptr(radii), C.c_int32(radii.shape[0]), C.c_int64(n), _lib.ptr(flags),
-                                               stream_ptr()), "misplat_visible_rows")
+        run("misplat_visible_rows", _lib.ptr(radii), radii.shape[0], n, _lib.ptr(flags))
     return flags
 
 
@@ -163,7 +160,6 @@ _row_ws: Dict[torch.device, dict] = {}                   # the row list's work a
 def _row_list(visibility: torch.Tensor):
     """(ids, count): the ascending ids of the flagged rows in an int32 list of capacity N and their number, which stays on the
     device.  Four small launches over work arrays that live from step to step (as ``parallel.GradientBuckets._ws``)."""
-    lib = _lib.load()
     n, dev = visibility.numel(), visibility.device
     nbytes = (n + 7) // 8
     n_blocks = (nbytes + 255) // 256
@@ -178,14 +174,10 @@ def _row_list(visibility: torch.Tensor):
     flags = visibility
     if not flags.is_contiguous() or flags.data_ptr() % 8:   # (misplat_touched_bits reads 8 flags at a time)
         flags = ws["flags"].copy_(visibility)
-    s = stream_ptr()
-    check(lib.misplat_touched_bits(C.c_void_p(flags.data_ptr()), C.c_int64(n), _lib.ptr(ws["bits"]), s), "misplat_touched_bits")
-    check(lib.misplat_union_count(_lib.ptr(ws["bits"]), C.c_int32(1), C.c_int64(nbytes), _lib.ptr(ws["counts"]), s),
-          "misplat_union_count")
-    check(lib.misplat_union_scan(_lib.ptr(ws["counts"]), C.c_int64(n_blocks), _lib.ptr(ws["offs"]), _lib.ptr(ws["total"]), s),
-          "misplat_union_scan")
-    check(lib.misplat_union_ids(_lib.ptr(ws["bits"]), C.c_int32(1), C.c_int64(nbytes), _lib.ptr(ws["offs"]), _lib.ptr(ws["ids"]),
-                                C.c_int64(n), s), "misplat_union_ids")
+    run("misplat_touched_bits", C.c_void_p(flags.data_ptr()), n, _lib.ptr(ws["bits"]))
+    run("misplat_union_count", _lib.ptr(ws["bits"]), 1, nbytes, _lib.ptr(ws["counts"]))
+    run("misplat_union_scan", _lib.ptr(ws["counts"]), n_blocks, _lib.ptr(ws["offs"]), _lib.ptr(ws["total"]))
+    run("misplat_union_ids", _lib.ptr(ws["bits"]), 1, nbytes, _lib.ptr(ws["offs"]), _lib.ptr(ws["ids"]), n)
     return ws["ids"], ws["total"]
 
 
@@ -217,7 +209,6 @@ def _launch_rows(entries: List[tuple], visibility) -> None:
             by_hyper.setdefault(e[3:], []).append(e + (g,))
         else:                                            # (a tensor of no elements has nothing to step but its count)
             e[1]["step"] += 1
-    lib = _lib.load()
     with torch.cuda.device(visibility.device):
         if by_hyper:
             ids, count = _row_list(visibility)
@@ -226,11 +217,10 @@ def _launch_rows(entries: List[tuple], visibility) -> None:
                 chunk = es[i:i + MAX_TENSORS]
                 k = len(chunk)
                 vp = C.c_void_p * k
-                check(lib.misplat_adam_step_rows(
-                    C.c_int32(k), vp(*[e[0].data_ptr() for e in chunk]), vp(*[e[6].data_ptr() for e in chunk]),
+                run("misplat_adam_step_rows", k, vp(*[e[0].data_ptr() for e in chunk]), vp(*[e[6].data_ptr() for e in chunk]),
                     vp(*[e[1]["exp_avg"].data_ptr() for e in chunk]), vp(*[e[1]["exp_avg_sq"].data_ptr() for e in chunk]),
-                    (C.c_int32 * k)(*[e[0].numel() // n for e in chunk]), C.c_int64(n), (C.c_float * k)(*[e[2] for e in chunk]),
-                    (C.c_int64 * k)(*[int(e[1]["step"].item()) + 1 for e in chunk]), C.c_double(b1), C.c_double(b2),
-                    C.c_double(eps), _lib.ptr(ids), C.c_int64(n), _lib.ptr(count), stream_ptr()), "misplat_adam_step_rows")
+                    (C.c_int32 * k)(*[e[0].numel() // n for e in chunk]), n, (C.c_float * k)(*[e[2] for e in chunk]),
+                    (C.c_int64 * k)(*[int(e[1]["step"].item()) + 1 for e in chunk]), b1, b2, eps, _lib.ptr(ids), n,
+                    _lib.ptr(count))
                 for e in chunk:                          # (whatever the mask holds: the count is the step's, not the row's)
                     e[1]["step"] += 1

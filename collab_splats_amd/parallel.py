@@ -327,7 +327,6 @@ class GradientBuckets:
         if t.is_cuda and _backend() != "gloo":
             import ctypes as C
             from . import _lib
-            lib = _lib.load()
             n_blocks = (nbytes + 255) // 256
             # (the small work arrays of this path live with the sink: no allocator call and no library scan per step -- the
             # first torch op behind the backward's launch used to block the autograd thread for 0.9 ms a step at 5 M)
@@ -339,12 +338,10 @@ class GradientBuckets:
                                      offs=torch.empty(n_blocks, device=t.device, dtype=torch.int64),
                                      total=torch.empty(1, device=t.device, dtype=torch.int64), ids=None)
             bits, gathered, counts, offs, total_dev = ws["bits"], ws["gathered"], ws["counts"], ws["offs"], ws["total"]
-            _lib.check(lib.misplat_touched_bits(_lib.ptr(t), C.c_int64(n), _lib.ptr(bits), _lib.stream_ptr()), "misplat_touched_bits")
+            _lib.run("misplat_touched_bits", _lib.ptr(t), n, _lib.ptr(bits))
             _gather_bits(gathered, bits)
-            _lib.check(lib.misplat_union_count(_lib.ptr(gathered), C.c_int32(world), C.c_int64(nbytes), _lib.ptr(counts),
-                                               _lib.stream_ptr()), "misplat_union_count")
-            _lib.check(lib.misplat_union_scan(_lib.ptr(counts), C.c_int64(n_blocks), _lib.ptr(offs), _lib.ptr(total_dev),
-                                              _lib.stream_ptr()), "misplat_union_scan")
+            _lib.run("misplat_union_count", _lib.ptr(gathered), world, nbytes, _lib.ptr(counts))
+            _lib.run("misplat_union_scan", _lib.ptr(counts), n_blocks, _lib.ptr(offs), _lib.ptr(total_dev))
             cap = self._row_cap
             if cap is None:                                                # first sparse step of this sink: one host read
                 total = int(total_dev.item())
@@ -353,8 +350,7 @@ class GradientBuckets:
                 if SPARSE != "1" and total > SPARSE_MAX_FRACTION * n:
                     return None
                 ids = torch.empty(max(total, 1), device=t.device, dtype=torch.int32)
-                _lib.check(lib.misplat_union_ids(_lib.ptr(gathered), C.c_int32(world), C.c_int64(nbytes), _lib.ptr(offs), _lib.ptr(ids),
-                                                 C.c_int64(ids.numel()), _lib.stream_ptr()), "misplat_union_ids")
+                _lib.run("misplat_union_ids", _lib.ptr(gathered), world, nbytes, _lib.ptr(offs), _lib.ptr(ids), ids.numel())
                 ids = ids[:total]
             else:
                 # the size goes to a pinned slot behind everything else of the step; allreduce() reads it at the end
@@ -370,8 +366,7 @@ class GradientBuckets:
                 if ws["ids"] is None or ws["ids"].numel() != cap:
                     ws["ids"] = torch.empty(cap, device=t.device, dtype=torch.int32)
                 ids = ws["ids"]
-                _lib.check(lib.misplat_union_ids(_lib.ptr(gathered), C.c_int32(world), C.c_int64(nbytes), _lib.ptr(offs), _lib.ptr(ids),
-                                                 C.c_int64(cap), _lib.stream_ptr()), "misplat_union_ids")
+                _lib.run("misplat_union_ids", _lib.ptr(gathered), world, nbytes, _lib.ptr(offs), _lib.ptr(ids), cap)
                 self._union = ids
                 self._union_counted = True
                 return ids
@@ -437,13 +432,10 @@ class GradientBuckets:
         if packed.is_cuda:
             import ctypes as C
             from . import _lib
-            lib = _lib.load()
             ptrs = (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
             wid = (C.c_int32 * len(widths))(*widths)
-            fn = lib.misplat_rows_pack if pack else lib.misplat_rows_unpack
-            _lib.check(fn(C.c_int32(len(tensors)), ptrs, wid, _lib.ptr(ids), C.c_int64(ids.numel()),
-                          _lib.ptr(self._count_dev) if counted else None, _lib.ptr(packed),
-                          _lib.stream_ptr()), "misplat_rows_pack" if pack else "misplat_rows_unpack")
+            _lib.run("misplat_rows_pack" if pack else "misplat_rows_unpack", len(tensors), ptrs, wid, _lib.ptr(ids), ids.numel(),
+                     _lib.ptr(self._count_dev) if counted else None, _lib.ptr(packed))
             return
         rows = ids.long()
         view = packed[:ids.numel() * sum(widths)].view(ids.numel(), sum(widths))

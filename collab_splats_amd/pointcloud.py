@@ -9,14 +9,13 @@ torch on the device.  There is no CPU fallback.
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import Optional, Sequence, Tuple
 
 import torch
 from torch import Tensor
 
-from ._lib import MisplatError, check, load, ptr, require_gpu, stream_ptr
+from ._lib import MisplatError, load, ptr, require_gpu, run
 from .meshmap import COORD_CELLS, _prep
 
 MAX_K = 32
@@ -65,7 +64,7 @@ def _finite(name: str, *clouds: Tensor) -> None:
 
 
 def _workspace(n: int, kind: int, device) -> Tensor:
-    b = int(load().misplat_pointcloud_workspace(C.c_int64(n), kind))
+    b = int(load().misplat_pointcloud_workspace(n, kind))
     if b < 0:
         raise ValueError(f"pointcloud: {n} points are beyond the library's limits")
     return torch.empty(b, dtype=torch.uint8, device=device)
@@ -73,8 +72,7 @@ def _workspace(n: int, kind: int, device) -> Tensor:
 
 def _occupied_cells(p: Tensor, edge: float, ws: Tensor) -> int:
     out = torch.empty(1, dtype=torch.int32, device=p.device)
-    check(load().misplat_pointcloud_cells(ptr(p), C.c_int64(p.shape[0]), C.c_float(edge), ptr(ws), C.c_int64(ws.numel()), ptr(out),
-                                          stream_ptr()), "misplat_pointcloud_cells")
+    run("misplat_pointcloud_cells", ptr(p), p.shape[0], edge, ptr(ws), ws.numel(), ptr(out))
     return int(out.item())
 
 
@@ -139,9 +137,8 @@ def knn_mean_distance(points: Tensor, k: int, queries: Optional[Tensor] = None) 
         edge = max(forced, floor)
     else:
         edge = _auto_edge(p, min(k, n), floor, head[2:], ws)
-    check(load().misplat_pointcloud_knn(ptr(p), C.c_int64(n), ptr(q), C.c_int64(nq), min(k, n), C.c_float(edge), LANES_PER_QUERY,
-                                        ptr(ws), C.c_int64(ws.numel()), ptr(mean), ptr(nearest), stream_ptr()),
-          "misplat_pointcloud_knn")
+    run("misplat_pointcloud_knn", ptr(p), n, ptr(q), nq, min(k, n), edge, LANES_PER_QUERY, ptr(ws), ws.numel(), ptr(mean),
+        ptr(nearest))
     return mean, nearest
 
 
@@ -169,8 +166,7 @@ def statistical_outlier_mask(points: Tensor, nb_neighbors: int = 20, std_ratio: 
     mean, _ = knn_mean_distance(points, nb_neighbors)
     keep = torch.empty(n, dtype=torch.uint8, device=mean.device)
     ws = _workspace(n, _OUTLIER, mean.device)
-    check(load().misplat_pointcloud_outlier_mask(ptr(mean), C.c_int64(n), C.c_double(ratio), ptr(ws), C.c_int64(ws.numel()),
-                                                 ptr(keep), stream_ptr()), "misplat_pointcloud_outlier_mask")
+    run("misplat_pointcloud_outlier_mask", ptr(mean), n, ratio, ptr(ws), ws.numel(), ptr(keep))
     return keep.bool(), mean
 
 
@@ -206,8 +202,7 @@ def radius_count(points: Tensor, radius: float, queries: Optional[Tensor] = None
     if n == 0 or nq == 0:
         return counts
     ws = _workspace(n, _RADIUS, p.device)
-    check(load().misplat_pointcloud_radius_count(ptr(p), C.c_int64(n), ptr(q), C.c_int64(nq), C.c_float(r), ptr(ws),
-                                                 C.c_int64(ws.numel()), ptr(counts), stream_ptr()), "misplat_pointcloud_radius_count")
+    run("misplat_pointcloud_radius_count", ptr(p), n, ptr(q), nq, r, ptr(ws), ws.numel(), ptr(counts))
     return counts
 
 
@@ -286,15 +281,13 @@ def voxel_down_sample(points: Tensor, voxel_size: float, attributes: Sequence[Te
     offsets = torch.empty(n + 1, dtype=torch.int32, device=dev)
     count = torch.empty(1, dtype=torch.int32, device=dev)
     ws = _workspace(n, _VOXEL, dev)
-    check(load().misplat_pointcloud_voxel_group(ptr(p), C.c_int64(n), C.c_double(origin[0]), C.c_double(origin[1]),
-                                                C.c_double(origin[2]), C.c_double(vs), ptr(ws), C.c_int64(ws.numel()), ptr(order),
-                                                ptr(offsets), ptr(count), stream_ptr()), "misplat_pointcloud_voxel_group")
+    run("misplat_pointcloud_voxel_group", ptr(p), n, origin[0], origin[1], origin[2], vs, ptr(ws), ws.numel(), ptr(order),
+        ptr(offsets), ptr(count))
     v = int(count.item())                                           # host read 2 of 2
     outs = []
     for x in [p] + vals:
         out = torch.empty((v, x.shape[1]), dtype=torch.float32, device=dev)
-        check(load().misplat_pointcloud_voxel_mean(ptr(x), C.c_int64(n), x.shape[1], ptr(order), ptr(offsets), C.c_int64(v),
-                                                   ptr(out), stream_ptr()), "misplat_pointcloud_voxel_mean")
+        run("misplat_pointcloud_voxel_mean", ptr(x), n, x.shape[1], ptr(order), ptr(offsets), v, ptr(out))
         outs.append(out)
     first = order[offsets[:v].long()].long()
     return outs[0], tuple(outs[1:]), first, offsets[1:v + 1] - offsets[:v]

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 from torch import Tensor
 
-from ._lib import MisplatError, check, load, ptr, require_gpu, stream_ptr
+from ._lib import MisplatError, load, ptr, require_gpu, run
 from .depthcloud import _backproject, _cameras, _depth, _flag, _map3
 from .meshmap import _prep
 from .unitvolume import (MAX_UNITS, UNIT_VOXELS, Grid, GrowingVolume, Stages, _unit_range, empty_mesh, make_grid, marching_cubes,
@@ -128,12 +128,11 @@ class PointTSDFVolume(GrowingVolume):
             n = min(CHUNK_RAYS, P - c0)
             p, o = p32[c0:c0 + n], (o32[c0:c0 + n] if per_point else o32)
             col = None if c32 is None else c32[c0:c0 + n]
-            stride, N = (3 if per_point else 0), C.c_int64(n)
-            ws = torch.empty(int(lib.misplat_ptsdf_workspace(N, C.c_int64(0))), dtype=torch.uint8, device=dev)
+            stride = 3 if per_point else 0
+            ws = torch.empty(int(lib.misplat_ptsdf_workspace(n, 0)), dtype=torch.uint8, device=dev)
             pair_off = torch.empty(n + 1, dtype=torch.int32, device=dev)
             total = torch.empty(1, dtype=torch.int64, device=dev)
-            check(lib.misplat_ptsdf_count(g, ptr(p), ptr(o), stride, N, carve, ptr(ws), C.c_int64(ws.numel()), ptr(pair_off),
-                                          ptr(total), stream_ptr()), "misplat_ptsdf_count")
+            run("misplat_ptsdf_count", g, ptr(p), ptr(o), stride, n, carve, ptr(ws), ws.numel(), ptr(pair_off), ptr(total))
             n_pairs = int(total.item())                                              # host read
             mark("count")
             if n_pairs == 0:
@@ -141,23 +140,21 @@ class PointTSDFVolume(GrowingVolume):
             if n_pairs >= MAX_PAIRS:
                 raise MisplatError(f"{name}: {n_pairs} (unit, ray) pairs in one chunk, above the cap of {MAX_PAIRS}: pass bounds= "
                                    f"or a larger voxel_size")
-            E = C.c_int64(n_pairs)
             keys = torch.empty(n_pairs, dtype=torch.int32, device=dev)
             ids = torch.empty(n_pairs, dtype=torch.int32, device=dev)
             self._begin_batch()
-            check(lib.misplat_ptsdf_emit(g, ptr(p), ptr(o), stride, N, carve, ptr(pair_off), E, ptr(keys), ptr(ids),
-                                         ptr(self._words), stream_ptr()), "misplat_ptsdf_emit")
+            run("misplat_ptsdf_emit", g, ptr(p), ptr(o), stride, n, carve, ptr(pair_off), n_pairs, ptr(keys), ptr(ids),
+                ptr(self._words))
             n_units, n_touched = self._alloc(grid)                                   # host read
             self._grow_planes(n_units)
             self.n_units = n_units
             mark("emit_alloc")
             ids_sorted, ranges = unit_lists(grid, self._slot_map, keys, ids, n_pairs, n_units)
             mark("lists")
-            ws = torch.empty(int(lib.misplat_ptsdf_workspace(C.c_int64(n_touched), C.c_int64(0))), dtype=torch.uint8, device=dev)
-            check(lib.misplat_ptsdf_accumulate(g, ptr(self._touched), n_touched, ptr(p), ptr(o), stride, ptr(col), carve,
-                                               ptr(ids_sorted), ptr(ranges), E, ptr(ws), C.c_int64(ws.numel()), ptr(self._sum_q),
-                                               ptr(self._count), ptr(self._rgb_sum), ptr(self._rgb_count), stream_ptr()),
-                  "misplat_ptsdf_accumulate")
+            ws = torch.empty(int(lib.misplat_ptsdf_workspace(n_touched, 0)), dtype=torch.uint8, device=dev)
+            run("misplat_ptsdf_accumulate", g, ptr(self._touched), n_touched, ptr(p), ptr(o), stride, ptr(col), carve,
+                ptr(ids_sorted), ptr(ranges), n_pairs, ptr(ws), ws.numel(), ptr(self._sum_q), ptr(self._count), ptr(self._rgb_sum),
+                ptr(self._rgb_count))
             mark("accumulate")
             self.n_pairs += n_pairs
             del keys, ids, ids_sorted, ws
@@ -190,8 +187,8 @@ class PointTSDFVolume(GrowingVolume):
 
     def _pool(self, min_weight: int) -> Tensor:
         pool = torch.empty((self.n_units, 5, UNIT_VOXELS), dtype=torch.float32, device=self.device)
-        check(load().misplat_ptsdf_finalize(self.n_units, ptr(self._sum_q), ptr(self._count), ptr(self._rgb_sum),
-                                            ptr(self._rgb_count), int(min_weight), ptr(pool), stream_ptr()), "misplat_ptsdf_finalize")
+        run("misplat_ptsdf_finalize", self.n_units, ptr(self._sum_q), ptr(self._count), ptr(self._rgb_sum),
+            ptr(self._rgb_count), int(min_weight), ptr(pool))
         return pool
 
     def extract_mesh(self, min_weight: int = 5) -> Tuple[Tensor, Tensor, Tensor]:

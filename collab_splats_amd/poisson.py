@@ -10,7 +10,6 @@ tests/poisson_restatement.py.  There is no CPU fallback.
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import Optional, Sequence, Tuple
 
@@ -18,7 +17,7 @@ import numpy as np
 import torch
 from torch import Tensor
 
-from ._lib import MisplatError, check, load, ptr, require_gpu, stream_ptr
+from ._lib import MisplatError, load, ptr, require_gpu, run
 from .meshclean import _attributes, _mesh
 from .meshmap import _prep
 from .pointcloud import _cloud, _finite, _positive32
@@ -39,7 +38,7 @@ def _depth(name: str, depth) -> int:
 
 
 def _workspace(depth: int, n_points: int, device) -> Tensor:
-    b = int(load().misplat_poisson_workspace(depth, C.c_int64(n_points)))
+    b = int(load().misplat_poisson_workspace(depth, n_points))
     if b < 0:
         raise ValueError(f"poisson: depth {depth} with {n_points} points is beyond the library's limits")
     return torch.empty(b, dtype=torch.uint8, device=device)
@@ -78,16 +77,11 @@ def _oriented(name: str, points, normals, colors) -> Tuple[Tensor, Tensor, Optio
     return _prep(points), _prep(normals), None if colors is None else _prep(colors)
 
 
-def _frame(o: np.ndarray, h) -> Tuple[C.c_float, C.c_float, C.c_float, C.c_float]:
-    return C.c_float(float(o[0])), C.c_float(float(o[1])), C.c_float(float(o[2])), C.c_float(float(h))
-
-
 def _sample(field: Tensor, depth: int, o: np.ndarray, h, queries: Tensor) -> Tensor:
     """[Nq, C] fp32: the trilinear value of field [C,G,G,G] at the queries."""
     nch = field.shape[0]
     out = torch.empty((queries.shape[0], nch), dtype=torch.float32, device=field.device)
-    check(load().misplat_poisson_sample(ptr(field), nch, depth, *_frame(o, h), ptr(queries), C.c_int64(queries.shape[0]), ptr(out),
-                                        stream_ptr()), "misplat_poisson_sample")
+    run("misplat_poisson_sample", ptr(field), nch, depth, o[0], o[1], o[2], h, ptr(queries), queries.shape[0], ptr(out))
     return out
 
 
@@ -125,8 +119,7 @@ def _splat(p: Tensor, n: Tensor, c: Optional[Tensor], depth: int, o: np.ndarray,
     W = torch.empty((G, G, G), dtype=torch.int64, device=dev)
     V = torch.empty((3, G, G, G), dtype=torch.int64, device=dev)
     Cq = None if c is None else torch.empty((3, G, G, G), dtype=torch.int64, device=dev)
-    check(load().misplat_poisson_splat(ptr(p), ptr(n), ptr(c), C.c_int64(p.shape[0]), depth, *_frame(o, h), ptr(W), ptr(V), ptr(Cq),
-                                       stream_ptr()), "misplat_poisson_splat")
+    run("misplat_poisson_splat", ptr(p), ptr(n), ptr(c), p.shape[0], depth, o[0], o[1], o[2], h, ptr(W), ptr(V), ptr(Cq))
     return W, V, Cq
 
 
@@ -147,8 +140,7 @@ def poisson_splat(points: Tensor, normals: Tensor, colors: Optional[Tensor] = No
 def _system(W: Tensor, V: Tensor, depth: int, point_weight: float, ws: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
     G = 1 << depth
     Wf, b, D = (torch.empty((G, G, G), dtype=torch.float32, device=W.device) for _ in range(3))
-    check(load().misplat_poisson_system(ptr(W), ptr(V), depth, C.c_float(point_weight), ptr(ws), C.c_int64(ws.numel()), ptr(Wf),
-                                        ptr(b), ptr(D), stream_ptr()), "misplat_poisson_system")
+    run("misplat_poisson_system", ptr(W), ptr(V), depth, point_weight, ptr(ws), ws.numel(), ptr(Wf), ptr(b), ptr(D))
     return Wf, b, D
 
 
@@ -177,18 +169,15 @@ def poisson_system(W: Tensor, V: Tensor, point_weight: float = 1.0) -> Tuple[Ten
 
 # ------------------------------------------------------------------------------------------------------------ solve
 def _solve(b: Tensor, D: Tensor, depth: int, tol: float, max_iters: int, ws: Tensor) -> Tuple[Tensor, dict]:
-    lib = load()
     x, r, z, p, ap = (torch.empty_like(b) for _ in range(5))
-    nws = C.c_int64(ws.numel())
-    check(lib.misplat_poisson_cg_init(ptr(b), ptr(D), depth, max_iters, ptr(ws), nws, ptr(x), ptr(r), ptr(z), ptr(p), stream_ptr()),
-          "misplat_poisson_cg_init")
+    run("misplat_poisson_cg_init", ptr(b), ptr(D), depth, max_iters, ptr(ws), ws.numel(), ptr(x), ptr(r), ptr(z), ptr(p))
     state = ws[:64].view(torch.float64)
     while True:
         st = state.tolist()                                         # the host read, every CHECK_EVERY iterations
         if st[6] != 0:
             break
-        check(lib.misplat_poisson_cg_iterate(ptr(D), depth, CHECK_EVERY, C.c_double(tol), max_iters, ptr(ws), nws, ptr(x), ptr(r),
-                                             ptr(z), ptr(p), ptr(ap), stream_ptr()), "misplat_poisson_cg_iterate")
+        run("misplat_poisson_cg_iterate", ptr(D), depth, CHECK_EVERY, tol, max_iters, ptr(ws), ws.numel(), ptr(x), ptr(r), ptr(z),
+            ptr(p), ptr(ap))
     info = {"iterations": int(st[7]), "residual": math.sqrt(st[2] / st[3]) if st[3] > 0 else 0.0, "converged": st[6] == 1.0}
     return x, info
 
@@ -228,8 +217,7 @@ def poisson_solve(W: Tensor, V: Tensor, point_weight: float = 1.0, tol: float = 
 def _iso(chi: Tensor, depth: int, o: np.ndarray, h, p: Tensor, ws: Tensor) -> float:
     vals = _sample(chi[None], depth, o, h, p).reshape(-1)
     mean = torch.empty(1, dtype=torch.float64, device=chi.device)
-    check(load().misplat_poisson_mean(ptr(vals), C.c_int64(vals.shape[0]), ptr(ws), C.c_int64(ws.numel()), ptr(mean), stream_ptr()),
-          "misplat_poisson_mean")
+    run("misplat_poisson_mean", ptr(vals), vals.shape[0], ptr(ws), ws.numel(), ptr(mean))
     return float(mean.item())                                       # host read
 
 
@@ -241,7 +229,7 @@ def _extract(chi: Tensor, iso: float, depth: int, o: np.ndarray, h, Wf: Tensor, 
     U = (1 << depth) // UNIT
     n = U ** 3
     pool = torch.empty((n, 5, UNIT_VOXELS), dtype=torch.float32, device=dev)
-    check(load().misplat_poisson_mc_pool(ptr(chi), depth, C.c_float(iso), ptr(pool), stream_ptr()), "misplat_poisson_mc_pool")
+    run("misplat_poisson_mc_pool", ptr(chi), depth, iso, ptr(pool))
     slot_map = torch.arange(n, dtype=torch.int32, device=dev)       # every unit allocated, in map order: the order too
     mesh = marching_cubes(make_grid(1.0, 1.0, 1.0, (0, 0, 0), (U, U, U)), slot_map, n, pool, order=slot_map)
     del pool

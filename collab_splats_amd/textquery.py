@@ -16,8 +16,7 @@ from typing import NamedTuple, Optional, Sequence
 import torch
 from torch import Tensor
 
-from . import _lib
-from ._lib import check, ptr, require_gpu, stream_ptr
+from ._lib import ptr, require_gpu, run
 from .featureloss import MAX_HIDDEN, MAX_LATENT, Decoder, _features_view, _flat
 
 MAX_QUERIES = 64
@@ -83,8 +82,7 @@ def fold_text_queries(decoder: Decoder, name: str, text_embeddings: Tensor, n_po
     dev = emb.device
     A = torch.empty(Q, hidden, device=dev, dtype=torch.float32)
     c = torch.empty(Q, device=dev, dtype=torch.float32)
-    check(_lib.load().misplat_textquery_fold(C.c_int32(Q), C.c_int32(channels), C.c_int32(hidden), ptr(emb), ptr(w_o), ptr(b_o),
-                                             ptr(A), ptr(c), stream_ptr()), "misplat_textquery_fold")
+    run("misplat_textquery_fold", Q, channels, hidden, ptr(emb), ptr(w_o), ptr(b_o), ptr(A), ptr(c))
     return TextQuery(A, c, w_h.detach().clone().contiguous(), b_h.detach().clone().contiguous(), n_positive, Q)
 
 
@@ -136,19 +134,15 @@ def similarity_map(features: Tensor, query: TextQuery, work_hw: Sequence[int], o
     h, w = _hw(what, "work_hw", work_hw)
     Ho, Wo = (h, w) if out_hw is None else _hw(what, "out_hw", out_hw)
     require_gpu(feats, *query[:4])
-    lib = _lib.load()
     H, W, L = (int(v) for v in feats.shape)
     work = torch.empty(h, w, 1, device=feats.device, dtype=torch.float32)
-    check(lib.misplat_textquery_map(C.c_int32(H), C.c_int32(W), C.c_int32(L), C.c_int32(stride), C.c_void_p(feats.data_ptr()),
-                                    C.c_int32(hidden), ptr(query.w_hidden), ptr(query.b_hidden), C.c_int32(query.Q),
-                                    C.c_int32(query.n_positive), ptr(query.A), ptr(query.c), C.c_int32(METHODS.index(method)),
-                                    C.c_float(softmax_temp), C.c_int32(h), C.c_int32(w), ptr(work), stream_ptr()),
-          "misplat_textquery_map")
+    run("misplat_textquery_map", H, W, L, stride, C.c_void_p(feats.data_ptr()), hidden, ptr(query.w_hidden),
+        ptr(query.b_hidden), query.Q, query.n_positive, ptr(query.A), ptr(query.c), METHODS.index(method), softmax_temp, h, w,
+        ptr(work))
     if (Ho, Wo) == (h, w):
         return work
     out = torch.empty(Ho, Wo, 1, device=feats.device, dtype=torch.float32)
-    check(lib.misplat_textquery_upsample(C.c_int32(h), C.c_int32(w), ptr(work), C.c_int32(Ho), C.c_int32(Wo), ptr(out), stream_ptr()),
-          "misplat_textquery_upsample")
+    run("misplat_textquery_upsample", h, w, ptr(work), Ho, Wo, ptr(out))
     return out
 
 
@@ -168,11 +162,8 @@ def gaussian_similarity(latents: Tensor, query: TextQuery, method: str = "pairwi
     rows = latents.detach().contiguous()
     require_gpu(rows, *query[:4])
     out = torch.empty(N, device=rows.device, dtype=torch.float32)
-    check(_lib.load().misplat_textquery_rows(C.c_int64(N), C.c_int32(L), C.c_int32(L), ptr(rows), C.c_int32(hidden),
-                                             ptr(query.w_hidden), ptr(query.b_hidden), C.c_int32(query.Q),
-                                             C.c_int32(query.n_positive), ptr(query.A), ptr(query.c),
-                                             C.c_int32(METHODS.index(method)), C.c_float(softmax_temp), ptr(out), stream_ptr()),
-          "misplat_textquery_rows")
+    run("misplat_textquery_rows", N, L, L, ptr(rows), hidden, ptr(query.w_hidden), ptr(query.b_hidden), query.Q,
+        query.n_positive, ptr(query.A), ptr(query.c), METHODS.index(method), softmax_temp, ptr(out))
     return out
 
 

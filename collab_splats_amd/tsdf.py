@@ -14,7 +14,7 @@ import numpy as np
 import torch
 from torch import Tensor
 
-from ._lib import MisplatError, check, load, ptr, require_gpu, stream_ptr  # noqa: F401
+from ._lib import MisplatError, check, load, ptr, require_gpu, run, stream_ptr  # noqa: F401
 from .unitvolume import (MAX_UNITS, UNIT, UNIT_VOXELS, Grid, GrowingVolume, _unit_range, empty_mesh, make_grid,  # noqa: F401
                          map_span, marching_cubes, unit_coords)
 
@@ -108,7 +108,6 @@ class TSDFVolume(GrowingVolume):
         if not self._cover(*self._frusta_units(viewmats, Ks, H, W)):
             self.n_views += V                      # every view lies outside the bounds: nothing to update
             return
-        lib = load()
         grid = self._grid()
         for b in range(0, V, MAX_VIEWS):
             n = min(MAX_VIEWS, V - b)
@@ -116,16 +115,14 @@ class TSDFVolume(GrowingVolume):
             c = rgbs[b:b + n] if rgbs is not None else None
             mk = masks[b:b + n] if masks is not None else None
             self._begin_batch()
-            check(lib.misplat_tsdf_mark(C.byref(grid), ptr(d), ptr(mk), n, H, W, ptr(vm), ptr(k), ptr(self._words), stream_ptr()),
-                  "misplat_tsdf_mark")
+            run("misplat_tsdf_mark", C.byref(grid), ptr(d), ptr(mk), n, H, W, ptr(vm), ptr(k), ptr(self._words))
             n_units, n_touched = self._alloc(grid)                               # the batch's one host read
             if n_touched == 0:
                 continue
             self._grow_pool(n_units)
             self.n_units = n_units
-            check(lib.misplat_tsdf_integrate(C.byref(grid), ptr(self._touched), n_touched, ptr(self._words), ptr(d), ptr(mk),
-                                             ptr(c), n, H, W, ptr(vm), ptr(k), ptr(self._pool), stream_ptr()),
-                  "misplat_tsdf_integrate")
+            run("misplat_tsdf_integrate", C.byref(grid), ptr(self._touched), n_touched, ptr(self._words), ptr(d), ptr(mk),
+                ptr(c), n, H, W, ptr(vm), ptr(k), ptr(self._pool))
         self.n_views += V
 
     def extract_mesh(self) -> Tuple[Tensor, Tensor, Tensor]:

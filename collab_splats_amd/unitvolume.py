@@ -14,7 +14,7 @@ import numpy as np
 import torch
 from torch import Tensor
 
-from ._lib import MisplatError, check, load, ptr, stream_ptr
+from ._lib import MisplatError, load, ptr, run
 
 UNIT = 16
 UNIT_VOXELS = UNIT ** 3
@@ -73,8 +73,7 @@ def map_order(slot_map: Tensor) -> Tensor:
 def alloc_units(grid: Grid, words: Tensor, slot_map: Tensor, counters: Tensor, touched: Tensor) -> Tuple[int, int]:
     """``misplat_tsdf_alloc`` over the marked ``words`` and its one host read: (allocated units so far, units touched now).
     ``counters`` {allocated slots, touched units}: the second zeroed by the caller."""
-    check(load().misplat_tsdf_alloc(C.byref(grid), ptr(words), ptr(slot_map), ptr(counters), ptr(touched), stream_ptr()),
-          "misplat_tsdf_alloc")
+    run("misplat_tsdf_alloc", C.byref(grid), ptr(words), ptr(slot_map), ptr(counters), ptr(touched))
     n_units, n_touched = (int(x) for x in counters.tolist())                     # host read
     return n_units, n_touched
 
@@ -83,13 +82,13 @@ def unit_lists(grid: Grid, slot_map: Tensor, keys: Tensor, ids: Tensor, n_pairs:
     """The (unit map index, item) pairs sorted by unit, stable (``misplat_unit_lists``; ``keys`` and ``ids`` are used as
     scratch): (ids_sorted [n_pairs] int32, ranges [n_units, 2] int32), unit slot s owning ``ids_sorted[ranges[s, 0]:ranges[s,
     1]]``.  ``ranges`` starts as zeros: a unit allocated earlier and not listed now reads as the empty range."""
-    lib, dev, E = load(), slot_map.device, C.c_int64(n_pairs)
-    ws = torch.empty(int(lib.misplat_density_workspace(C.c_int64(0), E)), dtype=torch.uint8, device=dev)
+    dev = slot_map.device
+    ws = torch.empty(int(load().misplat_density_workspace(0, n_pairs)), dtype=torch.uint8, device=dev)
     keys_sorted = torch.empty(n_pairs, dtype=torch.int32, device=dev)
     ids_sorted = torch.empty(n_pairs, dtype=torch.int32, device=dev)
     ranges = torch.zeros((n_units, 2), dtype=torch.int32, device=dev)
-    check(lib.misplat_unit_lists(C.byref(grid), ptr(slot_map), ptr(keys), ptr(ids), E, n_units, ptr(ws), C.c_int64(ws.numel()),
-                                 ptr(keys_sorted), ptr(ids_sorted), ptr(ranges), stream_ptr()), "misplat_unit_lists")
+    run("misplat_unit_lists", C.byref(grid), ptr(slot_map), ptr(keys), ptr(ids), n_pairs, n_units, ptr(ws), ws.numel(),
+        ptr(keys_sorted), ptr(ids_sorted), ptr(ranges))
     return ids_sorted, ranges
 
 
@@ -185,19 +184,19 @@ def marching_cubes(grid: Grid, slot_map: Tensor, n_units: int, pool: Tensor, ord
     """(vertices [M,3] fp32 in lattice coordinates times ``grid.voxel_size``, triangles [T,3] int32, colors [M,3] fp32 in [0,1])
     of the ``n_units`` allocated units, in the deterministic order of DESIGN.md section 14.1, or None when no edge is crossed.
     ``order``: the allocated units' map indices, ascending (``misplat_tsdf_order`` finds them when None).  One host read."""
-    lib, dev, n, g = load(), pool.device, n_units, C.byref(grid)
+    dev, n, g = pool.device, n_units, C.byref(grid)
     if order is None:
         nb = (grid.dims[0] * grid.dims[1] * grid.dims[2] + 4095) // 4096
         scratch = torch.empty(2 * nb + 1, dtype=torch.int32, device=dev)
         order = torch.empty(n, dtype=torch.int32, device=dev)
-        check(lib.misplat_tsdf_order(g, ptr(slot_map), ptr(scratch), ptr(order), stream_ptr()), "misplat_tsdf_order")
+        run("misplat_tsdf_order", g, ptr(slot_map), ptr(scratch), ptr(order))
     code = torch.empty(n * UNIT_VOXELS, dtype=torch.int16, device=dev)
     cnt = torch.empty(n * UNIT_VOXELS, dtype=torch.uint8, device=dev)
     unit_counts = torch.empty(2 * n, dtype=torch.int32, device=dev)
     unit_offs = torch.empty(2 * n, dtype=torch.int32, device=dev)
     totals = torch.empty(2, dtype=torch.int32, device=dev)
-    check(lib.misplat_tsdf_mc_count(g, ptr(slot_map), ptr(order), n, ptr(pool), ptr(code), ptr(cnt), ptr(unit_counts),
-                                    ptr(unit_offs), ptr(totals), stream_ptr()), "misplat_tsdf_mc_count")
+    run("misplat_tsdf_mc_count", g, ptr(slot_map), ptr(order), n, ptr(pool), ptr(code), ptr(cnt), ptr(unit_counts),
+        ptr(unit_offs), ptr(totals))
     M, T = (int(x) for x in totals.tolist())                        # host read
     if M == 0:
         return None
@@ -205,7 +204,6 @@ def marching_cubes(grid: Grid, slot_map: Tensor, n_units: int, pool: Tensor, ord
     vertices = torch.empty((M, 3), dtype=torch.float32, device=dev)
     colors = torch.empty((M, 3), dtype=torch.float32, device=dev)
     triangles = torch.empty((T, 3), dtype=torch.int32, device=dev)
-    check(lib.misplat_tsdf_mc_emit(g, ptr(slot_map), ptr(order), n, ptr(pool), ptr(code), ptr(cnt), ptr(unit_offs),
-                                   ptr(vert_base), ptr(vertices), ptr(colors), ptr(triangles), stream_ptr()),
-          "misplat_tsdf_mc_emit")
+    run("misplat_tsdf_mc_emit", g, ptr(slot_map), ptr(order), n, ptr(pool), ptr(code), ptr(cnt), ptr(unit_offs), ptr(vert_base),
+        ptr(vertices), ptr(colors), ptr(triangles))
     return vertices, triangles, colors

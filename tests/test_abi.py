@@ -15,6 +15,27 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "misplat.h")
 
 
+ARG_KIND = {"int": "i", "int32_t": "i", "int64_t": "q", "float": "f", "double": "d", "uint32_t": "u", "size_t": "Q",
+            "misplat_stream_t": "s"}
+RET_KIND = {"int": "i", "int64_t": "q", "void": "v", "const char*": "z", "misplat_graph_cache*": "p"}
+
+
+def declared_signatures():
+    """name -> signature string (the format of _lib.SYMBOLS) of every prototype of the header."""
+    text = open(HEADER).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+    sigs = {}
+    for ret, name, args in re.findall(r"^\s*((?:const\s+)?\w+(?:\s*\*)?)\s*(misplat_\w+)\s*\(([^()]*)\)\s*;", text, flags=re.M):
+        kinds = ""
+        for a in ([] if args.strip() in ("", "void") else args.split(",")):
+            # a pointer is a pointer whatever it points to; a value is named by the first word after any const
+            kinds += "p" if "*" in a or "[" in a else ARG_KIND[re.sub(r"\bconst\b", "", a).split()[0]]
+        assert name not in sigs, name
+        sigs[name] = (RET_KIND[re.sub(r"\s*\*", "*", " ".join(ret.split()))] + " " + kinds).strip()
+    return sigs
+
+
 def declared_symbols():
     text = open(HEADER).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
@@ -22,8 +43,36 @@ def declared_symbols():
 
 
 def test_header_and_binding_agree():
+    """Every prototype of the header has its signature in _lib.SYMBOLS and nothing else is there: the return kind, every
+    argument's kind, and the stream exactly where the header says misplat_stream_t."""
     from collab_splats_amd import _lib
-    assert declared_symbols() == sorted(_lib.SYMBOLS)
+    sigs = declared_signatures()
+    assert sorted(sigs) == declared_symbols()              # the prototype pattern missed no name the header calls
+    assert sorted(sigs) == sorted(_lib.SYMBOLS)
+    wrong = {n: (s, _lib.SYMBOLS[n]) for n, s in sigs.items() if s != _lib.SYMBOLS[n]}
+    assert not wrong, wrong
+    assert all(set(s[2:]) <= set(_lib._ARG) and s[0] in _lib._RET for s in _lib.SYMBOLS.values())
+
+
+def test_argument_count_and_kind_are_checked(built_lib):
+    from collab_splats_amd import _lib
+    size = _lib.load().misplat_mcmc_sample_workspace_bytes
+    with pytest.raises(_lib.MisplatError, match="0 arguments passed, the C ABI takes 1"):
+        size()
+    with pytest.raises(_lib.MisplatError, match="2 arguments passed, the C ABI takes 1"):
+        size(4, 4)
+    with pytest.raises(C.ArgumentError):
+        size(4.0)
+
+
+def test_sixty_four_bit_arguments_and_returns_keep_their_width(built_lib):
+    """Host-only size functions: csrc/mcmc.hip admits 1 .. 2^31 - 1 rows and carves more than 8 bytes a row."""
+    from collab_splats_amd import _lib
+    size = _lib.load().misplat_mcmc_sample_workspace_bytes
+    assert size(2 ** 32 + 5) == -1                         # (a 32-bit pass would see 5 and return a size)
+    assert size(2 ** 31 - 1) > 2 ** 31
+    for n in (1, 1000, 2 ** 31 - 1, 2 ** 32 + 5):
+        assert size(n) == size(C.c_int64(n))
 
 
 def test_library_exports_every_declared_symbol(built_lib):

@@ -240,9 +240,9 @@ def test_abi_of_the_view_matrix_gradient(built_lib):
         assert m is not None, name
         assert len(m.group(1).split(",")) == n_args, name
         assert re.search(r" T " + name + r"\b", exported), name
-        assert name in _lib.SYMBOLS and _lib.SYMBOLS[name][1] == n_args
+        assert name in _lib.SYMBOLS and len(_lib.SYMBOLS[name].split(" ")[1]) == n_args
         assert hasattr(lib, name)
-    assert _lib.SYMBOLS["misplat_project_bwd_pose_workspace"][0] is C.c_int64
+    assert _lib.SYMBOLS["misplat_project_bwd_pose_workspace"][0] == "q" and _lib._RET["q"] is C.c_int64
     # sizes need no GPU: 12 fp64 partials per workgroup and camera, a workgroup count that depends on N only and is capped
     ws = lambda n, c: int(lib.misplat_project_bwd_pose_workspace(n, c))
     assert ws(1, 1) >= 96 and ws(70001, 3) >= 3 * 274 * 96
