@@ -4,6 +4,8 @@
 (d2, vertex index), d = sqrt(d2) (correctly rounded), valid iff d[0] <= float32(sdf_trunc).
 ``aggregate``: the map of steps 1-7 in fp64 from given neighbours, with the build's two divergences from the reference: the
 row-shifted weights (a row whose exps all underflow stays finite) and weights 1/k when sigma = 0.
+``aggregate_ordered``: the same map in fp32, in the kernel's written order and chunking: the yardstick of the rounding that
+the fp64 form is blind to, and bit for bit the kernel's output where no exp is involved (k = 1, sigma = 0).
 """
 from __future__ import annotations
 
@@ -73,6 +75,68 @@ def aggregate(n_vertices, idx, d, valid, values, normalise=False):
     out = np.where(den[:, None] > 0, num / np.where(den > 0, den, 1.0)[:, None], 0.0)
     if normalise:
         out = out / (np.linalg.norm(out, axis=1, keepdims=True) + 1e-8)
+    return out
+
+
+def row_weights_fp32(d, valid):
+    """Row weights [N,k] fp32 (0 on invalid rows) in the kernel's written order: sigma in fp64 from the fp32 distances,
+    c = float32(1 / (2 sigma^2)), delta = dj dj - d0 d0 in fp32, e = 1 when flat or delta <= 0 else exp(-(delta c)), the row
+    sum in j order, w = e / sum."""
+    d = np.ascontiguousarray(d, np.float32)
+    valid = np.asarray(valid, bool)
+    w = np.zeros(d.shape, np.float32)
+    if not valid.any():
+        return w
+    k = d.shape[1]
+    dv = d[valid]
+    sigma = float(dv.astype(np.float64).sum() / (len(dv) * k))
+    flat = not sigma > 0.0
+    c = np.float32(0.0 if flat else 1.0 / (2.0 * sigma * sigma))
+    delta = dv * dv - (dv[:, :1] * dv[:, :1])
+    with np.errstate(under="ignore"):
+        e = np.where(flat | ~(delta > 0), np.float32(1), np.exp(-(np.where(delta > 0, delta, np.float32(0)) * c)))
+    e = e.astype(np.float32)
+    s = np.zeros(len(dv), np.float32)
+    for j in range(k):
+        s = s + e[:, j]
+    w[valid] = e / s[:, None]
+    return w
+
+
+def aggregate_ordered(n_vertices, idx, d, valid, values, normalise=False, chunk=512):
+    """[M,D] fp32: the map in the kernel's arithmetic and order.  The weights of ``row_weights_fp32``; per vertex the
+    contributions w F in (i, j) order, summed in fp32 from 0 in chunks of ``chunk``, the chunk sums in chunk order from 0, the
+    division by the weight sum (summed the same way; 0 unless it is positive); with ``normalise`` the first three channels
+    divided by (sqrt((x x + y y) + z z) + float32(1e-8)).  With k = 1 (w = 1) and with sigma = 0 (w = float32(1) / float32(k))
+    no exp is involved and the kernel's output is this one bit for bit."""
+    F = np.ascontiguousarray(values, np.float32)
+    idx = np.asarray(idx)
+    valid = np.asarray(valid, bool)
+    M, D = n_vertices, F.shape[1]
+    k = idx.shape[1]
+    out = np.zeros((M, D), np.float32)
+    w = row_weights_fp32(d, valid)
+    iv = np.nonzero(valid)[0]
+    if len(iv):
+        vert = idx[iv].reshape(-1)
+        order = np.argsort(vert, kind="stable")                           # each list in (i, j) order
+        rows = np.repeat(iv, k)[order]
+        ws = w[iv].reshape(-1)[order]
+        terms = np.concatenate([ws[:, None] * F[rows], ws[:, None]], axis=1)      # fp32 products; column D: the weight
+        offs = np.searchsorted(vert[order], np.arange(M + 1))
+        zero = np.zeros((1, D + 1), np.float32)
+        for v in np.nonzero(offs[1:] > offs[:-1])[0]:
+            parts = [zero]
+            for e0 in range(offs[v], offs[v + 1], chunk):
+                e1 = min(e0 + chunk, offs[v + 1])
+                parts.append(np.add.accumulate(np.concatenate([zero, terms[e0:e1]]), axis=0)[-1:])
+            tot = np.add.accumulate(np.concatenate(parts), axis=0)[-1]
+            if tot[D] > 0:
+                out[v] = tot[:D] / tot[D]
+    if normalise:
+        x, y, z = out[:, 0].copy(), out[:, 1].copy(), out[:, 2].copy()
+        nrm = np.sqrt((x * x + y * y) + z * z) + np.float32(1e-8)
+        out[:, 0], out[:, 1], out[:, 2] = x / nrm, y / nrm, z / nrm
     return out
 
 
