@@ -88,6 +88,21 @@ _use_count = getattr(torch._C, "_storage_Use_Count", None)
 _ESIZE = {torch.float32: 4, torch.int32: 4, torch.uint8: 1, torch.int64: 8, torch.int16: 2, torch.float64: 8}
 
 
+def place(off: int, nbytes: int):
+    """THE offset rule: (start, new offset) of a take of ``nbytes`` bytes at offset ``off``."""
+    align = ALIGN_BIG if nbytes >= BIG else ALIGN_SMALL
+    start = (off + align - 1) // align * align
+    return start, start + nbytes
+
+
+def demand(takes: Sequence[int]) -> int:
+    """What a slot must hold to serve takes of these byte counts, in this order."""
+    off = 0
+    for nbytes in takes:
+        off = place(off, nbytes)[1]
+    return off
+
+
 class Slot:
     """One arena: a 2 MiB-aligned byte range carved front to back by ``take``; ``demand`` records what a call wanted."""
 
@@ -146,17 +161,17 @@ class Slot:
         self.off = 0
         self.demand = 0
 
+    def served_all(self) -> bool:
+        """Every take since ``begin`` came from this slot (none fell back to the allocator): what a cached plan needs."""
+        return self.demand <= self.size
+
     def take(self, count: int, dtype: torch.dtype) -> Optional[Tensor]:
         """``count`` elements of ``dtype`` from the slot, or None when it is full (the caller then asks the allocator)."""
         esize = _ESIZE[dtype]
-        nbytes = int(count) * esize
-        align = ALIGN_BIG if nbytes >= BIG else ALIGN_SMALL
-        start = (self.off + align - 1) // align * align
-        self.demand = start + nbytes                                        # (what a slot must hold to serve this call)
-        if start + nbytes > self.size:
-            self.off = start + nbytes                                       # keep counting: the demand of the whole call
+        start, self.off = place(self.off, int(count) * esize)               # (keeps counting past the end: the whole call)
+        self.demand = self.off                                              # (what a slot must hold to serve this call)
+        if self.off > self.size:
             return None
-        self.off = start + nbytes
         first = start // esize                                              # (align is a multiple of every element size)
         return self.typed[dtype][first:first + int(count)]
 
@@ -254,10 +269,9 @@ class Carver:
         self.shadow = 0                                           # demand counted when there is no slot
 
     def reserve(self, nbytes: int) -> None:
-        """Before the first ``take`` of a ring's FIRST call: the caller's own estimate of the call's demand (an upper bound
-        is fine; an estimate that falls short only means allocator memory for what does not fit, as without it).  The ring
-        then owns a slot from call one -- the addresses, and with them the graph keys, of the first call are those of
-        every later one."""
+        """Before the first ``take`` of a ring's FIRST call: the call's demand (``demand`` of the takes to come; a figure that
+        falls short means allocator memory for what does not fit, and no cached plan for that call).  The ring then owns a
+        slot from call one -- the addresses, and with them the graph keys, of the first call are those of every later one."""
         if self.ring is not None and self.slot is None and self.ring.want == 0 and not self.ring.slots and nbytes > 0:
             self.ring.want = int(nbytes)
             self.slot = self.ring.acquire()
@@ -270,9 +284,7 @@ class Carver:
                 return t
             STATS["fallbacks"] += 1
         elif self.ring is not None:
-            nbytes = count * _ESIZE[dtype]
-            align = ALIGN_BIG if nbytes >= BIG else ALIGN_SMALL
-            self.shadow = (self.shadow + align - 1) // align * align + nbytes
+            self.shadow = place(self.shadow, count * _ESIZE[dtype])[1]
             with pool_ctx(self.dev, self.ring.pool):              # (a ring's first call: see USE_POOL)
                 return torch.empty(max(count, 0), device=self.dev, dtype=dtype)
         return torch.empty(max(count, 0), device=self.dev, dtype=dtype)

@@ -64,8 +64,8 @@ class GraphedStep:
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
         self.capacity = int(capacity)
         if not ops.fused_node_ok():
-            raise ops._lib.MisplatError("GraphedStep needs the default single-node path (MISPLAT_FUSED / MISPLAT_FUSED_NODE / "
-                                        "atomic gradient mode)")
+            raise ops._lib.MisplatError("GraphedStep needs the default single-node path (collab_splats_amd.ops.FUSED_ENTRY "
+                                        "and FUSED_NODE left True, atomic gradient mode)")
         # the count of every replay lands in a pinned word of this graph's own (advisor, round 4: with one word per device a
         # view's overflow was overwritten by the next view's replay before anybody looked)
         self._count = torch.zeros(1, dtype=torch.int64, pin_memory=True)

@@ -72,6 +72,17 @@ def _order_slots(table: Tensor, stride: int) -> int:
     return table.numel() // stride
 
 
+def _set_unit_order(blk, by_view, perm: Optional[Tensor]) -> None:
+    """The launch order of a compositing backward in ``blk`` (Params or RasterBwdArgs: the same field names): the view-keyed
+    record (table, sel, stride) where there is one, else the permutation the forward left."""
+    if by_view is not None:
+        table, sel, stride = by_view
+        blk.unit_perm, blk.unit_sel, blk.unit_stride, blk.unit_slots = (table.data_ptr(), sel.data_ptr(), stride,
+                                                                        _order_slots(table, stride))
+    else:
+        blk.unit_perm = _dp(perm)
+
+
 def _order_table(P: Params, dev: torch.device):
     """(table, sel, stride) of this device / stream / shape, or None when view-keyed orders are off."""
     if not (UNIT_ORDER and ORDER_SLOTS > 0):
@@ -109,7 +120,8 @@ def _order_table(P: Params, dev: torch.device):
 class _UnitSchedule:
     """Per-call launch-order state of one compositing forward/backward pair."""
 
-    def __init__(self, P: Params, dev: torch.device, by_view=None, cv=None):
+    def __init__(self, P: Params, dev: torch.device, by_view=None, arrays=None):
+        """``arrays``: (work, perm) the caller carved from its arena slot (_layout_b); else they come from the allocator."""
         self.on = UNIT_ORDER
         self.perm_bwd = None
         self.by_view = by_view if self.on else None        # (table, sel, stride): the order lives in a view-keyed record
@@ -118,8 +130,7 @@ class _UnitSchedule:
         self.units = P.tile_w * P.tile_h * P.n_cams * BANDS
         self.key = (dev.index, _stream_id(), P.n_cams, P.tile_w, P.tile_h)
         # (the host-keyed previous-call order outlives the call in _LAST_ORDER: not from the call's arena slot)
-        self.work, self.perm = _carve(dev, (self.units, 8 * ((self.units + 7) // 8) if self.by_view is None else 0),
-                                      cv if self.by_view is not None else None)
+        self.work, self.perm = arrays or _carve(dev, [t.count for t in _unit_takes(self.units, self.by_view is not None)])
 
     def before_forward(self, P: Params) -> None:
         if not self.on:
@@ -138,11 +149,7 @@ class _UnitSchedule:
         self.perm_bwd = self.perm
 
     def before_backward(self, P: Params) -> None:
-        if self.by_view is not None:
-            table, sel, stride = self.by_view
-            P.unit_perm, P.unit_sel, P.unit_stride, P.unit_slots = table.data_ptr(), sel.data_ptr(), stride, _order_slots(table, stride)
-        else:
-            P.unit_perm = self.perm_bwd.data_ptr() if self.perm_bwd is not None else None
+        _set_unit_order(P, self.by_view, self.perm_bwd)
         P.unit_work = None
 
     @staticmethod
@@ -155,14 +162,9 @@ class _UnitSchedule:
 GRAD_SINK = None
 
 
-def _grad_out(inp: Tensor, cv: "Optional[arena.Carver]" = None) -> Tensor:
-    if GRAD_SINK is not None:
-        v = GRAD_SINK.sink(inp)
-        if v is not None:
-            return v
-    if cv is not None:
-        return cv.take(inp.numel(), inp.dtype).view(inp.shape)
-    return torch.empty_like(inp)
+def _grad_out(inp: Tensor) -> Tensor:
+    v = GRAD_SINK.sink(inp) if GRAD_SINK is not None else None
+    return v if v is not None else torch.empty_like(inp)
 
 
 # Optional per-kernel timing (bench.py): name -> list of (start_event, end_event) recorded on the
@@ -217,18 +219,151 @@ def _carve(dev: torch.device, sizes, cv: "Optional[arena.Carver]" = None, dtype=
     caching allocator -- or one contiguous piece of the call's arena slot (``cv``) -- instead of one per scratch array."""
     # (ONE split call makes all the views: a Python-level slice per array was the largest single item of a small scene's
     # forward on the host -- ~25 arrays per call, 55 of its ~270 us under the profiler)
-    parts, tot = [], 0
+    tot, parts = _carve_elems(sizes), []
     for n in sizes:
-        n = int(n)
-        padded = (n + 63) // 64 * 64
-        parts.append(n)
-        parts.append(padded - n)
-        tot += padded
-    if tot < 64:
-        parts.append(64 - tot)
-        tot = 64
+        parts += (int(n), -int(n) % 64)
+    parts.append(tot - sum(parts))                                    # (the 64-element floor; usually an empty part)
     buf = cv.take(tot, dtype) if cv is not None else torch.empty(tot, device=dev, dtype=dtype)
     return list(torch.split_with_sizes(buf, parts)[0:2 * len(sizes):2])
+
+
+def _carve_elems(sizes) -> int:
+    """Elements of one carve: every array rounded up to 64 elements, 64 at the least."""
+    return max(sum((int(n) + 63) // 64 * 64 for n in sizes), 64)
+
+
+# The arrays of a call, described ONCE: a layout is the ordered sequence of its takes.  Takes that share a ``carve`` number are
+# cut from one piece of the slot (_carve: 64-element rounding between them); ``carve`` -1 is a take of its own, of exactly
+# ``count`` elements.  The calls carve FROM a layout (_carve_all) and reserve the demand OF it (_demand), so the two cannot
+# disagree; where an array lies in the slot follows from the order here alone (measured, not assumed: arena.py).
+Take = collections.namedtuple("Take", "name dtype count carve")
+
+
+def _pieces(takes) -> list:
+    """[(dtype, elements, [takes])], one entry per trip to the arena."""
+    out = []
+    for t in takes:
+        if t.carve >= 0 and out and out[-1][2][0].carve == t.carve:
+            out[-1][2].append(t)
+        else:
+            out.append((t.dtype, None, [t]))
+    return [(dt, ts[0].count if ts[0].carve < 0 else _carve_elems([t.count for t in ts]), ts) for dt, _, ts in out]
+
+
+def _demand(takes) -> int:
+    """Bytes of arena slot that these takes, in this order, need."""
+    return arena.demand([n * arena._ESIZE[dt] for dt, n, _ in _pieces(takes)])
+
+
+def _carve_all(cv: "arena.Carver", takes) -> Dict[str, Tensor]:
+    """{name: array} of a layout, taken from ``cv`` in order (an array the layout does not list is simply not there)."""
+    out = {}
+    for dt, n, ts in _pieces(takes):
+        if ts[0].carve < 0:
+            out[ts[0].name] = cv.take(n, dt)
+        else:
+            out.update(zip([t.name for t in ts], _carve(cv.dev, [t.count for t in ts], cv, dt)))
+    return out
+
+
+def _unit_takes(units: int, keyed: bool) -> tuple:
+    """_UnitSchedule's two arrays (``keyed``: the order lives in a view-keyed record, no permutation of the call's own)."""
+    return (Take("unit_work", torch.int32, units, 1), Take("unit_perm", torch.int32, 0 if keyed else 8 * ((units + 7) // 8), 1))
+
+
+def _layout_a(P: Params, n_cells: int, n_blocks: int, want_grad: bool, want_aux: bool, absgrad: bool, nxq: int, lazy: bool,
+              indexed: bool) -> list:
+    """Phase A of the forward: the per-Gaussian outputs, the packed records and their gradient rows, the bucketing workspace."""
+    f, i = torch.float32, torch.int32
+    rows, n_tiles = P.n_cams * P.n_gauss, P.tile_w * P.tile_h * P.n_cams
+    t = [Take("means2d", f, 2 * rows, 0), Take("depths", f, rows, 0), Take("comps", f, rows, 0),
+         Take("sh_aux", f, 12 * rows if want_aux else 0, 0), Take("grec", f, MISPLAT_REC * rows, -1)]
+    if want_grad:
+        t.append(Take("v_grec_zero", f, MISPLAT_REC * rows, -1))
+    if want_grad and absgrad:
+        t.append(Take("v_abs_zero", f, 2 * rows, -1))
+    # N-D colours (the features model, nxq > 0): channels 4.. of every row, and their gradient rows
+    # (on-demand N-D records: no featx -- the compositing kernels read the feature rows themselves)
+    if nxq > 0 and not lazy:
+        t.append(Take("featx", f, 4 * nxq * rows, -1))
+    if nxq > 0 and want_grad:
+        t.append(Take("v_featx_zero", f, 4 * nxq * rows, -1))
+    # (cell_count, cell_cursor, counters, tile_count back to back: the projection kernel clears that contiguous range -- no
+    # memset, no clearing launch)
+    return t + [Take(n, i, c, 1) for n, c in (
+        ("radii", 2 * rows), ("tiles_per_gauss", rows), ("rect2", 2 * rows), ("cellhist", n_blocks * n_cells),
+        ("cell_count", n_cells), ("cell_cursor", n_cells), ("counters", 4), ("tile_count", n_tiles + 1),
+        ("cell_offs", n_cells + 1), ("order", rows), ("rect_sorted", 2 * rows), ("touched", (rows + 3) // 4 if want_grad else 0),
+        ("depth_sorted", rows if indexed else 0))]
+
+
+def _layout_b(P: Params, keyed: bool, front: bool, cd: int, cap: int) -> list:
+    """Phase B: the images, _UnitSchedule's arrays (``keyed``: a view-keyed order table exists), the per-pixel and per-tile
+    lists, the three intersection buffers of ``cap`` entries."""
+    f, i = torch.float32, torch.int32
+    n_pix, n_tiles = P.n_cams * P.height * P.width, P.tile_w * P.tile_h * P.n_cams
+    t = [Take("render", f, cd * n_pix, 0), Take("alpha", f, n_pix, 0), Take("exp_depth", f, n_pix, 0),
+         Take("med_depth", f, n_pix, 0), Take("normal", f, 3 * n_pix, 0)]
+    if keyed:
+        t += _unit_takes(n_tiles * BANDS, True)
+    t += [Take(n, i, c, 2) for n, c in (
+        ("last_ids", n_pix), ("median_ids", n_pix), ("offsets", n_tiles + 2), ("reach", n_tiles * BANDS if keyed else 0),
+        ("front_n", n_tiles if front else 0), ("tile_flag", n_tiles if front else 0))]
+    return t + _isect_takes(cap)
+
+
+def _isect_takes(cap: int) -> list:
+    return [Take("payload", torch.int32, cap, -1), Take("flatten_ids", torch.int32, cap, -1), Take("scratch", torch.int32, 2 * cap, -1)]
+
+
+def _bwd_takes(ins, rows: int, nxq: int, deg: int, need_grec: bool, need_featx: bool, m2d: bool):
+    """(sunk, layout) of a one-node backward whose seven differentiable inputs (GRAD_NAMES order, None: absent) are ``ins``:
+    the gradient tensors a data-parallel sink provides (GRAD_SINK.sink hands each out once), and the takes for all the rest."""
+    sunk = [GRAD_SINK.sink(t) if (GRAD_SINK is not None and t is not None) else None for t in ins]
+    counts = [None if (t is None or s is not None) else t.numel() for t, s in zip(ins, sunk)]
+    return sunk, _layout_bwd(rows, nxq, counts, ins[3].numel() if deg >= 0 else None, need_grec, need_featx, m2d)
+
+
+def _rows_hold_mean_gradient(simple: bool, sparse: bool, have_m2d: bool) -> bool:
+    """Are columns 0:2 of the packed gradient rows the screen-space gradient?  Not after a one-call flagged-rows backward
+    (``sparse``: the kernels keep the sums of the means there) that was given no tensor of its own for it."""
+    return not (simple and sparse and not have_m2d)
+
+
+def _colour_project_bwd(P: Params, color_args, depth_slot: int, means, quats, scales, opacities, colors, colors_rest, viewmats, Ks,
+                        radii, comps, sh_aux, v_means2d, v_grec, v_colors, v_colors_rest, v_means_dir, v_means, v_quats, v_scales,
+                        v_opac) -> None:
+    """The per-Gaussian backward stage by stage: colours (SH or pass-through), then the projection."""
+    deg, kd, n_color, per_cam = color_args
+    run("misplat_color_bwd", C.byref(P), deg, kd, n_color, per_cam, ptr(means), ptr(viewmats), ptr(colors),
+        ptr(colors_rest), ptr(radii), ptr(v_grec), ptr(v_colors), ptr(v_colors_rest), ptr(v_means_dir), ptr(sh_aux))
+    if GRAD_SINK is not None:
+        GRAD_SINK.colour_ready()                          # the colour bucket's all-reduce starts now, overlapped with the rest
+    run("misplat_project_pack_bwd", C.byref(P), depth_slot, ptr(means), ptr(quats), ptr(scales), ptr(opacities),
+        ptr(viewmats), ptr(Ks), ptr(radii), ptr(comps), ptr(v_means2d), ptr(v_grec), ptr(v_means_dir), ptr(v_means),
+        ptr(v_quats), ptr(v_scales), ptr(v_opac), None, 0)
+
+
+GRAD_NAMES = ("v_colors", "v_colors_rest", "v_features", "v_means", "v_quats", "v_scales", "v_opac")
+
+
+def _layout_bwd(rows: int, nxq: int, counts, n_dir: Optional[int], need_grec: bool, need_featx: bool, m2d: bool) -> list:
+    """The one-node backward.  ``counts``: elements of the seven gradients of GRAD_NAMES, None where the call does not allocate one
+    (no such input, or a data-parallel sink owns it); ``n_dir``: elements of the direction gradient (SH colours), or None."""
+    t = []
+
+    def add(name, n, on=True):
+        if on and n is not None:
+            t.append(Take(name, torch.float32, n, -1))
+    add("v_grec", rows * MISPLAT_REC, need_grec)
+    for name, n in zip(GRAD_NAMES[:3], counts):
+        add(name, n)
+    add("v_featx", rows * 4 * nxq, need_featx)
+    add("v_means_dir", n_dir)
+    for name, n in zip(GRAD_NAMES[3:], counts[3:]):
+        add(name, n)
+    add("v_m2d", rows * 2, m2d)
+    return t
 
 
 def bucket_plan(P: Params) -> Tuple[int, int]:
@@ -284,10 +419,6 @@ def key_trace_report(period: int, start: int = 0) -> list:
     return out
 _CAP_HINT: Dict[tuple, int] = {}
 _READBACK: Dict[tuple, Tensor] = {}
-
-
-def _carve_f(dev: torch.device, sizes, cv: "Optional[arena.Carver]" = None) -> list:
-    return _carve(dev, sizes, cv, torch.float32)
 
 
 # hipGraph replay of the launch sequences (csrc/raster.hip): one graph per distinct argument block, LRU per device.
@@ -463,13 +594,23 @@ def _lazy_colour_ok(P: Params, dev, deg: int, kd: int, n_color: int, want_grad: 
     return hint is not None and hint >= LAZY_SH_MIN_BUCKET * P.tile_w * P.tile_h * P.n_cams
 
 
-def _front_only_wanted(P: Params, dev) -> bool:
-    """Front-only ordering for this call?  Needs the view-keyed records (pivots), a capacity hint (the typical bucket) and
-    an eager, non-static call; decided before phase A, which then also lays the buckets out for it (entries = positions in the cell-ordered row list)."""
-    if FRONT_ONLY == "0" or _STATIC_CAP is not None or not (SPECULATE and UNIT_ORDER):
+def _indexed(P: Params, dev) -> bool:
+    """Front-only ordering for this call, i.e. bucket entries as positions in the cell-ordered row list?  Needs the view-keyed
+    records (pivots), a capacity hint (the typical bucket), an eager, non-static call and rows that fit 23 index bits (+ 9 bits
+    of depth code); decided ONCE per call, before phase A -- it names the call's arena ring and lays its buckets out.
+    (Pays where the per-tile sort's depth gather misses the L2: dense scenes; at 1 M Gaussians it costs the sort a second
+    gather: 55 -> 86 us.)"""
+    if FRONT_ONLY == "0" or _STATIC_CAP is not None or not (SPECULATE and UNIT_ORDER) or P.n_cams * P.n_gauss >= (1 << 23):
         return False
     hint = _CAP_HINT.get(_cap_key(P, dev))
     return hint is not None and (FRONT_ONLY == "1" or hint >= FRONT_MIN_AVG * P.tile_w * P.tile_h * P.n_cams)
+
+
+def _color_args(colors: Tensor, colors_rest: Optional[Tensor], sh_degree) -> Tuple[int, int, int, int]:
+    """(deg, kd, n_color, per_cam) of a colour input: SH coefficients of ``sh_degree``, or (deg = -1) colours passed through."""
+    if sh_degree is not None:
+        return int(sh_degree), (colors.shape[1] if colors_rest is None else 1 + colors_rest.shape[1]), 3, 0
+    return -1, colors.shape[-1], colors.shape[-1], int(colors.dim() == 3)
 
 
 def _fwd_ring_key(P: Params, dev, kd: int, want_grad, want_aux, absgrad, depth_channel, indexed, nxq) -> tuple:
@@ -480,50 +621,39 @@ def _fwd_ring_key(P: Params, dev, kd: int, want_grad, want_aux, absgrad, depth_c
 def _raster_phase_a(P: Params, means, quats, scales, opacities, colors, colors_rest, viewmats, Ks, deg: int, kd: int,
                     n_color: int, per_cam: int, depth_channel: bool, want_aux: bool, want_grad: bool, defer: bool = False,
                     lazy: bool = False, flags: bool = False, absgrad: bool = False, nxq: int = 0, features=None,
-                    probe: bool = False, cd_hint: int = 20, cv: "Optional[arena.Carver]" = None):
+                    probe: bool = False, cd_hint: int = 20, cv: "Optional[arena.Carver]" = None, indexed: Optional[bool] = None):
     """Allocations + phase A of misplat_raster_fwd (``defer``: phase A is launched together with B, by _raster_phase_b).
     Returns (radii, means2d, depths, comps, grec, sh_aux, state)."""
     lib = _lib.load()
     dev = means.device
     N, Cn = P.n_gauss, P.n_cams
     rows = Cn * N
-    n_tiles = P.tile_w * P.tile_h * Cn
-    n_cells, n_blocks = bucket_plan(P)
     # Every array of the call from ONE slot of a persistent ring (arena.py): the same call finds the same addresses every
-    # step -- an argument block recurs whenever its camera tensor does, so its hipGraph is replayed --, and the gather targets
-    # (records, lists) start on 2 MiB boundaries.  A slot is handed out again only when nothing refers to its storage.
-    # (bucket entries as positions in the cell-ordered row list: pays where the per-tile sort's depth gather misses the L2 --
-    # dense scenes, i.e. together with front-only ordering; at 1 M Gaussians it costs the sort a second gather: 55 -> 86 us)
-    indexed = _front_only_wanted(P, dev) and rows < (1 << 23)          # (23 index bits + 9 bits of depth code)
+    # step -- an argument block recurs whenever its camera tensor does, so its hipGraph is replayed.  Inside the slot the arrays
+    # are packed at 256-byte granularity, in the order of the layout.  A slot is handed out again only when nothing refers to
+    # its storage.
+    if indexed is None:
+        indexed = _indexed(P, dev)
     if cv is None:
         cv = arena.Carver(None if probe else _fwd_ring_key(P, dev, kd, want_grad, want_aux, absgrad, depth_channel, indexed, nxq), dev)
-    if defer and not probe and _STATIC_CAP is None and _CAP_HINT.get(_cap_key(P, dev)) is not None:
-        # a ring's first call: its demand, summed the way the takes below (and phase B's) go -- 64-element rounding inside a
-        # carve, 256 bytes between takes --, so that the slot exists from call one (arena.Carver.reserve)
-        g_, nd_ = int(bool(want_grad)), int(nxq > 0)
-        n_pix_, units_ = Cn * P.height * P.width, n_tiles * BANDS
-        cap_ = _choose_cap(_cap_key(P, dev), _CAP_HINT[_cap_key(P, dev)])
-        carves = ((2 * rows, rows, rows, 12 * rows * int(bool(want_aux))), (MISPLAT_REC * rows,), (MISPLAT_REC * rows * g_,),
-                  (2 * rows * g_ * int(bool(absgrad)),), (4 * nxq * rows * nd_ * int(not lazy),), (4 * nxq * rows * nd_ * g_,),
-                  (2 * rows, rows, 2 * rows, n_blocks * n_cells, n_cells, n_cells, 4, n_tiles + 1, n_cells + 1, rows, 2 * rows,
-                   (rows + 3) // 4 * g_, rows * int(bool(indexed))),
-                  (cd_hint * n_pix_, n_pix_, n_pix_, n_pix_, 3 * n_pix_), (units_, 8 * ((units_ + 7) // 8)),
-                  (n_pix_, n_pix_, n_tiles + 2, units_, n_tiles, n_tiles), (cap_,), (cap_,), (2 * cap_,))
-        cv.reserve(sum(4 * sum((int(n) + 63) // 64 * 64 for n in c) + 512 for c in carves))
-    means2d, depths, comps, sh_aux = _carve_f(dev, (2 * rows, rows, rows, 12 * rows if want_aux else 0), cv)
-    grec = cv.take(MISPLAT_REC * rows, torch.float32)
-    v_grec_zero = cv.take(MISPLAT_REC * rows, torch.float32).view(rows, MISPLAT_REC) if want_grad else None
-    v_abs_zero = cv.take(2 * rows, torch.float32).view(rows, 2) if (want_grad and absgrad) else None
-    # N-D colours (the features model, nxq > 0): channels 4.. of every row, and their gradient rows
-    # (on-demand N-D records: no featx -- the compositing kernels read the feature rows themselves)
-    featx = cv.take(4 * nxq * rows, torch.float32).view(rows, 4 * nxq) if (nxq > 0 and not lazy) else None
-    v_featx_zero = cv.take(4 * nxq * rows, torch.float32).view(rows, 4 * nxq) if (nxq > 0 and want_grad) else None
-    # (cell_count, cell_cursor, counters, tile_count back to back: the projection kernel clears that contiguous range -- no
-    # memset, no clearing launch)
-    (radii, tiles_per_gauss, rect2, cellhist, cell_count, cell_cursor, counters, tile_count, cell_offs, order, rect_sorted,
-     touched, depth_sorted) = _carve(
-        dev, (2 * rows, rows, 2 * rows, n_blocks * n_cells, n_cells, n_cells, 4, n_tiles + 1, n_cells + 1, rows, 2 * rows,
-              (rows + 3) // 4 if want_grad else 0, rows if indexed else 0), cv)
+    order = _order_table(P, dev)
+    layout = _layout_a(P, *bucket_plan(P), want_grad, want_aux, absgrad, nxq, lazy, indexed)
+    hint = _CAP_HINT.get(_cap_key(P, dev))
+    if defer and not probe and _STATIC_CAP is None and hint is not None:
+        # a deferred call knows its capacity and with it all of phase B's layout: the demand of both, so that the ring owns a
+        # slot from call one (arena.Carver.reserve)
+        cv.reserve(_demand(layout + _layout_b(P, order is not None, order is not None and indexed, cd_hint,
+                                              _choose_cap(_cap_key(P, dev), hint))))
+    g = _carve_all(cv, layout).get
+    means2d, depths, comps, sh_aux, grec = g("means2d"), g("depths"), g("comps"), g("sh_aux"), g("grec")
+    v_grec_zero = g("v_grec_zero").view(rows, MISPLAT_REC) if want_grad else None
+    v_abs_zero = g("v_abs_zero").view(rows, 2) if (want_grad and absgrad) else None
+    featx = g("featx").view(rows, 4 * nxq) if (nxq > 0 and not lazy) else None
+    v_featx_zero = g("v_featx_zero").view(rows, 4 * nxq) if (nxq > 0 and want_grad) else None
+    radii, tiles_per_gauss, rect2, cellhist, cell_count, cell_cursor, counters, tile_count, cell_offs, row_order, rect_sorted = [
+        g(n) for n in ("radii", "tiles_per_gauss", "rect2", "cellhist", "cell_count", "cell_cursor", "counters", "tile_count",
+                       "cell_offs", "order", "rect_sorted")]
+    touched, depth_sorted = g("touched"), g("depth_sorted")
     # one byte per row: cleared by the projection kernel, set by the compositing backward, read by the per-Gaussian
     # backward kernels (misplat_params.touched).  Only where the compositing backward is the ONLY source of the packed
     # gradient rows (the single autograd node): with the two-node form a loss on the projection's own outputs reaches the
@@ -542,7 +672,7 @@ def _raster_phase_a(P: Params, means, quats, scales, opacities, colors, colors_r
     a.nxq, a.featx, a.v_featx_zero = int(nxq), _dp(featx), _dp(v_featx_zero)
     a.features, a.n_feat = _dp(features), (int(features.shape[-1]) if features is not None else 0)
     a.tiles_per_gauss, a.rect2, a.cellhist, a.cell_count = _dp(tiles_per_gauss), _dp(rect2), _dp(cellhist), _dp(cell_count)
-    a.cell_offs, a.order, a.counters, a.tile_count = _dp(cell_offs), _dp(order), _dp(counters), _dp(tile_count)
+    a.cell_offs, a.order, a.counters, a.tile_count = _dp(cell_offs), _dp(row_order), _dp(counters), _dp(tile_count)
     a.cell_cursor = _dp(cell_cursor)
     a.rect_sorted = _dp(rect_sorted)
     # bucket entries = positions in the cell-ordered row list (the per-tile sort then gathers its depth keys locally)
@@ -553,48 +683,44 @@ def _raster_phase_a(P: Params, means, quats, scales, opacities, colors, colors_r
     rows_on_touch = bool(lazy and want_grad and flags and Cn == 1 and N >= SPARSE_BWD_MIN_ROWS and not want_aux and kd == 16
                          and ROWS_ON_TOUCH)
     a.lazy_colour = 2 if rows_on_touch else int(lazy)
-    row_order = order                                                 # (the cell-ordered row list; `order` below: the launch-order table)
-    order = _order_table(P, dev)
-    if order is not None:
+    if order is not None:                                             # (the launch-order table; `row_order`: the cell-ordered row list)
         a.order_table, a.order_sel, a.order_slots, a.order_stride = (_dp(order[0]), _dp(order[1]),
                                                                      _order_slots(order[0], order[2]), order[2])
     PATH_STATS["forward_rows_on_touch"] += int(rows_on_touch)
     if not defer:
         check(lib.misplat_raster_fwd(C.byref(P), C.byref(a), 1, stream_ptr(), _graph_cache(dev)),
               "misplat_raster_fwd(A)")
-    state = dict(args=a, host=host, tiles_per_gauss=tiles_per_gauss, depths=depths, v_grec_zero=v_grec_zero, v_abs_zero=v_abs_zero,
-                 deferred=defer, rows_on_touch=rows_on_touch, order=order, carver=cv, featx=featx, v_featx_zero=v_featx_zero,
-                 counters=counters, touched=touched,
-                 keep=(rect2, cellhist, cell_count, cell_offs, row_order, counters, tile_count, radii, cell_cursor, depth_sorted),
-                 row_map=row_order, depth_sorted=depth_sorted.view(torch.float32) if indexed else None)
+    state = _FwdState()
+    state.args, state.host, state.deferred, state.rows_on_touch, state.order, state.carver = a, host, defer, rows_on_touch, order, cv
+    state.tiles_per_gauss, state.depths, state.counters, state.tile_count, state.touched = tiles_per_gauss, depths, counters, tile_count, touched
+    state.v_grec_zero, state.v_abs_zero, state.featx, state.v_featx_zero = v_grec_zero, v_abs_zero, featx, v_featx_zero
+    state.row_map, state.depth_sorted = row_order, depth_sorted.view(torch.float32) if indexed else None
+    state.alive = (rect2, cellhist, cell_count, cell_offs, radii, cell_cursor, depth_sorted)
     return (radii.view(Cn, N, 2), means2d.view(Cn, N, 2), depths.view(Cn, N), comps.view(Cn, N), grec.view(rows, MISPLAT_REC),
             sh_aux.view(rows, 12) if want_aux else None, state)
 
 
-def _raster_phase_b(P: Params, state: dict, cd: int):
+def _raster_phase_b(P: Params, state: "_FwdState", cd: int):
     """Phase B of misplat_raster_fwd with a speculative capacity; returns (images..., bins, sched)."""
     prep = _phase_b_prepare(P, state, cd)
-    return _phase_b_launch(P, state, prep, cd, state.get("carver"))
+    return _phase_b_launch(P, state, prep, cd, state.carver)
 
 
-def _phase_b_prepare(P: Params, state: dict, cd: int) -> dict:
+def _phase_b_prepare(P: Params, state: "_FwdState", cd: int) -> "_FwdPrep":
     """Everything of phase B that does not depend on this call's intersection count: the capacity, the images and lists carved
     from the call's arena slot, the argument block filled in.  A function of (P, the state phase A left, the capacity hint) --
     which is what makes it cacheable per arena slot (_FwdPlan)."""
-    a = state["args"]
-    dev = state["depths"].device
-    Cn, H, W = P.n_cams, P.height, P.width
-    n_pix = Cn * H * W
-    n_tiles = P.tile_w * P.tile_h * Cn
+    a = state.args
+    dev = state.depths.device
     key = _cap_key(P, dev)
     hint = _CAP_HINT.get(key) if SPECULATE else None
     n_known = None
-    static = _STATIC_CAP is not None and state.get("deferred")
+    static = _STATIC_CAP is not None and state.deferred
     if static:
         cap = max(int(_STATIC_CAP), 1)
     elif hint is None:                                                # first call of this shape: exact, as before
-        assert not state.get("deferred")
-        n_known = _wait_count(state["host"])
+        assert not state.deferred
+        n_known = _wait_count(state.host)
         cap = max(n_known, 1)
     else:
         cap = _choose_cap(key, hint)
@@ -603,23 +729,23 @@ def _phase_b_prepare(P: Params, state: dict, cd: int) -> dict:
         a.est_isects = int(cap / CAP_FIRST_MARGIN)
     if cap >= 2 ** 31:
         raise _lib.MisplatError(f"{cap} tile intersections exceed int32 indexing")
-    cv = state.get("carver")
-    render, alpha, exp_depth, med_depth, normal = _carve_f(dev, (cd * n_pix, n_pix, n_pix, n_pix, 3 * n_pix), cv)
-    sched = _UnitSchedule(P, dev, by_view=state.get("order"), cv=cv)
-    by_view = sched.on and sched.by_view is not None
-    front = bool(by_view and not static and hint is not None and state.get("depth_sorted") is not None)   # (_front_only_wanted)
-    last_ids, median_ids, offsets, reach, front_n, tile_flag = _carve(
-        dev, (n_pix, n_pix, n_tiles + 2, n_tiles * BANDS if by_view else 0, n_tiles if front else 0, n_tiles if front else 0), cv)
-    a.unit_reach = _dp(reach) if by_view else None
-    a.front_n, a.tile_flag = (_dp(front_n), _dp(tile_flag)) if front else (None, None)
+    cv, keyed = state.carver, state.order is not None
+    front = bool(keyed and not static and hint is not None and state.depth_sorted is not None)   # (_indexed)
+    g = _carve_all(cv, _layout_b(P, keyed, front, cd, cap))
+    sched = _UnitSchedule(P, dev, by_view=state.order, arrays=(g["unit_work"], g["unit_perm"]) if keyed else None)
+    prep = _FwdPrep()
+    prep.cap, prep.n_known, prep.static, prep.front, prep.sched, prep.overflow = cap, n_known, static, front, sched, False
+    for name in _FwdPrep.ARRAYS:
+        setattr(prep, name, g[name])
+    a.unit_reach = _dp(prep.reach) if keyed else None
+    a.front_n, a.tile_flag = (_dp(prep.front_n), _dp(prep.tile_flag)) if front else (None, None)
     a.front_margin, a.front_min_bucket = FRONT_MARGIN, FRONT_MIN_BUCKET
     PATH_STATS["forward_front_only"] += int(front)
-    payload, flatten_ids, scratch = _isect_buffers(dev, cv, cap)
     a.color_dim = cd
-    a.offsets, a.render, a.alpha, a.exp_depth, a.med_depth, a.normal = (_dp(offsets), _dp(render), _dp(alpha), _dp(exp_depth),
-                                                                        _dp(med_depth), _dp(normal))
-    a.last_ids, a.median_ids = _dp(last_ids), _dp(median_ids)
-    if sched.on and sched.by_view is not None:
+    a.offsets, a.render, a.alpha, a.exp_depth, a.med_depth, a.normal = (_dp(prep.offsets), _dp(prep.render), _dp(prep.alpha),
+                                                                        _dp(prep.exp_depth), _dp(prep.med_depth), _dp(prep.normal))
+    a.last_ids, a.median_ids = _dp(prep.last_ids), _dp(prep.median_ids)
+    if keyed:
         PATH_STATS["forward_view_order"] += 1
         a.unit_perm_in, a.unit_work, a.unit_perm_out = None, _dp(sched.work), None
     elif sched.on:
@@ -632,32 +758,24 @@ def _phase_b_prepare(P: Params, state: dict, cd: int) -> dict:
         a.unit_perm_in, a.unit_work, a.unit_perm_out = _dp(last), _dp(sched.work), _dp(sched.perm)
     else:
         a.unit_perm_in, a.unit_work, a.unit_perm_out = None, None, None
-    a.payload, a.flatten_ids, a.scratch, a.cap_isects = _dp(payload), _dp(flatten_ids), _dp(scratch), cap
-    return dict(cap=cap, n_known=n_known, static=static, front=front, sched=sched, render=render, alpha=alpha, exp_depth=exp_depth,
-                med_depth=med_depth, normal=normal, last_ids=last_ids, median_ids=median_ids, offsets=offsets, reach=reach,
-                front_n=front_n, tile_flag=tile_flag, payload=payload, flatten_ids=flatten_ids, scratch=scratch)
+    a.payload, a.flatten_ids, a.scratch, a.cap_isects = _dp(prep.payload), _dp(prep.flatten_ids), _dp(prep.scratch), cap
+    return prep
 
 
-def _isect_buffers(dev, cv, c: int):
-    if cv is None:
-        return _carve(dev, (c, c, 2 * c))
-    return cv.take(c, torch.int32), cv.take(c, torch.int32), cv.take(2 * c, torch.int32)
-
-
-def _phase_b_launch(P: Params, state: dict, prep: dict, cd: int, cv):
+def _phase_b_launch(P: Params, state: "_FwdState", prep: "_FwdPrep", cd: int, cv: "arena.Carver"):
     """The launch (both phases in one call when phase A was deferred), the wait for this call's intersection count, the exact redo
-    when the capacity fell short, and the per-call results: (images, bins, sched).  Returns prep["overflow"] = True after a redo
+    when the capacity fell short, and the per-call results: (images, bins, sched).  Sets prep.overflow after a redo
     (the buffers of ``prep`` are then no longer the ones the call used)."""
     lib = _lib.load()
-    a = state["args"]
-    dev = state["depths"].device
+    a = state.args
+    dev = state.depths.device
     Cn, H, W = P.n_cams, P.height, P.width
     n_tiles = P.tile_w * P.tile_h * Cn
     key = _cap_key(P, dev)
-    cap, n_known, static, front, sched = prep["cap"], prep["n_known"], prep["static"], prep["front"], prep["sched"]
-    payload, flatten_ids, scratch = prep["payload"], prep["flatten_ids"], prep["scratch"]
-    offsets, reach, front_n, tile_flag = prep["offsets"], prep["reach"], prep["front_n"], prep["tile_flag"]
-    phases = 3 if state.get("deferred") else 2
+    cap, n_known, static, front, sched = prep.cap, prep.n_known, prep.static, prep.front, prep.sched
+    payload, flatten_ids, scratch = prep.payload, prep.flatten_ids, prep.scratch
+    offsets, reach, front_n, tile_flag = prep.offsets, prep.reach, prep.front_n, prep.tile_flag
+    phases = 3 if state.deferred else 2
     while True:
         a.payload, a.flatten_ids, a.scratch, a.cap_isects = _dp(payload), _dp(flatten_ids), _dp(scratch), cap
         if KERNEL_EVENTS is not None:                                 # a measurement pass: events around the compositing forward
@@ -675,17 +793,17 @@ def _phase_b_launch(P: Params, state: dict, prep: dict, cd: int, cv):
             _STATIC_SEEN[dev.index if dev.index is not None else torch.cuda.current_device()] = cap
             break
         if n_known is None:
-            n_known = _wait_count(state["host"])                      # usually long there: phase B was enqueued meanwhile
+            n_known = _wait_count(state.host)                      # usually long there: phase B was enqueued meanwhile
         if n_known <= cap:
             break
         cap = n_known                                                 # the guess was too small: exact size, once more
-        prep["overflow"] = True
+        prep.overflow = True
         PATH_STATS["capacity_redo"] += 1
-        tc = state["keep"][6]                                         # tile_count: phase B expects it cleared
+        tc = state.tile_count                                         # phase B expects it cleared
         check(lib.misplat_zero_bytes(ptr(tc), 4 * tc.numel(), stream_ptr()), "misplat_zero_bytes")
         if cap >= 2 ** 31:
             raise _lib.MisplatError(f"{cap} tile intersections exceed int32 indexing")
-        payload, flatten_ids, scratch = _isect_buffers(dev, cv, cap)
+        payload, flatten_ids, scratch = _carve_all(cv, _isect_takes(cap)).values()
     if not static:
         # a very slowly decaying maximum: consecutive training views differ in their counts by tens of percent (1 M random
         # Gaussians, the eight views of configs[3]: 3.8 - 6.4 M), a guess that falls short costs a second phase B, a
@@ -695,27 +813,25 @@ def _phase_b_launch(P: Params, state: dict, prep: dict, cd: int, cv):
     if sched.on and sched.by_view is None:
         _LAST_ORDER[sched.key] = sched.perm
         sched.perm_bwd = sched.perm
-    if cv is not None:
-        cv.done()
-        PATH_STATS["forward_arena_slot"] += int(cv.slot is not None)
-    bins = dict(tiles_per_gauss=state["tiles_per_gauss"], n_isects=cap if static else n_known, depths=state["depths"],
-                tile_ids=None, v_grec_zero=state.get("v_grec_zero"), v_abs_zero=state.get("v_abs_zero"),
-                featx=state.get("featx"),
+    cv.done()
+    PATH_STATS["forward_arena_slot"] += int(cv.slot is not None)
+    bins = dict(tiles_per_gauss=state.tiles_per_gauss, n_isects=cap if static else n_known, depths=state.depths,
+                tile_ids=None, v_grec_zero=state.v_grec_zero, v_abs_zero=state.v_abs_zero, featx=state.featx, plan=None,
                 # (on-demand N-D records without rows-on-touch: nobody has cleared the featx gradient rows -- the backward does)
-                v_featx_zero=(state.get("v_featx_zero") if (a.lazy_colour != 1 or a.nxq == 0) else None),
-                rows_on_touch=bool(state.get("rows_on_touch")), n_isects_dev=state["counters"].view(torch.int64)[0] if static else None,
+                v_featx_zero=(state.v_featx_zero if (a.lazy_colour != 1 or a.nxq == 0) else None),
+                rows_on_touch=bool(state.rows_on_touch), n_isects_dev=state.counters.view(torch.int64)[0] if static else None,
                 n_tiles=n_tiles, slots=None, flatten_ids=flatten_ids[:cap if static else n_known], cap_isects=int(cap),
                 isect_offsets=offsets[:n_tiles + 1], _keep=(scratch, payload, reach),
                 # one byte per row, set by the atomic compositing backward for the rows it adds a gradient to
-                touched=(state["touched"].view(torch.uint8)[:P.n_gauss * Cn] if P.touched else None),
+                touched=(state.touched.view(torch.uint8)[:P.n_gauss * Cn] if P.touched else None),
                 # front-only ordering: flatten_ids holds the sorted head of every list (all the compositing and the
                 # backward read); complete_bins() sorts the rest when someone wants the whole lists
                 partial=(dict(cap=cap, offsets=offsets, payload=payload, scratch=scratch, flatten_ids=flatten_ids,
-                              front_n=front_n, tile_flag=tile_flag, row_map=state["row_map"],
-                              depth_sorted=state["depth_sorted"]) if front else None))
-    imgs = (prep["render"].view(Cn, H, W, cd), prep["alpha"].view(Cn, H, W, 1), prep["exp_depth"].view(Cn, H, W, 1),
-            prep["med_depth"].view(Cn, H, W, 1), prep["normal"].view(Cn, H, W, 3), prep["last_ids"].view(Cn, H, W),
-            prep["median_ids"].view(Cn, H, W))
+                              front_n=front_n, tile_flag=tile_flag, row_map=state.row_map,
+                              depth_sorted=state.depth_sorted) if front else None))
+    imgs = (prep.render.view(Cn, H, W, cd), prep.alpha.view(Cn, H, W, 1), prep.exp_depth.view(Cn, H, W, 1),
+            prep.med_depth.view(Cn, H, W, 1), prep.normal.view(Cn, H, W, 3), prep.last_ids.view(Cn, H, W),
+            prep.median_ids.view(Cn, H, W))
     return imgs, bins, sched
 
 
@@ -727,7 +843,7 @@ def _phase_b_launch(P: Params, state: dict, prep: dict, cd: int, cv):
 # OUTPUT of the node; gsplat's contract -- ``meta["means2d"].grad`` / ``.absgrad`` hold the screen-space gradient
 # after ``backward()`` (rade_gs_model.py:191-198) -- is kept by assigning both from inside the backward.  The other
 # per-Gaussian intermediates in ``meta`` (conics, ray planes, ...) are not differentiable in this form; set
-# MISPLAT_FUSED_NODE=0 (the two-node form) to differentiate through them.
+# ``collab_splats_amd.ops.FUSED_NODE = False`` (the two-node form) to differentiate through them.
 FUSED_NODE = True
 
 
@@ -755,7 +871,22 @@ class _FwdPlan:
 
 
 class _BwdPlan:
-    __slots__ = ("key", "b", "grads", "v_grec", "v_abs", "v_featx", "v_m2d", "sparse", "off", "demand", "on_touch", "flags", "refs")
+    __slots__ = ("key", "b", "grads", "v_grec", "v_abs", "v_featx", "v_m2d", "v_means_dir", "sparse", "off", "demand", "on_touch",
+                 "flags", "refs")
+
+
+class _FwdState:
+    """What phase A leaves for phase B and the backward.  ``alive``: arrays nobody reads from Python again, held so that the
+    memory the argument block points at stays the call's (a call without an arena slot has only these references)."""
+    __slots__ = ("args", "host", "deferred", "rows_on_touch", "order", "carver", "tiles_per_gauss", "depths", "counters",
+                 "tile_count", "touched", "v_grec_zero", "v_abs_zero", "featx", "v_featx_zero", "row_map", "depth_sorted", "alive")
+
+
+class _FwdPrep:
+    """What _phase_b_prepare leaves for the launch: the capacity and how it was chosen, the images and the lists."""
+    ARRAYS = ("render", "alpha", "exp_depth", "med_depth", "normal", "last_ids", "median_ids", "offsets", "reach", "front_n",
+              "tile_flag", "payload", "flatten_ids", "scratch")
+    __slots__ = ("cap", "n_known", "static", "front", "sched", "overflow") + ARRAYS
 
 
 _PLAN_IDS = iter(range(1, 1 << 62))
@@ -769,12 +900,7 @@ class _RasterFused(torch.autograd.Function):
         if ctx.needs_input_grad[7]:
             raise NotImplementedError(POSE_GRAD_MESSAGE.format(node="_RasterFused"))
         require_gpu(means, quats, scales, opacities, colors, viewmats, Ks, features)
-        if sh_degree is not None:
-            kd = colors.shape[1] if colors_rest is None else 1 + colors_rest.shape[1]
-            deg, n_color, per_cam = int(sh_degree), 3, 0
-        else:
-            deg, kd, per_cam = -1, colors.shape[-1], int(colors.dim() == 3)
-            n_color = kd
+        deg, kd, n_color, per_cam = _color_args(colors, colors_rest, sh_degree)
         want_grad = any(ctx.needs_input_grad[:7])
         # N-D colours in one pass (a8, rade_features_model.py:427-476): cd = D' composited channels, 4 in the record + 4 nxq
         nxq = (cd - 4 + 3) // 4 if cd > 4 else 0
@@ -788,7 +914,7 @@ class _RasterFused(torch.autograd.Function):
             Pp = Params.from_buffer_copy(bytes(P))
             st = _raster_phase_a(Pp, means, quats, scales, opacities, colors, colors_rest, viewmats, Ks, deg, kd, n_color, per_cam,
                                  depth_channel, False, False, nxq=nxq, features=features, probe=True)[-1]
-            _CAP_HINT[_cap_key(P, means.device)] = max(_wait_count(st["host"]), 1)
+            _CAP_HINT[_cap_key(P, means.device)] = max(_wait_count(st.host), 1)
             del st
             PATH_STATS["forward_probe"] += 1
             lazy = _lazy_colour_ok(P, means.device, deg, kd, n_color, want_grad, cd, nxq, features)
@@ -805,8 +931,8 @@ class _RasterFused(torch.autograd.Function):
         plannable = (PLAN_CACHE and defer and _STATIC_CAP is None and KERNEL_EVENTS is None and KEY_TRACE is None and UNIT_ORDER
                      and arena.ENABLED and not torch.cuda.is_current_stream_capturing())
         cv, plan, pkey = None, None, None
+        indexed = _indexed(P, dev)
         if plannable:
-            indexed = _front_only_wanted(P, dev) and rows < (1 << 23)
             cv = arena.Carver(_fwd_ring_key(P, dev, kd, want_grad, want_aux, absgrad, depth_channel, indexed, nxq), dev)
             if cv.slot is not None:
                 ck = _cap_key(P, dev)
@@ -821,7 +947,7 @@ class _RasterFused(torch.autograd.Function):
             C.memmove(C.addressof(P), plan.P_image, C.sizeof(P))
             state, prep = plan.state, plan.prep
             cv.slot.off, cv.slot.demand = plan.off, plan.demand
-            state["host"][0] = -1
+            state.host[0] = -1
             for k, v in plan.stats.items():
                 PATH_STATS[k] += v
             PATH_STATS["forward_plan_hit"] += 1
@@ -832,12 +958,14 @@ class _RasterFused(torch.autograd.Function):
             r0, m0, d0, c0, g0, s0, state = _raster_phase_a(
                 P, means, quats, scales, opacities, colors, colors_rest, viewmats, Ks, deg, kd, n_color, per_cam, depth_channel,
                 want_aux, want_grad, defer=defer, lazy=lazy, flags=True, absgrad=bool(absgrad), nxq=nxq, features=features, cd_hint=cd,
-                cv=cv)
-            cv = state["carver"]
+                cv=cv, indexed=indexed)
+            cv = state.carver
             prep = _phase_b_prepare(P, state, cd)
-            state["carver"] = None            # (a plan that kept its carver would close a cycle slot -> plan -> carver -> ring -> slot:
+            state.carver = None               # (a plan that kept its carver would close a cycle slot -> plan -> carver -> ring -> slot:
                                               #  a dropped ring's memory would then wait for the cyclic collector)
-            if pkey is not None and prep["sched"].by_view is not None and cv.slot is not None:
+            # (a plan holds raw pointers: only of a build that took everything from the slot -- memory of a take that fell back to
+            # the allocator is gone when the call's tensors are)
+            if pkey is not None and prep.sched.by_view is not None and cv.slot is not None and cv.slot.served_all():
                 plan = _FwdPlan()
                 plan.key, plan.state, plan.prep, plan.outs = pkey, state, prep, (r0, m0, d0, c0, g0, s0)
                 plan.P_image = C.create_string_buffer(bytes(P), C.sizeof(P))
@@ -848,9 +976,9 @@ class _RasterFused(torch.autograd.Function):
                 new_refs = cv.slot._count() - c_before
         imgs, bins, sched = _phase_b_launch(P, state, prep, cd, cv)
         if plan is not None:
-            if prep.get("overflow"):                                  # the capacity fell short: this plan's lists were replaced
+            if prep.overflow:                                         # the capacity fell short: this plan's lists were replaced
                 cv.slot.drop_plan(pkey)
-                prep.pop("overflow", None)
+                prep.overflow = False
             elif cv.slot.plans.get(pkey) is not plan:
                 cv.slot.put_plan(pkey, plan, new_refs)
             bins["plan"] = plan.ident
@@ -894,26 +1022,31 @@ class _RasterFused(torch.autograd.Function):
         # the gradients this call hands to autograd, from the backward's own arena ring (they may live on as `.grad` of the
         # caller's parameters: the slot is reused when nothing refers to it any more -- arena.py)
         cvb = arena.Carver(("bwd", dev.index, _stream_id(), P.n_gauss, P.n_cams, kd, int(colors_rest is not None), deg), dev)
-        # (the ring's first call: an upper bound of what the takes below ask for -- every gradient tensor, the packed rows, the
-        # direction gradient, means2d's own tensor)
-        cvb.reserve(sum(4 * ((int(n) + 63) // 64 * 64) + 512 for n in (
-            rows * MISPLAT_REC, colors.numel(), colors_rest.numel() if colors_rest is not None else 0,
-            features.numel() if features is not None else 0, rows * 4 * nxq, means.numel(), means.numel(), quats.numel(),
-            scales.numel(), opacities.numel(), rows * 2)))
         simple = v_means2d_in is None
         m2d_alive = ctx.means2d_ref() is not None
+        if nxq > 0 and not simple:
+            raise _lib.MisplatError("a gradient reached meta['means2d'] from outside the rasterizer in a call with more than four "
+                                    "colour channels: that combination goes stage by stage only "
+                                    "(collab_splats_amd.ops.FUSED_NODE = False)")
+        # the rows the forward left cleared (v_grec: by the colour stage, v_abs: by the projection kernel): first backward only
+        v_grec, v_abs, v_featx = bins["v_grec_zero"], bins["v_abs_zero"], bins["v_featx_zero"]
+        bins["v_grec_zero"] = bins["v_abs_zero"] = bins["v_featx_zero"] = None
+        ins = (colors, colors_rest, features, means, quats, scales, opacities)
+        takes = None
+        if cvb.slot is None:                  # (possibly the ring's first call: it gets its slot now -- arena.Carver.reserve)
+            takes = _bwd_takes(ins, rows, nxq, deg, v_grec is None, nxq > 0 and v_featx is None, simple and m2d_alive)
+            cvb.reserve(_demand(takes[1]))
         # A steady-state backward finds its argument block and its gradient views on its arena slot (see _FwdPlan): keyed by
         # the forward's plan, the upstream gradients' addresses and what the forward left cleared.
-        bp, bkey = None, None
+        bp, bkey, sparse = None, None, 0
         if (PLAN_CACHE and simple and KERNEL_EVENTS is None and KEY_TRACE is None and GRAD_SINK is None and cvb.slot is not None
-                and bins.get("plan") is not None and (not ctx.absgrad or bins.get("v_abs_zero") is not None)):
-            bkey = (bins["plan"], tuple(_dp(t) for t in ups), m2d_alive, bool(ctx.absgrad), bins.get("v_grec_zero") is not None,
-                    bins.get("v_abs_zero") is not None, bins.get("v_featx_zero") is not None, bins.get("cap_isects"))
+                and bins["plan"] is not None and (not ctx.absgrad or v_abs is not None)):
+            bkey = (bins["plan"], tuple(_dp(t) for t in ups), m2d_alive, bool(ctx.absgrad), v_grec is not None,
+                    v_abs is not None, v_featx is not None, bins["cap_isects"])
             bp = cvb.slot.get_plan(bkey)
         if bp is not None:
-            # (the rows the forward left cleared are the FORWARD slot's: taken from this call's bins, never kept in this plan -- a
-            # tensor of another slot held here would keep that slot busy for ever)
-            v_grec, v_abs, v_featx = bins.pop("v_grec_zero", None), bins.pop("v_abs_zero", None), bins.pop("v_featx_zero", None)
+            # (the rows the forward left cleared are the FORWARD slot's: they come with this call's bins, never kept in this plan
+            # -- a tensor of another slot held here would keep that slot busy for ever)
             v_grec = bp.v_grec if v_grec is None else v_grec
             v_featx = bp.v_featx if v_featx is None else v_featx
             b, sparse, v_m2d, on_touch, flags = bp.b, bp.sparse, bp.v_m2d, bp.on_touch, bp.flags
@@ -922,52 +1055,39 @@ class _RasterFused(torch.autograd.Function):
             PATH_STATS["backward_plan_hit"] += 1
         else:
             c_before = cvb.slot._count() if bkey is not None else 0
-            v_grec = bins.pop("v_grec_zero", None)
-            flags = 1 if v_grec is not None else 0
+            flags = (1 if v_grec is not None else 0) | (2 if ctx.absgrad else 0) | (4 if v_featx is not None else 0)
             # (rows cleared on first touch by the forward: as good as cleared for a backward that reads flagged rows only)
-            on_touch = bool(bins.get("rows_on_touch")) and v_grec is not None
-            if v_grec is None:
-                v_grec = cvb.take(rows * MISPLAT_REC, torch.float32).view(rows, MISPLAT_REC)
-            v_abs = None
-            if ctx.absgrad:
-                v_abs = bins.pop("v_abs_zero", None)                # cleared by the forward's projection kernel
-                if v_abs is None:
-                    v_abs = torch.zeros(rows, 2, device=dev, dtype=torch.float32)
-                flags |= 2
-            v_colors = _grad_out(colors, cvb)
-            v_colors_rest = _grad_out(colors_rest, cvb) if colors_rest is not None else None
-            v_features = _grad_out(features, cvb) if features is not None else None
-            v_featx = None
-            if nxq > 0:
-                v_featx = bins.pop("v_featx_zero", None)                 # cleared by the forward's colour stage
-                if v_featx is not None:
-                    flags |= 4
-                else:
-                    v_featx = cvb.take(rows * 4 * nxq, torch.float32).view(rows, 4 * nxq)
-                if v_means2d_in is not None:
-                    raise _lib.MisplatError("a gradient reached meta['means2d'] from outside the rasterizer in a call with more than four "
-                                            "colour channels: that combination goes stage by stage only (MISPLAT_FUSED_NODE=0)")
-            v_means_dir = cvb.take(means.numel(), torch.float32).view(means.shape) if deg >= 0 else None
-            v_means, v_quats = _grad_out(means, cvb), _grad_out(quats, cvb)
-            v_scales, v_opac = _grad_out(scales, cvb), _grad_out(opacities, cvb)
+            on_touch = bins["rows_on_touch"] and v_grec is not None
+            if ctx.absgrad and v_abs is None:
+                v_abs = torch.zeros(rows, 2, device=dev, dtype=torch.float32)
+            sunk, layout = takes or _bwd_takes(ins, rows, nxq, deg, v_grec is None, nxq > 0 and v_featx is None, simple and m2d_alive)
+            g = _carve_all(cvb, layout)
+            v_colors, v_colors_rest, v_features, v_means, v_quats, v_scales, v_opac = [
+                s if s is not None else (g[n].view(t.shape) if t is not None else None) for n, t, s in zip(GRAD_NAMES, ins, sunk)]
+            if "v_grec" in g:
+                v_grec = g["v_grec"].view(rows, MISPLAT_REC)
+            if "v_featx" in g:
+                v_featx = g["v_featx"].view(rows, 4 * nxq)
+            v_means_dir = g["v_means_dir"].view(means.shape) if deg >= 0 else None
+            # meta["means2d"].grad, when someone still holds meta["means2d"]: a tensor of its own in the flagged-rows
+            # backward (v_grec may then be defined in flagged rows only), a slice of v_grec otherwise
+            v_m2d = g["v_m2d"].view(rows, 2) if "v_m2d" in g else None
+            del g
             perm = ctx.sched.perm_bwd if ctx.sched is not None else None
             by_view = ctx.sched.by_view if ctx.sched is not None else None
             # (a data-parallel gradient sink only changes where the six outputs are written: the slices of its flat buffer are
             # plain pointers like any other, so the one-call backward -- graph replay, both per-Gaussian stages in one launch,
             # zeros written in the background of the compositing backward -- serves it too)
-            v_m2d = None
             if simple:
                 b = RasterBwdArgs()
                 b.Ks, b.grec, b.flatten_ids, b.offsets = _dp(Ks), _dp(grec), _dp(bins["flatten_ids"]), _dp(bins["isect_offsets"])
                 # (the CAPACITY of the lists, not this call's count: the kernels take every range from `offsets`, and the count of
                 # a scene that is being trained changes with every step -- it must not be part of the graph key)
-                b.n_isects = bins.get("cap_isects") or bins["n_isects"]
+                b.n_isects = bins["cap_isects"] or bins["n_isects"]
                 b.alpha, b.last_ids, b.median_ids, b.render = _dp(alpha), _dp(last_ids), _dp(median_ids), _dp(render)
                 b.v_render, b.v_alpha, b.v_exp_depth, b.v_med_depth, b.v_normal = [_dp(t) for t in ups]
-                b.v_grec, b.v_abs, b.unit_perm = _dp(v_grec), _dp(v_abs), _dp(perm)
-                if by_view is not None:
-                    b.unit_perm, b.unit_sel, b.unit_stride = _dp(by_view[0]), _dp(by_view[1]), by_view[2]
-                    b.unit_slots = _order_slots(by_view[0], by_view[2])
+                b.v_grec, b.v_abs = _dp(v_grec), _dp(v_abs)
+                _set_unit_order(b, by_view, perm)
                 b.color_dim, b.zero_flags = cd, flags
                 b.sh_degree, b.K_or_D, b.n_color, b.per_cam, b.depth_slot = deg, kd, n_color, per_cam, ctx.depth_slot
                 b.means, b.quats, b.scales, b.opacities = _dp(means), _dp(quats), _dp(scales), _dp(opacities)
@@ -984,10 +1104,6 @@ class _RasterFused(torch.autograd.Function):
                     ev = _kernel_event_pair()
                     b.ev_blend_begin, b.ev_blend_end = ev[0].cuda_event, ev[1].cuda_event
                     KERNEL_EVENTS.setdefault("blend_bwd", []).append(ev)
-                # meta["means2d"].grad, when someone still holds meta["means2d"]: a tensor of its own in the flagged-rows
-                # backward (v_grec may then be defined in flagged rows only), a slice of v_grec otherwise
-                m2d_alive = ctx.means2d_ref() is not None
-                v_m2d = cvb.take(rows * 2, torch.float32).view(rows, 2) if m2d_alive else None
                 b.v_means2d_out = _dp(v_m2d)
                 sparse = int(lib.misplat_raster_bwd_plan(C.byref(P), C.byref(b)) & 1)
                 if not sparse:
@@ -995,16 +1111,17 @@ class _RasterFused(torch.autograd.Function):
                 if on_touch and not sparse:                               # every row is going to be read: clear them all first
                     b.zero_flags = flags & ~1 & (~4 if nxq > 0 else ~0)
                     PATH_STATS["backward_rows_refilled"] += 1
-                if bkey is not None:
+                # (a plan holds raw pointers: only of a build that took everything from the slot, and the direction gradient,
+                # which nothing else refers to, stays alive with it)
+                if bkey is not None and cvb.slot.served_all():
                     bp = _BwdPlan()
-                    bp.key, bp.b, bp.sparse, bp.v_abs, bp.v_m2d = bkey, b, sparse, None, v_m2d
+                    bp.key, bp.b, bp.sparse, bp.v_abs, bp.v_m2d, bp.v_means_dir = bkey, b, sparse, None, v_m2d, v_means_dir
                     # (only what was carved from THIS slot: the rows the forward cleared come with every call's bins)
                     bp.v_grec = v_grec if bkey[4] is False else None
                     bp.v_featx = v_featx if (nxq > 0 and bkey[6] is False) else None
                     bp.on_touch, bp.flags = on_touch, flags
                     bp.grads = (v_means, v_quats, v_scales, v_opac, v_colors, v_colors_rest, v_features)
                     bp.off, bp.demand = cvb.slot.off, cvb.slot.demand
-                    del v_means_dir
                     # (what refers to the backward's slot now is the plan's: the gradient views are handed out afresh below)
                     cvb.slot.put_plan(bkey, bp, cvb.slot._count() - c_before)
         if simple:
@@ -1017,38 +1134,31 @@ class _RasterFused(torch.autograd.Function):
             if GRAD_SINK is not None:
                 PATH_STATS["backward_sink"] += 1
                 # (the row flags let the data-parallel reduce move only the rows that have a gradient: parallel.py)
-                GRAD_SINK.rasterizer_done(bins.get("touched") if P.n_cams == 1 else None)
+                GRAD_SINK.rasterizer_done(bins["touched"] if P.n_cams == 1 else None)
         else:
             # a gradient that reached means2d from another consumer: stage by stage
             PATH_STATS["backward_staged"] += 1
             if on_touch:
                 flags &= ~1
                 PATH_STATS["backward_rows_refilled"] += 1
-            _with_perm = C.c_void_p(perm.data_ptr()) if perm is not None else None
-            P.unit_perm = _with_perm
-            if by_view is not None:
-                P.unit_perm, P.unit_sel, P.unit_stride = by_view[0].data_ptr(), by_view[1].data_ptr(), by_view[2]
-                P.unit_slots = _order_slots(by_view[0], by_view[2])
+            _set_unit_order(P, by_view, perm)
             run("misplat_blend_bwd_atomic", C.byref(P), cd, ptr(Ks), ptr(grec), ptr(bins["flatten_ids"]),
                 ptr(bins["isect_offsets"]), bins["n_isects"], ptr(alpha), ptr(last_ids), ptr(median_ids), ptr(render),
                 *[ptr(t) for t in ups], ptr(v_grec), ptr(v_abs), flags)
-            P.unit_perm, P.unit_sel, P.unit_stride, P.unit_slots = None, None, 0, 0
-            run("misplat_color_bwd", C.byref(P), deg, kd, n_color, per_cam, ptr(means), ptr(viewmats), ptr(colors),
-                ptr(colors_rest), ptr(radii), ptr(v_grec), ptr(v_colors), ptr(v_colors_rest), ptr(v_means_dir), ptr(sh_aux))
-            if GRAD_SINK is not None:
-                GRAD_SINK.colour_ready()
-            vm2d = None
-            if v_means2d_in is not None:
-                vm2d = (v_grec.view(P.n_cams, P.n_gauss, MISPLAT_REC)[..., 0:2] + v_means2d_in).contiguous()
-            run("misplat_project_pack_bwd", C.byref(P), ctx.depth_slot, ptr(means), ptr(quats), ptr(scales), ptr(opacities),
-                ptr(viewmats), ptr(Ks), ptr(radii), ptr(comps), ptr(vm2d), ptr(v_grec), ptr(v_means_dir), ptr(v_means),
-                ptr(v_quats), ptr(v_scales), ptr(v_opac), None, 0)
+            _UnitSchedule.done(P)
+            vm2d = (v_grec.view(P.n_cams, P.n_gauss, MISPLAT_REC)[..., 0:2] + v_means2d_in).contiguous()
+            _colour_project_bwd(P, ctx.color_args, ctx.depth_slot, means, quats, scales, opacities, colors, colors_rest, viewmats, Ks,
+                                radii, comps, sh_aux, vm2d, v_grec, v_colors, v_colors_rest, v_means_dir, v_means, v_quats, v_scales,
+                                v_opac)
         cvb.done()
         # gsplat's contract: the screen-space gradient rides on meta["means2d"]
         m2d = ctx.means2d_ref()
         if m2d is not None:
             if simple and v_m2d is not None:
                 g2d = v_m2d.view(P.n_cams, P.n_gauss, 2)
+            elif not _rows_hold_mean_gradient(simple, bool(sparse), v_m2d is not None):
+                raise _lib.MisplatError("the flagged-rows backward ran without a tensor for meta['means2d'].grad: the packed rows hold "
+                                        "its sums there, not the screen-space gradient")
             else:
                 g2d = v_grec.view(P.n_cams, P.n_gauss, MISPLAT_REC)[..., 0:2]
             m2d.grad = g2d if v_means2d_in is None else g2d + v_means2d_in

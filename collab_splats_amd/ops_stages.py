@@ -168,7 +168,9 @@ def bin_tiles(P: Params, means2d: Tensor, radii: Tensor, depths: Tensor,
     if n_isects >= 2 ** 31:
         raise _lib.MisplatError(f"{n_isects} tile intersections exceed int32 indexing")
     depths = depths.contiguous()
-    out = dict(tiles_per_gauss=tiles_per_gauss, n_isects=n_isects, depths=depths, tile_ids=None, n_tiles=n_tiles)
+    # (every key of the one-entry path's bins -- ops._phase_b_launch -- that a reader of either dict looks at)
+    out = dict(tiles_per_gauss=tiles_per_gauss, n_isects=n_isects, depths=depths, tile_ids=None, n_tiles=n_tiles, partial=None,
+               v_grec_zero=None, rows_on_touch=False, n_isects_dev=None)
     offsets, payload, flatten_ids, scratch, isect_gid = _o._carve(
         dev, (n_tiles + 2, n_isects, n_isects, 2 * n_isects, n_isects if deterministic else 0))
     cum = None
@@ -192,7 +194,7 @@ def complete_bins(bins: Dict[str, Tensor]) -> Tensor:
     is there (the part the compositing and the backward read); this sorts every bucket in full from ``payload``, which is
     still a permutation of it -- the heads come out as they were (they are the first entries of the sorted lists), so it may
     run before or after the backward."""
-    part = bins.get("partial")
+    part = bins["partial"]
     if part is not None:
         n_tiles = bins["n_tiles"]
         if part["cap"] > 0:
@@ -337,12 +339,7 @@ class _ProjectPack(torch.autograd.Function):
         require_gpu(means, quats, scales, opacities, colors, viewmats, Ks)
         N, Cn = P.n_gauss, P.n_cams
         dev = means.device
-        if sh_degree is not None:
-            kd = colors.shape[1] if colors_rest is None else 1 + colors_rest.shape[1]
-            deg, n_color, per_cam = int(sh_degree), 3, 0
-        else:
-            deg, kd, per_cam = -1, colors.shape[-1], int(colors.dim() == 3)
-            n_color = kd
+        deg, kd, n_color, per_cam = _o._color_args(colors, colors_rest, sh_degree)
         if prebin is not None and _o.fused_entry_ok() and N > 0:
             # one host entry: projection, row bucketing, asynchronous n_isects read-back, colours
             want_grad = any(ctx.needs_input_grad[:6])
@@ -350,33 +347,24 @@ class _ProjectPack(torch.autograd.Function):
             radii, means2d, depths, comps, grec, sh_aux, state = _o._raster_phase_a(
                 P, means, quats, scales, opacities, colors, colors_rest, viewmats, Ks, deg, kd, n_color, per_cam,
                 depth_channel, want_aux, want_grad)
-            prebin["fused"] = state
-            ctx.P, ctx.color_args = P, (deg, kd, n_color, per_cam)
-            ctx.depth_slot = 12 + n_color if depth_channel else -1
-            ctx.has_rest = colors_rest is not None
-            ctx.has_aux = sh_aux is not None
-            ctx.save_for_backward(means, quats, scales, opacities, colors, viewmats, Ks, radii, comps,
-                                  colors_rest if colors_rest is not None else colors,
-                                  sh_aux if sh_aux is not None else comps)
-            ctx.mark_non_differentiable(radii, depths, comps)
-            ctx.set_materialize_grads(False)
-            return radii, means2d, depths, comps, grec
-        radii = torch.empty(Cn, N, 2, device=dev, dtype=torch.int32)
-        means2d = torch.empty(Cn, N, 2, device=dev, dtype=torch.float32)
-        depths = torch.empty(Cn, N, device=dev, dtype=torch.float32)
-        comps = torch.empty(Cn, N, device=dev, dtype=torch.float32)
-        grec = torch.empty(Cn * N, MISPLAT_REC, device=dev, dtype=torch.float32)
-        run("misplat_project_pack_fwd", C.byref(P), ptr(means), ptr(quats), ptr(scales), ptr(opacities), ptr(viewmats), ptr(Ks),
-            ptr(radii), ptr(means2d), ptr(depths), ptr(comps), ptr(grec), ptr(None), 0, ptr(None), ptr(None))
-        if prebin is not None:                         # count tiles + start the n_isects read-back before the colours
-            prebin["pending"] = start_binning(P, means2d, radii)
-        # SH + a backward to come: keep d rgb / d dir (48 B per (camera, Gaussian)) so that the backward does not
-        # read the coefficients (192 B at degree 3) again
-        sh_aux = None
-        if deg >= 0 and any(ctx.needs_input_grad[:6]):
-            sh_aux = torch.empty(Cn * N, 12, device=dev, dtype=torch.float32)
-        run("misplat_color_fwd", C.byref(P), deg, kd, n_color, per_cam, int(depth_channel), ptr(means), ptr(viewmats),
-            ptr(colors), ptr(colors_rest), ptr(radii), ptr(depths), ptr(grec), ptr(sh_aux), ptr(None))
+            prebin["fused"] = {"phase_a": state}        # (blend_packed() makes this dict the finished bins)
+        else:
+            radii = torch.empty(Cn, N, 2, device=dev, dtype=torch.int32)
+            means2d = torch.empty(Cn, N, 2, device=dev, dtype=torch.float32)
+            depths = torch.empty(Cn, N, device=dev, dtype=torch.float32)
+            comps = torch.empty(Cn, N, device=dev, dtype=torch.float32)
+            grec = torch.empty(Cn * N, MISPLAT_REC, device=dev, dtype=torch.float32)
+            run("misplat_project_pack_fwd", C.byref(P), ptr(means), ptr(quats), ptr(scales), ptr(opacities), ptr(viewmats), ptr(Ks),
+                ptr(radii), ptr(means2d), ptr(depths), ptr(comps), ptr(grec), ptr(None), 0, ptr(None), ptr(None))
+            if prebin is not None:                         # count tiles + start the n_isects read-back before the colours
+                prebin["pending"] = start_binning(P, means2d, radii)
+            # SH + a backward to come: keep d rgb / d dir (48 B per (camera, Gaussian)) so that the backward does not
+            # read the coefficients (192 B at degree 3) again
+            sh_aux = None
+            if deg >= 0 and any(ctx.needs_input_grad[:6]):
+                sh_aux = torch.empty(Cn * N, 12, device=dev, dtype=torch.float32)
+            run("misplat_color_fwd", C.byref(P), deg, kd, n_color, per_cam, int(depth_channel), ptr(means), ptr(viewmats),
+                ptr(colors), ptr(colors_rest), ptr(radii), ptr(depths), ptr(grec), ptr(sh_aux), ptr(None))
         ctx.P, ctx.color_args = P, (deg, kd, n_color, per_cam)
         ctx.depth_slot = 12 + n_color if depth_channel else -1
         ctx.has_rest = colors_rest is not None
@@ -396,20 +384,15 @@ class _ProjectPack(torch.autograd.Function):
         if not ctx.has_aux:
             sh_aux = None
         P = ctx.P
-        deg, kd, n_color, per_cam = ctx.color_args
         v_means2d, v_grec = _grads_of_pack(P, v_means2d, v_grec)
         v_colors = _o._grad_out(colors)
         v_colors_rest = _o._grad_out(colors_rest) if colors_rest is not None else None
-        v_means_dir = torch.empty_like(means) if deg >= 0 else None
-        run("misplat_color_bwd", C.byref(P), deg, kd, n_color, per_cam, ptr(means), ptr(viewmats), ptr(colors),
-            ptr(colors_rest), ptr(radii), ptr(v_grec), ptr(v_colors), ptr(v_colors_rest), ptr(v_means_dir), ptr(sh_aux))
-        if _o.GRAD_SINK is not None:
-            _o.GRAD_SINK.colour_ready()                   # the colour bucket's all-reduce starts now, overlapped with the rest
+        v_means_dir = torch.empty_like(means) if ctx.color_args[0] >= 0 else None
         v_means, v_quats = _o._grad_out(means), _o._grad_out(quats)
         v_scales, v_opac = _o._grad_out(scales), _o._grad_out(opacities)
-        run("misplat_project_pack_bwd", C.byref(P), ctx.depth_slot, ptr(means), ptr(quats), ptr(scales), ptr(opacities),
-            ptr(viewmats), ptr(Ks), ptr(radii), ptr(comps), ptr(v_means2d), ptr(v_grec), ptr(v_means_dir), ptr(v_means),
-            ptr(v_quats), ptr(v_scales), ptr(v_opac), None, 0)
+        _o._colour_project_bwd(P, ctx.color_args, ctx.depth_slot, means, quats, scales, opacities, colors, colors_rest, viewmats, Ks,
+                               radii, comps, sh_aux, v_means2d, v_grec, v_colors, v_colors_rest, v_means_dir, v_means, v_quats,
+                               v_scales, v_opac)
         return v_means, v_quats, v_scales, v_opac, v_colors, v_colors_rest, None, None, None, None, None, None
 
 
@@ -434,9 +417,9 @@ class _BlendPacked(torch.autograd.Function):
     def forward(ctx, means2d, grec, Ks, P: Params, bins: Dict[str, Tensor], absgrad: bool, cd: int):
         Cn, H, W = P.n_cams, P.height, P.width
         dev = grec.device
-        if "args" in bins:                             # phase-A state of the one-entry path: buckets, sort, compositing
-            imgs, done, sched = _o._raster_phase_b(P, bins, cd)
-            bins.clear()
+        state = bins.pop("phase_a", None)
+        if state is not None:                          # phase-A state of the one-entry path: buckets, sort, compositing
+            imgs, done, sched = _o._raster_phase_b(P, state, cd)
             bins.update(done)                          # the caller's dict becomes the finished bins (meta reads it)
             render, alpha, exp_depth, med_depth, normal, last_ids, median_ids = imgs
             ctx.sched = sched
@@ -491,8 +474,8 @@ def _blend_backward(ctx, v_render, v_alpha, v_exp_depth, v_med_depth, v_normal):
     ups = _o._upstream(P, cd, dev, v_render, v_alpha, v_exp_depth, v_med_depth, v_normal)
     if bins["slots"] is None:                      # binned in atomic mode (ops.DETERMINISTIC_BACKWARD was False)
         # the one-entry forward left a cleared gradient buffer behind (written by the colour kernel): first backward only
-        v_grec = bins.pop("v_grec_zero", None)
-        prezeroed = v_grec is not None and not bins.get("rows_on_touch")
+        v_grec, bins["v_grec_zero"] = bins["v_grec_zero"], None
+        prezeroed = v_grec is not None and not bins["rows_on_touch"]
         if v_grec is None:
             v_grec = torch.empty(rows, MISPLAT_REC, device=dev, dtype=torch.float32)
         v_abs = torch.empty(rows, 2, device=dev, dtype=torch.float32) if ctx.absgrad else None
